@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the `bce -c` hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A step = one full compression (K1 rotation sort/BWT, K2 planes, K3 enumeration, K4 model, host range
 coders, framing) of one input block per GPU, input already resident in HBM, archive bytes ready on the
@@ -17,14 +17,21 @@ enwik9-sized (synth-text v1 seed 1, 10^9 bytes; --file if given), cut into N con
 are gathered to rank 0 over RCCL inside the timed step, where they form the BCEM container `bce -cN` writes.
 The total work is fixed (strong scaling): value = 10^9 B x steps / time.  Every gathered block is compared on
 rank 0 with the ORACLE's archive of that block alone (tests/golden/oracle_fullsize.json, synth-text-1e9-bRofN:
-the reference has one block per archive, bce.cpp:1151-1157): `oracle_golden_blocks`.
+the reference has one block per archive, bce.cpp:1151-1157): `oracle_golden_blocks` (--full).
 
-Besides the headline the line carries (N = 1 only, all untimed with respect to `value`):
+A plain run sets up, warms up, times the K steps and prints the line: the headline, the K3 / K1 / K2 / K4 rooflines and
+the stage breakdown of the timed steps.  --dump-outputs DIR writes what the last timed step returned (dump_outputs).
+With --full the line also carries (the legs below N = 1 only, all untimed with respect to `value`):
+  oracle_golden     whether the headline archive equals the oracle's (tests/golden/oracle_fullsize.json); for N > 1
+                    oracle_golden_blocks, per block
+  cli               the cold `bce -c / -d / -s` child processes (value_cli_cold)
+  value_stream      a stream of such inputs through a pool of contexts
+  decode            the headline archive through the GPU-assisted decoder, compared with the input
   workloads         the same measurement on harder inputs of the same size class: the natural and binary corpora built
                     from this image's own files (tools/make_corpus.py, make_binary_corpus.py) and synth-rand
   value_end_to_end  the headline workload from a HOST buffer (H2D copy inside the timed region)
   cpu_baseline      the oracle on a bounded sample, and the GPU path on the SAME sample: parity_sample_identical
-  oracle_golden     whether the headline archive equals the oracle's (tests/golden/oracle_fullsize.json)
+The --no-* options leave single legs of --full out.
 """
 import argparse
 import hashlib
@@ -79,7 +86,17 @@ def parse():
                          "`bce -c` writes (sharding.single_archive; whole-file compressed size, no throughput gain). Default: one block per GPU")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the real multi-GPU path); gloo = rehearsal of the N>1 control flow on one GPU")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes what the last timed step returned to DIR/<name>.npy (float32 / float64, see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: oracle known answers, cold CLI, host buffer, stream, decode, "
+                         "extra workloads, CPU baseline (default: the headline only)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def make_input(args, rank, world):
@@ -433,6 +450,26 @@ def cpu_baseline(data, sample_bytes, ctx, dev):
             "gpu_over_cpu_same_sample": round(gpu_v / cpu_v, 2)}
 
 
+DUMP_SAMPLE = 8 << 20     # archive bytes --dump-outputs writes at most (32 MB as float32)
+DUMP_SEED = 20240611
+
+
+def dump_outputs(out_dir, archives, st):
+    """--dump-outputs: what the timed path returned in its last step, so that two builds can be compared output for output.
+    archive_lengths.npy  float64, the byte length of every archive rank 0 holds (one, or one per block for N > 1)
+    archive_sample.npy   float32, the bytes of those archives laid end to end: all of them up to DUMP_SAMPLE bytes, beyond
+                         that DUMP_SAMPLE bytes at positions drawn with a fixed seed (in increasing order)
+    counts.npy           float64, nodes / symbols / rounds / sort_rounds / flushes of the last step's statistics"""
+    os.makedirs(out_dir, exist_ok=True)
+    blob = np.frombuffer(b"".join(bytes(a) for a in archives), dtype=np.uint8)
+    if len(blob) > DUMP_SAMPLE:
+        blob = blob[np.sort(np.random.default_rng(DUMP_SEED).integers(0, len(blob), DUMP_SAMPLE))]
+    np.save(os.path.join(out_dir, "archive_lengths.npy"), np.array([len(a) for a in archives], dtype=np.float64))
+    np.save(os.path.join(out_dir, "archive_sample.npy"), blob.astype(np.float32))
+    np.save(os.path.join(out_dir, "counts.npy"),
+            np.array([st[k] for k in ("nodes", "symbols", "rounds", "sort_rounds", "flushes")], dtype=np.float64))
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -451,7 +488,7 @@ def main():
             local = local % max(1, torch.cuda.device_count())     # rehearsal: ranks may share a GPU
     n_gpus = world
     cli, cli_arch = None, None
-    if world == 1 and not args.no_cli:
+    if world == 1 and args.full and not args.no_cli:
         # the cold `bce` child processes run before this process touches the GPU (see cli_leg)
         try:
             cli_data = np.fromfile(args.file, dtype=np.uint8) if args.file else (bce_amd.synth_text if args.workload == "synth-text" else bce_amd.synth_rand)(1, args.size)
@@ -556,7 +593,7 @@ def main():
         steps = max(1, args.steps)
         st = sts[-1]
         roof = roofline(n, sts)
-        table = golden_table()
+        table = golden_table() if args.full else None
         # HBM bytes from the PMC counters are collected offline (tools/profile.sh: separate rocprofv3 --pmc passes), not in this
         # run; the static file is only quoted when it was measured on THIS workload with THIS result (same archive hash)
         try:
@@ -572,9 +609,9 @@ def main():
         except Exception:
             pass
         blocks_verdict, blocks_detail, container_bytes = None, None, None
-        if dist is not None and gathered[0] is not None and not one:
+        if dist is not None and gathered[0] is not None and not one and (args.full or args.container_out):
             # the gathered per-block streams form the multi-block container (bce_amd/container.py, = what `bce -cN` writes);
-            # every block is checked against the ORACLE's archive of that block alone (rank 0 holds the whole input)
+            # with --full every block is checked against the ORACLE's archive of that block alone (rank 0 holds the whole input)
             from bce_amd import container
             blob = container.pack_blocks(gathered[0], sizes)
             assert bytes(container.unpack_blocks(blob)[0][0]) == bytes(arch)
@@ -583,7 +620,7 @@ def main():
                 with open(args.container_out, "wb") as f:
                     f.write(blob)
             del blob
-            if config is None and whole is not None:
+            if args.full and config is None and whole is not None:
                 blocks_detail = []
                 for r in range(world):
                     lo, hi = sharding.block_range(len(whole), world, r)
@@ -603,8 +640,7 @@ def main():
                                                 "(BASELINE configs[3]: enwik9 block-sharded)" % n_gpus) if n_gpus > 1 else "single block"},
             "archive_bytes": total_arch, "archive_sha256": hashlib.sha256(arch).hexdigest(),
             "archive_sha256_of": "rank 0's block" if (n_gpus > 1 and not one) else "the archive",
-            "oracle_golden": golden_verdict(table, data, arch) if config is None else None,
-            "oracle_golden_blocks": blocks_verdict, "oracle_golden_per_block": blocks_detail, "container_bytes": container_bytes,
+            "container_bytes": container_bytes,
             "ratio": round(total_arch / total_bytes, 5),
             "roofline": roof,
             "roofline_families": roofline_families(n, sts, hashlib.sha256(arch).hexdigest()) if n_gpus == 1 else None,
@@ -620,7 +656,12 @@ def main():
                            "gather_ms_per_rank": [r["gather_ms"] for r in per_rank_info],
                            "gather_bytes": int(sum(len(g) for g in gathered[0])) if gathered[0] is not None else None,
                            "note": "gather_ms is inside ms_per_step; it includes waiting for the slowest rank's archive"}
-        if n_gpus == 1 and not args.no_e2e:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, [arch] if (one or dist is None or gathered[0] is None) else gathered[0], st)
+        if args.full:
+            out["oracle_golden"] = golden_verdict(table, data, arch) if config is None else None
+            out["oracle_golden_blocks"], out["oracle_golden_per_block"] = blocks_verdict, blocks_detail
+        if n_gpus == 1 and args.full and not args.no_e2e:
             # SURVEY 8d's "file read -> archive bytes ready": the same workload from a (pageable) HOST buffer, H2D inside
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -636,12 +677,13 @@ def main():
                 cli["archive_identical_to_headline"] = bool(cli_arch == bytes(arch)) and cli.pop("all_runs_ok")
                 out["value_cli_cold"] = cli["value"]
             out["cli"] = cli
-        out["metric_scope"] = ("`value`: input resident in HBM when the clock starts, archive bytes on the host when it stops (this round's bench "
-                               "contract: a host-buffer rate is never `value`).  SURVEY 8d's metric -- file / host buffer -> archive bytes, the scope of "
-                               "the reference's own timer (bce.cpp:1404-1422) -- stands beside it as `value_host_buffer_to_archive` (warm context, H2D "
-                               "inside) and `value_cli_cold` (a fresh `bce -c` process: start-up, allocations, file read and write inside)")
+        if args.full:
+            out["metric_scope"] = ("`value`: input resident in HBM when the clock starts, archive bytes on the host when it stops (this round's bench "
+                                   "contract: a host-buffer rate is never `value`).  SURVEY 8d's metric -- file / host buffer -> archive bytes, the scope of "
+                                   "the reference's own timer (bce.cpp:1404-1422) -- stands beside it as `value_host_buffer_to_archive` (warm context, H2D "
+                                   "inside) and `value_cli_cold` (a fresh `bce -c` process: start-up, allocations, file read and write inside)")
         pool = None
-        if n_gpus == 1 and not args.no_stream:
+        if n_gpus == 1 and args.full and not args.no_stream:
             try:
                 pool = bce_amd.ContextPool(max(1, args.stream_contexts), local)
                 out["value_stream"] = stream_leg(pool, t_in, n, args.stream_steps or max(12, args.steps), arch, config)
@@ -652,7 +694,7 @@ def main():
                 if pool is not None:
                     pool.close()
                 pool = None
-        if n_gpus == 1 and not args.no_decode and n <= 1_000_000_000:
+        if n_gpus == 1 and args.full and not args.no_decode and n <= 1_000_000_000:
             # untimed: the archive of the last step through the GPU-assisted decoder (`bce -d`), compared with the input.
             # (One decode first to warm the context's decoder buffers up, as the compression steps have their warm-up: on a
             # card whose memory an earlier process has just given back the driver clears it first, 27 ms per GB.)
@@ -661,7 +703,7 @@ def main():
             out["decode"] = {"value": round(n / td / 1e6, 3), "unit": "MB/s", "seconds": round(td, 3), "roundtrip_identical": same,
                              "list_restarts": timed_decode.restarts,
                              "note": "bce_hip_decompress_device(archive -> caller's buffer) in a warm context: GPU passes + 8 host range decoders; not part of `value`"}
-        if n_gpus == 1 and not args.no_workloads and not args.file and args.workload == "synth-text":
+        if n_gpus == 1 and args.full and not args.no_workloads and not args.file and args.workload == "synth-text":
             out["workloads"] = extra_workloads(ctx, dev, table, pool, args.stream_steps or 12, decode=not args.no_decode)
             if pool is not None:
                 pool.close()
@@ -677,7 +719,7 @@ def main():
             missing = [w_.get("workload", "?")[:40] for w_ in out["workloads"] if w_.get("oracle_golden") is None]
             out["skipped_vectors"] = len(missing) + (1 if out["oracle_golden"] is None and config is None else 0)
             out["skipped_vector_names"] = missing
-        if n_gpus == 1 and not args.no_cpu:
+        if n_gpus == 1 and args.full and not args.no_cpu:
             cb = cpu_baseline(data, min(args.cpu_sample, n), ctx, dev)
             out["cpu_baseline"] = cb
             out["gpu_over_cpu"] = round(out["value"] / cb["value"], 2)

@@ -172,7 +172,7 @@ def test_gather_streams_ragged_sizes_world3():
 
 def _run_bench_ranks(world, total, extra=(), timeout=900, backend="gloo"):
     """bench.py as the driver launches it for N > 1 (torch.distributed.run, one rank per process), rehearsed on ONE GPU with
-    the gloo backend.  -> (the JSON line, the BCEM container rank 0 wrote)."""
+    the gloo backend; --full for the per-block oracle verdicts.  -> (the JSON line, the BCEM container rank 0 wrote)."""
     import json
     import subprocess
     import tempfile
@@ -181,7 +181,7 @@ def _run_bench_ranks(world, total, extra=(), timeout=900, backend="gloo"):
         cpath = os.path.join(td, "blocks.bcem")
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-               "--total-size", str(total), "--backend", backend, "--no-cpu", "--container-out", cpath] + list(extra)
+               "--total-size", str(total), "--backend", backend, "--no-cpu", "--full", "--container-out", cpath] + list(extra)
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-3000:]
         line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
