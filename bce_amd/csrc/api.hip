@@ -109,12 +109,22 @@ size_t ctx_trim(bce_hip_ctx *c) {
             &c->sval[1], &c->sout, &c->sesc, &c->skey_alt, &c->sesc_alt, &c->scanrec, &c->k4w};
     if (c->phase == 1) give.push_back(&c->gran);
   } else if (c->phase == 4) {
-    // a decode uses the suffix arrays, the low key words, the rank array, the record arrays and nlist[0] as its scratch; the rest
-    // of the encoder's buffers it never touches
-    give = {&c->nlist[1], &c->sout, &c->k4w, &c->scanrec, &c->skey_alt, &c->sesc_alt, &c->khi[0], &c->khi[1], &c->k2, &c->nrk, &c->act[0], &c->act[1],
+    // a decode uses the suffix arrays, the low key words, the rank array, the record arrays and its own node lists as its scratch;
+    // the rest of the encoder's buffers it never touches.  Within a decode: the rounds (dec_part 1) leave what the planes and the
+    // inverse BWT use, and those leave the rounds' lists and query buffers -- the inverse BWT (3) the boundary ranks as well.
+    give = {&c->nlist[0], &c->nlist[1], &c->sout, &c->k4w, &c->scanrec, &c->skey_alt, &c->sesc_alt, &c->khi[0], &c->khi[1], &c->k2, &c->nrk, &c->act[0], &c->act[1],
             &c->actv[0], &c->actv[1], &c->kflag, &c->dl[0], &c->dl[1], &c->dl[2], &c->dl[3], &c->ptmp[0], &c->ptmp[1], &c->sval[0], &c->sval[1],
             &c->k3tw, &c->k3grp};
+    if (c->dec_part == 1) {
+      for (DevBuf *b : {&c->sa[0], &c->sa[1], &c->key[0], &c->key[1], &c->rank, &c->gran, &c->bwt, &c->text}) give.push_back(b);
+    } else if (c->dec_part >= 2) {
+      for (auto &par : c->dlist) for (DevBuf &b : par) give.push_back(&b);
+      for (DevBuf *b : {&c->skey[0], &c->skey[1], &c->sesc, &c->tilecnt, &c->tileoff}) give.push_back(b);
+      if (c->dec_part == 3) give.push_back(&c->dfs);
+    }
   }
+  if (c->phase >= 1 && c->phase <= 3)                  // (an encoder's phase: the decoder's lists are idle)
+    for (auto &par : c->dlist) for (DevBuf &b : par) give.push_back(&b);
   size_t freed = 0;
   bool synced = false;
   for (DevBuf *b : give) {
@@ -395,6 +405,7 @@ void bce_hip_destroy(bce_hip_ctx *c) {
                     &c->tileoff, &c->runs, &c->smwords, &c->k3tw, &c->k3grp, &c->truns, &c->skey[0], &c->skey[1], &c->sval[0], &c->sval[1], &c->sout,
                     &c->sesc, &c->stat, &c->dcfg, &c->k4w, &c->scanrec, &c->dfs, &c->skey_alt, &c->sesc_alt, &c->rs_hist_k4};
   for (DevBuf *b : bufs) release(*b);
+  for (auto &par : c->dlist) for (DevBuf &b : par) release(b);
   k4_prepin_join(c, true);
   if (c->h_ctl) (void)hipHostFree(c->h_ctl);
   if (c->h_small) (void)hipHostFree(c->h_small);
@@ -465,6 +476,7 @@ int bce_hip_debug_set(bce_hip_ctx *c, int knob, uint32_t value) {
     case 10: c->dbg_tail_round = value; break;
     case 11: c->overlap = value != 0; break;
     case 12: c->dbg_capp_div = value; break;
+    case 13: c->dbg_dec_budget = value; break;
     case 2: c->dbg_no_tail = value; break;
     case 3: c->dbg_no_skip = value; break;
     default: return BCE_HIP_E_ARG;
@@ -1127,6 +1139,7 @@ int bce_hip_get_stats(const bce_hip_ctx *c, bce_hip_stats *out) {
   if (!c || !out) return BCE_HIP_E_ARG;
   *out = c->stats;
   out->reg_maps = c->reg_maps; out->reg_unmaps = c->reg_unmaps; out->dec_restarts = c->dec_restarts;
+  out->dec_list_grows = c->dec_list_grows; out->dec_split_rounds = c->dec_split_rounds;
   return BCE_HIP_OK;
 }
 

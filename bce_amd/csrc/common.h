@@ -163,6 +163,7 @@ struct bce_hip_ctx {
   int sa_res = 0;
   // debug knobs (bce_hip_debug_set): 0 = default
   uint32_t dbg_dfs_budget = 0, dbg_no_dfs = 0, dbg_no_tail = 0, dbg_no_skip = 0, dbg_no_small = 0, dbg_step_small = 0, dbg_no_fused = 0, dbg_no_local = 0, dbg_capp_div = 0, dbg_local_from = 0, dbg_local_budget = 0, dbg_tail_round = 0;
+  uint32_t dbg_dec_budget = 0;                   // knob 13: the decoder's query budget (0 = 2^30)
   uint64_t sym_cap_user = 0;
   bool sync_flush = false;                       // BCE_HIP_SYNC_FLUSH: flushes wait for their copy (profiling)
   bce_hip_progress_fn progress = nullptr;        // bce_hip_set_progress
@@ -179,10 +180,12 @@ struct bce_hip_ctx {
   uint32_t ngran = 0;                            // granules per plane
   // node lists: one buffer per round parity, 8 planes x capL[parity] nodes each (a round reads one parity and writes the
   // other; the one about to be written holds nothing and can be replaced by a larger one without a copy: k3_grow_lists).
-  // The decoder keeps both parities in nlist[0]: 2 x 8 planes x capP nodes.
   bce::DevBuf nlist[2];
   uint32_t capL[2] = {0, 0};
-  uint32_t capP = 0;
+  // The decoder's node lists: one buffer per (parity, plane).  In a round only plane p writes plane p + 1's list of the other
+  // parity, so a list that is too small for a plane's children is replaced alone (kd_decode.hip).
+  bce::DevBuf dlist[2][8];
+  int dec_part = 0;                              // of a decode (phase 4): 1 the rounds, 2 planes and unbwt, 3 the inverse BWT
   bce::DevBuf ctl, tilecnt, tileoff, runs;       // K3 control
   bce::DevBuf smwords;                           // k3_small_kernel: one published count word per tile
   size_t k3_groups = 0;
@@ -204,9 +207,8 @@ struct bce_hip_ctx {
   void *h_small = nullptr;                       // 4 KB of pinned host memory for read_back()
   void *h_big = nullptr;                         // pinned host memory for the decoder's host tail (the boundary ranks: 32 (n + 1) bytes), grow-only
   size_t h_big_cap = 0;
-  uint64_t dec_cap_next = 0;                     // a decode that ran out of list room starts again with this many nodes per list
-  bool dec_list_overflow = false;
-  uint32_t dec_restarts = 0;
+  uint32_t dec_restarts = 0;                     // (no decode starts again since the lists grow in place: stays 0)
+  uint64_t dec_list_grows = 0, dec_split_rounds = 0;
   uint32_t reg_maps = 0, reg_unmaps = 0;         // registered host mappings made / given back since the context was created
   bool h_big_registered = false;                 // h_big is big_host_alloc's private mapping under hipHostRegister
   void *dec_pin[3] = {nullptr, nullptr, nullptr};  // the decoder's pinned query / escape-record / answer buffers, kept from one decode to the next (grow-only)
@@ -293,7 +295,13 @@ inline int ensure(bce_hip_ctx *c, DevBuf &b, size_t bytes) {
     b.p = nullptr;
     if (ctx_trim(c) || pretend) e = hipMalloc(&b.p, bytes);
   }
-  if (e != hipSuccess) { b.p = nullptr; BCE_HIP_TRY(c, e); }
+  if (e != hipSuccess) {
+    b.p = nullptr;
+    // (the failed retry leaves its error behind in the runtime: a caller that falls back to a smaller size must not have its
+    //  next launch check report this one)
+    if (e == hipErrorOutOfMemory) (void)hipGetLastError();
+    BCE_HIP_TRY(c, e);
+  }
   c->alloc_s += now_s() - t0; c->alloc_bytes += bytes; c->alloc_calls++;
   if (now_s() - t0 > 0.02 && getenv("BCE_ALLOC_TRACE")) fprintf(stderr, "alloc: hipMalloc of %.1f MB took %.3f s\n", bytes / 1e6, now_s() - t0);
   b.cap = bytes;

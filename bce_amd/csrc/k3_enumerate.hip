@@ -1025,7 +1025,6 @@ uint64_t k3_symbol_capacity(const bce_hip_ctx *c, uint32_t n) {
 int k3_begin(bce_hip_ctx *c) {
   const uint32_t n = c->n;
   for (int par = 0; par < 2; ++par) {
-    // (a buffer the decoder left in nlist[0] holds both of ITS parities: as one parity's lists here it is simply larger)
     c->capL[par] = initial_capP(c, n, full_capP(n), par);
     BCE_TRY(ensure(c, c->nlist[par], (size_t)8 * c->capL[par] * sizeof(Node)));
   }

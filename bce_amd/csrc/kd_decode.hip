@@ -45,8 +45,9 @@ struct DecCtl {
   uint32_t ptot[8][4];       // per plane totals of the scan in flight: child0, child1, queries, escape queries
   uint32_t qbase[8];         // first query of each plane in this round's query buffer
   uint32_t ebase[8];         // first escape record (k > 31) of each plane
-  uint32_t ticket, err;      // err: 1 inconsistent archive, 2 node list overflow
-  uint32_t next_nodes, pad;
+  uint32_t ticket, err;      // err: 1 inconsistent archive, 2 node list overflow in a one-launch round (cannot happen), 4 a wait too long
+  uint32_t ovf, pad;         // bit q: plane q's children do not fit plane q + 1's list of the next parity (nothing of them written)
+  uint64_t next_nodes;       // (8 planes of up to n / 2 + 2 nodes: more than 2^32)
   uint64_t nodes_total;
 };
 static_assert(sizeof(DecCtl) <= 4096, "read_back() moves it through 4 KB of pinned memory");
@@ -54,7 +55,8 @@ static_assert(sizeof(DecCtl) <= 4096, "read_back() moves it through 4 KB of pinn
 struct DecInfo {             // what the host needs after the query pass (pinned host memory)
   uint32_t qbase[8], qtot[8];
   uint32_t ebase[8], etot[8];
-  uint32_t cur_nodes, err;
+  uint64_t cur_nodes;
+  uint32_t err, pad;
   uint64_t nodes_total;
 };
 
@@ -63,14 +65,15 @@ constexpr uint32_t kEscape = 0x80000000u;
 struct DecArgs {
   DecCtl *ctl;
   DecInfo *info;             // device pointer of the pinned DecInfo
-  Node *nodes;               // [2][8][capP]
+  Node *list[2][8];          // [parity][plane]: cap[par][p] nodes each, child0s from the front, child1s from the back
   uint32_t *R;               // [8][n + 1] boundary ranks, kUnknown where not learnt yet
   uint32_t *tilecnt, *tileoff;   // [tiles][4]: 0 child0, 1 child1, 2 queries, 3 escape queries
   uint32_t *Q;               // queries of the round: k | ctx << 5 with the context resolved (k <= 31), or kEscape
   uint4 *E;                  // escape queries (k > 31) in the same order: (k, c1, c2, cs)
   const PlaneCfg *cfg;       // [8] the archive's context-bit tables (the preamble of each stream)
   const uint32_t *res;       // answers, same indexing
-  uint32_t capP, n, par;
+  uint32_t cap[2][8];
+  uint32_t n, par;
   uint32_t zeros[8];         // zeros of plane p = C[(p+1)&7]: the child1 lists of plane p start there
   // Mailbox of the wave tail kernel (pinned, host-coherent; nullptr = leave at every query round):
   //   [0] device -> host: number of the query round whose queries are in Q / E / info
@@ -84,11 +87,14 @@ struct DecArgs {
   // on, the order in which the planes' queries lie in Q (4 bits each, first plane lowest), whether this children pass is
   // the round's last (it alone adds up the round)
   uint32_t pmask = 0xFFu, order = 0x76543210u, final = 1u;
+  // Rounds with more nodes than the query budget run plane group by plane group: the planes of the group whose queries share
+  // the query buffer now (the query bases count only these; each group's queries start at 0 -- below 2^32 by the budget, or a
+  // plane's n / 2 + 2 nodes where one plane alone is more than the budget)
+  uint32_t gmask = 0xFFu;
+  uint64_t ecap = ~0ull;     // escape records the buffer E holds (dec_tiles_kernel<1> checks)
 };
 
-__device__ __forceinline__ Node *dec_nodes(const DecArgs &a, uint32_t par, uint32_t p) {
-  return a.nodes + ((size_t)(par * 8u + p)) * a.capP;
-}
+__device__ __forceinline__ Node *dec_nodes(const DecArgs &a, uint32_t par, uint32_t p) { return a.list[par][p]; }
 
 __device__ __forceinline__ void dec_tile_prefix(const DecArgs &a, uint32_t tp[9]) {
   uint32_t acc = 0;
@@ -206,7 +212,7 @@ __global__ __launch_bounds__(K3_T) void dec_tiles_kernel(DecArgs a) {
       const uint32_t q = ti * K3_TILE + (uint32_t)it * K3_T + tid;
       valid[it] = q < M ? 1u : 0u;
       const uint32_t qq = valid[it] ? q : ti * K3_TILE;
-      nd[it] = src[qq < c0n ? qq : (a.capP - 1u - (qq - c0n))];
+      nd[it] = src[qq < c0n ? qq : (a.cap[a.par][p] - 1u - (qq - c0n))];
     }
 #pragma unroll
     for (int it = 0; it < K3_NPT; ++it) {
@@ -219,6 +225,7 @@ __global__ __launch_bounds__(K3_T) void dec_tiles_kernel(DecArgs a) {
     uint32_t qr[K3_NPT], er[K3_NPT], d2[K3_NPT], tot[3];
     tile_ranks(isq, ise, zero, lds_cnt, qr, er, d2, tot);
     if (bad) a.ctl->err = 1;
+    if (MODE == 3 && ((a.ctl->ovf >> p) & 1u)) continue;        // the children do not fit: the host grows the list and runs this again
     if (MODE == 0) {
       if (tid == 0) { a.tilecnt[(size_t)tile * 4 + 2] = tot[0]; a.tilecnt[(size_t)tile * 4 + 3] = tot[1]; }
       continue;
@@ -237,7 +244,8 @@ __global__ __launch_bounds__(K3_T) void dec_tiles_kernel(DecArgs a) {
             a.Q[qb + qr[it]] = k | (ctxv << 5);
           } else {
             a.Q[qb + qr[it]] = kEscape;
-            a.E[eb + er[it]] = make_uint4(k, c1, c2, x);
+            if ((uint64_t)eb + er[it] < a.ecap) a.E[eb + er[it]] = make_uint4(k, c1, c2, x);
+            else a.ctl->err = 1;                                 // (more escapes than disjoint nodes of >= 32 positions: not an archive of ours)
           }
         }
       continue;
@@ -265,7 +273,7 @@ __global__ __launch_bounds__(K3_T) void dec_tiles_kernel(DecArgs a) {
 #pragma unroll
     for (int it = 0; it < K3_NPT; ++it) {
       if (has0[it]) dst[o0 + r0[it]] = c0[it];
-      if (has1[it]) dst[a.capP - 1u - (o1 + r1[it])] = c1[it];
+      if (has1[it]) dst[a.cap[a.par ^ 1u][(p + 1u) & 7u] - 1u - (o1 + r1[it])] = c1[it];
       if (valid[it] && !cl[it].bad) R[nd[it].s + nd[it].x0] = rval[it];        // ranks[i].set(s + _x0, s1 + _1x0) :1277,1285,1350
     }
   }
@@ -333,29 +341,28 @@ __global__ __launch_bounds__(1024) void dec_scan_kernel(DecArgs a) {
         a.info->ebase[q] = eacc;
         a.info->etot[q] = pt[q][3];
       }
-      acc += pt[q][2];
-      eacc += pt[q][3];
+      if ((a.gmask >> q) & 1u) { acc += pt[q][2]; eacc += pt[q][3]; }   // (32 bits: a group's queries are bounded, see DecArgs::gmask)
     }
-    a.info->cur_nodes = (uint32_t)curn;
+    a.info->cur_nodes = curn;
     a.info->nodes_total = ctl->nodes_total;
     __threadfence_system();
     a.info->err = ctl->err;
   } else {
     uint64_t nextn = 0;
-    bool ovf = false;
+    uint32_t ovf = 0;
     for (uint32_t q = 0; q < 8; ++q) {
       const uint32_t qn = (q + 1u) & 7u;
       if ((a.pmask >> q) & 1u) {
         ctl->cnt[a.par ^ 1u][qn][0] = pt[q][0];
         ctl->cnt[a.par ^ 1u][qn][1] = pt[q][1];
-        if ((uint64_t)pt[q][0] + pt[q][1] > a.capP) ovf = true;
+        if ((uint64_t)pt[q][0] + pt[q][1] > a.cap[a.par ^ 1u][qn]) ovf |= 1u << q;
       }
       nextn += (uint64_t)pt[q][0] + pt[q][1];
     }
-    if (ovf && !ctl->err) ctl->err = 2;
+    ctl->ovf |= ovf;
     if (a.final) {                                               // (every plane's totals are this round's by now)
       ctl->nodes_total += curn;
-      ctl->next_nodes = (uint32_t)nextn;
+      ctl->next_nodes = nextn;
     }
   }
 }
@@ -416,7 +423,7 @@ __global__ __launch_bounds__(K3_T) void dec_small_kernel(DecArgs a) {
     const uint32_t q = ti * K3_TILE + (uint32_t)it * K3_T + tid;
     valid[it] = q < M ? 1u : 0u;
     const uint32_t qq = valid[it] ? q : ti * K3_TILE;
-    nd[it] = src[qq < c0n ? qq : (a.capP - 1u - (qq - c0n))];
+    nd[it] = src[qq < c0n ? qq : (a.cap[a.par][p] - 1u - (qq - c0n))];
   }
 #pragma unroll
   for (int it = 0; it < K3_NPT; ++it) {
@@ -485,10 +492,12 @@ __global__ __launch_bounds__(K3_T) void dec_small_kernel(DecArgs a) {
       }
   } else {
     Node *dst = dec_nodes(a, a.par ^ 1u, (p + 1u) & 7u);
+    const uint32_t dcap = a.cap[a.par ^ 1u][(p + 1u) & 7u];
 #pragma unroll
     for (int it = 0; it < K3_NPT; ++it) {
-      if (has0[it]) dst[o0 + r0[it]] = c0[it];
-      if (has1[it]) dst[a.capP - 1u - (o1 + r1[it])] = c1[it];
+      // (the host runs this kernel only where twice the round's nodes fit every list: the bounds never bite)
+      if (has0[it] && o0 + r0[it] < dcap) dst[o0 + r0[it]] = c0[it];
+      if (has1[it] && o1 + r1[it] < dcap) dst[dcap - 1u - (o1 + r1[it])] = c1[it];
       if (valid[it] && !cl[it].bad) R[nd[it].s + nd[it].x0] = rval[it];
     }
   }
@@ -524,7 +533,7 @@ __global__ __launch_bounds__(K3_T) void dec_small_kernel(DecArgs a) {
       a.info->ebase[q] = eacc; a.info->etot[q] = te;
       acc += tq; eacc += te;
     }
-    a.info->cur_nodes = (uint32_t)curn;
+    a.info->cur_nodes = curn;
     a.info->nodes_total = ctl->nodes_total;
     __threadfence_system();
     a.info->err = ctl->err;
@@ -536,11 +545,11 @@ __global__ __launch_bounds__(K3_T) void dec_small_kernel(DecArgs a) {
       ctl->cnt[a.par ^ 1u][qn][0] = t0;
       ctl->cnt[a.par ^ 1u][qn][1] = t1;
       nextn += (uint64_t)t0 + t1;
-      if ((uint64_t)t0 + t1 > a.capP) ovf = true;
+      if ((uint64_t)t0 + t1 > a.cap[a.par ^ 1u][qn]) ovf = true;
     }
     if (ovf && !ctl->err) ctl->err = 2;
     ctl->nodes_total += curn;
-    ctl->next_nodes = (uint32_t)nextn;
+    ctl->next_nodes = nextn;
   }
 }
 
@@ -590,7 +599,7 @@ __global__ __launch_bounds__(DT_T) void dec_tail_kernel(DecArgs a, uint32_t max_
 #pragma unroll
     for (int k = 1; k < 8; ++k) p += (q >= off[k]) ? 1u : 0u;
     const uint32_t i = q - off[p], c0 = cnt[par][p][0];
-    buf[0][q] = dec_nodes(a, par, p)[i < c0 ? i : (a.capP - 1u - (i - c0))];
+    buf[0][q] = dec_nodes(a, par, p)[i < c0 ? i : (a.cap[par][p] - 1u - (i - c0))];
   }
   uint64_t nodes_total = ctl->nodes_total;
   uint32_t why = 0;
@@ -773,7 +782,7 @@ __global__ __launch_bounds__(DT_T) void dec_tail_kernel(DecArgs a, uint32_t max_
 #pragma unroll
     for (int k = 1; k < 8; ++k) p += (q >= off[k]) ? 1u : 0u;
     const uint32_t i = q - off[p], c0 = cnt[par][p][0];
-    dec_nodes(a, par, p)[i < c0 ? i : (a.capP - 1u - (i - c0))] = buf[cur][q];
+    dec_nodes(a, par, p)[i < c0 ? i : (a.cap[par][p] - 1u - (i - c0))] = buf[cur][q];
   }
   if (tid < 16) ctl->cnt[par][tid >> 1][tid & 1] = cnt[par][tid >> 1][tid & 1];
   if (tid == 0) {
@@ -820,7 +829,7 @@ __global__ __launch_bounds__(64) void dec_tail64_kernel(DecArgs a, uint32_t max_
       const uint32_t m = cnt[p][0] + cnt[p][1];
       if (lane >= acc && lane < acc + m) {
         const uint32_t i = lane - acc;
-        nd = dec_nodes(a, par, p)[i < cnt[p][0] ? i : (a.capP - 1u - (i - cnt[p][0]))];
+        nd = dec_nodes(a, par, p)[i < cnt[p][0] ? i : (a.cap[par][p] - 1u - (i - cnt[p][0]))];
         pl = p;
       }
       acc += m;
@@ -929,7 +938,7 @@ __global__ __launch_bounds__(64) void dec_tail64_kernel(DecArgs a, uint32_t max_
       const uint32_t m = cnt[p][0] + cnt[p][1];
       if (lane >= acc && lane < acc + m && lane < total) {
         const uint32_t i = lane - acc;
-        dec_nodes(a, par, p)[i < cnt[p][0] ? i : (a.capP - 1u - (i - cnt[p][0]))] = nd;
+        dec_nodes(a, par, p)[i < cnt[p][0] ? i : (a.cap[par][p] - 1u - (i - cnt[p][0]))] = nd;
       }
       acc += m;
     }
@@ -1432,12 +1441,12 @@ int dec_host_tail(bce_hip_ctx *c, const DecArgs &a, const DecCtl &ctl, std::vect
   BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
   for (uint32_t p = 0; p < 8; ++p) {
     const uint32_t c0 = ctl.cnt[par][p][0], c1 = ctl.cnt[par][p][1];
-    const Node *base = a.nodes + ((size_t)(par * 8u + p)) * a.capP;
+    const Node *base = a.list[par][p];
     cur[p][0].resize(c0);
     if (c0) BCE_HIP_TRY(c, hipMemcpy(cur[p][0].data(), base, (size_t)c0 * sizeof(Node), hipMemcpyDeviceToHost));
     cur[p][1].resize(c1);
     if (c1) {
-      BCE_HIP_TRY(c, hipMemcpy(cur[p][1].data(), base + (a.capP - c1), (size_t)c1 * sizeof(Node), hipMemcpyDeviceToHost));
+      BCE_HIP_TRY(c, hipMemcpy(cur[p][1].data(), base + (a.cap[par][p] - c1), (size_t)c1 * sizeof(Node), hipMemcpyDeviceToHost));
       for (uint32_t i = 0; i < c1 / 2; ++i) std::swap(cur[p][1][i], cur[p][1][c1 - 1u - i]);     // child1 lists grow downwards
     }
   }
@@ -1664,13 +1673,15 @@ int dec_host_tail(bce_hip_ctx *c, const DecArgs &a, const DecCtl &ctl, std::vect
   return BCE_HIP_OK;
 }
 
-// The node lists of a decode: at most n / 2 + 2 nodes each (the worst case: disjoint intervals of width >= 2), and to begin with an
-// eighth of n (what k3_begin starts the encoder with: text fills 0.02-0.03 n, random bytes 0.15-0.3 n) or what the context's
-// buffer already holds.  A round whose children would not fit stops the decode before it writes them (the scan of the
-// children pass checks; the one-launch kernel, which checks afterwards, is only used where twice the round's nodes fit) and
-// the decode starts again with twice the room (decompress_device_body).  Test knob 12 / BCE_HIP_CAPP_DIV as for the encoder.
+// The node lists of a decode: one per (parity, plane), at most n / 2 + 2 nodes each (the worst case: disjoint intervals of width
+// >= 2), and to begin with an eighth of n (what k3_begin starts the encoder with: text fills 0.02-0.03 n, random bytes 0.15-0.3 n)
+// or what the context's buffer already holds.  A round whose children would not fit a list does not write them (the scan of
+// the children pass checks; the one-launch kernel, which checks afterwards, is only used where twice the round's nodes fit):
+// that one list -- the next parity's list of plane q + 1, which only plane q's children pass writes -- is replaced by a larger
+// one and the pass runs again from the answers it already has (decompress_device_once: grow_lists).  Test knob 12 /
+// BCE_HIP_CAPP_DIV as for the encoder.
 uint32_t dec_full_capP(uint32_t n) { return (uint32_t)((uint64_t)n / 2 + 2); }
-uint32_t dec_capP(const bce_hip_ctx *c, uint32_t n, size_t archive_bytes) {
+uint32_t dec_capP(const bce_hip_ctx *c, uint32_t n, size_t archive_bytes, bool *forced_out) {
   const uint64_t full = dec_full_capP(n);
   uint64_t div = 8;
   bool forced = false;
@@ -1682,12 +1693,17 @@ uint32_t dec_capP(const bce_hip_ctx *c, uint32_t n, size_t archive_bytes) {
   if (!forced && cap < ((uint64_t)4 << 20)) cap = (uint64_t)4 << 20;
   // How full the lists get goes with how well the input compresses -- text (archive = 0.23 n) fills 0.03 n per list, random
   // bytes (1.0 n) 0.2-0.3 n -- and the archive's size is known before the first round: 0.25 x archive bytes nodes per list
-  // spares a high-entropy archive the decodes that run out of room and start again (1.5 * 10^9 random bytes: one of 40 s).
+  // spares a high-entropy archive most of the lists that grow in the middle of a round.
   if (!forced) { const uint64_t by_ratio = (uint64_t)(0.25 * (double)archive_bytes) + 4096; if (by_ratio > cap) cap = by_ratio; }
-  const uint64_t held = c->nlist[0].cap / (16 * sizeof(Node));
-  if (held > cap && !forced) cap = held;
-  if (c->dec_cap_next > cap) cap = c->dec_cap_next;             // (a decode that ran out of room: this much the next time)
+  *forced_out = forced;
   return (uint32_t)(cap < full ? cap : full);
+}
+
+// The query budget: the nodes whose queries one pass of a round holds (test knob 13; at least DT_CAP, so that the rounds the
+// tail kernels hand back with their answers -- at most DT_CAP nodes -- are never split).
+uint64_t dec_budget(const bce_hip_ctx *c) {
+  if (!c->dbg_dec_budget) return (uint64_t)1 << 30;
+  return c->dbg_dec_budget > DT_CAP ? c->dbg_dec_budget : DT_CAP;
 }
 
 }  // namespace
@@ -1706,20 +1722,8 @@ extern "C" int bce_hip_decompress_device(bce_hip_ctx *c, const uint8_t *archive,
 static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t len, uint8_t *out, size_t cap, size_t *out_len);
 static int decompress_device_body(bce_hip_ctx *c, const uint8_t *archive, size_t len, uint8_t *out, size_t cap, size_t *out_len) {
   if (!c) return BCE_HIP_E_ARG;
-  c->dec_cap_next = 0;
-  for (;;) {
-    c->dec_list_overflow = false;
-    const int rc = decompress_device_once(c, archive, len, out, cap, out_len);
-    if (rc != BCE_HIP_E_OVERFLOW || !c->dec_list_overflow) { c->dec_cap_next = 0; return rc; }
-    // a round did not fit the node lists (nothing of it was written): the same decode again with twice the room
-    const uint32_t full = dec_full_capP((uint32_t)*out_len);
-    if (c->capP >= full) { c->dec_cap_next = 0; return rc; }
-    c->dec_cap_next = (uint64_t)c->capP * 2 < full ? (uint64_t)c->capP * 2 : full;
-    c->dec_restarts++;
-    if (getenv("BCE_DEC_TIMING") || getenv("BCE_ALLOC_TRACE")) fprintf(stderr, "gpu decode: a round does not fit the node lists of %u nodes: once more with %llu\n", c->capP, (unsigned long long)c->dec_cap_next);
-    (void)hipDeviceSynchronize();
-    c->err[0] = 0;
-  }
+  struct PartEnd { bce_hip_ctx *c; ~PartEnd() { c->dec_part = 0; } } part_end{c};
+  return decompress_device_once(c, archive, len, out, cap, out_len);
 }
 static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t len, uint8_t *out, size_t cap, size_t *out_len) {
   if (!c || !archive || !out_len) return BCE_HIP_E_ARG;
@@ -1740,10 +1744,26 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
 
   // ---- buffers ----
   const size_t rstride = (size_t)n + 1;
-  c->capP = dec_capP(c, n, len);
-  BCE_TRY(ensure(c, c->nlist[0], (size_t)16 * c->capP * sizeof(Node)));
+  c->dec_part = 1;
+  DecArgs a;
+  const uint32_t full_cap = dec_full_capP(n);
+  uint32_t max_cap = 0;
+  {
+    bool forced = false;
+    const uint32_t start = dec_capP(c, n, len, &forced);
+    for (int par = 0; par < 2; ++par)
+      for (int p = 0; p < 8; ++p) {
+        uint64_t lc = start;
+        const uint64_t held = c->dlist[par][p].cap / sizeof(Node);
+        if (!forced && held > lc) lc = held < full_cap ? held : full_cap;
+        BCE_TRY(ensure(c, c->dlist[par][p], (size_t)lc * sizeof(Node)));
+        a.cap[par][p] = (uint32_t)lc;
+        a.list[par][p] = c->dlist[par][p].as<Node>();
+        if (lc > max_cap) max_cap = (uint32_t)lc;
+      }
+  }
   BCE_TRY(ensure(c, c->ctl, sizeof(DecCtl) > sizeof(EnumCtl) ? sizeof(DecCtl) : sizeof(EnumCtl)));
-  const size_t max_tiles = (size_t)8 * ((c->capP + K3_TILE - 1) / K3_TILE + 1);
+  const size_t max_tiles = (size_t)8 * ((max_cap + K3_TILE - 1) / K3_TILE + 1);
   BCE_TRY(ensure(c, c->tilecnt, max_tiles * 16));
   BCE_TRY(ensure(c, c->tileoff, max_tiles * 16));
   DevBuf &Rbuf = c->dfs;                                        // 8 x (n + 1) boundary ranks
@@ -1759,7 +1779,7 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
     BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));            // stack temporaries
     if (hd.C[i] && n - hd.C[i]) {                               // :1214-1216
       const Node root = {0u, hd.C[i], n - hd.C[i]};
-      BCE_HIP_TRY(c, hipMemcpyAsync(c->nlist[0].as<Node>() + (size_t)i * c->capP, &root, sizeof root, hipMemcpyHostToDevice, c->stream));
+      BCE_HIP_TRY(c, hipMemcpyAsync(a.list[0][i], &root, sizeof root, hipMemcpyHostToDevice, c->stream));
       BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
       ctl.cnt[0][i][0] = 1;
     }
@@ -1778,18 +1798,24 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
   uint32_t dbg_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   double t_split = 0, ts_issue = 0, ts_first = 0, ts_lanes = 0, ts_wait = 0, ts_rb = 0;
   const bool no_split = getenv("BCE_DEC_NO_SPLIT") != nullptr;
+  const uint64_t budget = dec_budget(c);                       // nodes whose queries one pass of a round holds (see the plane groups)
+  uint64_t grouped_rounds = 0, list_grows = 0;
+  const bool trace_mem = timing || getenv("BCE_ALLOC_TRACE") != nullptr;
+  size_t peak_used = 0;                                        // device memory in use, sampled after every allocation stage (BCE_DEC_TIMING / BCE_ALLOC_TRACE)
+  auto sample_mem = [&] {
+    size_t fr = 0, tot = 0;
+    if (trace_mem && hipMemGetInfo(&fr, &tot) == hipSuccess && tot - fr > peak_used) peak_used = tot - fr;
+  };
   BCE_TRY(pin_info.ensure(c, sizeof(DecInfo), 4096));          // (a few words: not the 16 MB the query buffers start with -- 4 ms of pinning per decode)
   DecInfo *info = static_cast<DecInfo *>(pin_info.p);
   memset(info, 0, sizeof *info);
 
-  DecArgs a;
   a.ctl = c->ctl.as<DecCtl>();
   a.info = info;                                                // pinned host memory is device-accessible at the same address
-  a.nodes = c->nlist[0].as<Node>();
   a.R = R;
   a.tilecnt = c->tilecnt.as<uint32_t>();
   a.tileoff = c->tileoff.as<uint32_t>();
-  a.capP = c->capP; a.n = n;
+  a.n = n;
   for (int p = 0; p < 8; ++p) a.zeros[p] = hd.C[(p + 1) & 7];
   {
     PlaneCfg hcfg[8];
@@ -1945,7 +1971,7 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
         BCE_TRY(read_back(c, done, d_rounds, 20));
         BCE_TRY(read_back(c, &ctl, c->ctl.p, sizeof ctl));
         BCE_HIP_TRY(c, hipGetLastError());
-        if (getenv("BCE_DEC_TRACE")) fprintf(stderr, "tail: round %u wave %d resume %d -> done %u why %u next %u\n", round, (int)wave, (int)resume, done[0], done[1], ctl.next_nodes);
+        if (getenv("BCE_DEC_TRACE")) fprintf(stderr, "tail: round %u wave %d resume %d -> done %u why %u next %llu\n", round, (int)wave, (int)resume, done[0], done[1], (unsigned long long)ctl.next_nodes);
         round += done[0]; tail_rounds += done[0];
         if (wave) { ++launches_wave; rounds_wave += done[0]; nodes_wave += ctl.nodes_total - nodes_total; t_wave += now_s() - t_launch; }
         else { ++launches_wg; rounds_wg += done[0]; nodes_wg += ctl.nodes_total - nodes_total; t_wg += now_s() - t_launch; }
@@ -1999,9 +2025,58 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
     }
     // Rounds of up to kDirectNodes nodes exchange their queries and answers through pinned host memory (as the tail kernels do):
     // the kernels write / read it over the bus, and the round is two launches and two syncs with no copy in between.
-    // (dec_small_kernel writes the children before it knows their number: only where twice the round's nodes fit a list)
-    const bool small_round = cur_nodes <= DS_MAXNODES && !no_small && 2ull * cur_nodes <= c->capP;
+    // (dec_small_kernel writes the children before it knows their number: only where twice the round's nodes fit every list)
+    uint32_t min_next_cap = ~0u;
+    for (int p = 0; p < 8; ++p) min_next_cap = std::min(min_next_cap, a.cap[(round & 1u) ^ 1u][p]);
+    const bool small_round = cur_nodes <= DS_MAXNODES && !no_small && 2ull * cur_nodes <= min_next_cap && cur_nodes <= budget;
     const bool direct = small_round && cur_nodes <= kDirectNodes && !answered_pending;
+    const bool small = small_round;                                // one launch per pass (dec_small_kernel)
+    const bool lanes = !small && !answered_pending && !no_split;   // six launches, plane by plane (see below)
+    uint64_t pnodes[8];
+    for (int p = 0; p < 8; ++p) pnodes[p] = (uint64_t)ctl.cnt[round & 1u][p][0] + ctl.cnt[round & 1u][p][1];
+    {
+      // the tile arrays for this round's lists (a list that grew may hold more tiles than they were made for)
+      uint64_t tiles = 8;
+      for (int p = 0; p < 8; ++p) tiles += (pnodes[p] + K3_TILE - 1) / K3_TILE;
+      BCE_TRY(ensure(c, c->tilecnt, (size_t)tiles * 16));
+      BCE_TRY(ensure(c, c->tileoff, (size_t)tiles * 16));
+      a.tilecnt = c->tilecnt.as<uint32_t>();
+      a.tileoff = c->tileoff.as<uint32_t>();
+    }
+    uint32_t ord[8] = {0, 1, 2, 3, 4, 5, 6, 7};
+    if (lanes) {
+      // (the bulk of the queries moves from plane p to plane p + 1 with every round -- a node's children are the next plane's
+      //  nodes -- and the busiest decoder with it: plane p is as busy as plane p - 1 was last round.  Node counts say less:
+      //  how many of a plane's nodes are forced differs from plane to plane.)
+      uint64_t weight[8];
+      for (int q = 0; q < 8; ++q) weight[q] = ((uint64_t)prev_qtot[(q + 7) & 7] << 1) + (pnodes[q] ? 1u : 0u);
+      std::stable_sort(ord, ord + 8, [&](uint32_t x, uint32_t y) { return weight[x] > weight[y]; });
+    }
+    // Plane groups: consecutive runs of `ord` (busiest first in the six-launch rounds, plane order otherwise) with at most `budget`
+    // nodes together -- one group of all eight planes when the round is within the budget, which is then run exactly as it
+    // always was.  A plane alone may hold more than the budget (up to n / 2 + 2 nodes): it is a group of its own.
+    uint32_t gm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int ng = 0;
+    uint64_t gmax = 0, emax = 0;
+    {
+      uint64_t acc = 0;
+      for (int i = 0; i < 8; ++i) {
+        const uint32_t p = ord[i];
+        if (ng == 0 || acc + pnodes[p] > budget) { gm[ng++] = 0; acc = 0; }
+        gm[ng - 1] |= 1u << p;
+        acc += pnodes[p];
+      }
+      for (int g = 0; g < ng; ++g) {
+        uint64_t gn = 0;
+        for (int p = 0; p < 8; ++p) if ((gm[g] >> p) & 1u) gn += pnodes[p];
+        // an escape query (k > 31) needs a node of at least 32 positions, and a plane's nodes are disjoint intervals of [0, n]:
+        // at most n / 32 + 1 of them per plane, however many nodes the group holds
+        const uint64_t ebound = std::min<uint64_t>(gn, (uint64_t)__builtin_popcount(gm[g]) * ((uint64_t)n / 32 + 1));
+        gmax = std::max(gmax, gn);
+        emax = std::max(emax, ebound);
+      }
+    }
+    if (ng > 1 && answered_pending) { snprintf(c->err, sizeof c->err, "decode: a resumed round of %llu nodes is over the query budget", (unsigned long long)cur_nodes); return BCE_HIP_E_INTERNAL; }
     if (direct) {
       BCE_TRY(pin_q.ensure(c, (size_t)(cur_nodes + 16) * 4));
       BCE_TRY(pin_e.ensure(c, (size_t)(cur_nodes + 16) * sizeof(uint4)));
@@ -2009,130 +2084,198 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
       a.Q = static_cast<uint32_t *>(pin_q.p);
       a.E = static_cast<uint4 *>(pin_e.p);
       a.res = static_cast<const uint32_t *>(pin_res.p);
+      a.ecap = cur_nodes + 16;
     } else {
-      BCE_TRY(ensure(c, Qbuf, (size_t)(cur_nodes + 16) * 4));
-      BCE_TRY(ensure(c, Ebuf, (size_t)(cur_nodes + 16) * sizeof(uint4)));
-      BCE_TRY(ensure(c, Rsbuf, (size_t)(cur_nodes + 16) * 4));
+      BCE_TRY(ensure(c, Qbuf, (size_t)(gmax + 16) * 4));
+      BCE_TRY(ensure(c, Ebuf, (size_t)(emax + 16) * sizeof(uint4)));
+      BCE_TRY(ensure(c, Rsbuf, (size_t)(gmax + 16) * 4));
       a.Q = Qbuf.as<uint32_t>();
       a.E = Ebuf.as<uint4>();
       a.res = Rsbuf.as<uint32_t>();
+      a.ecap = emax + 16;
     }
+    if (ng > 1) { ++grouped_rounds; c->dec_split_rounds++; }
+    if (cur_nodes >= (1u << 20)) sample_mem();
     uint64_t want = (cur_nodes + K3_TILE - 1) / K3_TILE + 8;
     const uint32_t grid = (uint32_t)(want < 2048 ? want : 2048);
     uint32_t hb = 0;
     const double t_round0 = timing ? now_s() : 0.0;
     if (timing) { while ((2ull << hb) <= cur_nodes && hb < 31) ++hb; wide_hist[hb]++; wide_nodes[hb] += cur_nodes; }
-    const bool small = small_round;                                // one launch per pass (dec_small_kernel)
     a.round = round;
-    if (!small && !answered_pending && !no_split) {
+    // A children pass found that the children of the planes in `ovf` do not fit their lists (it wrote none of them; the counts
+    // are in the control block): each such list -- plane q + 1's of the next parity, which only plane q's pass writes, so it
+    // holds nothing yet -- is replaced by one of 1.25 x the need (exactly the need if the device has no more room, after the
+    // other phases' buffers have gone back), and the pass runs again from the answers already in the answer buffer.  A plane's
+    // decoder is never asked twice.
+    auto grow_lists = [&](uint32_t ovf) -> int {
+      const uint32_t out = (round & 1u) ^ 1u;
+      BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+      for (uint32_t q = 0; q < 8; ++q) {
+        if (!((ovf >> q) & 1u)) continue;
+        const uint32_t qn = (q + 1u) & 7u;
+        const uint64_t need = (uint64_t)ctl.cnt[out][qn][0] + ctl.cnt[out][qn][1];
+        const uint32_t had = a.cap[out][qn];
+        if (need <= had || need > full_cap) {
+          snprintf(c->err, sizeof c->err, "decode: round %u reports a list of %llu nodes (it holds %u, n = %u)", round, (unsigned long long)need, had, n);
+          return BCE_HIP_E_INTERNAL;
+        }
+        release(c->dlist[out][qn]);
+        a.list[out][qn] = nullptr; a.cap[out][qn] = 0;
+        uint64_t want = need + need / 4;
+        if (want > full_cap) want = full_cap;
+        int rc = ensure(c, c->dlist[out][qn], (size_t)want * sizeof(Node));
+        if (rc == BCE_HIP_E_NOMEM) {
+          want = need;
+          rc = ensure(c, c->dlist[out][qn], (size_t)want * sizeof(Node));
+        }
+        if (rc != BCE_HIP_OK) {
+          if (rc == BCE_HIP_E_NOMEM) snprintf(c->err, sizeof c->err, "decode: no device memory for a node list of %llu nodes (round %u, n = %u)", (unsigned long long)need, round, n);
+          return rc;
+        }
+        a.list[out][qn] = c->dlist[out][qn].as<Node>();
+        a.cap[out][qn] = (uint32_t)want;
+        c->dec_list_grows++;
+        ++list_grows;
+        if (timing || getenv("BCE_ALLOC_TRACE"))
+          fprintf(stderr, "gpu decode: round %u does not fit the node lists: the children of plane %u (%llu nodes) in plane %u's list of %u (parity %u), grown in place to %llu\n",
+                  round, q, (unsigned long long)need, qn, had, out, (unsigned long long)want);
+      }
+      BCE_HIP_TRY(c, hipMemsetAsync(&a.ctl->ovf, 0, sizeof(uint32_t), c->stream));
+      return BCE_HIP_OK;
+    };
+    // after the children passes of a group, with `ctl` just read back: errors, and the lists that must grow
+    auto settle_group = [&]() -> int {
+      for (int tries = 0;; ++tries) {
+        if (ctl.err) {
+          if (ctl.err == 4) snprintf(c->err, sizeof c->err, "decode: a two-launch round waited too long for a predecessor tile (round %u)", round);
+          else if (ctl.err == 2) snprintf(c->err, sizeof c->err, "decode: node list overflow in a one-launch round (round %u)", round);
+          else snprintf(c->err, sizeof c->err, "decode: inconsistent archive (round %u)", round);
+          return BCE_HIP_E_INTERNAL;
+        }
+        if (!ctl.ovf) return BCE_HIP_OK;
+        if (tries == 2) { snprintf(c->err, sizeof c->err, "decode: node lists still too small after growing (round %u)", round); return BCE_HIP_E_INTERNAL; }
+        const uint32_t ovf = ctl.ovf;
+        BCE_TRY(grow_lists(ovf));
+        const uint32_t pm = a.pmask, fin = a.final;
+        a.pmask = ovf;
+        a.final = 0;                                               // (the round's totals were added up by its last pass already)
+        hipLaunchKernelGGL((dec_tiles_kernel<2>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+        hipLaunchKernelGGL((dec_scan_kernel<false>), dim3(8), dim3(1024), 0, c->stream, a);
+        hipLaunchKernelGGL((dec_tiles_kernel<3>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+        a.pmask = pm; a.final = fin;
+        BCE_TRY(read_back(c, &ctl, c->ctl.p, sizeof ctl));
+        BCE_HIP_TRY(c, hipGetLastError());
+      }
+    };
+    if (lanes) {
       // A six-launch round plane by plane.  The round's time is the busiest planes' sequential decoders (text: planes 0
       // and 1 hold half of all queries) with the query passes in front of them and the children passes behind.  The planes
       // of a round do not meet (plane p's children are plane p + 1's nodes of the NEXT round), so each plane is a lane of
       // its own -- query pass, copy out, decoder, answers in, children pass -- and the lanes start in the order of their
       // node counts: the busiest decoder starts as soon as ITS queries are out and only its own children pass is
-      // left when it is done; everything else runs beside it.
+      // left when it is done; everything else runs beside it.  Over the query budget the lanes run group by group, each group
+      // with the whole query and answer buffers to itself.
       const double ts0 = now_s();
       for (int i = 0; i < 8; ++i) if (!ev.e[i]) BCE_HIP_TRY(c, hipEventCreateWithFlags(&ev.e[i], hipEventDisableTiming));
-      uint32_t ord[8] = {0, 1, 2, 3, 4, 5, 6, 7};
-      // (the bulk of the queries moves from plane p to plane p + 1 with every round -- a node's children are the next plane's
-      //  nodes -- and the busiest decoder with it: plane p is as busy as plane p - 1 was last round.  Node counts say less:
-      //  how many of a plane's nodes are forced differs from plane to plane.)
-      uint64_t weight[8];
-      for (int q = 0; q < 8; ++q) weight[q] = ((uint64_t)prev_qtot[(q + 7) & 7] << 1) + ((ctl.cnt[round & 1u][q][0] + ctl.cnt[round & 1u][q][1]) ? 1u : 0u);
-      std::stable_sort(ord, ord + 8, [&](uint32_t x, uint32_t y) { return weight[x] > weight[y]; });
       uint32_t order = 0;
       for (int i = 0; i < 8; ++i) order |= ord[i] << (4 * i);
-      BCE_TRY(pin_q.ensure(c, (size_t)(cur_nodes + 16) * 4));      // (a plane's queries lie at its base: the bases are exact, the size is a bound)
-      BCE_TRY(pin_res.ensure(c, (size_t)(cur_nodes + 16) * 4));
+      BCE_TRY(pin_q.ensure(c, (size_t)(gmax + 16) * 4));          // (a plane's queries lie at its base: the bases are exact, the size is a bound)
+      BCE_TRY(pin_res.ensure(c, (size_t)(gmax + 16) * 4));
       a.order = order;
       a.final = 0;
-      auto ask = [&](int i) -> int {                               // the query pass of lane i
-        a.pmask = 1u << ord[i];
-        a.final = 0;
-        hipLaunchKernelGGL((dec_tiles_kernel<0>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-        hipLaunchKernelGGL((dec_scan_kernel<true>), dim3(8), dim3(1024), 0, c->stream, a);
-        hipLaunchKernelGGL((dec_tiles_kernel<1>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-        BCE_HIP_TRY(c, hipEventRecord(ev.e[i], c->stream));
-        return BCE_HIP_OK;
-      };
-      BCE_TRY(ask(0));                                             // (launching costs the host ~60 us a lane: the busiest decoder does not wait for all eight)
-      BCE_TRY(ask(1));
-      const double tsa = now_s();
-      ts_issue += tsa - ts0;
-      QueryPool::Job jobs[8] = {};
-      struct Settle {                                              // no decoder outlives this round (its buffers, an early return)
-        QueryPool &pool; uint32_t mask;
-        ~Settle() { if (mask) pool.wait(mask); }
-      } settle{pool, 0u};
       uint64_t qtotal = 0;
       uint32_t new_qtot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      uint32_t launched = 0, children_done = 0;                    // planes whose decoders run / whose children pass is queued
-      auto children = [&](uint32_t p, bool last) -> int {
-        if (jobs[p].cnt) BCE_HIP_TRY(c, hipMemcpyAsync(Rsbuf.as<uint32_t>() + (jobs[p].r - static_cast<uint32_t *>(pin_res.p)), jobs[p].r, (size_t)jobs[p].cnt * 4, hipMemcpyHostToDevice, c->stream));
-        a.pmask = 1u << p;
-        a.final = last ? 1u : 0u;
-        hipLaunchKernelGGL((dec_tiles_kernel<2>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-        hipLaunchKernelGGL((dec_scan_kernel<false>), dim3(8), dim3(1024), 0, c->stream, a);
-        hipLaunchKernelGGL((dec_tiles_kernel<3>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-        children_done |= 1u << p;
-        return BCE_HIP_OK;
-      };
-      for (int i = 0; i < 8; ++i) {
-        const uint32_t p = ord[i];
-        if (i > 0 && i + 1 < 8) BCE_TRY(ask(i + 1));               // one lane ahead of the one being waited for
-        BCE_HIP_TRY(c, hipEventSynchronize(ev.e[i]));
-        if (i == 0) ts_first += now_s() - tsa;
-        const DecInfo in = *info;                                  // (plane p's fields and those of the planes before it; the rest are being written)
-        if (in.err == 2) { snprintf(c->err, sizeof c->err, "decode: node list overflow (capP=%u)", c->capP); c->dec_list_overflow = true; return BCE_HIP_E_OVERFLOW; }
-        if (in.err) { snprintf(c->err, sizeof c->err, "decode: inconsistent archive (round %u)", round); return BCE_HIP_E_INTERNAL; }
-        const uint32_t qn = in.qtot[p], en = in.etot[p], qb = in.qbase[p], eb = in.ebase[p];
-        new_qtot[p] = qn;
-        qtotal += qn;
-        if ((size_t)eb + en + 1 > pin_e.cap / sizeof(uint4)) {     // escape records are few, their number is not known ahead: grow between decoders
-          if (settle.mask) { pool.wait(settle.mask); }
-          BCE_TRY(pin_e.ensure(c, 2 * ((size_t)eb + en + 1) * sizeof(uint4)));
+      uint32_t launched = 0;                                       // planes whose decoders ran (all groups)
+      int lo = 0;                                                  // the group's first lane in `ord`
+      for (int g = 0; g < ng; ++g) {
+        const bool last_group = g + 1 == ng;
+        const uint32_t gmask = gm[g];
+        const int L = __builtin_popcount(gmask);
+        a.gmask = gmask;
+        auto ask = [&](int i) -> int {                             // the query pass of lane i of the group
+          a.pmask = 1u << ord[lo + i];
+          a.final = 0;
+          hipLaunchKernelGGL((dec_tiles_kernel<0>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+          hipLaunchKernelGGL((dec_scan_kernel<true>), dim3(8), dim3(1024), 0, c->stream, a);
+          hipLaunchKernelGGL((dec_tiles_kernel<1>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+          BCE_HIP_TRY(c, hipEventRecord(ev.e[i], c->stream));
+          return BCE_HIP_OK;
+        };
+        BCE_TRY(ask(0));                                           // (launching costs the host ~60 us a lane: the busiest decoder does not wait for all eight)
+        if (L > 1) BCE_TRY(ask(1));
+        const double tsa = now_s();
+        if (g == 0) ts_issue += tsa - ts0;
+        QueryPool::Job jobs[8] = {};
+        struct Settle {                                            // no decoder outlives this group (its buffers, an early return)
+          QueryPool &pool; uint32_t mask;
+          ~Settle() { if (mask) pool.wait(mask); }
+        } settle{pool, 0u};
+        uint32_t glaunched = 0, children_done = 0;                 // planes whose decoders run / whose children pass is queued
+        auto children = [&](uint32_t p, bool last) -> int {
+          if (jobs[p].cnt) BCE_HIP_TRY(c, hipMemcpyAsync(Rsbuf.as<uint32_t>() + (jobs[p].r - static_cast<uint32_t *>(pin_res.p)), jobs[p].r, (size_t)jobs[p].cnt * 4, hipMemcpyHostToDevice, c->stream));
+          a.pmask = 1u << p;
+          a.final = last && last_group ? 1u : 0u;
+          hipLaunchKernelGGL((dec_tiles_kernel<2>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+          hipLaunchKernelGGL((dec_scan_kernel<false>), dim3(8), dim3(1024), 0, c->stream, a);
+          hipLaunchKernelGGL((dec_tiles_kernel<3>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+          children_done |= 1u << p;
+          return BCE_HIP_OK;
+        };
+        for (int i = 0; i < L; ++i) {
+          const uint32_t p = ord[lo + i];
+          if (i > 0 && i + 1 < L) BCE_TRY(ask(i + 1));             // one lane ahead of the one being waited for
+          BCE_HIP_TRY(c, hipEventSynchronize(ev.e[i]));
+          if (i == 0 && g == 0) ts_first += now_s() - tsa;
+          const DecInfo in = *info;                                // (plane p's fields and those of the planes before it; the rest are being written)
+          if (in.err) { snprintf(c->err, sizeof c->err, "decode: inconsistent archive (round %u)", round); return BCE_HIP_E_INTERNAL; }
+          const uint32_t qn = in.qtot[p], en = in.etot[p], qb = in.qbase[p], eb = in.ebase[p];
+          new_qtot[p] = qn;
+          qtotal += qn;
+          if ((size_t)eb + en + 1 > pin_e.cap / sizeof(uint4)) {   // escape records are few, their number is not known ahead: grow between decoders
+            if (settle.mask) { pool.wait(settle.mask); }
+            BCE_TRY(pin_e.ensure(c, 2 * ((size_t)eb + en + 1) * sizeof(uint4)));
+          }
+          if (qn) {
+            BCE_HIP_TRY(c, hipMemcpyAsync(static_cast<uint32_t *>(pin_q.p) + qb, a.Q + qb, (size_t)qn * 4, hipMemcpyDeviceToHost, c->copy_stream));
+            if (en) BCE_HIP_TRY(c, hipMemcpyAsync(static_cast<uint4 *>(pin_e.p) + eb, a.E + eb, (size_t)en * sizeof(uint4), hipMemcpyDeviceToHost, c->copy_stream));
+            BCE_HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
+            jobs[p] = QueryPool::Job{static_cast<const uint32_t *>(pin_q.p) + qb, static_cast<const uint4 *>(pin_e.p) + eb, static_cast<uint32_t *>(pin_res.p) + qb, qn};
+            pool.run_async(jobs, 1u << p);
+            settle.mask |= 1u << p;
+            glaunched |= 1u << p;
+          } else {
+            jobs[p] = QueryPool::Job{nullptr, nullptr, static_cast<uint32_t *>(pin_res.p) + qb, 0u};
+            BCE_TRY(children(p, i == L - 1 && (glaunched & ~children_done) == 0u));   // nothing to ask: its children pass at once (the round's last one only if nobody is out)
+          }
+          // decoders that have finished meanwhile: their children passes go out between the copies
+          const uint32_t fin = pool.done(glaunched & ~children_done);
+          for (uint32_t q = 0; q < 8; ++q)
+            if ((fin >> q) & 1u) { settle.mask &= ~(1u << q); BCE_TRY(children(q, i == L - 1 && (children_done | (1u << q)) == gmask)); }
         }
-        if (qn) {
-          BCE_HIP_TRY(c, hipMemcpyAsync(static_cast<uint32_t *>(pin_q.p) + qb, a.Q + qb, (size_t)qn * 4, hipMemcpyDeviceToHost, c->copy_stream));
-          if (en) BCE_HIP_TRY(c, hipMemcpyAsync(static_cast<uint4 *>(pin_e.p) + eb, a.E + eb, (size_t)en * sizeof(uint4), hipMemcpyDeviceToHost, c->copy_stream));
-          BCE_HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
-          jobs[p] = QueryPool::Job{static_cast<const uint32_t *>(pin_q.p) + qb, static_cast<const uint4 *>(pin_e.p) + eb, static_cast<uint32_t *>(pin_res.p) + qb, qn};
-          pool.run_async(jobs, 1u << p);
-          settle.mask |= 1u << p;
-          launched |= 1u << p;
-        } else {
-          jobs[p] = QueryPool::Job{nullptr, nullptr, static_cast<uint32_t *>(pin_res.p) + qb, 0u};
-          BCE_TRY(children(p, i == 7 && (launched & ~children_done) == 0u));   // nothing to ask: its children pass at once (the round's last one only if nobody is out)
+        const double tsb = now_s();
+        ts_lanes += tsb - tsa;
+        while (children_done != gmask) {
+          const uint32_t fin = pool.wait_any(glaunched & ~children_done);
+          for (uint32_t q = 0; q < 8; ++q)
+            if ((fin >> q) & 1u) { settle.mask &= ~(1u << q); BCE_TRY(children(q, (children_done | (1u << q)) == gmask)); }
         }
-        // decoders that have finished meanwhile: their children passes go out between the copies
-        const uint32_t fin = pool.done(launched & ~children_done);
-        for (uint32_t q = 0; q < 8; ++q)
-          if ((fin >> q) & 1u) { settle.mask &= ~(1u << q); BCE_TRY(children(q, i == 7 && (children_done | (1u << q)) == 0xFFu)); }
+        launched |= glaunched;
+        const double tsc = now_s();
+        ts_wait += tsc - tsb;
+        // (the next group reuses the query and answer buffers: this read-back also waits for the last copy of answers)
+        BCE_TRY(read_back(c, &ctl, c->ctl.p, sizeof ctl));
+        ts_rb += now_s() - tsc;
+        BCE_HIP_TRY(c, hipGetLastError());
+        BCE_TRY(settle_group());
+        lo += L;
       }
-      const double tsb = now_s();
-      ts_lanes += tsb - tsa;
-      while (children_done != 0xFFu) {
-        const uint32_t fin = pool.wait_any(launched & ~children_done);
-        for (uint32_t q = 0; q < 8; ++q)
-          if ((fin >> q) & 1u) { settle.mask &= ~(1u << q); BCE_TRY(children(q, (children_done | (1u << q)) == 0xFFu)); }
-      }
-      a.pmask = 0xFFu; a.order = 0x76543210u; a.final = 1u;
-      const double tsc = now_s();
+      a.pmask = 0xFFu; a.order = 0x76543210u; a.final = 1u; a.gmask = 0xFFu;
       if (timing) {
         double last = 0; int lastp = -1;
         for (int q = 0; q < 8; ++q) if (((launched >> q) & 1u) && pool.t_end[q] > last) { last = pool.t_end[q]; lastp = q; }
         if ((launched >> ord[0]) & 1u) { dbg_r[0] += pool.t_begin[ord[0]] - ts0; dbg_r[1] += pool.t_end[ord[0]] - ts0; }
         if (lastp >= 0) { dbg_r[2] += last - ts0; dbg_r[3] += pool.t_begin[lastp] - ts0; dbg_last[lastp]++; }
-        dbg_r[4] += tsc - ts0;
-      }
-      ts_wait += tsc - tsb;
-      BCE_TRY(read_back(c, &ctl, c->ctl.p, sizeof ctl));
-      ts_rb += now_s() - tsc;
-      BCE_HIP_TRY(c, hipGetLastError());
-      if (ctl.err) {
-        snprintf(c->err, sizeof c->err, ctl.err == 2 ? "decode: node list overflow (capP=%u)" : "decode: inconsistent archive (round %u)", ctl.err == 2 ? c->capP : round);
-        c->dec_list_overflow = ctl.err == 2;
-        return ctl.err == 2 ? BCE_HIP_E_OVERFLOW : BCE_HIP_E_INTERNAL;
+        dbg_r[4] += now_s() - ts0;
       }
       for (int q = 0; q < 8; ++q) prev_qtot[q] = new_qtot[q];
       ++split_rounds;
@@ -2145,75 +2288,82 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
       ++round;
       continue;
     }
-    if (small) {
-      hipLaunchKernelGGL((dec_small_kernel<true>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-      ++small_rounds;
-    } else {
-      hipLaunchKernelGGL((dec_tiles_kernel<0>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-      hipLaunchKernelGGL((dec_scan_kernel<true>), dim3(8), dim3(1024), 0, c->stream, a);
-      hipLaunchKernelGGL((dec_tiles_kernel<1>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-    }
-    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    BCE_HIP_TRY(c, hipGetLastError());
-    const DecInfo in = *info;
-    { const double t1 = now_s(); t_q += t1 - t0; t0 = t1; }
-    if (in.err == 2) { snprintf(c->err, sizeof c->err, "decode: node list overflow (capP=%u)", c->capP); c->dec_list_overflow = true; return BCE_HIP_E_OVERFLOW; }
-    if (in.err) { snprintf(c->err, sizeof c->err, "decode: inconsistent archive (round %u)", round); return BCE_HIP_E_INTERNAL; }
-    uint64_t qtotal = 0, etotal = 0;
-    for (int p = 0; p < 8; ++p) { qtotal += in.qtot[p]; etotal += in.etot[p]; prev_qtot[p] = in.qtot[p]; }
-    if (qtotal && answered_pending) {
-      // the tail kernel emitted exactly these queries (same order) and the decoders answered them: do not ask twice
-      BCE_HIP_TRY(c, hipMemcpyAsync(Rsbuf.p, pin_res.p, qtotal * 4, hipMemcpyHostToDevice, c->stream));
-    } else if (qtotal && direct) {
-      pool.Q = static_cast<const uint32_t *>(pin_q.p);
-      pool.E = static_cast<const uint4 *>(pin_e.p);
-      pool.res = static_cast<uint32_t *>(pin_res.p);
-      pool.run(in);
-      { const double t1 = now_s(); t_host += t1 - t0; t0 = t1; }
-    } else if (qtotal) {
-      BCE_TRY(pin_q.ensure(c, qtotal * 4));
-      BCE_TRY(pin_e.ensure(c, (etotal + 1) * sizeof(uint4)));
-      BCE_TRY(pin_res.ensure(c, qtotal * 4));
-      BCE_HIP_TRY(c, hipMemcpyAsync(pin_q.p, a.Q, qtotal * 4, hipMemcpyDeviceToHost, c->stream));
-      if (etotal) BCE_HIP_TRY(c, hipMemcpyAsync(pin_e.p, a.E, etotal * sizeof(uint4), hipMemcpyDeviceToHost, c->stream));
+    // One pass over all planes (or the planes of one group after the other): query pass, the decoders, children pass.
+    uint64_t round_q = 0;
+    for (int g = 0; g < ng; ++g) {
+      const bool last_group = g + 1 == ng;
+      a.pmask = a.gmask = gm[g];
+      a.final = last_group ? 1u : 0u;
+      if (small) {
+        hipLaunchKernelGGL((dec_small_kernel<true>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+        ++small_rounds;
+      } else {
+        hipLaunchKernelGGL((dec_tiles_kernel<0>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+        hipLaunchKernelGGL((dec_scan_kernel<true>), dim3(8), dim3(1024), 0, c->stream, a);
+        hipLaunchKernelGGL((dec_tiles_kernel<1>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+      }
       BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-      { const double t1 = now_s(); t_copy += t1 - t0; t0 = t1; }
-      pool.Q = static_cast<const uint32_t *>(pin_q.p);
-      pool.E = static_cast<const uint4 *>(pin_e.p);
-      pool.res = static_cast<uint32_t *>(pin_res.p);
-      pool.run(in);
-      { const double t1 = now_s(); t_host += t1 - t0; t0 = t1; }
-      BCE_HIP_TRY(c, hipMemcpyAsync(Rsbuf.p, pin_res.p, qtotal * 4, hipMemcpyHostToDevice, c->stream));
+      BCE_HIP_TRY(c, hipGetLastError());
+      DecInfo in = *info;
+      for (int p = 0; p < 8; ++p)                                  // (the query pass of a group writes its own planes' fields only)
+        if (!((gm[g] >> p) & 1u)) { in.qbase[p] = in.qtot[p] = in.ebase[p] = in.etot[p] = 0; }
+      { const double t1 = now_s(); t_q += t1 - t0; t0 = t1; }
+      if (in.err == 2) { snprintf(c->err, sizeof c->err, "decode: node list overflow in a one-launch round (round %u)", round); return BCE_HIP_E_INTERNAL; }
+      if (in.err) { snprintf(c->err, sizeof c->err, "decode: inconsistent archive (round %u)", round); return BCE_HIP_E_INTERNAL; }
+      uint64_t qtotal = 0, etotal = 0;
+      for (int p = 0; p < 8; ++p) { qtotal += in.qtot[p]; etotal += in.etot[p]; if ((gm[g] >> p) & 1u) prev_qtot[p] = in.qtot[p]; }
+      if (qtotal && answered_pending) {
+        // the tail kernel emitted exactly these queries (same order) and the decoders answered them: do not ask twice
+        BCE_HIP_TRY(c, hipMemcpyAsync(Rsbuf.p, pin_res.p, qtotal * 4, hipMemcpyHostToDevice, c->stream));
+      } else if (qtotal && direct) {
+        pool.Q = static_cast<const uint32_t *>(pin_q.p);
+        pool.E = static_cast<const uint4 *>(pin_e.p);
+        pool.res = static_cast<uint32_t *>(pin_res.p);
+        pool.run(in);
+        { const double t1 = now_s(); t_host += t1 - t0; t0 = t1; }
+      } else if (qtotal) {
+        BCE_TRY(pin_q.ensure(c, qtotal * 4));
+        BCE_TRY(pin_e.ensure(c, (etotal + 1) * sizeof(uint4)));
+        BCE_TRY(pin_res.ensure(c, qtotal * 4));
+        BCE_HIP_TRY(c, hipMemcpyAsync(pin_q.p, a.Q, qtotal * 4, hipMemcpyDeviceToHost, c->stream));
+        if (etotal) BCE_HIP_TRY(c, hipMemcpyAsync(pin_e.p, a.E, etotal * sizeof(uint4), hipMemcpyDeviceToHost, c->stream));
+        BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        { const double t1 = now_s(); t_copy += t1 - t0; t0 = t1; }
+        pool.Q = static_cast<const uint32_t *>(pin_q.p);
+        pool.E = static_cast<const uint4 *>(pin_e.p);
+        pool.res = static_cast<uint32_t *>(pin_res.p);
+        pool.run(in);
+        { const double t1 = now_s(); t_host += t1 - t0; t0 = t1; }
+        BCE_HIP_TRY(c, hipMemcpyAsync(Rsbuf.p, pin_res.p, qtotal * 4, hipMemcpyHostToDevice, c->stream));
+      }
+      answered_pending = false;
+      if (small) {
+        hipLaunchKernelGGL((dec_small_kernel<false>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+      } else {
+        hipLaunchKernelGGL((dec_tiles_kernel<2>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+        hipLaunchKernelGGL((dec_scan_kernel<false>), dim3(8), dim3(1024), 0, c->stream, a);
+        hipLaunchKernelGGL((dec_tiles_kernel<3>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+      }
+      // the next round's size: read the control block (the query pass of the next round would tell, but its grid needs it)
+      BCE_TRY(read_back(c, &ctl, c->ctl.p, sizeof ctl));
+      BCE_HIP_TRY(c, hipGetLastError());
+      BCE_TRY(settle_group());
+      round_q += qtotal;
     }
-    answered_pending = false;
-    if (small) {
-      hipLaunchKernelGGL((dec_small_kernel<false>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-    } else {
-      hipLaunchKernelGGL((dec_tiles_kernel<2>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-      hipLaunchKernelGGL((dec_scan_kernel<false>), dim3(8), dim3(1024), 0, c->stream, a);
-      hipLaunchKernelGGL((dec_tiles_kernel<3>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-    }
-    // the next round's size: read the control block (the query pass of the next round would tell, but its grid needs it)
-    BCE_TRY(read_back(c, &ctl, c->ctl.p, sizeof ctl));
-    BCE_HIP_TRY(c, hipGetLastError());
-    if (ctl.err) {
-      if (ctl.err == 4) snprintf(c->err, sizeof c->err, "decode: a two-launch round waited too long for a predecessor tile (round %u)", round);
-      else snprintf(c->err, sizeof c->err, ctl.err == 2 ? "decode: node list overflow (capP=%u)" : "decode: inconsistent archive (round %u)",
-                    ctl.err == 2 ? c->capP : round);
-      c->dec_list_overflow = ctl.err == 2;
-      return ctl.err == 2 ? BCE_HIP_E_OVERFLOW : BCE_HIP_E_INTERNAL;
-    }
+    a.pmask = a.gmask = 0xFFu; a.final = 1u;
     t_c += now_s() - t0;
     if (timing) wide_time[hb] += now_s() - t_round0;
     cur_nodes = ctl.next_nodes;
     nodes_total = ctl.nodes_total;
     if (c->progress) c->progress(nodes_total, 8ull * n, c->progress_user);
-    queries_total += qtotal;
+    queries_total += round_q;
     ++round;
   }
   if (timing) { fprintf(stderr, "gpu decode: %u rounds (%llu of them in the tail kernels, %llu query rounds answered through the mailbox), %llu nodes, %llu queries: %.3f s (query pass %.3f, copy out %.3f, host decoders %.3f, children pass %.3f)\n",
                         round, (unsigned long long)tail_rounds, (unsigned long long)mbox_rounds, (unsigned long long)nodes_total, (unsigned long long)queries_total, now_s() - tp0, t_q, t_copy, t_host, t_c); tp0 = now_s(); }
 
+  if (trace_mem) fprintf(stderr, "gpu decode: %llu rounds over the query budget of %llu nodes run in plane groups, %llu node lists grown in place; device memory in use during the rounds: %.1f GB at most\n",
+                         (unsigned long long)grouped_rounds, (unsigned long long)budget, (unsigned long long)list_grows, peak_used / 1e9);
   if (timing) fprintf(stderr, "gpu decode: %llu six-launch rounds plane by plane (busiest first): %.3f s (launching the query passes %.3f, the first plane's %.3f, all lanes started after %.3f, waiting for decoders %.3f, last children pass %.3f)\n",
                       (unsigned long long)split_rounds, t_split, ts_issue, ts_first, ts_lanes, ts_wait, ts_rb);
   if (timing) {
@@ -2232,11 +2382,33 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
                       (unsigned long long)launches_wave, (unsigned long long)rounds_wave, (unsigned long long)nodes_wave, t_wave,
                       (unsigned long long)launches_wg, (unsigned long long)rounds_wg, (unsigned long long)nodes_wg, t_wg);
   // ---- R -> planes -> granules -> BWT bytes ----
+  // From here on the lists and the rounds' query buffers are idle (an allocation that finds the device full gets them back:
+  // ctx_trim).  Where what follows would not fit twice into the device memory that is free beside them, they go back now, so
+  // that the planes and the inverse BWT never allocate on top of them: 16 lists of 541 M nodes and ~10 GB of query buffers at
+  // 2^31 bytes.  At 10^8 bytes they stay with the context for its next decode.  (BCE_DEC_GIVE_BACK=1: always.)
+  c->dec_part = 2;
   FillArgs f;
   f.R = R; f.n = n;
   f.chunks = (uint32_t)(((uint64_t)n + 1 + FG_CHUNK - 1) / FG_CHUNK);
   f.nwords = (uint32_t)(((uint64_t)n + 31) / 32) + 3;
   const uint32_t ngran = (uint32_t)((uint64_t)n / 96) + 2;
+  {
+    auto more = [](const DevBuf &b, size_t want) -> uint64_t { return want > b.cap ? want - b.cap : 0; };
+    const size_t b4n = (size_t)n * 4;
+    const uint64_t post = more(c->sa[0], std::max<size_t>(8 * rstride, b4n)) + more(c->sa[1], b4n) +
+                          more(c->key[0], std::max<size_t>((size_t)8 * f.nwords * 4, b4n)) + more(c->key[1], std::max<size_t>((size_t)8 * f.nwords * 4, b4n)) +
+                          more(c->rank, b4n) + more(c->gran, (size_t)8 * ngran * sizeof(Granule)) + more(c->bwt, n) + more(c->text, n);
+    size_t fr = 0, tot = 0;
+    const bool force = getenv("BCE_DEC_GIVE_BACK") != nullptr;
+    if (force || (hipMemGetInfo(&fr, &tot) == hipSuccess && fr < 2 * post)) {
+      BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+      size_t freed = 0;
+      for (auto &par : c->dlist) for (DevBuf &b : par) { freed += b.cap; release(b); }
+      for (DevBuf *b : {&Qbuf, &Ebuf, &Rsbuf, &c->tilecnt, &c->tileoff}) { freed += b->cap; release(*b); }
+      if (trace_mem) fprintf(stderr, "gpu decode: after the rounds: %.1f GB of node lists and query buffers given back (%.1f GB were free, the planes and the inverse BWT add %.1f GB)\n",
+                             freed / 1e9, fr / 1e9, post / 1e9);
+    }
+  }
   BCE_TRY(ensure(c, c->blk, (size_t)8 * f.chunks * 4 + 64));
   f.cmax = c->blk.as<uint32_t>();
   f.err = f.cmax + (size_t)8 * f.chunks;
@@ -2247,6 +2419,7 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
   f.words = c->key[0].as<uint32_t>();
   f.rankw = c->key[1].as<uint32_t>();
   BCE_TRY(ensure(c, c->gran, (size_t)8 * ngran * sizeof(Granule)));
+  sample_mem();
   BCE_HIP_TRY(c, hipMemsetAsync(f.err, 0, 4, c->stream));
   BCE_HIP_TRY(c, hipMemsetAsync(f.words, 0, (size_t)8 * f.nwords * 4, c->stream));
   BCE_HIP_TRY(c, hipMemsetAsync(f.rankw, 0, (size_t)8 * f.nwords * 4, c->stream));
@@ -2265,6 +2438,7 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
   BCE_TRY(ensure(c, c->bwt, n));
   BCE_TRY(ensure(c, c->text, n));
   BCE_TRY(ensure(c, c->stat, 64));
+  sample_mem();
   uint32_t *dz = c->stat.as<uint32_t>();
   BCE_HIP_TRY(c, hipMemcpyAsync(dz, a.zeros, 32, hipMemcpyHostToDevice, c->stream));
   BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2273,15 +2447,18 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
   if (timing) { BCE_HIP_TRY(c, hipStreamSynchronize(c->stream)); fprintf(stderr, "gpu decode: planes + unbwt %.3f s\n", now_s() - tp0); tp0 = now_s(); }
 
   // ---- inverse BWT ----
+  c->dec_part = 3;                                              // (... and the boundary ranks, once access_kernel has read them)
   const size_t b4 = (size_t)n * 4;
   for (int i = 0; i < 2; ++i) { BCE_TRY(ensure(c, c->sa[i], b4)); BCE_TRY(ensure(c, c->key[i], b4)); }
   BCE_TRY(ensure(c, c->rank, b4));
+  sample_mem();
   uint32_t *key[2] = {c->key[0].as<uint32_t>(), c->key[1].as<uint32_t>()};
   uint32_t *val[2] = {c->sa[0].as<uint32_t>(), c->sa[1].as<uint32_t>()};
   uint32_t *lf = c->rank.as<uint32_t>();
   hipLaunchKernelGGL(lf_keys_kernel, dim3(gn), dim3(256), 0, c->stream, c->bwt.as<uint8_t>(), n, key[0], val[0]);
   int res = 0;
   BCE_TRY(radix_sort_pairs(c, key, val, n, 0, 8, &res, 8));
+  sample_mem();                                                 // (the sort's histograms)
   hipLaunchKernelGGL(lf_scatter_kernel, dim3(gn), dim3(256), 0, c->stream, val[res], n, lf);
   uint32_t sh = 0;
   while (((uint64_t)n >> sh) > (1u << 19)) ++sh;                // at most 2^19 walkers
@@ -2335,6 +2512,7 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
   BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
   BCE_HIP_TRY(c, hipGetLastError());
   if (timing) fprintf(stderr, "gpu decode: inverse BWT (%s, %u walkers) %.3f s\n", single_cycle ? "one cycle" : "periodic", m, now_s() - tp0);
+  if (trace_mem) fprintf(stderr, "gpu decode: device memory in use over the whole decode (sampled after every allocation stage): %.1f GB at most\n", peak_used / 1e9);
   if (timing) fprintf(stderr, "gpu decode: this context so far: device allocations %u calls %.1f MB %.3f s, pinned (query / answer buffers) %u calls %.1f MB %.3f s\n",
                       c->alloc_calls, c->alloc_bytes / 1e6, c->alloc_s, c->pin_calls, c->pin_bytes / 1e6, c->pin_s);
   return BCE_HIP_OK;

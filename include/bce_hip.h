@@ -76,6 +76,8 @@ int bce_hip_set_progress(bce_hip_ctx *ctx, bce_hip_progress_fn fn, void *user);
  * 10 = round from which the tail may start although the node count still grows (exercises the spill path),
  * 11 = model flushes (K4) on a stream of their own beside the next K3 rounds, double-buffered symbol records (also BCE_HIP_OVERLAP=1),
  * 12 = d: the node lists start with n / d + 4096 nodes instead of n / 8 + 4096 (also BCE_HIP_CAPP_DIV=d; large d: the lists grow many times).
+ * 13 = B: the GPU-assisted decoder's query budget, the nodes one pass of a round may hold (default 2^30, 0 = default, values below
+ *      4096 count as 4096): a round with more nodes runs plane group by plane group (bce_hip_stats.dec_split_rounds).
  * The archive never depends on them. */
 int bce_hip_debug_set(bce_hip_ctx *ctx, int knob, uint32_t value);
 
@@ -89,9 +91,11 @@ int bce_hip_debug_set(bce_hip_ctx *ctx, int knob, uint32_t value);
  * device runs out of memory the buffers of the stages that are not running (the suffix sort's scratch) go back first.  Every
  * valid input -- any 1 <= n < 2^31, as the reference (bce.cpp:173,374,901) -- fits an otherwise idle 288 GB MI355X: the worst
  * case is 72 n bytes of lists beside 13 n bytes that stay.  A round that emits more symbols than one model flush takes (2^31
- * records) is run plane group by plane group (bce_hip_stats.split_rounds).  (The GPU-assisted DECODER, bce_hip_decompress_device,
- * holds 32 n bytes of boundary ranks beside its lists and a round's queries: a high-entropy archive of more than ~1.6 * 10^9 bytes
- * ends in BCE_HIP_E_NOMEM there -- never in wrong bytes -- and is decoded by bce_hip_decompress, `bce -ds`.) */
+ * records) is run plane group by plane group (bce_hip_stats.split_rounds).  The GPU-assisted DECODER, bce_hip_decompress_device,
+ * holds 32 n bytes of boundary ranks beside 16 node lists of their own per (parity, plane) -- at most 72 n bytes together, each
+ * list grown in place when a round's children do not fit (bce_hip_stats.dec_list_grows) -- and per-round query buffers bounded by
+ * a budget of 2^30 queries (a wider round runs plane group by plane group: dec_split_rounds); after the rounds the lists and query
+ * buffers go back before the planes and the inverse BWT allocate, where free memory would be short.  Largest archive decoded: 2^31 - 2 random bytes (2 166 438 056 B). */
 int bce_hip_load_host(bce_hip_ctx *ctx, const uint8_t *in, uint32_t n);
 int bce_hip_load_device(bce_hip_ctx *ctx, const void *d_in, uint32_t n);
 
@@ -201,8 +205,11 @@ typedef struct bce_hip_stats {
   /* since the context was created (not reset by a load): */
   double reg_maps;             /* host mappings registered with the runtime (flush slots, the decoder's boundary ranks) */
   double reg_unmaps;           /* ... and given back (after waiting for the work that touches them) */
-  double dec_restarts;         /* GPU-assisted decodes started again with larger node lists (kd_decode.hip) */
+  double dec_restarts;         /* GPU-assisted decodes started again with larger node lists (kd_decode.hip; stays 0: the lists grow in place) */
   double t_model_kernels;      /* of t_model: GPU seconds of K4's kernels alone (sort, window, long, emit), without the device-to-host copies */
+  /* since the context was created (not reset by a load), like dec_restarts: */
+  double dec_list_grows;       /* GPU-assisted decodes: a node list replaced by a larger one in the middle of a round (kd_decode.hip) */
+  double dec_split_rounds;     /* GPU-assisted decodes: rounds with more nodes than the query budget, run plane group by plane group */
 } bce_hip_stats;
 int bce_hip_get_stats(const bce_hip_ctx *ctx, bce_hip_stats *out);
 
