@@ -108,6 +108,13 @@ size_t ctx_trim(bce_hip_ctx *c) {
     give = {&c->nlist[0], &c->nlist[1], &c->dfs, &c->tilecnt, &c->tileoff, &c->k3tw, &c->k3grp, &c->skey[0], &c->skey[1], &c->sval[0],
             &c->sval[1], &c->sout, &c->sesc, &c->skey_alt, &c->sesc_alt, &c->scanrec, &c->k4w};
     if (c->phase == 1) give.push_back(&c->gran);
+  } else if (c->phase == 5) {
+    // the inverse BWT of the seam keeps the text, the BWT, its input (ptmp[0]), the suffix and key arrays, the rank array and
+    // the sort's histograms; the context's compression state is gone (kd_inverse_bw_transform)
+    give = {&c->nlist[0], &c->nlist[1], &c->dfs, &c->tilecnt, &c->tileoff, &c->k3tw, &c->k3grp, &c->skey[0], &c->skey[1], &c->sval[0],
+            &c->sval[1], &c->sout, &c->sesc, &c->skey_alt, &c->sesc_alt, &c->scanrec, &c->k4w, &c->k2, &c->nrk, &c->act[0], &c->act[1],
+            &c->khi[0], &c->khi[1], &c->dl[0], &c->dl[1], &c->dl[2], &c->dl[3], &c->kflag, &c->actv[0], &c->actv[1], &c->ptmp[1], &c->gran};
+    for (auto &par : c->dlist) for (DevBuf &b : par) give.push_back(&b);
   } else if (c->phase == 4) {
     // a decode uses the suffix arrays, the low key words, the rank array, the record arrays and its own node lists as its scratch;
     // the rest of the encoder's buffers it never touches.  Within a decode: the rounds (dec_part 1) leave what the planes and the
@@ -477,6 +484,7 @@ int bce_hip_debug_set(bce_hip_ctx *c, int knob, uint32_t value) {
     case 11: c->overlap = value != 0; break;
     case 12: c->dbg_capp_div = value; break;
     case 13: c->dbg_dec_budget = value; break;
+    case 14: if (value > 3) return BCE_HIP_E_ARG; c->dbg_oom = value; break;
     case 2: c->dbg_no_tail = value; break;
     case 3: c->dbg_no_skip = value; break;
     default: return BCE_HIP_E_ARG;
@@ -559,6 +567,8 @@ int bce_hip_inverse_bwt(bce_hip_ctx *c, const uint8_t *in, uint8_t *out, uint32_
   return bce_guarded(c, [&]() -> int {
     BCE_HIP_TRY(c, hipSetDevice(c->device));
     c->coder->drain();
+    c->phase = 5;
+    struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
     return kd_inverse_bw_transform(c, in, out, n, primary);
   });
 }
@@ -591,13 +601,17 @@ int bce_hip_rank1(bce_hip_ctx *c, int plane, const uint32_t *idx, uint32_t count
   if (!idx || !out || plane < 0 || plane > 7) return BCE_HIP_E_ARG;
   for (uint32_t i = 0; i < count; ++i) if (idx[i] > c->n) return BCE_HIP_E_ARG;
   BCE_HIP_TRY(c, hipSetDevice(c->device));
+  c->phase = 3;                                  // (it reads the planes: what goes back is what an enumeration beside them would give)
+  struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
   return k2_rank1(c, plane, idx, count, out);
 }
 
 // ---- stepping interface ---------------------------------------------------------------------------
+// (each call runs as phase 3, the enumeration's, and leaves phase 0 behind: between the calls other entry points run in this context)
 int bce_hip_enum_begin(bce_hip_ctx *c) {
   BCE_TRY(check_stage(c, 3));
   c->phase = 3;
+  struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
   BCE_HIP_TRY(c, hipSetDevice(c->device));
   BCE_TRY(k4_prepare(c));
   BCE_TRY(k3_begin(c));
@@ -613,6 +627,8 @@ int bce_hip_enum_nodes(bce_hip_ctx *c, int plane, uint32_t *out, uint32_t cap_no
 int bce_hip_enum_round(bce_hip_ctx *c, uint64_t *next_nodes) {
   if (!c || !c->enum_active) return BCE_HIP_E_STATE;
   BCE_HIP_TRY(c, hipSetDevice(c->device));
+  c->phase = 3;
+  struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
   const uint32_t first = c->round;
   if (c->dbg_step_small) BCE_TRY(k3_rounds_small(c, 1, K3_SMALL_NODES, false));   // test hook: step with the one-launch kernel
   else BCE_TRY(k3_rounds(c, 1, 0));
@@ -660,6 +676,8 @@ int bce_hip_enum_model(bce_hip_ctx *c, uint32_t *out, uint64_t cap_records, uint
   *count = ctl.sym_total;
   if (ctl.sym_total > cap_records) return BCE_HIP_E_OVERFLOW;
   c->coder->drain();
+  c->phase = 3;
+  struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
   BCE_TRY(k4_flush(c, ctl.sym_total, c->slot[0]));
   for (uint64_t i = 0; i < ctl.sym_total; ++i) {
     const uint64_t o = c->slot[0].h_out[i];

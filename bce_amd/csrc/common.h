@@ -151,7 +151,8 @@ struct bce_hip_ctx {
 
   uint32_t n = 0;
   int stage = 0;  // 0 empty, 1 loaded, 2 bwt, 3 planes, 4 encoded
-  int phase = 0;  // what is running: 1 K1, 2 K2, 3 the enumeration / model (-c, -s), 4 a decode; 0 nothing.  ctx_trim() gives back the
+  int phase = 0;  // what is running: 1 K1, 2 K2, 3 the enumeration / model (-c, -s), 4 a decode, 5 the inverse BWT of the libdivsufsort
+                  // seam (bce_hip_inverse_bwt); 0 nothing.  Every entry point that sets it sets it back to 0.  ctx_trim() gives back the
                   // buffers the running phase does not use when the device runs out of memory (the context keeps every stage's
                   // buffers for its next input; at n ~ 2^31 they do not all fit together)
   uint32_t offset = 0;
@@ -164,6 +165,7 @@ struct bce_hip_ctx {
   // debug knobs (bce_hip_debug_set): 0 = default
   uint32_t dbg_dfs_budget = 0, dbg_no_dfs = 0, dbg_no_tail = 0, dbg_no_skip = 0, dbg_no_small = 0, dbg_step_small = 0, dbg_no_fused = 0, dbg_no_local = 0, dbg_capp_div = 0, dbg_local_from = 0, dbg_local_budget = 0, dbg_tail_round = 0;
   uint32_t dbg_dec_budget = 0;                   // knob 13: the decoder's query budget (0 = 2^30)
+  uint32_t dbg_oom = 0;                          // knob 14: allocations that fail for real (common.h: test_oom_fails)
   uint64_t sym_cap_user = 0;
   bool sync_flush = false;                       // BCE_HIP_SYNC_FLUSH: flushes wait for their copy (profiling)
   bce_hip_progress_fn progress = nullptr;        // bce_hip_set_progress
@@ -275,7 +277,27 @@ inline bool test_oom_now() {
   static std::atomic<unsigned long> count{0};
   return k && (count.fetch_add(1) + 1) % k == 0;
 }
-inline int ensure(bce_hip_ctx *c, DevBuf &b, size_t bytes) {
+// What an allocation is, for test knob 14: a node list's growth at its first-choice size, or at the size it falls back to when
+// that one does not fit (k3_grow_lists; the decoder's grow_lists), or anything else.
+enum AllocSite { kAllocPlain = 0, kAllocListFirst = 1, kAllocListFallback = 2 };
+// Test knob 14 (bce_hip_debug_set), per context, 0 = off: which attempts of ensure() fail -- for real, not pretended: hipMalloc is
+// asked for more than the device holds (hipMemGetInfo's total + 1 GiB), so the error is the runtime's own and stays set until it is
+// read, exactly as on a full device.  1 = both attempts at a node list's first-choice size (its fallback size succeeds), 2 = every
+// attempt of a node list's growth, 3 = the first attempt of every allocation (the second, after ctx_trim, asks for the real size).
+inline bool test_oom_fails(const bce_hip_ctx *c, int site, int attempt) {
+  switch (c->dbg_oom) {
+    case 1: return site == kAllocListFirst;
+    case 2: return site != kAllocPlain;
+    case 3: return attempt == 0;
+    default: return false;
+  }
+}
+inline size_t test_oom_bytes(size_t bytes) {
+  size_t fr = 0, tot = 0;
+  if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); return bytes; }
+  return tot + ((size_t)1 << 30);
+}
+inline int ensure(bce_hip_ctx *c, DevBuf &b, size_t bytes, int site = kAllocPlain) {
   if (bytes <= b.cap) return BCE_HIP_OK;
   if (b.p) {
     // The old buffer may still be read or written by work this context has queued (a model flush and its copy run
@@ -286,14 +308,15 @@ inline int ensure(bce_hip_ctx *c, DevBuf &b, size_t bytes) {
     b.p = nullptr; b.cap = 0;
   }
   const double t0 = now_s();
-  hipError_t e = hipMalloc(&b.p, bytes);
+  const bool hooked = c->dbg_oom != 0;
+  hipError_t e = hipMalloc(&b.p, test_oom_fails(c, site, 0) ? test_oom_bytes(bytes) : bytes);
   const bool pretend = e == hipSuccess && test_oom_now();
   if (pretend) { (void)hipFree(b.p); e = hipErrorOutOfMemory; }
   if (e == hipErrorOutOfMemory) {
     // the buffers of the stages that are not running go back, then once more
     (void)hipGetLastError();
     b.p = nullptr;
-    if (ctx_trim(c) || pretend) e = hipMalloc(&b.p, bytes);
+    if (ctx_trim(c) || pretend || hooked) e = hipMalloc(&b.p, test_oom_fails(c, site, 1) ? test_oom_bytes(bytes) : bytes);
   }
   if (e != hipSuccess) {
     b.p = nullptr;

@@ -1010,11 +1010,12 @@ __global__ __launch_bounds__(K1_T) void k1_divbwt_gather_kernel(const uint8_t *_
 int k1_divbwt(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n, uint32_t *pidx_out) {
   if (n == 0 || n >= 0x7FFFFFFFu) return BCE_HIP_E_ARG;
   const uint32_t m = n + 1u;
+  // the context's compression state is gone -- before the first allocation, which may give back its planes and node lists
+  c->stage = 0; c->k1_valid = false; c->enum_active = false;
   BCE_TRY(ensure(c, c->text, m));
   BCE_TRY(ensure(c, c->bwt, m));
   uint8_t *T = c->text.as<uint8_t>();
   BCE_HIP_TRY(c, hipMemcpyAsync(T, T_host, n, hipMemcpyHostToDevice, c->stream));
-  c->stage = 0; c->k1_valid = false; c->enum_active = false;          // the context's compression state is gone
   c->stats.sort_rounds = 0;
   BCE_TRY(k1_sort_rotations(c, T, m, true));
   uint32_t pidx = 0;

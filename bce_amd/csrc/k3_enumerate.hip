@@ -991,11 +991,11 @@ int k3_grow_lists(bce_hip_ctx *c, const EnumCtl &ctl) {
   c->capL[out] = 0;
   uint64_t want = need * 2 + 4096;
   if (want > full) want = full;
-  int rc = ensure(c, c->nlist[out], (size_t)8 * want * sizeof(Node));
+  int rc = ensure(c, c->nlist[out], (size_t)8 * want * sizeof(Node), kAllocListFirst);
   if (rc == BCE_HIP_E_NOMEM) {
     want = need + need / 16 + 4096;
     if (want > full) want = full;
-    rc = ensure(c, c->nlist[out], (size_t)8 * want * sizeof(Node));
+    rc = ensure(c, c->nlist[out], (size_t)8 * want * sizeof(Node), kAllocListFallback);
   }
   if (rc != BCE_HIP_OK) {
     if (rc == BCE_HIP_E_NOMEM) snprintf(c->err, sizeof c->err, "k3: no device memory for node lists of %llu nodes (round %u, n = %u)", (unsigned long long)want, c->round, c->n);

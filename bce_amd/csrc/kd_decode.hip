@@ -1170,12 +1170,14 @@ int kd_inverse_bw_transform(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_ho
   if (n == 0 || n >= 0x7FFFFFFFu || idx == 0 || idx > n) return BCE_HIP_E_ARG;
   const uint32_t m_rows = n + 1u;
   const size_t b4 = (size_t)m_rows * 4;
+  // the context's compression state is gone -- before the first allocation, which may give back its planes and node lists (ctx_trim,
+  // phase 5: the caller's)
+  c->stage = 0; c->k1_valid = false; c->enum_active = false;
   BCE_TRY(ensure(c, c->text, m_rows));
   BCE_TRY(ensure(c, c->bwt, m_rows));
   BCE_TRY(ensure(c, c->ptmp[0], m_rows));
   for (int i = 0; i < 2; ++i) { BCE_TRY(ensure(c, c->sa[i], b4)); BCE_TRY(ensure(c, c->key[i], b4)); }
   BCE_TRY(ensure(c, c->rank, b4));
-  c->stage = 0; c->k1_valid = false; c->enum_active = false;          // the context's compression state is gone
   uint8_t *d_in = c->ptmp[0].as<uint8_t>(), *rows = c->bwt.as<uint8_t>();
   BCE_HIP_TRY(c, hipMemcpyAsync(d_in, T_host, n, hipMemcpyHostToDevice, c->stream));
   uint32_t *key[2] = {c->key[0].as<uint32_t>(), c->key[1].as<uint32_t>()};
@@ -1558,6 +1560,7 @@ int dec_host_tail(bce_hip_ctx *c, const DecArgs &a, const DecCtl &ctl, std::vect
     }
   }
   struct Unpin { bool on; cpu_set_t *aff; ~Unpin() { if (on) (void)sched_setaffinity(0, sizeof *aff, aff); } } unpin{repin, &old_aff};
+  if (getenv("BCE_DEC_TIMING")) fprintf(stderr, "gpu decode: host tail on %s\n", !threaded ? "one thread" : repin ? "eight threads of one L3 domain" : "eight threads, not pinned");
   if (threaded) try {
     for (uint32_t w = 1; w < 8; ++w)
       pool.th.emplace_back([&, w] {
@@ -1858,7 +1861,10 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
   // then every tail that is worth the copy goes there and nothing is probed.
   // ... every LONG tail, that is: the copy and the threads cost ~0.1 s, which a tail of a few hundred rounds (text) does not have
   // to spare -- so the resident kernels always get the first kProbeRounds rounds.
-  const bool host_has_ccx = std::thread::hardware_concurrency() >= 8u && !getenv("BCE_DEC_TAIL_SERIAL") && tail_cpus().size() == 8;
+  const size_t tail_ncpu = tail_cpus().size();
+  const bool host_has_ccx = std::thread::hardware_concurrency() >= 8u && !getenv("BCE_DEC_TAIL_SERIAL") && tail_ncpu == 8;
+  if (timing) fprintf(stderr, "gpu decode: host tail CPUs: %zu of one L3 domain in the affinity mask, %u hardware threads: tails go to the host early %d\n",
+                      tail_ncpu, std::thread::hardware_concurrency(), (int)host_has_ccx);
   uint64_t wide_hist[32] = {0}, wide_nodes[32] = {0}, small_rounds = 0;
   double wide_time[32] = {0};
   constexpr uint64_t kDirectNodes = 1u << 18;
@@ -2123,10 +2129,10 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
         a.list[out][qn] = nullptr; a.cap[out][qn] = 0;
         uint64_t want = need + need / 4;
         if (want > full_cap) want = full_cap;
-        int rc = ensure(c, c->dlist[out][qn], (size_t)want * sizeof(Node));
+        int rc = ensure(c, c->dlist[out][qn], (size_t)want * sizeof(Node), kAllocListFirst);
         if (rc == BCE_HIP_E_NOMEM) {
           want = need;
-          rc = ensure(c, c->dlist[out][qn], (size_t)want * sizeof(Node));
+          rc = ensure(c, c->dlist[out][qn], (size_t)want * sizeof(Node), kAllocListFallback);
         }
         if (rc != BCE_HIP_OK) {
           if (rc == BCE_HIP_E_NOMEM) snprintf(c->err, sizeof c->err, "decode: no device memory for a node list of %llu nodes (round %u, n = %u)", (unsigned long long)need, round, n);
@@ -2362,6 +2368,8 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
   if (timing) { fprintf(stderr, "gpu decode: %u rounds (%llu of them in the tail kernels, %llu query rounds answered through the mailbox), %llu nodes, %llu queries: %.3f s (query pass %.3f, copy out %.3f, host decoders %.3f, children pass %.3f)\n",
                         round, (unsigned long long)tail_rounds, (unsigned long long)mbox_rounds, (unsigned long long)nodes_total, (unsigned long long)queries_total, now_s() - tp0, t_q, t_copy, t_host, t_c); tp0 = now_s(); }
 
+  if (timing) fprintf(stderr, "gpu decode: tail probe: %u rounds, %llu query rounds through the mailbox since it began; query-heavy %d\n",
+                      probe_rounds, (unsigned long long)(probe_rounds ? mbox_rounds - probe_mbox0 : 0), (int)query_heavy);
   if (trace_mem) fprintf(stderr, "gpu decode: %llu rounds over the query budget of %llu nodes run in plane groups, %llu node lists grown in place; device memory in use during the rounds: %.1f GB at most\n",
                          (unsigned long long)grouped_rounds, (unsigned long long)budget, (unsigned long long)list_grows, peak_used / 1e9);
   if (timing) fprintf(stderr, "gpu decode: %llu six-launch rounds plane by plane (busiest first): %.3f s (launching the query passes %.3f, the first plane's %.3f, all lanes started after %.3f, waiting for decoders %.3f, last children pass %.3f)\n",

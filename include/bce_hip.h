@@ -78,6 +78,11 @@ int bce_hip_set_progress(bce_hip_ctx *ctx, bce_hip_progress_fn fn, void *user);
  * 12 = d: the node lists start with n / d + 4096 nodes instead of n / 8 + 4096 (also BCE_HIP_CAPP_DIV=d; large d: the lists grow many times).
  * 13 = B: the GPU-assisted decoder's query budget, the nodes one pass of a round may hold (default 2^30, 0 = default, values below
  *      4096 count as 4096): a round with more nodes runs plane group by plane group (bce_hip_stats.dec_split_rounds).
+ * 14 = m: device allocations of this context that fail for real -- hipMalloc is asked for hipMemGetInfo's total + 1 GiB, so the
+ *      runtime's own out-of-memory error is what the code sees and what stays set until it is read, as on a full device.
+ *      1 = both attempts at a node list's first-choice size (encoder k3_grow_lists, decoder grow_lists: their fallback sizes
+ *      succeed), 2 = every attempt of a node list's growth (BCE_HIP_E_NOMEM, "no device memory for ... node list(s) of ..."),
+ *      3 = the first attempt of every allocation (the retry after the other phases' buffers have gone back succeeds); 0 = off.
  * The archive never depends on them. */
 int bce_hip_debug_set(bce_hip_ctx *ctx, int knob, uint32_t value);
 

@@ -167,11 +167,12 @@ def test_decode_into_a_callers_buffer():
         bce_amd.decompress_device(arch, out=np.zeros(len(data), dtype=np.uint16))
 
 
-def test_node_lists_of_the_decoder_grow_by_starting_again(capfd, monkeypatch):
-    """The decoder's node lists start with n / 8 (+ 4096) nodes per plane; a round whose children would not fit stops the decode
-    before it writes them, and the decode starts again with twice the room (kd_decode.hip: decompress_device_body).  Lists of
-    4096 nodes (test knob 12) on inputs whose rounds hold tens of thousands of nodes per plane: several restarts, the right
-    bytes; then the same context without the knob decodes in one go (its lists are large by now)."""
+def test_node_lists_of_the_decoder_grow_in_place(capfd, monkeypatch):
+    """The decoder has a node list per (parity, plane); a children pass whose children would not fit a list writes none of them,
+    that one list is replaced by a larger one in the middle of the round, and the pass runs again from the answers the host
+    already has (kd_decode.hip: grow_lists / settle_group) -- no decode starts again.  Lists of 4096 nodes (test knob 12) on inputs
+    whose rounds hold tens of thousands of nodes per plane: several lists grown, no restart, the right bytes; then the same context
+    without the knob decodes with lists of the default size, which these inputs never outgrow."""
     monkeypatch.setenv("BCE_ALLOC_TRACE", "1")
     for data in (oracle.synth_rand(12, 400000), oracle.synth_text(12, 3_000_000), bytes(_with_long_tail(1_500_000, 7))):
         arch = oracle.compress(data)
@@ -179,9 +180,12 @@ def test_node_lists_of_the_decoder_grow_by_starting_again(capfd, monkeypatch):
         try:
             ctx.check(ctx.lib.bce_hip_debug_set(ctx.h, 12, 1 << 30), "bce_hip_debug_set")
             capfd.readouterr()
+            s0 = bce_amd.stats_of(ctx)
             assert bce_amd.decompress_device(arch, ctx=ctx) == data
+            s1 = bce_amd.stats_of(ctx)
             err = capfd.readouterr().err
             assert err.count("does not fit the node lists") >= 2, err[-2000:]
+            assert s1["dec_restarts"] - s0["dec_restarts"] == 0 and s1["dec_list_grows"] - s0["dec_list_grows"] >= 2, (s0, s1)
             ctx.check(ctx.lib.bce_hip_debug_set(ctx.h, 12, 0), "bce_hip_debug_set")
             assert bce_amd.decompress_device(arch, ctx=ctx) == data
             assert "does not fit the node lists" not in capfd.readouterr().err

@@ -105,7 +105,7 @@ def test_out_of_memory_inside_a_decode(every):
     """BCE_HIP_TEST_OOM=k: every k-th device allocation of the process is reported out of memory at its first attempt (read
     once per process: a child).  The grown lists, the group buffers and the stages after the rounds then go through ctx_trim and
     a second attempt, which succeeds.  (The exact-need fallback of a list that still does not fit, and the error cleared after
-    a failed second attempt, need a device that is really full: no test provokes that.)"""
+    a failed second attempt, take allocations that fail for real: test knob 14 in test_gpu_oom.py.)"""
     env = dict(os.environ, BCE_HIP_TEST_OOM=every, PYTHONPATH=os.path.join(ROOT, "tests"))
     r = subprocess.run([sys.executable, "-c", _CHILD % ROOT], capture_output=True, text=True, timeout=900, env=env, cwd=os.path.join(ROOT, "tests"))
     assert r.returncode == 0 and "CHILD_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
