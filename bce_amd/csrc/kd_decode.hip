@@ -83,7 +83,7 @@ struct DecArgs {
   uint32_t seq_base;         // number of the first query round of this launch (numbers never repeat within a decode)
   unsigned long long *words; // dec_small_kernel: one tagged count word per tile
   uint32_t round;            // ... and the round number the tags are made of
-  // Six-launch rounds taken in two parts (the busiest plane first, see decompress_device): the planes this launch works
+  // Six-launch rounds taken in two parts (the busiest plane first, see Decode::lane_round): the planes this launch works
   // on, the order in which the planes' queries lie in Q (4 bits each, first plane lowest), whether this children pass is
   // the round's last (it alone adds up the round)
   uint32_t pmask = 0xFFu, order = 0x76543210u, final = 1u;
@@ -1164,6 +1164,56 @@ __global__ void seam_rows_kernel(const uint8_t *__restrict__ U, uint32_t n, uint
   }
 }
 
+uint32_t grid256(uint64_t items) { return (uint32_t)((items + 255) / 256 < 8192 ? (items + 255) / 256 : 8192); }
+
+// The inverse BWT's walk from row 0 through LF (`rows` rows; bwt[r]: the byte in front of row r) back to row 0, by walkers
+// that start at every 2^sh-th row (walk_len_kernel), their segments chained here and then written in place
+// (walk_write_kernel).  A cycle through all the rows lands at out[(i + off) % len]; a shorter one whose length divides `rows`
+// (a periodic input) at cycle[i], if `cycle` is given; any other is not written.  *lc: the cycle's length, 0 if the walk came
+// to a segment twice (LF is not a permutation); *walkers: how many walked.
+int lf_walk(bce_hip_ctx *c, const uint32_t *lf, const uint8_t *bwt, uint32_t rows, uint8_t *out, uint32_t len, uint32_t off,
+            uint8_t *cycle, uint64_t *lc, uint32_t *walkers) {
+  uint32_t sh = 0;
+  while (((uint64_t)rows >> sh) > (1u << 19)) ++sh;             // at most 2^19 walkers
+  // ... and at least 256 rows per walker while that leaves a few thousand of them: the host chains the segments one after
+  // the other (a random access each), which for one-row segments of a 1 MB input was 10 ms of a 36 ms decode
+  while (sh < 8 && ((uint64_t)rows >> (sh + 1)) >= 4096) ++sh;
+  const uint32_t m = (uint32_t)((((uint64_t)rows - 1) >> sh) + 1);
+  *walkers = m;
+  *lc = 0;
+  BCE_TRY(ensure(c, c->key[0], (size_t)3 * m * 4 + 16));         // (the callers' sort is done with its key buffers)
+  uint32_t *d_len = c->key[0].as<uint32_t>(), *d_end = d_len + m, *d_dest = d_len + 2 * (size_t)m;
+  hipLaunchKernelGGL(walk_len_kernel, dim3((m + 63) / 64), dim3(64), 0, c->stream, lf, m, sh, d_len, d_end);
+  std::vector<uint32_t> h_len(m), h_end(m), h_dest(m, 0);
+  BCE_HIP_TRY(c, hipMemcpyAsync(h_len.data(), d_len, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+  BCE_HIP_TRY(c, hipMemcpyAsync(h_end.data(), d_end, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
+  BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  BCE_HIP_TRY(c, hipGetLastError());
+  uint64_t l = 0;
+  uint32_t cur = 0;
+  std::vector<uint8_t> visited(m, 0);
+  std::vector<uint32_t> order;
+  do {
+    const uint32_t j = cur >> sh;
+    if (visited[j]) return BCE_HIP_OK;
+    visited[j] = 1;
+    order.push_back(j);
+    l += h_len[j];
+    cur = h_end[j];
+  } while (cur != 0);
+  *lc = l;
+  uint64_t pos = l;
+  for (uint32_t j : order) { h_dest[j] = (uint32_t)pos; pos -= h_len[j]; }
+  for (uint32_t j = 0; j < m; ++j) if (!visited[j]) h_len[j] = 0;      // rows off the cycle are never written
+  const bool whole = l == rows;
+  if (!whole && !(cycle && rows % l == 0)) return BCE_HIP_OK;
+  BCE_HIP_TRY(c, hipMemcpyAsync(d_dest, h_dest.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+  BCE_HIP_TRY(c, hipMemcpyAsync(d_len, h_len.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+  if (whole) hipLaunchKernelGGL(walk_write_kernel, dim3((m + 63) / 64), dim3(64), 0, c->stream, lf, bwt, m, sh, d_len, d_dest, len, off, out);
+  else hipLaunchKernelGGL(walk_write_kernel, dim3((m + 63) / 64), dim3(64), 0, c->stream, lf, bwt, m, sh, d_len, d_dest, (uint32_t)l, 0u, cycle);
+  return BCE_HIP_OK;
+}
+
 }  // namespace
 
 int kd_inverse_bw_transform(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n, uint32_t idx) {
@@ -1183,46 +1233,17 @@ int kd_inverse_bw_transform(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_ho
   uint32_t *key[2] = {c->key[0].as<uint32_t>(), c->key[1].as<uint32_t>()};
   uint32_t *val[2] = {c->sa[0].as<uint32_t>(), c->sa[1].as<uint32_t>()};
   uint32_t *lf = c->rank.as<uint32_t>();
-  const uint32_t gn = (uint32_t)((((uint64_t)m_rows + 255) / 256) < 8192 ? (((uint64_t)m_rows + 255) / 256) : 8192);
+  const uint32_t gn = grid256(m_rows);
   hipLaunchKernelGGL(seam_rows_kernel, dim3(gn), dim3(256), 0, c->stream, d_in, n, idx, rows, key[0], val[0]);
   int res = 0;
   BCE_TRY(radix_sort_pairs(c, key, val, m_rows, 0, 9, &res, 9));
   hipLaunchKernelGGL(lf_scatter_kernel, dim3(gn), dim3(256), 0, c->stream, val[res], m_rows, lf);
-  uint32_t sh = 0;
-  while (((uint64_t)m_rows >> sh) > (1u << 19)) ++sh;          // at most 2^19 walkers
-  while (sh < 8 && ((uint64_t)m_rows >> (sh + 1)) >= 4096) ++sh;   // ... of at least 256 rows each while a few thousand are left (see decompress_device)
-  const uint32_t m = (uint32_t)((((uint64_t)m_rows - 1) >> sh) + 1);
-  BCE_TRY(ensure(c, c->key[0], (size_t)3 * m * 4 + 16 > b4 ? (size_t)3 * m * 4 + 16 : b4));
-  uint32_t *d_len = c->key[0].as<uint32_t>(), *d_end = d_len + m, *d_dest = d_len + 2 * (size_t)m;
-  hipLaunchKernelGGL(walk_len_kernel, dim3((m + 63) / 64), dim3(64), 0, c->stream, lf, m, sh, d_len, d_end);
-  std::vector<uint32_t> h_len(m), h_end(m), h_dest(m, 0);
-  BCE_HIP_TRY(c, hipMemcpyAsync(h_len.data(), d_len, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
-  BCE_HIP_TRY(c, hipMemcpyAsync(h_end.data(), d_end, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
-  BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  BCE_HIP_TRY(c, hipGetLastError());
+  // the walk's positions are those of $T: shifted by n (= -1 mod n + 1) the text lands at [0, n), the sentinel's slot at n.
+  // (key[0] holds 4(n + 1) bytes already, which the walk's 3m + 4 words grow if they need more.)
   uint64_t lc = 0;
-  {
-    uint32_t cur = 0;
-    std::vector<uint8_t> visited(m, 0);
-    std::vector<uint32_t> order;
-    do {
-      const uint32_t j = cur >> sh;
-      if (visited[j]) return BCE_HIP_E_ARG;                      // not the BWT of anything (T / idx inconsistent)
-      visited[j] = 1;
-      order.push_back(j);
-      lc += h_len[j];
-      cur = h_end[j];
-    } while (cur != 0);
-    uint64_t pos = lc;
-    for (uint32_t j : order) { h_dest[j] = (uint32_t)pos; pos -= h_len[j]; }
-    for (uint32_t j = 0; j < m; ++j) if (!visited[j]) h_len[j] = 0;
-  }
-  if (lc != m_rows) return BCE_HIP_E_ARG;                        // several LF cycles: T / idx inconsistent
-  BCE_HIP_TRY(c, hipMemcpyAsync(d_dest, h_dest.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
-  BCE_HIP_TRY(c, hipMemcpyAsync(d_len, h_len.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
-  // the walk's positions are those of $T: shifted by n (= -1 mod n + 1) the text lands at [0, n), the sentinel's slot at n
-  hipLaunchKernelGGL(walk_write_kernel, dim3((m + 63) / 64), dim3(64), 0, c->stream, lf, rows, m, sh, d_len, d_dest, m_rows, n,
-                     c->text.as<uint8_t>());
+  uint32_t walkers = 0;
+  BCE_TRY(lf_walk(c, lf, rows, m_rows, c->text.as<uint8_t>(), m_rows, n, nullptr, &lc, &walkers));
+  if (lc != m_rows) return BCE_HIP_E_ARG;                        // not one LF cycle: T / idx inconsistent
   BCE_HIP_TRY(c, hipMemcpyAsync(U_host, c->text.p, n, hipMemcpyDeviceToHost, c->stream));
   BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
   BCE_HIP_TRY(c, hipGetLastError());
@@ -1361,6 +1382,29 @@ struct Mailbox {               // a few host-coherent words the wave tail kernel
   ~Mailbox() { if (host) (void)hipHostFree(host); }
 };
 
+// The decoder's switches, read from the environment once per decode.  BCE_DEC_NO_* / FORCE_* / HOST_ENTER / GIVE_BACK force
+// its routes (tests/test_gpu_decode_routes.py runs them all); BCE_DEC_TIMING, BCE_ALLOC_TRACE and BCE_DEC_TRACE print.
+struct DecEnv {
+  bool timing, alloc_trace, trace, no_small, no_split, no_tail, no_mailbox, no_host_tail, no_probe, force_host_tail, no_early_pin,
+      give_back, tail_serial, tail_nopin;
+  uint32_t host_enter;         // BCE_DEC_HOST_ENTER: how few nodes a round may hold for the host to take the tail early (8192)
+  uint64_t capp_div;           // BCE_HIP_CAPP_DIV: the node lists start with n / capp_div + 4096 nodes (0: not set)
+  bool mem() const { return timing || alloc_trace; }   // the device memory lines
+};
+DecEnv dec_env() {
+  auto var = [](const char *name) -> const char * { return getenv(name); };
+  DecEnv e;
+  e.timing = var("BCE_DEC_TIMING"); e.alloc_trace = var("BCE_ALLOC_TRACE"); e.trace = var("BCE_DEC_TRACE");
+  e.no_small = var("BCE_DEC_NO_SMALL"); e.no_split = var("BCE_DEC_NO_SPLIT"); e.no_tail = var("BCE_DEC_NO_TAIL");
+  e.no_mailbox = var("BCE_DEC_NO_MAILBOX"); e.no_host_tail = var("BCE_DEC_NO_HOST_TAIL"); e.no_probe = var("BCE_DEC_NO_PROBE");
+  e.force_host_tail = var("BCE_DEC_FORCE_HOST_TAIL"); e.no_early_pin = var("BCE_DEC_NO_EARLY_PIN"); e.give_back = var("BCE_DEC_GIVE_BACK");
+  e.tail_serial = var("BCE_DEC_TAIL_SERIAL"); e.tail_nopin = var("BCE_DEC_TAIL_NOPIN");
+  const char *h = var("BCE_DEC_HOST_ENTER"), *d = var("BCE_HIP_CAPP_DIV");
+  e.host_enter = h ? (uint32_t)strtoul(h, nullptr, 10) : 8192u;
+  e.capp_div = d ? strtoull(d, nullptr, 10) : 0;
+  return e;
+}
+
 // The very deep tail on the host.  A chain of a few nodes that goes on for millions of rounds (a megabyte run, a
 // whole-file duplicate) costs the wave kernel ~2 us per round -- the latency of one dependent load after the other
 // -- while a CPU core does the same round out of its caches in ~0.1 us.  So once the wave kernel has spent
@@ -1373,10 +1417,10 @@ __global__ void dec_scatter_kernel(uint32_t *__restrict__ R, const uint64_t *__r
 
 // Eight CPUs of the calling thread's L3 domain that its affinity mask allows (empty: fewer than eight, or no sysfs):
 // where the eight threads of dec_host_tail sit so that their per-round barrier stays inside one CCX.
-static std::vector<int> tail_cpus() {
+static std::vector<int> tail_cpus(const DecEnv &env) {
   std::vector<int> ccx;
   cpu_set_t aff;
-  if (getenv("BCE_DEC_TAIL_NOPIN") || sched_getaffinity(0, sizeof aff, &aff) != 0) return ccx;
+  if (env.tail_nopin || sched_getaffinity(0, sizeof aff, &aff) != 0) return ccx;
   char path[128];
   snprintf(path, sizeof path, "/sys/devices/system/cpu/cpu%d/cache/index3/shared_cpu_list", sched_getcpu());
   if (FILE *f = fopen(path, "r")) {
@@ -1407,7 +1451,7 @@ struct BigPin {
   void *p = nullptr;
   size_t bytes = 0;
   bool registered = false;
-  bool running = false;
+  bool running = false, timing = false;
   double t_start = 0, t_done = 0;
   void start(bce_hip_ctx *ctx, size_t want) {
     if (running || ctx->h_big_cap >= want) return;
@@ -1424,7 +1468,7 @@ struct BigPin {
     const double t0 = now_s();
     th.join();
     running = false;
-    if (getenv("BCE_DEC_TIMING")) fprintf(stderr, "gpu decode: pinned %.1f GB beside the rounds: %.3f s, the tail waited %.3f s of them\n", bytes / 1e9, t_done - t_start, now_s() - t0);
+    if (timing) fprintf(stderr, "gpu decode: pinned %.1f GB beside the rounds: %.3f s, the tail waited %.3f s of them\n", bytes / 1e9, t_done - t_start, now_s() - t0);
     if (p) {
       if (c->h_big) big_host_free(c, c->h_big, c->h_big_cap, c->h_big_registered);
       c->h_big = p; c->h_big_cap = bytes; c->h_big_registered = registered; p = nullptr;
@@ -1436,8 +1480,8 @@ struct BigPin {
 
 constexpr uint32_t kHostTailMin = 20000;                    // ... rounds, or n / 1000 if that is more (the copies cost ~n)
 
-int dec_host_tail(bce_hip_ctx *c, const DecArgs &a, const DecCtl &ctl, std::vector<Decoder> &dec, uint32_t n, uint32_t *round,
-                  uint64_t *nodes_total, uint64_t *queries_total, bool *bad_out) {
+int dec_host_tail(bce_hip_ctx *c, const DecEnv &env, const DecArgs &a, const DecCtl &ctl, std::vector<Decoder> &dec, uint32_t n,
+                  uint32_t *round, uint64_t *nodes_total, uint64_t *queries_total, bool *bad_out) {
   const uint32_t par = *round & 1u;
   std::vector<Node> cur[8][2], nxt[8][2];
   BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1466,7 +1510,7 @@ int dec_host_tail(bce_hip_ctx *c, const DecArgs &a, const DecCtl &ctl, std::vect
   const double tcp1 = now_s();
   BCE_HIP_TRY(c, hipMemcpyAsync(Rh, a.R, 8 * stride * 4, hipMemcpyDeviceToHost, c->stream));
   BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (getenv("BCE_DEC_TIMING")) fprintf(stderr, "gpu decode: host tail: pinned buffer %.3f s, boundary ranks to the host %.3f s (%.1f GB)\n", tcp1 - tcp0, now_s() - tcp1, 8 * stride * 4 / 1e9);
+  if (env.timing) fprintf(stderr, "gpu decode: host tail: pinned buffer %.3f s, boundary ranks to the host %.3f s (%.1f GB)\n", tcp1 - tcp0, now_s() - tcp1, 8 * stride * 4 / 1e9);
   // what the host learns goes back as (index, value) pairs, kept per plane (the planes are worked on side by side)
   // (each plane's output on cache lines of its own: the headers of neighbouring std::vectors share a line, and eight threads
   //  appending to neighbouring vectors took 13 us per round for what is 3 us of work)
@@ -1545,7 +1589,7 @@ int dec_host_tail(bce_hip_ctx *c, const DecArgs &a, const DecCtl &ctl, std::vect
     std::condition_variable cv;
     std::vector<std::thread> th;
   } pool;
-  bool threaded = !getenv("BCE_DEC_TAIL_SERIAL") && std::thread::hardware_concurrency() >= 8u;
+  bool threaded = !env.tail_serial && std::thread::hardware_concurrency() >= 8u;
   // The eight threads meet at a barrier every round: on cores that share an L3 (one CCX of the EPYC hosts) that is ~1 us, across
   // the package 4-5 us -- more than the round's work.  So for the duration of the tail they sit on eight CPUs of this
   // thread's L3 domain, if the affinity mask has that many (otherwise wherever the scheduler puts them).
@@ -1553,14 +1597,14 @@ int dec_host_tail(bce_hip_ctx *c, const DecArgs &a, const DecCtl &ctl, std::vect
   cpu_set_t old_aff;
   bool repin = false;
   if (threaded && sched_getaffinity(0, sizeof old_aff, &old_aff) == 0) {
-    ccx = tail_cpus();
+    ccx = tail_cpus(env);
     if (ccx.size() == 8) {
       cpu_set_t one; CPU_ZERO(&one); CPU_SET(ccx[0], &one);
       repin = sched_setaffinity(0, sizeof one, &one) == 0;
     }
   }
   struct Unpin { bool on; cpu_set_t *aff; ~Unpin() { if (on) (void)sched_setaffinity(0, sizeof *aff, aff); } } unpin{repin, &old_aff};
-  if (getenv("BCE_DEC_TIMING")) fprintf(stderr, "gpu decode: host tail on %s\n", !threaded ? "one thread" : repin ? "eight threads of one L3 domain" : "eight threads, not pinned");
+  if (env.timing) fprintf(stderr, "gpu decode: host tail on %s\n", !threaded ? "one thread" : repin ? "eight threads of one L3 domain" : "eight threads, not pinned");
   if (threaded) try {
     for (uint32_t w = 1; w < 8; ++w)
       pool.th.emplace_back([&, w] {
@@ -1595,7 +1639,6 @@ int dec_host_tail(bce_hip_ctx *c, const DecArgs &a, const DecCtl &ctl, std::vect
   }
   uint64_t par_rounds = 0, par_nodes = 0, ser_nodes = 0;
   double par_time = 0, ser_time = 0;
-  const bool tail_timing = getenv("BCE_DEC_TIMING") != nullptr;
   uint32_t rounds = 0, serial_run = 0;
   auto unpark = [&] { { std::lock_guard<std::mutex> lk(pool.mu); pool.parked.store(false); } pool.cv.notify_all(); };
   // `live`: the planes that have nodes this round.  The chains of the deep tail are a node or two in one or two planes for
@@ -1607,7 +1650,7 @@ int dec_host_tail(bce_hip_ctx *c, const DecArgs &a, const DecCtl &ctl, std::vect
     size_t tot = 0;
     for (uint32_t m = live; m; m &= m - 1) { const int i = __builtin_ctz(m); tot += cur[i][0].size() + cur[i][1].size(); }
     const bool par_round = threaded && tot >= kParMin;
-    const double tr0 = tail_timing && (par_round || (rounds & 63u) == 0) ? now_s() : 0.0;
+    const double tr0 = env.timing && (par_round || (rounds & 63u) == 0) ? now_s() : 0.0;
     if (par_round) {
       if (pool.parked.load(std::memory_order_relaxed)) unpark();
       serial_run = 0;
@@ -1620,7 +1663,7 @@ int dec_host_tail(bce_hip_ctx *c, const DecArgs &a, const DecCtl &ctl, std::vect
       for (uint32_t m = live; m && !bad_flag.load(std::memory_order_relaxed); m &= m - 1) do_plane((uint32_t)__builtin_ctz(m));
       if (threaded && ++serial_run == kParkAfter) pool.parked.store(true, std::memory_order_release);
     }
-    if (tail_timing) {                                                     // (serial rounds: one in 64 is timed -- the clock costs as much as the round)
+    if (env.timing) {                                                     // (serial rounds: one in 64 is timed -- the clock costs as much as the round)
       if (par_round) { par_time += now_s() - tr0; par_nodes += tot; }
       else { if ((rounds & 63u) == 0) ser_time += 64.0 * (now_s() - tr0); ser_nodes += tot; }
     }
@@ -1652,12 +1695,12 @@ int dec_host_tail(bce_hip_ctx *c, const DecArgs &a, const DecCtl &ctl, std::vect
   }
   if (!whole)
     for (int i = 0; i < 8; ++i) { widx.insert(widx.end(), po[i].wi.begin(), po[i].wi.end()); wval.insert(wval.end(), po[i].wv.begin(), po[i].wv.end()); }
-  if (tail_timing) fprintf(stderr, "gpu decode: host tail: %llu of %u rounds on eight threads (%llu nodes, %.3f s), the others on one (%llu nodes, %.3f s)\n",
+  if (env.timing) fprintf(stderr, "gpu decode: host tail: %llu of %u rounds on eight threads (%llu nodes, %.3f s), the others on one (%llu nodes, %.3f s)\n",
                            (unsigned long long)par_rounds, rounds, (unsigned long long)par_nodes, par_time, (unsigned long long)ser_nodes, ser_time);
   *bad_out = bad;
   if (bad) return BCE_HIP_OK;
   const double tcp2 = now_s();
-  if (getenv("BCE_DEC_TIMING")) fprintf(stderr, "gpu decode: host tail: %u rounds, %llu nodes in %.3f s\n", rounds, (unsigned long long)nodes, tcp2 - tcp0);
+  if (env.timing) fprintf(stderr, "gpu decode: host tail: %u rounds, %llu nodes in %.3f s\n", rounds, (unsigned long long)nodes, tcp2 - tcp0);
   if (whole) {                                                           // (more than an eighth of everything: the whole array)
     BCE_HIP_TRY(c, hipMemcpyAsync(a.R, Rh, 8 * stride * 4, hipMemcpyHostToDevice, c->stream));
     BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1681,15 +1724,15 @@ int dec_host_tail(bce_hip_ctx *c, const DecArgs &a, const DecCtl &ctl, std::vect
 // or what the context's buffer already holds.  A round whose children would not fit a list does not write them (the scan of
 // the children pass checks; the one-launch kernel, which checks afterwards, is only used where twice the round's nodes fit):
 // that one list -- the next parity's list of plane q + 1, which only plane q's children pass writes -- is replaced by a larger
-// one and the pass runs again from the answers it already has (decompress_device_once: grow_lists).  Test knob 12 /
+// one and the pass runs again from the answers it already has (Decode::grow_lists).  Test knob 12 /
 // BCE_HIP_CAPP_DIV as for the encoder.
 uint32_t dec_full_capP(uint32_t n) { return (uint32_t)((uint64_t)n / 2 + 2); }
-uint32_t dec_capP(const bce_hip_ctx *c, uint32_t n, size_t archive_bytes, bool *forced_out) {
+uint32_t dec_capP(const bce_hip_ctx *c, const DecEnv &env, uint32_t n, size_t archive_bytes, bool *forced_out) {
   const uint64_t full = dec_full_capP(n);
   uint64_t div = 8;
   bool forced = false;
   if (c->dbg_capp_div) { div = c->dbg_capp_div; forced = true; }
-  if (const char *e = getenv("BCE_HIP_CAPP_DIV")) { const uint64_t v = strtoull(e, nullptr, 10); if (v >= 1) { div = v; forced = true; } }
+  if (env.capp_div >= 1) { div = env.capp_div; forced = true; }
   uint64_t cap = (uint64_t)n / div + 4096;
   // (the one-launch rounds need twice a round's nodes to fit: 4 M nodes per list at least, i.e. the worst case up to 8 MB of
   //  input -- with n / 8 a 1 MB input left them for its widest rounds and decoded in 32 ms instead of 16)
@@ -1709,51 +1752,113 @@ uint64_t dec_budget(const bce_hip_ctx *c) {
   return c->dbg_dec_budget > DT_CAP ? c->dbg_dec_budget : DT_CAP;
 }
 
-}  // namespace
+struct Events {
+  hipEvent_t e[8] = {};
+  ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
 
-}  // namespace bce
+// What BCE_DEC_TIMING and BCE_ALLOC_TRACE report about the rounds
+struct DecStats {
+  double t_q = 0, t_copy = 0, t_host = 0, t_c = 0;      // query pass, copy out, host decoders, children pass (and the rest)
+  uint64_t tail_rounds = 0, mbox_rounds = 0, small_rounds = 0, grouped_rounds = 0, list_grows = 0;
+  size_t peak_used = 0;                                 // device memory in use, sampled after every allocation stage
+  // six-launch rounds: their time, launching the first query passes, waiting for the first plane's, all lanes started,
+  // waiting for the decoders, the last children pass; the lanes' begin / end times (dbg_r) and which plane ended last
+  uint64_t split_rounds = 0;
+  double t_split = 0, ts_issue = 0, ts_first = 0, ts_lanes = 0, ts_wait = 0, ts_rb = 0;
+  double dbg_r[5] = {0, 0, 0, 0, 0};
+  uint32_t dbg_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  uint64_t wide_hist[32] = {0}, wide_nodes[32] = {0};   // rounds outside the tail by log2 of their node count
+  double wide_time[32] = {0};
+  uint64_t launches_wave = 0, launches_wg = 0, rounds_wave = 0, rounds_wg = 0, nodes_wave = 0, nodes_wg = 0;
+  double t_wave = 0, t_wg = 0;
+};
 
-using namespace bce;
+// How a round outside the tail kernels runs (Decode::plan)
+struct RoundPlan {
+  bool small, direct, lanes;   // one launch per pass (dec_small_kernel); queries and answers in pinned memory; six launches
+  uint32_t ord[8];             // the planes, busiest first in six-launch rounds
+  uint32_t gm[8];              // the plane groups (masks), ng of them
+  int ng;
+  uint64_t gmax;               // the most nodes of a group
+  uint32_t grid, hb;           // the passes' grid; log2 of the node count (BCE_DEC_TIMING)
+  double t0;                   // when the round began (BCE_DEC_TIMING)
+};
 
-// `bce -d` on the GPU: archive -> original bytes (see the header of this file).  The context is only used for its
-// device, stream and scratch buffers; any compression state in it is dropped.
-static int decompress_device_body(bce_hip_ctx *c, const uint8_t *archive, size_t len, uint8_t *out, size_t cap, size_t *out_len);
-extern "C" int bce_hip_decompress_device(bce_hip_ctx *c, const uint8_t *archive, size_t len, uint8_t *out, size_t cap,
-                                         size_t *out_len) {
-  return bce_guarded(c, [&] { return decompress_device_body(c, archive, len, out, cap, out_len); });
-}
-static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t len, uint8_t *out, size_t cap, size_t *out_len);
-static int decompress_device_body(bce_hip_ctx *c, const uint8_t *archive, size_t len, uint8_t *out, size_t cap, size_t *out_len) {
-  if (!c) return BCE_HIP_E_ARG;
-  struct PartEnd { bce_hip_ctx *c; ~PartEnd() { c->dec_part = 0; } } part_end{c};
-  return decompress_device_once(c, archive, len, out, cap, out_len);
-}
-static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t len, uint8_t *out, size_t cap, size_t *out_len) {
-  if (!c || !archive || !out_len) return BCE_HIP_E_ARG;
-  ArchiveHead hd;
-  if (parse_archive(archive, len, hd, /*header_only=*/true) != 0) return BCE_HIP_E_ARG;
-  *out_len = hd.n;
-  if (!out) return BCE_HIP_OK;
-  if (cap < hd.n) return BCE_HIP_E_OVERFLOW;
-  if (parse_archive(archive, len, hd, false) != 0) return BCE_HIP_E_ARG;
-  BCE_HIP_TRY(c, hipSetDevice(c->device));
-  c->coder->drain();
-  c->stage = 0; c->enum_active = false; c->k1_valid = false;   // the scratch buffers below belong to the decoder now
-  c->phase = 4;
-  struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
-  const uint32_t n = hd.n;
-  const bool timing = getenv("BCE_DEC_TIMING") != nullptr;
-  double tp0 = now_s();
+uint32_t plane_words(uint32_t n) { return (uint32_t)(((uint64_t)n + 31) / 32) + 3; }   // of a plane's bits, with slack
+uint32_t plane_granules(uint32_t n) { return (uint32_t)((uint64_t)n / 96) + 2; }
 
-  // ---- buffers ----
-  const size_t rstride = (size_t)n + 1;
-  c->dec_part = 1;
+// One decode: the state its stages share.  decompress_device runs the stages in order.
+struct Decode {
+  bce_hip_ctx *c;
+  const DecEnv env = dec_env();
+  ArchiveHead &hd;
+  const uint32_t n;
+  const size_t rstride;                                        // of the boundary ranks R[8][n + 1]
+  const uint32_t full_cap;                                     // the largest node list a decode can need
   DecArgs a;
-  const uint32_t full_cap = dec_full_capP(n);
-  uint32_t max_cap = 0;
-  {
+  DecCtl ctl;                                                  // the control block as last read back
+  DecInfo *info = nullptr;
+  DecStats st;
+  double tp0 = now_s(), t0 = 0;                                // when the stage / the round began
+  // (query, escape-record and answer buffers stay with the context: pinning their ~150 MB anew was 0.05 s of every decode)
+  Pinned pin_info, pin_q, pin_e, pin_res;
+  Events ev;
+  QueryPool pool;
+  Mailbox mbox;                                                // of the wave tail kernel (see DecArgs::mbox)
+  BigPin big_pin;
+  DevBuf &Qbuf, &Ebuf, &Rsbuf;                                 // queries / escape queries / answers of a round (device side)
+  uint32_t *d_rounds = nullptr;                                // what a tail kernel launch did
+  // the rounds
+  uint64_t cur_nodes = 0, nodes_total = 0, queries_total = 0;
+  uint32_t round = 0;
+  bool answered_pending = false;                               // pin_res holds the answers of the round about to run
+  uint32_t next_seq = 1, last_answered = 0;                    // mailbox query rounds
+  uint32_t prev_qtot[8] = {0, 0, 0, 0, 0, 0, 0, 0};            // each plane's queries in the last round
+  const uint64_t budget;                                       // nodes whose queries one pass of a round holds (see the plane groups)
+  const bool host_tail_ok;
+  bool host_has_ccx = false;
+  uint32_t tail_after = 0;                                     // wave kernel rounds after which a chain goes to the host
+  const uint64_t tail_min;                                     // nodes still to come that make a tail worth a copy of the ranks
+  // Query-heavy tails (executables: something is coded in half of the rounds) go to the host as a whole: a query round costs the
+  // resident kernels a mailbox round trip (~10 us), the host -- eight threads, one per plane -- nothing.  Whether a tail is
+  // query-heavy is measured: the first kProbeRounds rounds of the tail kernels count their mailbox rounds.
+  static constexpr uint32_t kProbeRounds = 1024;
+  uint32_t probe_rounds = 0;
+  uint64_t probe_mbox0 = 0;
+  bool probe_done, query_heavy = false;
+
+  Decode(bce_hip_ctx *ctx, ArchiveHead &h)
+      : c(ctx), hd(h), n(h.n), rstride((size_t)h.n + 1), full_cap(dec_full_capP(h.n)),
+        pin_q(&ctx->dec_pin[0], &ctx->dec_pin_cap[0]), pin_e(&ctx->dec_pin[1], &ctx->dec_pin_cap[1]),
+        pin_res(&ctx->dec_pin[2], &ctx->dec_pin_cap[2]), Qbuf(ctx->skey[0]), Ebuf(ctx->skey[1]), Rsbuf(ctx->sesc),
+        budget(dec_budget(ctx)), host_tail_ok(!env.no_host_tail), tail_min((h.n >> 6) + (1u << 18)),
+        probe_done(env.no_probe) {
+    big_pin.timing = env.timing;
+    if (env.force_host_tail) { probe_done = true; query_heavy = true; }
+  }
+  uint64_t left() const { return 8ull * (n - 1u) - nodes_total; }   // nodes still to come
+  void sample_mem() {
+    size_t fr = 0, tot = 0;
+    if (env.mem() && hipMemGetInfo(&fr, &tot) == hipSuccess && tot - fr > st.peak_used) st.peak_used = tot - fr;
+  }
+  void progress() { if (c->progress) c->progress(nodes_total, 8ull * n, c->progress_user); }
+  void children_pass(uint32_t grid) {                          // the children and new boundary ranks of the planes in a.pmask
+    hipLaunchKernelGGL((dec_tiles_kernel<2>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+    hipLaunchKernelGGL((dec_scan_kernel<false>), dim3(8), dim3(1024), 0, c->stream, a);
+    hipLaunchKernelGGL((dec_tiles_kernel<3>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+  }
+  void query_pass(uint32_t grid) {                             // ... and their queries (count / scan / write, as both)
+    hipLaunchKernelGGL((dec_tiles_kernel<0>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+    hipLaunchKernelGGL((dec_scan_kernel<true>), dim3(8), dim3(1024), 0, c->stream, a);
+    hipLaunchKernelGGL((dec_tiles_kernel<1>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+  }
+
+  // ---- lists, boundary ranks, roots ----
+  int setup(size_t archive_bytes) {
+    uint32_t max_cap = 0;
     bool forced = false;
-    const uint32_t start = dec_capP(c, n, len, &forced);
+    const uint32_t start = dec_capP(c, env, n, archive_bytes, &forced);
     for (int par = 0; par < 2; ++par)
       for (int p = 0; p < 8; ++p) {
         uint64_t lc = start;
@@ -1764,280 +1869,239 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
         a.list[par][p] = c->dlist[par][p].as<Node>();
         if (lc > max_cap) max_cap = (uint32_t)lc;
       }
-  }
-  BCE_TRY(ensure(c, c->ctl, sizeof(DecCtl) > sizeof(EnumCtl) ? sizeof(DecCtl) : sizeof(EnumCtl)));
-  const size_t max_tiles = (size_t)8 * ((max_cap + K3_TILE - 1) / K3_TILE + 1);
-  BCE_TRY(ensure(c, c->tilecnt, max_tiles * 16));
-  BCE_TRY(ensure(c, c->tileoff, max_tiles * 16));
-  DevBuf &Rbuf = c->dfs;                                        // 8 x (n + 1) boundary ranks
-  BCE_TRY(ensure(c, Rbuf, 8 * rstride * 4));
-  uint32_t *R = Rbuf.as<uint32_t>();
-  BCE_HIP_TRY(c, hipMemsetAsync(R, 0xFF, 8 * rstride * 4, c->stream));
-  DecCtl ctl;
-  memset(&ctl, 0, sizeof ctl);
-  for (int i = 0; i < 8; ++i) {
-    const uint32_t zero = 0, ones = n - hd.C[i];               // R[p][0] = 0, R[(i+7)&7][n] = n - C[i]  (:1207-1211)
-    BCE_HIP_TRY(c, hipMemcpyAsync(R + (size_t)i * rstride, &zero, 4, hipMemcpyHostToDevice, c->stream));
-    BCE_HIP_TRY(c, hipMemcpyAsync(R + (size_t)((i + 7) & 7) * rstride + n, &ones, 4, hipMemcpyHostToDevice, c->stream));
-    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));            // stack temporaries
-    if (hd.C[i] && n - hd.C[i]) {                               // :1214-1216
-      const Node root = {0u, hd.C[i], n - hd.C[i]};
-      BCE_HIP_TRY(c, hipMemcpyAsync(a.list[0][i], &root, sizeof root, hipMemcpyHostToDevice, c->stream));
-      BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-      ctl.cnt[0][i][0] = 1;
+    BCE_TRY(ensure(c, c->ctl, sizeof(DecCtl) > sizeof(EnumCtl) ? sizeof(DecCtl) : sizeof(EnumCtl)));
+    const size_t max_tiles = (size_t)8 * ((max_cap + K3_TILE - 1) / K3_TILE + 1);
+    BCE_TRY(ensure(c, c->tilecnt, max_tiles * 16));
+    BCE_TRY(ensure(c, c->tileoff, max_tiles * 16));
+    DevBuf &Rbuf = c->dfs;                                        // 8 x (n + 1) boundary ranks
+    BCE_TRY(ensure(c, Rbuf, 8 * rstride * 4));
+    uint32_t *R = Rbuf.as<uint32_t>();
+    BCE_HIP_TRY(c, hipMemsetAsync(R, 0xFF, 8 * rstride * 4, c->stream));
+    memset(&ctl, 0, sizeof ctl);
+    for (int i = 0; i < 8; ++i) {
+      const uint32_t zero = 0, ones = n - hd.C[i];               // R[p][0] = 0, R[(i+7)&7][n] = n - C[i]  (:1207-1211)
+      BCE_HIP_TRY(c, hipMemcpyAsync(R + (size_t)i * rstride, &zero, 4, hipMemcpyHostToDevice, c->stream));
+      BCE_HIP_TRY(c, hipMemcpyAsync(R + (size_t)((i + 7) & 7) * rstride + n, &ones, 4, hipMemcpyHostToDevice, c->stream));
+      BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));            // stack temporaries
+      if (hd.C[i] && n - hd.C[i]) {                               // :1214-1216
+        const Node root = {0u, hd.C[i], n - hd.C[i]};
+        BCE_HIP_TRY(c, hipMemcpyAsync(a.list[0][i], &root, sizeof root, hipMemcpyHostToDevice, c->stream));
+        BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+        ctl.cnt[0][i][0] = 1;
+      }
     }
-  }
-  BCE_HIP_TRY(c, hipMemcpyAsync(c->ctl.p, &ctl, sizeof ctl, hipMemcpyHostToDevice, c->stream));
-  BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  // (query, escape-record and answer buffers stay with the context: pinning their ~150 MB anew was 0.05 s of every decode)
-  Pinned pin_info, pin_q(&c->dec_pin[0], &c->dec_pin_cap[0]), pin_e(&c->dec_pin[1], &c->dec_pin_cap[1]), pin_res(&c->dec_pin[2], &c->dec_pin_cap[2]);
-  struct Events {
-    hipEvent_t e[8] = {};
-    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-  } ev;
-  uint32_t prev_qtot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint64_t split_rounds = 0;
-  double dbg_r[5] = {0, 0, 0, 0, 0};
-  uint32_t dbg_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double t_split = 0, ts_issue = 0, ts_first = 0, ts_lanes = 0, ts_wait = 0, ts_rb = 0;
-  const bool no_split = getenv("BCE_DEC_NO_SPLIT") != nullptr;
-  const uint64_t budget = dec_budget(c);                       // nodes whose queries one pass of a round holds (see the plane groups)
-  uint64_t grouped_rounds = 0, list_grows = 0;
-  const bool trace_mem = timing || getenv("BCE_ALLOC_TRACE") != nullptr;
-  size_t peak_used = 0;                                        // device memory in use, sampled after every allocation stage (BCE_DEC_TIMING / BCE_ALLOC_TRACE)
-  auto sample_mem = [&] {
-    size_t fr = 0, tot = 0;
-    if (trace_mem && hipMemGetInfo(&fr, &tot) == hipSuccess && tot - fr > peak_used) peak_used = tot - fr;
-  };
-  BCE_TRY(pin_info.ensure(c, sizeof(DecInfo), 4096));          // (a few words: not the 16 MB the query buffers start with -- 4 ms of pinning per decode)
-  DecInfo *info = static_cast<DecInfo *>(pin_info.p);
-  memset(info, 0, sizeof *info);
+    BCE_HIP_TRY(c, hipMemcpyAsync(c->ctl.p, &ctl, sizeof ctl, hipMemcpyHostToDevice, c->stream));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    BCE_TRY(pin_info.ensure(c, sizeof(DecInfo), 4096));          // (a few words: not the 16 MB the query buffers start with -- 4 ms of pinning per decode)
+    info = static_cast<DecInfo *>(pin_info.p);
+    memset(info, 0, sizeof *info);
 
-  a.ctl = c->ctl.as<DecCtl>();
-  a.info = info;                                                // pinned host memory is device-accessible at the same address
-  a.R = R;
-  a.tilecnt = c->tilecnt.as<uint32_t>();
-  a.tileoff = c->tileoff.as<uint32_t>();
-  a.n = n;
-  for (int p = 0; p < 8; ++p) a.zeros[p] = hd.C[(p + 1) & 7];
-  {
-    PlaneCfg hcfg[8];
-    for (int p = 0; p < 8; ++p) hcfg[p] = hd.dec[p].cfg;
-    BCE_TRY(ensure(c, c->dcfg, sizeof hcfg));
-    BCE_HIP_TRY(c, hipMemcpy(c->dcfg.p, hcfg, sizeof hcfg, hipMemcpyHostToDevice));
-    a.cfg = c->dcfg.as<PlaneCfg>();
-  }
-  DevBuf &Qbuf = c->skey[0], &Ebuf = c->skey[1], &Rsbuf = c->sesc;   // queries / escape queries / answers of a round (device side)
-  QueryPool pool;
-  pool.dec = &hd.dec;
-  pool.start();
-
-  if (timing) { fprintf(stderr, "gpu decode: setup %.3f s\n", now_s() - tp0); tp0 = now_s(); }
-  // ---- the rounds (BCE::code mode 0, :1246-1371) ----
-  uint64_t cur_nodes = 0;
-  for (int i = 0; i < 8; ++i) cur_nodes += ctl.cnt[0][i][0];
-  uint32_t round = 0;
-  uint64_t nodes_total = 0, queries_total = 0;
-  double t_q = 0, t_copy = 0, t_host = 0, t_c = 0;
-  uint64_t tail_rounds = 0;
-  bool answered_pending = false;                              // pin_res holds the answers of the round about to run
-  Mailbox mbox;                                               // of the wave tail kernel (see DecArgs::mbox)
-  if (!getenv("BCE_DEC_NO_MAILBOX")) BCE_TRY(mbox.open(c));
-  uint32_t next_seq = 1, last_answered = 0;
-  const bool host_tail_ok = !getenv("BCE_DEC_NO_HOST_TAIL");
-  // (ski rental: the copies cost ~1.2 ns per input byte, a round ~1.0 us less on the host than in the wave kernel, so the
-  //  switch pays once n / 830 rounds are still to come -- which nobody knows -- and is made after that many have gone by)
-  const uint32_t kHostTailAfter = n / 2500u > kHostTailMin ? n / 2500u : kHostTailMin;
-  // Query-heavy tails (executables: something is coded in half of the rounds) go to the host as a whole: a query round costs the
-  // resident kernels a mailbox round trip (~10 us), the host -- eight threads, one per plane -- nothing.  Whether a tail is
-  // query-heavy is measured: the first kProbeRounds rounds of the tail kernels count their mailbox rounds.
-  constexpr uint32_t kProbeRounds = 1024;
-  uint32_t probe_rounds = 0;
-  uint64_t probe_mbox0 = 0;
-  bool probe_done = getenv("BCE_DEC_NO_PROBE") != nullptr, query_heavy = false;
-  if (getenv("BCE_DEC_FORCE_HOST_TAIL")) { probe_done = true; query_heavy = true; }
-  // With eight CPUs on one L3 for its threads the host does a node of a tail round in ~20 ns (measured: 18.8 M nodes of the
-  // binary corpus in 0.37 s, against 1.4 s in the resident kernels; the natural corpus' 20 M nodes in 0.6 s against 1.1 s):
-  // then every tail that is worth the copy goes there and nothing is probed.
-  // ... every LONG tail, that is: the copy and the threads cost ~0.1 s, which a tail of a few hundred rounds (text) does not have
-  // to spare -- so the resident kernels always get the first kProbeRounds rounds.
-  const size_t tail_ncpu = tail_cpus().size();
-  const bool host_has_ccx = std::thread::hardware_concurrency() >= 8u && !getenv("BCE_DEC_TAIL_SERIAL") && tail_ncpu == 8;
-  if (timing) fprintf(stderr, "gpu decode: host tail CPUs: %zu of one L3 domain in the affinity mask, %u hardware threads: tails go to the host early %d\n",
-                      tail_ncpu, std::thread::hardware_concurrency(), (int)host_has_ccx);
-  uint64_t wide_hist[32] = {0}, wide_nodes[32] = {0}, small_rounds = 0;
-  double wide_time[32] = {0};
-  constexpr uint64_t kDirectNodes = 1u << 18;
-  const bool no_small = getenv("BCE_DEC_NO_SMALL") != nullptr;
-  BCE_TRY(ensure(c, c->smwords, (size_t)DS_MAXTILES * 8));
-  BCE_HIP_TRY(c, hipMemsetAsync(c->smwords.p, 0, (size_t)DS_MAXTILES * 8, c->stream));      // pass tags of an earlier decode
-  a.words = c->smwords.as<unsigned long long>();
-  uint64_t mbox_rounds = 0, launches_wave = 0, launches_wg = 0, rounds_wg = 0, nodes_wave = 0, nodes_wg = 0, rounds_wave = 0;
-  double t_wave = 0, t_wg = 0;
-  BCE_TRY(ensure(c, c->runs, 64));
-  uint32_t *d_rounds = c->runs.as<uint32_t>();
-  // Rounds of a few thousand nodes cost the GPU ~40 us each (two launches, two syncs) whatever they hold; eight host threads
-  // do 8192 nodes in about that time and 1024 in a tenth of it.  Where the host takes the tail anyway (a CCX for its
-  // threads) it takes it from here on, provided the tail is LONG -- at least 512 more rounds at the present width, and worth
-  // the copy of the ranks: text's few hundred tail rounds stay on the device.
-  BigPin big_pin;
-  uint32_t host_enter = 8192;
-  if (const char *e = getenv("BCE_DEC_HOST_ENTER")) host_enter = (uint32_t)strtoul(e, nullptr, 10);
-  while (cur_nodes) {
-    double t0 = now_s();
-    a.par = round & 1u;
+    a.ctl = c->ctl.as<DecCtl>();
+    a.info = info;                                                // pinned host memory is device-accessible at the same address
+    a.R = R;
+    a.tilecnt = c->tilecnt.as<uint32_t>();
+    a.tileoff = c->tileoff.as<uint32_t>();
+    a.n = n;
+    for (int p = 0; p < 8; ++p) a.zeros[p] = hd.C[(p + 1) & 7];
     {
-      const uint64_t left = 8ull * (n - 1u) - nodes_total;
-      // past the half-way mark with 64 rounds' worth of the present width still to come: the widths of text fall
-      // geometrically from their peak (the ratio stays under ~50 until next to nothing is left), a long tail does not
-      if (host_tail_ok && host_has_ccx && !big_pin.running && left <= 4ull * (n - 1u) && left >= (n >> 6) + (1u << 18) &&
-          left >= 64ull * cur_nodes && !getenv("BCE_DEC_NO_EARLY_PIN"))
+      PlaneCfg hcfg[8];
+      for (int p = 0; p < 8; ++p) hcfg[p] = hd.dec[p].cfg;
+      BCE_TRY(ensure(c, c->dcfg, sizeof hcfg));
+      BCE_HIP_TRY(c, hipMemcpy(c->dcfg.p, hcfg, sizeof hcfg, hipMemcpyHostToDevice));
+      a.cfg = c->dcfg.as<PlaneCfg>();
+    }
+    pool.dec = &hd.dec;
+    pool.start();
+
+    if (env.timing) { fprintf(stderr, "gpu decode: setup %.3f s\n", now_s() - tp0); tp0 = now_s(); }
+    for (int i = 0; i < 8; ++i) cur_nodes += ctl.cnt[0][i][0];
+    if (!env.no_mailbox) BCE_TRY(mbox.open(c));
+    // (ski rental: the copies cost ~1.2 ns per input byte, a round ~1.0 us less on the host than in the wave kernel, so the
+    //  switch pays once n / 830 rounds are still to come -- which nobody knows -- and is made after that many have gone by)
+    tail_after = n / 2500u > kHostTailMin ? n / 2500u : kHostTailMin;
+    // With eight CPUs on one L3 for its threads the host does a node of a tail round in ~20 ns (measured: 18.8 M nodes of the
+    // binary corpus in 0.37 s, against 1.4 s in the resident kernels; the natural corpus' 20 M nodes in 0.6 s against 1.1 s):
+    // then every tail that is worth the copy goes there and nothing is probed.
+    // ... every LONG tail, that is: the copy and the threads cost ~0.1 s, which a tail of a few hundred rounds (text) does not have
+    // to spare -- so the resident kernels always get the first kProbeRounds rounds.
+    const size_t tail_ncpu = tail_cpus(env).size();
+    host_has_ccx = std::thread::hardware_concurrency() >= 8u && !env.tail_serial && tail_ncpu == 8;
+    if (env.timing) fprintf(stderr, "gpu decode: host tail CPUs: %zu of one L3 domain in the affinity mask, %u hardware threads: tails go to the host early %d\n",
+                            tail_ncpu, std::thread::hardware_concurrency(), (int)host_has_ccx);
+    BCE_TRY(ensure(c, c->smwords, (size_t)DS_MAXTILES * 8));
+    BCE_HIP_TRY(c, hipMemsetAsync(c->smwords.p, 0, (size_t)DS_MAXTILES * 8, c->stream));      // pass tags of an earlier decode
+    a.words = c->smwords.as<unsigned long long>();
+    BCE_TRY(ensure(c, c->runs, 64));
+    d_rounds = c->runs.as<uint32_t>();
+    return BCE_HIP_OK;
+  }
+
+  // ---- the rounds (BCE::code mode 0, :1246-1371) ----
+  int rounds() {
+    while (cur_nodes) {
+      t0 = now_s();
+      a.par = round & 1u;
+      // Rounds of a few thousand nodes cost the GPU ~40 us each (two launches, two syncs) whatever they hold; eight host threads
+      // do 8192 nodes in about that time and 1024 in a tenth of it.  Where the host takes the tail anyway (a CCX for its
+      // threads) it takes it from here on, provided the tail is LONG -- at least 512 more rounds at the present width, and worth
+      // the copy of the ranks: text's few hundred tail rounds stay on the device.
+      // (past the half-way mark with 64 rounds' worth of the present width still to come, its pinned buffer is started: the
+      //  widths of text fall geometrically from their peak -- the ratio stays under ~50 until next to nothing is left --, a long
+      //  tail does not)
+      if (host_tail_ok && host_has_ccx && !big_pin.running && left() <= 4ull * (n - 1u) && left() >= tail_min &&
+          left() >= 64ull * cur_nodes && !env.no_early_pin)
         big_pin.start(c, 8 * ((size_t)n + 1) * 4);
-      if (host_tail_ok && host_has_ccx && !answered_pending && !getenv("BCE_DEC_NO_TAIL") && cur_nodes <= host_enter &&
-          left >= (n >> 6) + (1u << 18) && left >= 512ull * cur_nodes && left <= 8ull * (n - 1u) / 8u) {
-        bool bad = false;
-        const double th = now_s();
-        const uint32_t r0 = round;
-        big_pin.settle();
-        BCE_TRY(dec_host_tail(c, a, ctl, hd.dec, n, &round, &nodes_total, &queries_total, &bad));
-        if (bad) { snprintf(c->err, sizeof c->err, "decode: inconsistent archive (round %u)", round); return BCE_HIP_E_INTERNAL; }
-        if (timing) fprintf(stderr, "gpu decode: %u rounds of the tail on the host from %llu nodes a round on, %.3f s with the copies\n", round - r0, (unsigned long long)cur_nodes, now_s() - th);
-        t_c += now_s() - t0;
-        cur_nodes = 0;
+      if (host_tail_ok && host_has_ccx && !answered_pending && !env.no_tail && cur_nodes <= env.host_enter &&
+          left() >= tail_min && left() >= 512ull * cur_nodes && left() <= 8ull * (n - 1u) / 8u) {
+        BCE_TRY(to_host("tail", true));
+        st.t_c += now_s() - t0;
         break;
       }
-    }
-    if (cur_nodes <= DT_ENTER && !getenv("BCE_DEC_NO_TAIL")) {
-      // Few nodes: the tail kernels run the forced rounds on the device; at a round with queries the workgroup kernel
-      // emits them straight into pinned memory, the host answers (inline: they are few) and the kernel resumes with
-      // the answers -- one launch and one sync per query round.
-      BCE_TRY(pin_q.ensure(c, (size_t)(DT_CAP + 16) * 4));
-      BCE_TRY(pin_e.ensure(c, (size_t)(DT_CAP + 16) * sizeof(uint4)));
-      BCE_TRY(pin_res.ensure(c, (size_t)(DT_CAP + 16) * 4));
-      DecArgs at = a;
-      at.Q = static_cast<uint32_t *>(pin_q.p);
-      at.E = static_cast<uint4 *>(pin_e.p);
-      at.res = static_cast<const uint32_t *>(pin_res.p);
-      bool resume = false, force_wg = false;
-      answered_pending = false;
-      auto answer_round = [&]() -> uint64_t {                   // the queries in pin_q / pin_e -> answers in pin_res
-        const DecInfo in = *info;
-        uint64_t qt = 0;
-        for (int p = 0; p < 8; ++p) {
-          QueryPool::answer(hd.dec[p], at.Q + in.qbase[p], at.E + in.ebase[p], static_cast<uint32_t *>(pin_res.p) + in.qbase[p], in.qtot[p]);
-          qt += in.qtot[p];
-        }
-        return qt;
-      };
-      for (;;) {
-        uint32_t done[5] = {0, 0, 0, 0, 0};
-        if (host_tail_ok && query_heavy && !resume && !answered_pending && cur_nodes && cur_nodes <= DT_CAP &&
-            8ull * (n - 1u) - nodes_total >= (n >> 6) + (1u << 18) && 8ull * (n - 1u) - nodes_total <= 8ull * (n - 1u) / 8u) {
-          // the whole tail on the host (see above): nothing of this round has been asked or answered yet
-          bool bad = false;
-          const double th = now_s();
-          const uint32_t r0 = round;
-          big_pin.settle();
-        BCE_TRY(dec_host_tail(c, a, ctl, hd.dec, n, &round, &nodes_total, &queries_total, &bad));
-          if (bad) { snprintf(c->err, sizeof c->err, "decode: inconsistent archive (round %u)", round); return BCE_HIP_E_INTERNAL; }
-          if (timing) fprintf(stderr, "gpu decode: %u rounds of the tail on the host, %.3f s with the copies\n", round - r0, now_s() - th);
-          cur_nodes = 0;
-          break;
-        }
-        const bool wave = !force_wg && cur_nodes <= 64;
-        at.par = round & 1u;
-        const double t_launch = now_s();
-        at.mbox = mbox.dev;
-        at.seq_base = next_seq;
-        if (at.mbox) __atomic_store_n(&mbox.host[2], 0u, __ATOMIC_RELEASE);
-        const uint64_t all_nodes = 8ull * (n - 1u);
-        const bool probing = host_tail_ok && !probe_done && all_nodes - nodes_total >= (n >> 6) + (1u << 18);   // (a tail worth a copy of the ranks)
-        if (probing && probe_rounds == 0) probe_mbox0 = mbox_rounds;
-        const uint32_t probe_left = kProbeRounds > probe_rounds ? kProbeRounds - probe_rounds : 1u;
-        const uint32_t max_wave = !host_tail_ok ? (1u << 30) : (probing && probe_left < kHostTailAfter ? probe_left : kHostTailAfter);
-        if (wave) hipLaunchKernelGGL(dec_tail64_kernel, dim3(1), dim3(64), 0, c->stream, at, max_wave, d_rounds, resume ? 1u : 0u);
-        else hipLaunchKernelGGL(dec_tail_kernel, dim3(1), dim3(DT_T), 0, c->stream, at, probing ? probe_left : (1u << 30), d_rounds, (resume ? 1u : 0u) | 2u);
-        if (at.mbox) {
-          // (before the copies below are queued: a device-to-host copy into pageable memory blocks the host until the kernel is done)
-          // the tail kernel stays resident over query rounds: serve its mailbox until it says it has left
-          const double t_poll = now_s();
-          for (uint32_t spins = 0;; ++spins) {
-            if (__atomic_load_n(&mbox.host[0], __ATOMIC_ACQUIRE) == next_seq) {
-              queries_total += answer_round();
-              __atomic_store_n(&mbox.host[1], next_seq, __ATOMIC_RELEASE);
-              last_answered = next_seq++;
-              ++mbox_rounds;
-              continue;
-            }
-            if (__atomic_load_n(&mbox.host[2], __ATOMIC_ACQUIRE)) break;
-            if ((spins & 1023u) == 1023u && (hipStreamQuery(c->stream) != hipErrorNotReady || now_s() - t_poll > 30.0)) break;   // a failed launch never raises the flag
-            __builtin_ia32_pause();
-          }
-        }
-        BCE_TRY(read_back(c, done, d_rounds, 20));
-        BCE_TRY(read_back(c, &ctl, c->ctl.p, sizeof ctl));
-        BCE_HIP_TRY(c, hipGetLastError());
-        if (getenv("BCE_DEC_TRACE")) fprintf(stderr, "tail: round %u wave %d resume %d -> done %u why %u next %llu\n", round, (int)wave, (int)resume, done[0], done[1], (unsigned long long)ctl.next_nodes);
-        round += done[0]; tail_rounds += done[0];
-        if (wave) { ++launches_wave; rounds_wave += done[0]; nodes_wave += ctl.nodes_total - nodes_total; t_wave += now_s() - t_launch; }
-        else { ++launches_wg; rounds_wg += done[0]; nodes_wg += ctl.nodes_total - nodes_total; t_wg += now_s() - t_launch; }
-        cur_nodes = ctl.next_nodes;
-        nodes_total = ctl.nodes_total;
-        // a resumed launch that could not even start its round (children outgrow the kernel, or an inconsistency):
-        // the decoders have ALREADY answered this round's queries -- whoever runs the round must reuse the answers
-        const bool stuck = done[4] != 0 && done[1] >= 2;          // the round the kernel stopped at has been answered already
-        resume = false;
-        force_wg = false;
-        if (done[1] == 1) {                                      // queries of round `round` are in pin_q / pin_e
-          // (a wave kernel that gave up waiting may have been answered through the mailbox at the same moment)
-          if (!(at.mbox && done[2] != 0 && done[2] == last_answered)) {
-            queries_total += answer_round();
-            if (at.mbox) { last_answered = done[2]; next_seq = done[2] + 1u; }
-          }
-          resume = true;
-          continue;
-        }
-        if (wave && done[1] == 2 && cur_nodes <= DT_CAP) {       // the children outgrow one wave: the workgroup kernel
-          force_wg = true;
-          resume = stuck;                                        // ... with the answers, if this round already has them
-          continue;
-        }
-        answered_pending = stuck;
-        if (probing) {
-          probe_rounds += done[0];
-          if (probe_rounds >= kProbeRounds) { probe_done = true; query_heavy = host_has_ccx || (mbox_rounds - probe_mbox0) * 3u >= probe_rounds * 2u; /* two rounds in three ask the decoders something */ }
-        }
-        if (host_tail_ok && done[1] == 0 && !stuck && cur_nodes &&
-            ((wave && done[0] >= kHostTailAfter && cur_nodes <= 64) || (query_heavy && cur_nodes <= DT_CAP))) {
-          // a long chain of a few nodes: the rest of the rounds on the host (dec_host_tail)
-          bool bad = false;
-          const double th = now_s();
-          const uint32_t r0 = round;
-          big_pin.settle();
-        BCE_TRY(dec_host_tail(c, a, ctl, hd.dec, n, &round, &nodes_total, &queries_total, &bad));
-          if (bad) { snprintf(c->err, sizeof c->err, "decode: inconsistent archive (round %u)", round); return BCE_HIP_E_INTERNAL; }
-          if (timing) fprintf(stderr, "gpu decode: %u rounds of the deep tail on the host, %.3f s with the copies\n", round - r0, now_s() - th);
-          cur_nodes = 0;
-          break;
-        }
-        if (done[1] == 0 && done[0] && cur_nodes && cur_nodes <= DT_ENTER) continue;   // handed back (few nodes again) or out of max_rounds
-        break;                                                   // nothing left, too many nodes (2) or an inconsistent node (3)
+      if (cur_nodes <= DT_ENTER && !env.no_tail) {
+        BCE_TRY(tail_kernels());
+        a.par = round & 1u;
+        st.t_c += now_s() - t0;
+        t0 = now_s();
+        progress();
+        if (!cur_nodes) break;
       }
-      a.par = round & 1u;
-      t_c += now_s() - t0;
-      t0 = now_s();
-      if (c->progress) c->progress(nodes_total, 8ull * n, c->progress_user);
-      if (!cur_nodes) break;
+      RoundPlan rp = {};
+      BCE_TRY(plan(rp));
+      uint64_t queries = 0;
+      BCE_TRY(rp.lanes ? lane_round(rp, &queries) : group_round(rp, &queries));
+      end_round(rp, queries);
     }
+    return BCE_HIP_OK;
+  }
+
+  // The rest of the rounds on the host (dec_host_tail).  The BCE_DEC_TIMING line names the `tail` and, if asked, the width it
+  // began at.
+  int to_host(const char *tail, bool say_width) {
+    bool bad = false;
+    const double th = now_s();
+    const uint32_t r0 = round;
+    big_pin.settle();
+    BCE_TRY(dec_host_tail(c, env, a, ctl, hd.dec, n, &round, &nodes_total, &queries_total, &bad));
+    if (bad) { snprintf(c->err, sizeof c->err, "decode: inconsistent archive (round %u)", round); return BCE_HIP_E_INTERNAL; }
+    if (env.timing) {
+      char width[64] = "";
+      if (say_width) snprintf(width, sizeof width, " from %llu nodes a round on", (unsigned long long)cur_nodes);
+      fprintf(stderr, "gpu decode: %u rounds of the %s on the host%s, %.3f s with the copies\n", round - r0, tail, width, now_s() - th);
+    }
+    cur_nodes = 0;
+    return BCE_HIP_OK;
+  }
+
+  uint64_t answer_tail(const DecArgs &at) {               // the queries in pin_q / pin_e -> answers in pin_res
+    const DecInfo in = *info;
+    uint64_t qt = 0;
+    for (int p = 0; p < 8; ++p) {
+      QueryPool::answer(hd.dec[p], at.Q + in.qbase[p], at.E + in.ebase[p], static_cast<uint32_t *>(pin_res.p) + in.qbase[p], in.qtot[p]);
+      qt += in.qtot[p];
+    }
+    return qt;
+  }
+
+  // Few nodes: the tail kernels run the forced rounds on the device; at a round with queries the workgroup kernel emits them
+  // straight into pinned memory, the host answers (inline: they are few) and the kernel resumes with the answers -- one launch
+  // and one sync per query round.
+  int tail_kernels() {
+    BCE_TRY(pin_q.ensure(c, (size_t)(DT_CAP + 16) * 4));
+    BCE_TRY(pin_e.ensure(c, (size_t)(DT_CAP + 16) * sizeof(uint4)));
+    BCE_TRY(pin_res.ensure(c, (size_t)(DT_CAP + 16) * 4));
+    DecArgs at = a;
+    at.Q = static_cast<uint32_t *>(pin_q.p);
+    at.E = static_cast<uint4 *>(pin_e.p);
+    at.res = static_cast<const uint32_t *>(pin_res.p);
+    bool resume = false, force_wg = false;
+    answered_pending = false;
+    for (;;) {
+      uint32_t done[5] = {0, 0, 0, 0, 0};
+      // the whole tail on the host (see above): nothing of this round has been asked or answered yet
+      if (host_tail_ok && query_heavy && !resume && !answered_pending && cur_nodes && cur_nodes <= DT_CAP && left() >= tail_min &&
+          left() <= 8ull * (n - 1u) / 8u)
+        return to_host("tail", false);
+      const bool wave = !force_wg && cur_nodes <= 64;
+      at.par = round & 1u;
+      const double t_launch = now_s();
+      at.mbox = mbox.dev;
+      at.seq_base = next_seq;
+      if (at.mbox) __atomic_store_n(&mbox.host[2], 0u, __ATOMIC_RELEASE);
+      const bool probing = host_tail_ok && !probe_done && left() >= tail_min;   // (a tail worth a copy of the ranks)
+      if (probing && probe_rounds == 0) probe_mbox0 = st.mbox_rounds;
+      const uint32_t probe_left = kProbeRounds > probe_rounds ? kProbeRounds - probe_rounds : 1u;
+      const uint32_t max_wave = !host_tail_ok ? (1u << 30) : (probing && probe_left < tail_after ? probe_left : tail_after);
+      if (wave) hipLaunchKernelGGL(dec_tail64_kernel, dim3(1), dim3(64), 0, c->stream, at, max_wave, d_rounds, resume ? 1u : 0u);
+      else hipLaunchKernelGGL(dec_tail_kernel, dim3(1), dim3(DT_T), 0, c->stream, at, probing ? probe_left : (1u << 30), d_rounds, (resume ? 1u : 0u) | 2u);
+      if (at.mbox) {
+        // (before the copies below are queued: a device-to-host copy into pageable memory blocks the host until the kernel is done)
+        // the tail kernel stays resident over query rounds: serve its mailbox until it says it has left
+        const double t_poll = now_s();
+        for (uint32_t spins = 0;; ++spins) {
+          if (__atomic_load_n(&mbox.host[0], __ATOMIC_ACQUIRE) == next_seq) {
+            queries_total += answer_tail(at);
+            __atomic_store_n(&mbox.host[1], next_seq, __ATOMIC_RELEASE);
+            last_answered = next_seq++;
+            ++st.mbox_rounds;
+            continue;
+          }
+          if (__atomic_load_n(&mbox.host[2], __ATOMIC_ACQUIRE)) break;
+          if ((spins & 1023u) == 1023u && (hipStreamQuery(c->stream) != hipErrorNotReady || now_s() - t_poll > 30.0)) break;   // a failed launch never raises the flag
+          __builtin_ia32_pause();
+        }
+      }
+      BCE_TRY(read_back(c, done, d_rounds, 20));
+      BCE_TRY(read_back(c, &ctl, c->ctl.p, sizeof ctl));
+      BCE_HIP_TRY(c, hipGetLastError());
+      if (env.trace) fprintf(stderr, "tail: round %u wave %d resume %d -> done %u why %u next %llu\n", round, (int)wave, (int)resume, done[0], done[1], (unsigned long long)ctl.next_nodes);
+      round += done[0]; st.tail_rounds += done[0];
+      if (wave) { ++st.launches_wave; st.rounds_wave += done[0]; st.nodes_wave += ctl.nodes_total - nodes_total; st.t_wave += now_s() - t_launch; }
+      else { ++st.launches_wg; st.rounds_wg += done[0]; st.nodes_wg += ctl.nodes_total - nodes_total; st.t_wg += now_s() - t_launch; }
+      cur_nodes = ctl.next_nodes;
+      nodes_total = ctl.nodes_total;
+      // a resumed launch that could not even start its round (children outgrow the kernel, or an inconsistency):
+      // the decoders have ALREADY answered this round's queries -- whoever runs the round must reuse the answers
+      const bool stuck = done[4] != 0 && done[1] >= 2;          // the round the kernel stopped at has been answered already
+      resume = false;
+      force_wg = false;
+      if (done[1] == 1) {                                      // queries of round `round` are in pin_q / pin_e
+        // (a wave kernel that gave up waiting may have been answered through the mailbox at the same moment)
+        if (!(at.mbox && done[2] != 0 && done[2] == last_answered)) {
+          queries_total += answer_tail(at);
+          if (at.mbox) { last_answered = done[2]; next_seq = done[2] + 1u; }
+        }
+        resume = true;
+        continue;
+      }
+      if (wave && done[1] == 2 && cur_nodes <= DT_CAP) {       // the children outgrow one wave: the workgroup kernel
+        force_wg = true;
+        resume = stuck;                                        // ... with the answers, if this round already has them
+        continue;
+      }
+      answered_pending = stuck;
+      if (probing) {
+        probe_rounds += done[0];
+        if (probe_rounds >= kProbeRounds) { probe_done = true; query_heavy = host_has_ccx || (st.mbox_rounds - probe_mbox0) * 3u >= probe_rounds * 2u; /* two rounds in three ask the decoders something */ }
+      }
+      if (host_tail_ok && done[1] == 0 && !stuck && cur_nodes &&
+          ((wave && done[0] >= tail_after && cur_nodes <= 64) || (query_heavy && cur_nodes <= DT_CAP)))
+        return to_host("deep tail", false);                    // a long chain of a few nodes: the rest of the rounds on the host
+      if (done[1] == 0 && done[0] && cur_nodes && cur_nodes <= DT_ENTER) continue;   // handed back (few nodes again) or out of max_rounds
+      return BCE_HIP_OK;                                       // nothing left, too many nodes (2) or an inconsistent node (3)
+    }
+  }
+
+  // How a round outside the tail kernels runs: its passes, the order of its planes, its plane groups and its buffers.
+  int plan(RoundPlan &rp) {
     // Rounds of up to kDirectNodes nodes exchange their queries and answers through pinned host memory (as the tail kernels do):
     // the kernels write / read it over the bus, and the round is two launches and two syncs with no copy in between.
     // (dec_small_kernel writes the children before it knows their number: only where twice the round's nodes fit every list)
+    constexpr uint64_t kDirectNodes = 1u << 18;
     uint32_t min_next_cap = ~0u;
     for (int p = 0; p < 8; ++p) min_next_cap = std::min(min_next_cap, a.cap[(round & 1u) ^ 1u][p]);
-    const bool small_round = cur_nodes <= DS_MAXNODES && !no_small && 2ull * cur_nodes <= min_next_cap && cur_nodes <= budget;
-    const bool direct = small_round && cur_nodes <= kDirectNodes && !answered_pending;
-    const bool small = small_round;                                // one launch per pass (dec_small_kernel)
-    const bool lanes = !small && !answered_pending && !no_split;   // six launches, plane by plane (see below)
+    rp.small = cur_nodes <= DS_MAXNODES && !env.no_small && 2ull * cur_nodes <= min_next_cap && cur_nodes <= budget;
+    rp.direct = rp.small && cur_nodes <= kDirectNodes && !answered_pending;
+    rp.lanes = !rp.small && !answered_pending && !env.no_split;  // six launches, plane by plane (see lane_round)
     uint64_t pnodes[8];
     for (int p = 0; p < 8; ++p) pnodes[p] = (uint64_t)ctl.cnt[round & 1u][p][0] + ctl.cnt[round & 1u][p][1];
     {
@@ -2049,41 +2113,39 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
       a.tilecnt = c->tilecnt.as<uint32_t>();
       a.tileoff = c->tileoff.as<uint32_t>();
     }
-    uint32_t ord[8] = {0, 1, 2, 3, 4, 5, 6, 7};
-    if (lanes) {
+    for (int i = 0; i < 8; ++i) rp.ord[i] = (uint32_t)i;
+    if (rp.lanes) {
       // (the bulk of the queries moves from plane p to plane p + 1 with every round -- a node's children are the next plane's
       //  nodes -- and the busiest decoder with it: plane p is as busy as plane p - 1 was last round.  Node counts say less:
       //  how many of a plane's nodes are forced differs from plane to plane.)
       uint64_t weight[8];
       for (int q = 0; q < 8; ++q) weight[q] = ((uint64_t)prev_qtot[(q + 7) & 7] << 1) + (pnodes[q] ? 1u : 0u);
-      std::stable_sort(ord, ord + 8, [&](uint32_t x, uint32_t y) { return weight[x] > weight[y]; });
+      std::stable_sort(rp.ord, rp.ord + 8, [&](uint32_t x, uint32_t y) { return weight[x] > weight[y]; });
     }
     // Plane groups: consecutive runs of `ord` (busiest first in the six-launch rounds, plane order otherwise) with at most `budget`
     // nodes together -- one group of all eight planes when the round is within the budget, which is then run exactly as it
     // always was.  A plane alone may hold more than the budget (up to n / 2 + 2 nodes): it is a group of its own.
-    uint32_t gm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int ng = 0;
-    uint64_t gmax = 0, emax = 0;
+    uint64_t emax = 0;
     {
       uint64_t acc = 0;
       for (int i = 0; i < 8; ++i) {
-        const uint32_t p = ord[i];
-        if (ng == 0 || acc + pnodes[p] > budget) { gm[ng++] = 0; acc = 0; }
-        gm[ng - 1] |= 1u << p;
+        const uint32_t p = rp.ord[i];
+        if (rp.ng == 0 || acc + pnodes[p] > budget) { rp.gm[rp.ng++] = 0; acc = 0; }
+        rp.gm[rp.ng - 1] |= 1u << p;
         acc += pnodes[p];
       }
-      for (int g = 0; g < ng; ++g) {
+      for (int g = 0; g < rp.ng; ++g) {
         uint64_t gn = 0;
-        for (int p = 0; p < 8; ++p) if ((gm[g] >> p) & 1u) gn += pnodes[p];
+        for (int p = 0; p < 8; ++p) if ((rp.gm[g] >> p) & 1u) gn += pnodes[p];
         // an escape query (k > 31) needs a node of at least 32 positions, and a plane's nodes are disjoint intervals of [0, n]:
         // at most n / 32 + 1 of them per plane, however many nodes the group holds
-        const uint64_t ebound = std::min<uint64_t>(gn, (uint64_t)__builtin_popcount(gm[g]) * ((uint64_t)n / 32 + 1));
-        gmax = std::max(gmax, gn);
+        const uint64_t ebound = std::min<uint64_t>(gn, (uint64_t)__builtin_popcount(rp.gm[g]) * ((uint64_t)n / 32 + 1));
+        rp.gmax = std::max(rp.gmax, gn);
         emax = std::max(emax, ebound);
       }
     }
-    if (ng > 1 && answered_pending) { snprintf(c->err, sizeof c->err, "decode: a resumed round of %llu nodes is over the query budget", (unsigned long long)cur_nodes); return BCE_HIP_E_INTERNAL; }
-    if (direct) {
+    if (rp.ng > 1 && answered_pending) { snprintf(c->err, sizeof c->err, "decode: a resumed round of %llu nodes is over the query budget", (unsigned long long)cur_nodes); return BCE_HIP_E_INTERNAL; }
+    if (rp.direct) {
       BCE_TRY(pin_q.ensure(c, (size_t)(cur_nodes + 16) * 4));
       BCE_TRY(pin_e.ensure(c, (size_t)(cur_nodes + 16) * sizeof(uint4)));
       BCE_TRY(pin_res.ensure(c, (size_t)(cur_nodes + 16) * 4));
@@ -2092,436 +2154,432 @@ static int decompress_device_once(bce_hip_ctx *c, const uint8_t *archive, size_t
       a.res = static_cast<const uint32_t *>(pin_res.p);
       a.ecap = cur_nodes + 16;
     } else {
-      BCE_TRY(ensure(c, Qbuf, (size_t)(gmax + 16) * 4));
+      BCE_TRY(ensure(c, Qbuf, (size_t)(rp.gmax + 16) * 4));
       BCE_TRY(ensure(c, Ebuf, (size_t)(emax + 16) * sizeof(uint4)));
-      BCE_TRY(ensure(c, Rsbuf, (size_t)(gmax + 16) * 4));
+      BCE_TRY(ensure(c, Rsbuf, (size_t)(rp.gmax + 16) * 4));
       a.Q = Qbuf.as<uint32_t>();
       a.E = Ebuf.as<uint4>();
       a.res = Rsbuf.as<uint32_t>();
       a.ecap = emax + 16;
     }
-    if (ng > 1) { ++grouped_rounds; c->dec_split_rounds++; }
+    if (rp.ng > 1) { ++st.grouped_rounds; c->dec_split_rounds++; }
     if (cur_nodes >= (1u << 20)) sample_mem();
-    uint64_t want = (cur_nodes + K3_TILE - 1) / K3_TILE + 8;
-    const uint32_t grid = (uint32_t)(want < 2048 ? want : 2048);
-    uint32_t hb = 0;
-    const double t_round0 = timing ? now_s() : 0.0;
-    if (timing) { while ((2ull << hb) <= cur_nodes && hb < 31) ++hb; wide_hist[hb]++; wide_nodes[hb] += cur_nodes; }
+    const uint64_t want = (cur_nodes + K3_TILE - 1) / K3_TILE + 8;
+    rp.grid = (uint32_t)(want < 2048 ? want : 2048);
+    rp.t0 = env.timing ? now_s() : 0.0;
+    if (env.timing) { while ((2ull << rp.hb) <= cur_nodes && rp.hb < 31) ++rp.hb; st.wide_hist[rp.hb]++; st.wide_nodes[rp.hb] += cur_nodes; }
     a.round = round;
-    // A children pass found that the children of the planes in `ovf` do not fit their lists (it wrote none of them; the counts
-    // are in the control block): each such list -- plane q + 1's of the next parity, which only plane q's pass writes, so it
-    // holds nothing yet -- is replaced by one of 1.25 x the need (exactly the need if the device has no more room, after the
-    // other phases' buffers have gone back), and the pass runs again from the answers already in the answer buffer.  A plane's
-    // decoder is never asked twice.
-    auto grow_lists = [&](uint32_t ovf) -> int {
-      const uint32_t out = (round & 1u) ^ 1u;
-      BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-      for (uint32_t q = 0; q < 8; ++q) {
-        if (!((ovf >> q) & 1u)) continue;
-        const uint32_t qn = (q + 1u) & 7u;
-        const uint64_t need = (uint64_t)ctl.cnt[out][qn][0] + ctl.cnt[out][qn][1];
-        const uint32_t had = a.cap[out][qn];
-        if (need <= had || need > full_cap) {
-          snprintf(c->err, sizeof c->err, "decode: round %u reports a list of %llu nodes (it holds %u, n = %u)", round, (unsigned long long)need, had, n);
-          return BCE_HIP_E_INTERNAL;
+    return BCE_HIP_OK;
+  }
+
+  // A six-launch round plane by plane.  The round's time is the busiest planes' sequential decoders (text: planes 0 and 1 hold
+  // half of all queries) with the query passes in front of them and the children passes behind.  The planes of a round do not
+  // meet (plane p's children are plane p + 1's nodes of the NEXT round), so each plane is a lane of its own -- query pass, copy
+  // out, decoder, answers in, children pass -- and the lanes start in the order of their node counts: the busiest decoder starts
+  // as soon as ITS queries are out and only its own children pass is left when it is done; everything else runs beside it.
+  // Over the query budget the lanes run group by group, each group with the whole query and answer buffers to itself.
+  int lane_round(const RoundPlan &rp, uint64_t *queries) {
+    const uint32_t *ord = rp.ord;
+    const double ts0 = now_s();
+    for (int i = 0; i < 8; ++i) if (!ev.e[i]) BCE_HIP_TRY(c, hipEventCreateWithFlags(&ev.e[i], hipEventDisableTiming));
+    uint32_t order = 0;
+    for (int i = 0; i < 8; ++i) order |= ord[i] << (4 * i);
+    BCE_TRY(pin_q.ensure(c, (size_t)(rp.gmax + 16) * 4));        // (a plane's queries lie at its base: the bases are exact, the size is a bound)
+    BCE_TRY(pin_res.ensure(c, (size_t)(rp.gmax + 16) * 4));
+    a.order = order;
+    a.final = 0;
+    uint64_t qtotal = 0;
+    uint32_t new_qtot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint32_t launched = 0;                                       // planes whose decoders ran (all groups)
+    int lo = 0;                                                  // the group's first lane in `ord`
+    for (int g = 0; g < rp.ng; ++g) {
+      const bool last_group = g + 1 == rp.ng;
+      const uint32_t gmask = rp.gm[g];
+      const int L = __builtin_popcount(gmask);
+      a.gmask = gmask;
+      auto ask = [&](int i) -> int {                             // the query pass of lane i of the group
+        a.pmask = 1u << ord[lo + i];
+        a.final = 0;
+        query_pass(rp.grid);
+        BCE_HIP_TRY(c, hipEventRecord(ev.e[i], c->stream));
+        return BCE_HIP_OK;
+      };
+      BCE_TRY(ask(0));                                           // (launching costs the host ~60 us a lane: the busiest decoder does not wait for all eight)
+      if (L > 1) BCE_TRY(ask(1));
+      const double tsa = now_s();
+      if (g == 0) st.ts_issue += tsa - ts0;
+      QueryPool::Job jobs[8] = {};
+      struct Settle {                                            // no decoder outlives this group (its buffers, an early return)
+        QueryPool &pool; uint32_t mask;
+        ~Settle() { if (mask) pool.wait(mask); }
+      } settle{pool, 0u};
+      uint32_t glaunched = 0, children_done = 0;                 // planes whose decoders run / whose children pass is queued
+      auto children = [&](uint32_t p, bool last) -> int {
+        if (jobs[p].cnt) BCE_HIP_TRY(c, hipMemcpyAsync(Rsbuf.as<uint32_t>() + (jobs[p].r - static_cast<uint32_t *>(pin_res.p)), jobs[p].r, (size_t)jobs[p].cnt * 4, hipMemcpyHostToDevice, c->stream));
+        a.pmask = 1u << p;
+        a.final = last && last_group ? 1u : 0u;
+        children_pass(rp.grid);
+        children_done |= 1u << p;
+        return BCE_HIP_OK;
+      };
+      for (int i = 0; i < L; ++i) {
+        const uint32_t p = ord[lo + i];
+        if (i > 0 && i + 1 < L) BCE_TRY(ask(i + 1));             // one lane ahead of the one being waited for
+        BCE_HIP_TRY(c, hipEventSynchronize(ev.e[i]));
+        if (i == 0 && g == 0) st.ts_first += now_s() - tsa;
+        const DecInfo in = *info;                                // (plane p's fields and those of the planes before it; the rest are being written)
+        if (in.err) { snprintf(c->err, sizeof c->err, "decode: inconsistent archive (round %u)", round); return BCE_HIP_E_INTERNAL; }
+        const uint32_t qn = in.qtot[p], en = in.etot[p], qb = in.qbase[p], eb = in.ebase[p];
+        new_qtot[p] = qn;
+        qtotal += qn;
+        if ((size_t)eb + en + 1 > pin_e.cap / sizeof(uint4)) {   // escape records are few, their number is not known ahead: grow between decoders
+          if (settle.mask) { pool.wait(settle.mask); }
+          BCE_TRY(pin_e.ensure(c, 2 * ((size_t)eb + en + 1) * sizeof(uint4)));
         }
-        release(c->dlist[out][qn]);
-        a.list[out][qn] = nullptr; a.cap[out][qn] = 0;
-        uint64_t want = need + need / 4;
-        if (want > full_cap) want = full_cap;
-        int rc = ensure(c, c->dlist[out][qn], (size_t)want * sizeof(Node), kAllocListFirst);
-        if (rc == BCE_HIP_E_NOMEM) {
-          want = need;
-          rc = ensure(c, c->dlist[out][qn], (size_t)want * sizeof(Node), kAllocListFallback);
+        if (qn) {
+          BCE_HIP_TRY(c, hipMemcpyAsync(static_cast<uint32_t *>(pin_q.p) + qb, a.Q + qb, (size_t)qn * 4, hipMemcpyDeviceToHost, c->copy_stream));
+          if (en) BCE_HIP_TRY(c, hipMemcpyAsync(static_cast<uint4 *>(pin_e.p) + eb, a.E + eb, (size_t)en * sizeof(uint4), hipMemcpyDeviceToHost, c->copy_stream));
+          BCE_HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
+          jobs[p] = QueryPool::Job{static_cast<const uint32_t *>(pin_q.p) + qb, static_cast<const uint4 *>(pin_e.p) + eb, static_cast<uint32_t *>(pin_res.p) + qb, qn};
+          pool.run_async(jobs, 1u << p);
+          settle.mask |= 1u << p;
+          glaunched |= 1u << p;
+        } else {
+          jobs[p] = QueryPool::Job{nullptr, nullptr, static_cast<uint32_t *>(pin_res.p) + qb, 0u};
+          BCE_TRY(children(p, i == L - 1 && (glaunched & ~children_done) == 0u));   // nothing to ask: its children pass at once (the round's last one only if nobody is out)
         }
-        if (rc != BCE_HIP_OK) {
-          if (rc == BCE_HIP_E_NOMEM) snprintf(c->err, sizeof c->err, "decode: no device memory for a node list of %llu nodes (round %u, n = %u)", (unsigned long long)need, round, n);
-          return rc;
-        }
-        a.list[out][qn] = c->dlist[out][qn].as<Node>();
-        a.cap[out][qn] = (uint32_t)want;
-        c->dec_list_grows++;
-        ++list_grows;
-        if (timing || getenv("BCE_ALLOC_TRACE"))
-          fprintf(stderr, "gpu decode: round %u does not fit the node lists: the children of plane %u (%llu nodes) in plane %u's list of %u (parity %u), grown in place to %llu\n",
-                  round, q, (unsigned long long)need, qn, had, out, (unsigned long long)want);
+        // decoders that have finished meanwhile: their children passes go out between the copies
+        const uint32_t fin = pool.done(glaunched & ~children_done);
+        for (uint32_t q = 0; q < 8; ++q)
+          if ((fin >> q) & 1u) { settle.mask &= ~(1u << q); BCE_TRY(children(q, i == L - 1 && (children_done | (1u << q)) == gmask)); }
       }
-      BCE_HIP_TRY(c, hipMemsetAsync(&a.ctl->ovf, 0, sizeof(uint32_t), c->stream));
-      return BCE_HIP_OK;
-    };
-    // after the children passes of a group, with `ctl` just read back: errors, and the lists that must grow
-    auto settle_group = [&]() -> int {
-      for (int tries = 0;; ++tries) {
-        if (ctl.err) {
-          if (ctl.err == 4) snprintf(c->err, sizeof c->err, "decode: a two-launch round waited too long for a predecessor tile (round %u)", round);
-          else if (ctl.err == 2) snprintf(c->err, sizeof c->err, "decode: node list overflow in a one-launch round (round %u)", round);
-          else snprintf(c->err, sizeof c->err, "decode: inconsistent archive (round %u)", round);
-          return BCE_HIP_E_INTERNAL;
-        }
-        if (!ctl.ovf) return BCE_HIP_OK;
-        if (tries == 2) { snprintf(c->err, sizeof c->err, "decode: node lists still too small after growing (round %u)", round); return BCE_HIP_E_INTERNAL; }
-        const uint32_t ovf = ctl.ovf;
-        BCE_TRY(grow_lists(ovf));
-        const uint32_t pm = a.pmask, fin = a.final;
-        a.pmask = ovf;
-        a.final = 0;                                               // (the round's totals were added up by its last pass already)
-        hipLaunchKernelGGL((dec_tiles_kernel<2>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-        hipLaunchKernelGGL((dec_scan_kernel<false>), dim3(8), dim3(1024), 0, c->stream, a);
-        hipLaunchKernelGGL((dec_tiles_kernel<3>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-        a.pmask = pm; a.final = fin;
-        BCE_TRY(read_back(c, &ctl, c->ctl.p, sizeof ctl));
-        BCE_HIP_TRY(c, hipGetLastError());
+      const double tsb = now_s();
+      st.ts_lanes += tsb - tsa;
+      while (children_done != gmask) {
+        const uint32_t fin = pool.wait_any(glaunched & ~children_done);
+        for (uint32_t q = 0; q < 8; ++q)
+          if ((fin >> q) & 1u) { settle.mask &= ~(1u << q); BCE_TRY(children(q, (children_done | (1u << q)) == gmask)); }
       }
-    };
-    if (lanes) {
-      // A six-launch round plane by plane.  The round's time is the busiest planes' sequential decoders (text: planes 0
-      // and 1 hold half of all queries) with the query passes in front of them and the children passes behind.  The planes
-      // of a round do not meet (plane p's children are plane p + 1's nodes of the NEXT round), so each plane is a lane of
-      // its own -- query pass, copy out, decoder, answers in, children pass -- and the lanes start in the order of their
-      // node counts: the busiest decoder starts as soon as ITS queries are out and only its own children pass is
-      // left when it is done; everything else runs beside it.  Over the query budget the lanes run group by group, each group
-      // with the whole query and answer buffers to itself.
-      const double ts0 = now_s();
-      for (int i = 0; i < 8; ++i) if (!ev.e[i]) BCE_HIP_TRY(c, hipEventCreateWithFlags(&ev.e[i], hipEventDisableTiming));
-      uint32_t order = 0;
-      for (int i = 0; i < 8; ++i) order |= ord[i] << (4 * i);
-      BCE_TRY(pin_q.ensure(c, (size_t)(gmax + 16) * 4));          // (a plane's queries lie at its base: the bases are exact, the size is a bound)
-      BCE_TRY(pin_res.ensure(c, (size_t)(gmax + 16) * 4));
-      a.order = order;
-      a.final = 0;
-      uint64_t qtotal = 0;
-      uint32_t new_qtot[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      uint32_t launched = 0;                                       // planes whose decoders ran (all groups)
-      int lo = 0;                                                  // the group's first lane in `ord`
-      for (int g = 0; g < ng; ++g) {
-        const bool last_group = g + 1 == ng;
-        const uint32_t gmask = gm[g];
-        const int L = __builtin_popcount(gmask);
-        a.gmask = gmask;
-        auto ask = [&](int i) -> int {                             // the query pass of lane i of the group
-          a.pmask = 1u << ord[lo + i];
-          a.final = 0;
-          hipLaunchKernelGGL((dec_tiles_kernel<0>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-          hipLaunchKernelGGL((dec_scan_kernel<true>), dim3(8), dim3(1024), 0, c->stream, a);
-          hipLaunchKernelGGL((dec_tiles_kernel<1>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-          BCE_HIP_TRY(c, hipEventRecord(ev.e[i], c->stream));
-          return BCE_HIP_OK;
-        };
-        BCE_TRY(ask(0));                                           // (launching costs the host ~60 us a lane: the busiest decoder does not wait for all eight)
-        if (L > 1) BCE_TRY(ask(1));
-        const double tsa = now_s();
-        if (g == 0) ts_issue += tsa - ts0;
-        QueryPool::Job jobs[8] = {};
-        struct Settle {                                            // no decoder outlives this group (its buffers, an early return)
-          QueryPool &pool; uint32_t mask;
-          ~Settle() { if (mask) pool.wait(mask); }
-        } settle{pool, 0u};
-        uint32_t glaunched = 0, children_done = 0;                 // planes whose decoders run / whose children pass is queued
-        auto children = [&](uint32_t p, bool last) -> int {
-          if (jobs[p].cnt) BCE_HIP_TRY(c, hipMemcpyAsync(Rsbuf.as<uint32_t>() + (jobs[p].r - static_cast<uint32_t *>(pin_res.p)), jobs[p].r, (size_t)jobs[p].cnt * 4, hipMemcpyHostToDevice, c->stream));
-          a.pmask = 1u << p;
-          a.final = last && last_group ? 1u : 0u;
-          hipLaunchKernelGGL((dec_tiles_kernel<2>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-          hipLaunchKernelGGL((dec_scan_kernel<false>), dim3(8), dim3(1024), 0, c->stream, a);
-          hipLaunchKernelGGL((dec_tiles_kernel<3>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-          children_done |= 1u << p;
-          return BCE_HIP_OK;
-        };
-        for (int i = 0; i < L; ++i) {
-          const uint32_t p = ord[lo + i];
-          if (i > 0 && i + 1 < L) BCE_TRY(ask(i + 1));             // one lane ahead of the one being waited for
-          BCE_HIP_TRY(c, hipEventSynchronize(ev.e[i]));
-          if (i == 0 && g == 0) ts_first += now_s() - tsa;
-          const DecInfo in = *info;                                // (plane p's fields and those of the planes before it; the rest are being written)
-          if (in.err) { snprintf(c->err, sizeof c->err, "decode: inconsistent archive (round %u)", round); return BCE_HIP_E_INTERNAL; }
-          const uint32_t qn = in.qtot[p], en = in.etot[p], qb = in.qbase[p], eb = in.ebase[p];
-          new_qtot[p] = qn;
-          qtotal += qn;
-          if ((size_t)eb + en + 1 > pin_e.cap / sizeof(uint4)) {   // escape records are few, their number is not known ahead: grow between decoders
-            if (settle.mask) { pool.wait(settle.mask); }
-            BCE_TRY(pin_e.ensure(c, 2 * ((size_t)eb + en + 1) * sizeof(uint4)));
-          }
-          if (qn) {
-            BCE_HIP_TRY(c, hipMemcpyAsync(static_cast<uint32_t *>(pin_q.p) + qb, a.Q + qb, (size_t)qn * 4, hipMemcpyDeviceToHost, c->copy_stream));
-            if (en) BCE_HIP_TRY(c, hipMemcpyAsync(static_cast<uint4 *>(pin_e.p) + eb, a.E + eb, (size_t)en * sizeof(uint4), hipMemcpyDeviceToHost, c->copy_stream));
-            BCE_HIP_TRY(c, hipStreamSynchronize(c->copy_stream));
-            jobs[p] = QueryPool::Job{static_cast<const uint32_t *>(pin_q.p) + qb, static_cast<const uint4 *>(pin_e.p) + eb, static_cast<uint32_t *>(pin_res.p) + qb, qn};
-            pool.run_async(jobs, 1u << p);
-            settle.mask |= 1u << p;
-            glaunched |= 1u << p;
-          } else {
-            jobs[p] = QueryPool::Job{nullptr, nullptr, static_cast<uint32_t *>(pin_res.p) + qb, 0u};
-            BCE_TRY(children(p, i == L - 1 && (glaunched & ~children_done) == 0u));   // nothing to ask: its children pass at once (the round's last one only if nobody is out)
-          }
-          // decoders that have finished meanwhile: their children passes go out between the copies
-          const uint32_t fin = pool.done(glaunched & ~children_done);
-          for (uint32_t q = 0; q < 8; ++q)
-            if ((fin >> q) & 1u) { settle.mask &= ~(1u << q); BCE_TRY(children(q, i == L - 1 && (children_done | (1u << q)) == gmask)); }
-        }
-        const double tsb = now_s();
-        ts_lanes += tsb - tsa;
-        while (children_done != gmask) {
-          const uint32_t fin = pool.wait_any(glaunched & ~children_done);
-          for (uint32_t q = 0; q < 8; ++q)
-            if ((fin >> q) & 1u) { settle.mask &= ~(1u << q); BCE_TRY(children(q, (children_done | (1u << q)) == gmask)); }
-        }
-        launched |= glaunched;
-        const double tsc = now_s();
-        ts_wait += tsc - tsb;
-        // (the next group reuses the query and answer buffers: this read-back also waits for the last copy of answers)
-        BCE_TRY(read_back(c, &ctl, c->ctl.p, sizeof ctl));
-        ts_rb += now_s() - tsc;
-        BCE_HIP_TRY(c, hipGetLastError());
-        BCE_TRY(settle_group());
-        lo += L;
-      }
-      a.pmask = 0xFFu; a.order = 0x76543210u; a.final = 1u; a.gmask = 0xFFu;
-      if (timing) {
-        double last = 0; int lastp = -1;
-        for (int q = 0; q < 8; ++q) if (((launched >> q) & 1u) && pool.t_end[q] > last) { last = pool.t_end[q]; lastp = q; }
-        if ((launched >> ord[0]) & 1u) { dbg_r[0] += pool.t_begin[ord[0]] - ts0; dbg_r[1] += pool.t_end[ord[0]] - ts0; }
-        if (lastp >= 0) { dbg_r[2] += last - ts0; dbg_r[3] += pool.t_begin[lastp] - ts0; dbg_last[lastp]++; }
-        dbg_r[4] += now_s() - ts0;
-      }
-      for (int q = 0; q < 8; ++q) prev_qtot[q] = new_qtot[q];
-      ++split_rounds;
-      t_split += now_s() - ts0;
-      if (timing) wide_time[hb] += now_s() - t_round0;
-      cur_nodes = ctl.next_nodes;
-      nodes_total = ctl.nodes_total;
-      if (c->progress) c->progress(nodes_total, 8ull * n, c->progress_user);
-      queries_total += qtotal;
-      ++round;
-      continue;
+      launched |= glaunched;
+      const double tsc = now_s();
+      st.ts_wait += tsc - tsb;
+      // (the next group reuses the query and answer buffers: this read-back also waits for the last copy of answers)
+      BCE_TRY(read_back(c, &ctl, c->ctl.p, sizeof ctl));
+      st.ts_rb += now_s() - tsc;
+      BCE_HIP_TRY(c, hipGetLastError());
+      BCE_TRY(settle_group(rp.grid));
+      lo += L;
     }
-    // One pass over all planes (or the planes of one group after the other): query pass, the decoders, children pass.
+    a.pmask = 0xFFu; a.order = 0x76543210u; a.final = 1u; a.gmask = 0xFFu;
+    if (env.timing) {
+      double last = 0; int lastp = -1;
+      for (int q = 0; q < 8; ++q) if (((launched >> q) & 1u) && pool.t_end[q] > last) { last = pool.t_end[q]; lastp = q; }
+      if ((launched >> ord[0]) & 1u) { st.dbg_r[0] += pool.t_begin[ord[0]] - ts0; st.dbg_r[1] += pool.t_end[ord[0]] - ts0; }
+      if (lastp >= 0) { st.dbg_r[2] += last - ts0; st.dbg_r[3] += pool.t_begin[lastp] - ts0; st.dbg_last[lastp]++; }
+      st.dbg_r[4] += now_s() - ts0;
+    }
+    for (int q = 0; q < 8; ++q) prev_qtot[q] = new_qtot[q];
+    ++st.split_rounds;
+    st.t_split += now_s() - ts0;
+    *queries = qtotal;
+    return BCE_HIP_OK;
+  }
+
+  // One pass over all planes (or the planes of one group after the other): query pass, the decoders, children pass.
+  int group_round(const RoundPlan &rp, uint64_t *queries) {
     uint64_t round_q = 0;
-    for (int g = 0; g < ng; ++g) {
-      const bool last_group = g + 1 == ng;
-      a.pmask = a.gmask = gm[g];
-      a.final = last_group ? 1u : 0u;
-      if (small) {
-        hipLaunchKernelGGL((dec_small_kernel<true>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-        ++small_rounds;
+    for (int g = 0; g < rp.ng; ++g) {
+      const uint32_t gm = rp.gm[g];
+      a.pmask = a.gmask = gm;
+      a.final = g + 1 == rp.ng ? 1u : 0u;
+      if (rp.small) {
+        hipLaunchKernelGGL((dec_small_kernel<true>), dim3(rp.grid), dim3(K3_T), 0, c->stream, a);
+        ++st.small_rounds;
       } else {
-        hipLaunchKernelGGL((dec_tiles_kernel<0>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-        hipLaunchKernelGGL((dec_scan_kernel<true>), dim3(8), dim3(1024), 0, c->stream, a);
-        hipLaunchKernelGGL((dec_tiles_kernel<1>), dim3(grid), dim3(K3_T), 0, c->stream, a);
+        query_pass(rp.grid);
       }
       BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
       BCE_HIP_TRY(c, hipGetLastError());
       DecInfo in = *info;
       for (int p = 0; p < 8; ++p)                                  // (the query pass of a group writes its own planes' fields only)
-        if (!((gm[g] >> p) & 1u)) { in.qbase[p] = in.qtot[p] = in.ebase[p] = in.etot[p] = 0; }
-      { const double t1 = now_s(); t_q += t1 - t0; t0 = t1; }
+        if (!((gm >> p) & 1u)) { in.qbase[p] = in.qtot[p] = in.ebase[p] = in.etot[p] = 0; }
+      { const double t1 = now_s(); st.t_q += t1 - t0; t0 = t1; }
       if (in.err == 2) { snprintf(c->err, sizeof c->err, "decode: node list overflow in a one-launch round (round %u)", round); return BCE_HIP_E_INTERNAL; }
       if (in.err) { snprintf(c->err, sizeof c->err, "decode: inconsistent archive (round %u)", round); return BCE_HIP_E_INTERNAL; }
       uint64_t qtotal = 0, etotal = 0;
-      for (int p = 0; p < 8; ++p) { qtotal += in.qtot[p]; etotal += in.etot[p]; if ((gm[g] >> p) & 1u) prev_qtot[p] = in.qtot[p]; }
+      for (int p = 0; p < 8; ++p) { qtotal += in.qtot[p]; etotal += in.etot[p]; if ((gm >> p) & 1u) prev_qtot[p] = in.qtot[p]; }
       if (qtotal && answered_pending) {
         // the tail kernel emitted exactly these queries (same order) and the decoders answered them: do not ask twice
         BCE_HIP_TRY(c, hipMemcpyAsync(Rsbuf.p, pin_res.p, qtotal * 4, hipMemcpyHostToDevice, c->stream));
-      } else if (qtotal && direct) {
-        pool.Q = static_cast<const uint32_t *>(pin_q.p);
-        pool.E = static_cast<const uint4 *>(pin_e.p);
-        pool.res = static_cast<uint32_t *>(pin_res.p);
-        pool.run(in);
-        { const double t1 = now_s(); t_host += t1 - t0; t0 = t1; }
       } else if (qtotal) {
-        BCE_TRY(pin_q.ensure(c, qtotal * 4));
-        BCE_TRY(pin_e.ensure(c, (etotal + 1) * sizeof(uint4)));
-        BCE_TRY(pin_res.ensure(c, qtotal * 4));
-        BCE_HIP_TRY(c, hipMemcpyAsync(pin_q.p, a.Q, qtotal * 4, hipMemcpyDeviceToHost, c->stream));
-        if (etotal) BCE_HIP_TRY(c, hipMemcpyAsync(pin_e.p, a.E, etotal * sizeof(uint4), hipMemcpyDeviceToHost, c->stream));
-        BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-        { const double t1 = now_s(); t_copy += t1 - t0; t0 = t1; }
+        if (!rp.direct) {
+          BCE_TRY(pin_q.ensure(c, qtotal * 4));
+          BCE_TRY(pin_e.ensure(c, (etotal + 1) * sizeof(uint4)));
+          BCE_TRY(pin_res.ensure(c, qtotal * 4));
+          BCE_HIP_TRY(c, hipMemcpyAsync(pin_q.p, a.Q, qtotal * 4, hipMemcpyDeviceToHost, c->stream));
+          if (etotal) BCE_HIP_TRY(c, hipMemcpyAsync(pin_e.p, a.E, etotal * sizeof(uint4), hipMemcpyDeviceToHost, c->stream));
+          BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+          { const double t1 = now_s(); st.t_copy += t1 - t0; t0 = t1; }
+        }
         pool.Q = static_cast<const uint32_t *>(pin_q.p);
         pool.E = static_cast<const uint4 *>(pin_e.p);
         pool.res = static_cast<uint32_t *>(pin_res.p);
         pool.run(in);
-        { const double t1 = now_s(); t_host += t1 - t0; t0 = t1; }
-        BCE_HIP_TRY(c, hipMemcpyAsync(Rsbuf.p, pin_res.p, qtotal * 4, hipMemcpyHostToDevice, c->stream));
+        { const double t1 = now_s(); st.t_host += t1 - t0; t0 = t1; }
+        if (!rp.direct) BCE_HIP_TRY(c, hipMemcpyAsync(Rsbuf.p, pin_res.p, qtotal * 4, hipMemcpyHostToDevice, c->stream));
       }
       answered_pending = false;
-      if (small) {
-        hipLaunchKernelGGL((dec_small_kernel<false>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-      } else {
-        hipLaunchKernelGGL((dec_tiles_kernel<2>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-        hipLaunchKernelGGL((dec_scan_kernel<false>), dim3(8), dim3(1024), 0, c->stream, a);
-        hipLaunchKernelGGL((dec_tiles_kernel<3>), dim3(grid), dim3(K3_T), 0, c->stream, a);
-      }
+      if (rp.small) hipLaunchKernelGGL((dec_small_kernel<false>), dim3(rp.grid), dim3(K3_T), 0, c->stream, a);
+      else children_pass(rp.grid);
       // the next round's size: read the control block (the query pass of the next round would tell, but its grid needs it)
       BCE_TRY(read_back(c, &ctl, c->ctl.p, sizeof ctl));
       BCE_HIP_TRY(c, hipGetLastError());
-      BCE_TRY(settle_group());
+      BCE_TRY(settle_group(rp.grid));
       round_q += qtotal;
     }
     a.pmask = a.gmask = 0xFFu; a.final = 1u;
-    t_c += now_s() - t0;
-    if (timing) wide_time[hb] += now_s() - t_round0;
+    st.t_c += now_s() - t0;
+    *queries = round_q;
+    return BCE_HIP_OK;
+  }
+
+  // The bookkeeping every round outside the tail kernels ends with
+  void end_round(const RoundPlan &rp, uint64_t queries) {
+    if (env.timing) st.wide_time[rp.hb] += now_s() - rp.t0;
     cur_nodes = ctl.next_nodes;
     nodes_total = ctl.nodes_total;
-    if (c->progress) c->progress(nodes_total, 8ull * n, c->progress_user);
-    queries_total += round_q;
+    progress();
+    queries_total += queries;
     ++round;
   }
-  if (timing) { fprintf(stderr, "gpu decode: %u rounds (%llu of them in the tail kernels, %llu query rounds answered through the mailbox), %llu nodes, %llu queries: %.3f s (query pass %.3f, copy out %.3f, host decoders %.3f, children pass %.3f)\n",
-                        round, (unsigned long long)tail_rounds, (unsigned long long)mbox_rounds, (unsigned long long)nodes_total, (unsigned long long)queries_total, now_s() - tp0, t_q, t_copy, t_host, t_c); tp0 = now_s(); }
 
-  if (timing) fprintf(stderr, "gpu decode: tail probe: %u rounds, %llu query rounds through the mailbox since it began; query-heavy %d\n",
-                      probe_rounds, (unsigned long long)(probe_rounds ? mbox_rounds - probe_mbox0 : 0), (int)query_heavy);
-  if (trace_mem) fprintf(stderr, "gpu decode: %llu rounds over the query budget of %llu nodes run in plane groups, %llu node lists grown in place; device memory in use during the rounds: %.1f GB at most\n",
-                         (unsigned long long)grouped_rounds, (unsigned long long)budget, (unsigned long long)list_grows, peak_used / 1e9);
-  if (timing) fprintf(stderr, "gpu decode: %llu six-launch rounds plane by plane (busiest first): %.3f s (launching the query passes %.3f, the first plane's %.3f, all lanes started after %.3f, waiting for decoders %.3f, last children pass %.3f)\n",
-                      (unsigned long long)split_rounds, t_split, ts_issue, ts_first, ts_lanes, ts_wait, ts_rb);
-  if (timing) {
+  // A children pass found that the children of the planes in `ovf` do not fit their lists (it wrote none of them; the counts
+  // are in the control block): each such list -- plane q + 1's of the next parity, which only plane q's pass writes, so it
+  // holds nothing yet -- is replaced by one of 1.25 x the need (exactly the need if the device has no more room, after the
+  // other phases' buffers have gone back), and the pass runs again from the answers already in the answer buffer.  A plane's
+  // decoder is never asked twice.
+  int grow_lists(uint32_t ovf) {
+    const uint32_t out = (round & 1u) ^ 1u;
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (uint32_t q = 0; q < 8; ++q) {
+      if (!((ovf >> q) & 1u)) continue;
+      const uint32_t qn = (q + 1u) & 7u;
+      const uint64_t need = (uint64_t)ctl.cnt[out][qn][0] + ctl.cnt[out][qn][1];
+      const uint32_t had = a.cap[out][qn];
+      if (need <= had || need > full_cap) {
+        snprintf(c->err, sizeof c->err, "decode: round %u reports a list of %llu nodes (it holds %u, n = %u)", round, (unsigned long long)need, had, n);
+        return BCE_HIP_E_INTERNAL;
+      }
+      release(c->dlist[out][qn]);
+      a.list[out][qn] = nullptr; a.cap[out][qn] = 0;
+      uint64_t want = need + need / 4;
+      if (want > full_cap) want = full_cap;
+      int rc = ensure(c, c->dlist[out][qn], (size_t)want * sizeof(Node), kAllocListFirst);
+      if (rc == BCE_HIP_E_NOMEM) {
+        want = need;
+        rc = ensure(c, c->dlist[out][qn], (size_t)want * sizeof(Node), kAllocListFallback);
+      }
+      if (rc != BCE_HIP_OK) {
+        if (rc == BCE_HIP_E_NOMEM) snprintf(c->err, sizeof c->err, "decode: no device memory for a node list of %llu nodes (round %u, n = %u)", (unsigned long long)need, round, n);
+        return rc;
+      }
+      a.list[out][qn] = c->dlist[out][qn].as<Node>();
+      a.cap[out][qn] = (uint32_t)want;
+      c->dec_list_grows++;
+      ++st.list_grows;
+      if (env.mem())
+        fprintf(stderr, "gpu decode: round %u does not fit the node lists: the children of plane %u (%llu nodes) in plane %u's list of %u (parity %u), grown in place to %llu\n",
+                round, q, (unsigned long long)need, qn, had, out, (unsigned long long)want);
+    }
+    BCE_HIP_TRY(c, hipMemsetAsync(&a.ctl->ovf, 0, sizeof(uint32_t), c->stream));
+    return BCE_HIP_OK;
+  }
+
+  // After the children passes of a group, with `ctl` just read back: errors, and the lists that must grow
+  int settle_group(uint32_t grid) {
+    for (int tries = 0;; ++tries) {
+      if (ctl.err) {
+        if (ctl.err == 4) snprintf(c->err, sizeof c->err, "decode: a two-launch round waited too long for a predecessor tile (round %u)", round);
+        else if (ctl.err == 2) snprintf(c->err, sizeof c->err, "decode: node list overflow in a one-launch round (round %u)", round);
+        else snprintf(c->err, sizeof c->err, "decode: inconsistent archive (round %u)", round);
+        return BCE_HIP_E_INTERNAL;
+      }
+      if (!ctl.ovf) return BCE_HIP_OK;
+      if (tries == 2) { snprintf(c->err, sizeof c->err, "decode: node lists still too small after growing (round %u)", round); return BCE_HIP_E_INTERNAL; }
+      const uint32_t ovf = ctl.ovf;
+      BCE_TRY(grow_lists(ovf));
+      const uint32_t pm = a.pmask, fin = a.final;
+      a.pmask = ovf;
+      a.final = 0;                                               // (the round's totals were added up by its last pass already)
+      children_pass(grid);
+      a.pmask = pm; a.final = fin;
+      BCE_TRY(read_back(c, &ctl, c->ctl.p, sizeof ctl));
+      BCE_HIP_TRY(c, hipGetLastError());
+    }
+  }
+
+  void report_rounds() {
+    if (env.timing) { fprintf(stderr, "gpu decode: %u rounds (%llu of them in the tail kernels, %llu query rounds answered through the mailbox), %llu nodes, %llu queries: %.3f s (query pass %.3f, copy out %.3f, host decoders %.3f, children pass %.3f)\n",
+                              round, (unsigned long long)st.tail_rounds, (unsigned long long)st.mbox_rounds, (unsigned long long)nodes_total, (unsigned long long)queries_total, now_s() - tp0, st.t_q, st.t_copy, st.t_host, st.t_c); tp0 = now_s(); }
+    if (env.timing) fprintf(stderr, "gpu decode: tail probe: %u rounds, %llu query rounds through the mailbox since it began; query-heavy %d\n",
+                            probe_rounds, (unsigned long long)(probe_rounds ? st.mbox_rounds - probe_mbox0 : 0), (int)query_heavy);
+    if (env.mem()) fprintf(stderr, "gpu decode: %llu rounds over the query budget of %llu nodes run in plane groups, %llu node lists grown in place; device memory in use during the rounds: %.1f GB at most\n",
+                           (unsigned long long)st.grouped_rounds, (unsigned long long)budget, (unsigned long long)st.list_grows, st.peak_used / 1e9);
+    if (!env.timing) return;
+    fprintf(stderr, "gpu decode: %llu six-launch rounds plane by plane (busiest first): %.3f s (launching the query passes %.3f, the first plane's %.3f, all lanes started after %.3f, waiting for decoders %.3f, last children pass %.3f)\n",
+            (unsigned long long)st.split_rounds, st.t_split, st.ts_issue, st.ts_first, st.ts_lanes, st.ts_wait, st.ts_rb);
     fprintf(stderr, "gpu decode: decoder threads (answers through the pool only):");
     for (int p = 0; p < 8; ++p) fprintf(stderr, " plane %d %.1f M in %.3f s (%.1f ns);", p, pool.asked_n[p] * 1e-6, pool.busy[p], pool.asked_n[p] ? pool.busy[p] * 1e9 / pool.asked_n[p] : 0.0);
     fprintf(stderr, "\n");
-  }
-  if (timing) fprintf(stderr, "gpu decode: lanes: busiest plane's decoder began %.3f, ended %.3f; the last decoder began %.3f, ended %.3f; all children passes queued %.3f (sums over the rounds, from the round's start); last to end: %u %u %u %u %u %u %u %u\n",
-                      dbg_r[0], dbg_r[1], dbg_r[3], dbg_r[2], dbg_r[4], dbg_last[0], dbg_last[1], dbg_last[2], dbg_last[3], dbg_last[4], dbg_last[5], dbg_last[6], dbg_last[7]);
-  if (timing) {
-    fprintf(stderr, "gpu decode: %llu rounds in two launches (dec_small_kernel); rounds outside the tail by node count:", (unsigned long long)small_rounds);
-    for (int b = 0; b < 32; ++b) if (wide_hist[b]) fprintf(stderr, " [2^%d) %llu rounds %.1f M nodes %.3f s;", b, (unsigned long long)wide_hist[b], wide_nodes[b] * 1e-6, wide_time[b]);
+    fprintf(stderr, "gpu decode: lanes: busiest plane's decoder began %.3f, ended %.3f; the last decoder began %.3f, ended %.3f; all children passes queued %.3f (sums over the rounds, from the round's start); last to end: %u %u %u %u %u %u %u %u\n",
+            st.dbg_r[0], st.dbg_r[1], st.dbg_r[3], st.dbg_r[2], st.dbg_r[4], st.dbg_last[0], st.dbg_last[1], st.dbg_last[2], st.dbg_last[3], st.dbg_last[4], st.dbg_last[5], st.dbg_last[6], st.dbg_last[7]);
+    fprintf(stderr, "gpu decode: %llu rounds in two launches (dec_small_kernel); rounds outside the tail by node count:", (unsigned long long)st.small_rounds);
+    for (int b = 0; b < 32; ++b) if (st.wide_hist[b]) fprintf(stderr, " [2^%d) %llu rounds %.1f M nodes %.3f s;", b, (unsigned long long)st.wide_hist[b], st.wide_nodes[b] * 1e-6, st.wide_time[b]);
     fprintf(stderr, "\n");
+    fprintf(stderr, "gpu decode: tail kernels: wave %llu launches (%llu rounds, %llu nodes) %.3f s, workgroup %llu launches (%llu rounds, %llu nodes) %.3f s\n",
+            (unsigned long long)st.launches_wave, (unsigned long long)st.rounds_wave, (unsigned long long)st.nodes_wave, st.t_wave,
+            (unsigned long long)st.launches_wg, (unsigned long long)st.rounds_wg, (unsigned long long)st.nodes_wg, st.t_wg);
   }
-  if (timing) fprintf(stderr, "gpu decode: tail kernels: wave %llu launches (%llu rounds, %llu nodes) %.3f s, workgroup %llu launches (%llu rounds, %llu nodes) %.3f s\n",
-                      (unsigned long long)launches_wave, (unsigned long long)rounds_wave, (unsigned long long)nodes_wave, t_wave,
-                      (unsigned long long)launches_wg, (unsigned long long)rounds_wg, (unsigned long long)nodes_wg, t_wg);
-  // ---- R -> planes -> granules -> BWT bytes ----
+
   // From here on the lists and the rounds' query buffers are idle (an allocation that finds the device full gets them back:
   // ctx_trim).  Where what follows would not fit twice into the device memory that is free beside them, they go back now, so
   // that the planes and the inverse BWT never allocate on top of them: 16 lists of 541 M nodes and ~10 GB of query buffers at
   // 2^31 bytes.  At 10^8 bytes they stay with the context for its next decode.  (BCE_DEC_GIVE_BACK=1: always.)
-  c->dec_part = 2;
-  FillArgs f;
-  f.R = R; f.n = n;
-  f.chunks = (uint32_t)(((uint64_t)n + 1 + FG_CHUNK - 1) / FG_CHUNK);
-  f.nwords = (uint32_t)(((uint64_t)n + 31) / 32) + 3;
-  const uint32_t ngran = (uint32_t)((uint64_t)n / 96) + 2;
-  {
+  int give_back() {
     auto more = [](const DevBuf &b, size_t want) -> uint64_t { return want > b.cap ? want - b.cap : 0; };
-    const size_t b4n = (size_t)n * 4;
-    const uint64_t post = more(c->sa[0], std::max<size_t>(8 * rstride, b4n)) + more(c->sa[1], b4n) +
-                          more(c->key[0], std::max<size_t>((size_t)8 * f.nwords * 4, b4n)) + more(c->key[1], std::max<size_t>((size_t)8 * f.nwords * 4, b4n)) +
-                          more(c->rank, b4n) + more(c->gran, (size_t)8 * ngran * sizeof(Granule)) + more(c->bwt, n) + more(c->text, n);
+    const size_t b4n = (size_t)n * 4, wb = (size_t)8 * plane_words(n) * 4;
+    const uint64_t post = more(c->sa[0], std::max<size_t>(8 * rstride, b4n)) + more(c->sa[1], b4n) + more(c->key[0], std::max(wb, b4n)) +
+                          more(c->key[1], std::max(wb, b4n)) + more(c->rank, b4n) + more(c->gran, (size_t)8 * plane_granules(n) * sizeof(Granule)) +
+                          more(c->bwt, n) + more(c->text, n);
     size_t fr = 0, tot = 0;
-    const bool force = getenv("BCE_DEC_GIVE_BACK") != nullptr;
-    if (force || (hipMemGetInfo(&fr, &tot) == hipSuccess && fr < 2 * post)) {
+    if (env.give_back || (hipMemGetInfo(&fr, &tot) == hipSuccess && fr < 2 * post)) {
       BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
       size_t freed = 0;
       for (auto &par : c->dlist) for (DevBuf &b : par) { freed += b.cap; release(b); }
       for (DevBuf *b : {&Qbuf, &Ebuf, &Rsbuf, &c->tilecnt, &c->tileoff}) { freed += b->cap; release(*b); }
-      if (trace_mem) fprintf(stderr, "gpu decode: after the rounds: %.1f GB of node lists and query buffers given back (%.1f GB were free, the planes and the inverse BWT add %.1f GB)\n",
+      if (env.mem()) fprintf(stderr, "gpu decode: after the rounds: %.1f GB of node lists and query buffers given back (%.1f GB were free, the planes and the inverse BWT add %.1f GB)\n",
                              freed / 1e9, fr / 1e9, post / 1e9);
     }
+    return BCE_HIP_OK;
   }
-  BCE_TRY(ensure(c, c->blk, (size_t)8 * f.chunks * 4 + 64));
-  f.cmax = c->blk.as<uint32_t>();
-  f.err = f.cmax + (size_t)8 * f.chunks;
-  BCE_TRY(ensure(c, c->sa[0], 8 * rstride));                   // gap types
-  f.type = c->sa[0].as<uint8_t>();
-  BCE_TRY(ensure(c, c->key[0], (size_t)8 * f.nwords * 4));
-  BCE_TRY(ensure(c, c->key[1], (size_t)8 * f.nwords * 4));
-  f.words = c->key[0].as<uint32_t>();
-  f.rankw = c->key[1].as<uint32_t>();
-  BCE_TRY(ensure(c, c->gran, (size_t)8 * ngran * sizeof(Granule)));
-  sample_mem();
-  BCE_HIP_TRY(c, hipMemsetAsync(f.err, 0, 4, c->stream));
-  BCE_HIP_TRY(c, hipMemsetAsync(f.words, 0, (size_t)8 * f.nwords * 4, c->stream));
-  BCE_HIP_TRY(c, hipMemsetAsync(f.rankw, 0, (size_t)8 * f.nwords * 4, c->stream));
-  hipLaunchKernelGGL(fill_chunkmax_kernel, dim3(f.chunks, 8), dim3(FG_T), 0, c->stream, f);
-  hipLaunchKernelGGL(fill_chunkscan_kernel, dim3(8), dim3(1024), 0, c->stream, f);
-  hipLaunchKernelGGL((fill_kernel<0>), dim3(f.chunks, 8), dim3(FG_T), 0, c->stream, f);
-  hipLaunchKernelGGL((fill_kernel<1>), dim3(f.chunks, 8), dim3(FG_T), 0, c->stream, f);
-  {
-    uint32_t gb = (ngran + 255) / 256;
+
+  // ---- R -> planes -> granules -> BWT bytes ----
+  int planes() {
+    FillArgs f;
+    f.R = a.R; f.n = n;
+    f.chunks = (uint32_t)(((uint64_t)n + 1 + FG_CHUNK - 1) / FG_CHUNK);
+    f.nwords = plane_words(n);
+    const uint32_t ngran = plane_granules(n);
+    BCE_TRY(ensure(c, c->blk, (size_t)8 * f.chunks * 4 + 64));
+    f.cmax = c->blk.as<uint32_t>();
+    f.err = f.cmax + (size_t)8 * f.chunks;
+    BCE_TRY(ensure(c, c->sa[0], 8 * rstride));                   // gap types
+    f.type = c->sa[0].as<uint8_t>();
+    BCE_TRY(ensure(c, c->key[0], (size_t)8 * f.nwords * 4));
+    BCE_TRY(ensure(c, c->key[1], (size_t)8 * f.nwords * 4));
+    f.words = c->key[0].as<uint32_t>();
+    f.rankw = c->key[1].as<uint32_t>();
+    BCE_TRY(ensure(c, c->gran, (size_t)8 * ngran * sizeof(Granule)));
+    sample_mem();
+    BCE_HIP_TRY(c, hipMemsetAsync(f.err, 0, 4, c->stream));
+    BCE_HIP_TRY(c, hipMemsetAsync(f.words, 0, (size_t)8 * f.nwords * 4, c->stream));
+    BCE_HIP_TRY(c, hipMemsetAsync(f.rankw, 0, (size_t)8 * f.nwords * 4, c->stream));
+    hipLaunchKernelGGL(fill_chunkmax_kernel, dim3(f.chunks, 8), dim3(FG_T), 0, c->stream, f);
+    hipLaunchKernelGGL(fill_chunkscan_kernel, dim3(8), dim3(1024), 0, c->stream, f);
+    hipLaunchKernelGGL((fill_kernel<0>), dim3(f.chunks, 8), dim3(FG_T), 0, c->stream, f);
+    hipLaunchKernelGGL((fill_kernel<1>), dim3(f.chunks, 8), dim3(FG_T), 0, c->stream, f);
+    const uint32_t gb = (ngran + 255) / 256;
     hipLaunchKernelGGL(gran_from_words_kernel, dim3(gb < 4096 ? gb : 4096, 8), dim3(256), 0, c->stream, f, c->gran.as<Granule>(), ngran);
+    uint32_t ferr = 0;
+    BCE_TRY(read_back(c, &ferr, f.err, 4));
+    BCE_HIP_TRY(c, hipGetLastError());
+    if (ferr) { snprintf(c->err, sizeof c->err, "decode: a mixed gap was never split"); return BCE_HIP_E_INTERNAL; }
+    BCE_TRY(ensure(c, c->bwt, n));
+    BCE_TRY(ensure(c, c->text, n));
+    BCE_TRY(ensure(c, c->stat, 64));
+    sample_mem();
+    uint32_t *dz = c->stat.as<uint32_t>();
+    BCE_HIP_TRY(c, hipMemcpyAsync(dz, a.zeros, 32, hipMemcpyHostToDevice, c->stream));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    hipLaunchKernelGGL(access_kernel, dim3(grid256(n)), dim3(256), 0, c->stream, c->gran.as<Granule>(), ngran, n, dz, c->bwt.as<uint8_t>());
+    if (env.timing) { BCE_HIP_TRY(c, hipStreamSynchronize(c->stream)); fprintf(stderr, "gpu decode: planes + unbwt %.3f s\n", now_s() - tp0); tp0 = now_s(); }
+    return BCE_HIP_OK;
   }
-  uint32_t ferr = 0;
-  BCE_TRY(read_back(c, &ferr, f.err, 4));
-  BCE_HIP_TRY(c, hipGetLastError());
-  if (ferr) { snprintf(c->err, sizeof c->err, "decode: a mixed gap was never split"); return BCE_HIP_E_INTERNAL; }
-  BCE_TRY(ensure(c, c->bwt, n));
-  BCE_TRY(ensure(c, c->text, n));
-  BCE_TRY(ensure(c, c->stat, 64));
-  sample_mem();
-  uint32_t *dz = c->stat.as<uint32_t>();
-  BCE_HIP_TRY(c, hipMemcpyAsync(dz, a.zeros, 32, hipMemcpyHostToDevice, c->stream));
-  BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const uint32_t gn = (uint32_t)((((uint64_t)n + 255) / 256) < 8192 ? (((uint64_t)n + 255) / 256) : 8192);
-  hipLaunchKernelGGL(access_kernel, dim3(gn), dim3(256), 0, c->stream, c->gran.as<Granule>(), ngran, n, dz, c->bwt.as<uint8_t>());
-  if (timing) { BCE_HIP_TRY(c, hipStreamSynchronize(c->stream)); fprintf(stderr, "gpu decode: planes + unbwt %.3f s\n", now_s() - tp0); tp0 = now_s(); }
 
   // ---- inverse BWT ----
+  int inverse_bwt(uint8_t *out) {
+    const size_t b4 = (size_t)n * 4;
+    const uint32_t gn = grid256(n);
+    for (int i = 0; i < 2; ++i) { BCE_TRY(ensure(c, c->sa[i], b4)); BCE_TRY(ensure(c, c->key[i], b4)); }
+    BCE_TRY(ensure(c, c->rank, b4));
+    sample_mem();
+    uint32_t *key[2] = {c->key[0].as<uint32_t>(), c->key[1].as<uint32_t>()};
+    uint32_t *val[2] = {c->sa[0].as<uint32_t>(), c->sa[1].as<uint32_t>()};
+    uint32_t *lf = c->rank.as<uint32_t>();
+    hipLaunchKernelGGL(lf_keys_kernel, dim3(gn), dim3(256), 0, c->stream, c->bwt.as<uint8_t>(), n, key[0], val[0]);
+    int res = 0;
+    BCE_TRY(radix_sort_pairs(c, key, val, n, 0, 8, &res, 8));
+    sample_mem();                                                 // (the sort's histograms)
+    hipLaunchKernelGGL(lf_scatter_kernel, dim3(gn), dim3(256), 0, c->stream, val[res], n, lf);
+    // one cycle through all n rows for a primitive input; a shorter cycle (length lc, the input's period pattern in BWT terms)
+    // otherwise, written once into V (the sort's value buffers are free again) and then unrolled
+    const uint32_t off = hd.offset % n;
+    uint8_t *V = reinterpret_cast<uint8_t *>(val[0]);
+    uint64_t lc = 0;
+    uint32_t walkers = 0;
+    BCE_TRY(lf_walk(c, lf, c->bwt.as<uint8_t>(), n, c->text.as<uint8_t>(), n, off, V, &lc, &walkers));
+    if (lc == 0 || lc > n || n % lc) { snprintf(c->err, sizeof c->err, "decode: LF cycle of length %llu in %u rows", (unsigned long long)lc, n); return BCE_HIP_E_INTERNAL; }
+    const bool single_cycle = lc == n;
+    // periodic input (the reference's decoder returns zeros here)
+    if (!single_cycle) hipLaunchKernelGGL(expand_cycle_kernel, dim3(gn), dim3(256), 0, c->stream, V, (uint32_t)lc, n, off, c->text.as<uint8_t>());
+    BCE_HIP_TRY(c, hipMemcpyAsync(out, c->text.p, n, hipMemcpyDeviceToHost, c->stream));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    BCE_HIP_TRY(c, hipGetLastError());
+    if (env.timing) fprintf(stderr, "gpu decode: inverse BWT (%s, %u walkers) %.3f s\n", single_cycle ? "one cycle" : "periodic", walkers, now_s() - tp0);
+    if (env.mem()) fprintf(stderr, "gpu decode: device memory in use over the whole decode (sampled after every allocation stage): %.1f GB at most\n", st.peak_used / 1e9);
+    if (env.timing) fprintf(stderr, "gpu decode: this context so far: device allocations %u calls %.1f MB %.3f s, pinned (query / answer buffers) %u calls %.1f MB %.3f s\n",
+                            c->alloc_calls, c->alloc_bytes / 1e6, c->alloc_s, c->pin_calls, c->pin_bytes / 1e6, c->pin_s);
+    return BCE_HIP_OK;
+  }
+};
+
+
+}  // namespace
+
+}  // namespace bce
+
+using namespace bce;
+
+// `bce -d` on the GPU: archive -> original bytes (see the header of this file).  The context is only used for its
+// device, stream and scratch buffers; any compression state in it is dropped.
+static int decompress_device(bce_hip_ctx *c, const uint8_t *archive, size_t len, uint8_t *out, size_t cap, size_t *out_len) {
+  if (!c) return BCE_HIP_E_ARG;
+  struct PartEnd { bce_hip_ctx *c; ~PartEnd() { c->dec_part = 0; } } part_end{c};
+  if (!archive || !out_len) return BCE_HIP_E_ARG;
+  ArchiveHead hd;
+  if (parse_archive(archive, len, hd, /*header_only=*/true) != 0) return BCE_HIP_E_ARG;
+  *out_len = hd.n;
+  if (!out) return BCE_HIP_OK;
+  if (cap < hd.n) return BCE_HIP_E_OVERFLOW;
+  if (parse_archive(archive, len, hd, false) != 0) return BCE_HIP_E_ARG;
+  BCE_HIP_TRY(c, hipSetDevice(c->device));
+  c->coder->drain();
+  c->stage = 0; c->enum_active = false; c->k1_valid = false;   // the scratch buffers below belong to the decoder now
+  c->phase = 4;
+  struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
+  Decode d(c, hd);
+  c->dec_part = 1;
+  BCE_TRY(d.setup(len));
+  BCE_TRY(d.rounds());
+  d.report_rounds();
+  c->dec_part = 2;
+  BCE_TRY(d.give_back());
+  BCE_TRY(d.planes());
   c->dec_part = 3;                                              // (... and the boundary ranks, once access_kernel has read them)
-  const size_t b4 = (size_t)n * 4;
-  for (int i = 0; i < 2; ++i) { BCE_TRY(ensure(c, c->sa[i], b4)); BCE_TRY(ensure(c, c->key[i], b4)); }
-  BCE_TRY(ensure(c, c->rank, b4));
-  sample_mem();
-  uint32_t *key[2] = {c->key[0].as<uint32_t>(), c->key[1].as<uint32_t>()};
-  uint32_t *val[2] = {c->sa[0].as<uint32_t>(), c->sa[1].as<uint32_t>()};
-  uint32_t *lf = c->rank.as<uint32_t>();
-  hipLaunchKernelGGL(lf_keys_kernel, dim3(gn), dim3(256), 0, c->stream, c->bwt.as<uint8_t>(), n, key[0], val[0]);
-  int res = 0;
-  BCE_TRY(radix_sort_pairs(c, key, val, n, 0, 8, &res, 8));
-  sample_mem();                                                 // (the sort's histograms)
-  hipLaunchKernelGGL(lf_scatter_kernel, dim3(gn), dim3(256), 0, c->stream, val[res], n, lf);
-  uint32_t sh = 0;
-  while (((uint64_t)n >> sh) > (1u << 19)) ++sh;                // at most 2^19 walkers
-  // ... and at least 256 rows per walker while that leaves a few thousand of them: the host chains the segments one after
-  // the other (a random access each), which for one-row segments of a 1 MB input was 10 ms of a 36 ms decode
-  while (sh < 8 && ((uint64_t)n >> (sh + 1)) >= 4096) ++sh;
-  const uint32_t m = (uint32_t)((((uint64_t)n - 1) >> sh) + 1);
-  BCE_TRY(ensure(c, c->key[0], (size_t)3 * m * 4 + 16));         // the sort's key buffers are free again
-  uint32_t *d_len = c->key[0].as<uint32_t>(), *d_end = d_len + m, *d_dest = d_len + 2 * (size_t)m;
-  hipLaunchKernelGGL(walk_len_kernel, dim3((m + 63) / 64), dim3(64), 0, c->stream, lf, m, sh, d_len, d_end);
-  std::vector<uint32_t> h_len(m), h_end(m), h_dest(m, 0);
-  BCE_HIP_TRY(c, hipMemcpyAsync(h_len.data(), d_len, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
-  BCE_HIP_TRY(c, hipMemcpyAsync(h_end.data(), d_end, (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
-  BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  BCE_HIP_TRY(c, hipGetLastError());
-  // chain the segments from row 0 (= the last text position) until the walk is back at row 0: one cycle through all
-  // n rows for a primitive input; a shorter cycle (length lc, the input's period pattern in BWT terms) otherwise
-  uint64_t lc = 0;
-  {
-    uint32_t cur = 0;
-    std::vector<uint8_t> visited(m, 0);
-    std::vector<uint32_t> order;
-    do {
-      const uint32_t j = cur >> sh;
-      if (visited[j]) return BCE_HIP_E_INTERNAL;                 // cannot happen: LF is a permutation
-      visited[j] = 1;
-      order.push_back(j);
-      lc += h_len[j];
-      cur = h_end[j];
-    } while (cur != 0);
-    uint64_t pos = lc;
-    for (uint32_t j : order) { h_dest[j] = (uint32_t)pos; pos -= h_len[j]; }
-    for (uint32_t j = 0; j < m; ++j) if (!visited[j]) h_len[j] = 0;      // rows off the cycle are never written
-  }
-  if (lc == 0 || lc > n || n % lc) { snprintf(c->err, sizeof c->err, "decode: LF cycle of length %llu in %u rows", (unsigned long long)lc, n); return BCE_HIP_E_INTERNAL; }
-  const uint32_t off = hd.offset % n;
-  const bool single_cycle = lc == n;
-  BCE_HIP_TRY(c, hipMemcpyAsync(d_dest, h_dest.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
-  BCE_HIP_TRY(c, hipMemcpyAsync(d_len, h_len.data(), (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
-  if (single_cycle) {
-    hipLaunchKernelGGL(walk_write_kernel, dim3((m + 63) / 64), dim3(64), 0, c->stream, lf, c->bwt.as<uint8_t>(), m, sh, d_len, d_dest,
-                       n, off, c->text.as<uint8_t>());
-  } else {
-    // periodic input (the reference's decoder returns zeros here): write the cycle once, then unroll it
-    uint8_t *V = reinterpret_cast<uint8_t *>(val[0]);            // the sort's value buffers are free again
-    hipLaunchKernelGGL(walk_write_kernel, dim3((m + 63) / 64), dim3(64), 0, c->stream, lf, c->bwt.as<uint8_t>(), m, sh, d_len, d_dest,
-                       (uint32_t)lc, 0u, V);
-    hipLaunchKernelGGL(expand_cycle_kernel, dim3(gn), dim3(256), 0, c->stream, V, (uint32_t)lc, n, off, c->text.as<uint8_t>());
-  }
-  BCE_HIP_TRY(c, hipMemcpyAsync(out, c->text.p, n, hipMemcpyDeviceToHost, c->stream));
-  BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  BCE_HIP_TRY(c, hipGetLastError());
-  if (timing) fprintf(stderr, "gpu decode: inverse BWT (%s, %u walkers) %.3f s\n", single_cycle ? "one cycle" : "periodic", m, now_s() - tp0);
-  if (trace_mem) fprintf(stderr, "gpu decode: device memory in use over the whole decode (sampled after every allocation stage): %.1f GB at most\n", peak_used / 1e9);
-  if (timing) fprintf(stderr, "gpu decode: this context so far: device allocations %u calls %.1f MB %.3f s, pinned (query / answer buffers) %u calls %.1f MB %.3f s\n",
-                      c->alloc_calls, c->alloc_bytes / 1e6, c->alloc_s, c->pin_calls, c->pin_bytes / 1e6, c->pin_s);
-  return BCE_HIP_OK;
+  return d.inverse_bwt(out);
+}
+
+extern "C" int bce_hip_decompress_device(bce_hip_ctx *c, const uint8_t *archive, size_t len, uint8_t *out, size_t cap,
+                                         size_t *out_len) {
+  return bce_guarded(c, [&] { return decompress_device(c, archive, len, out, cap, out_len); });
 }
