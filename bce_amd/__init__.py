@@ -7,6 +7,18 @@ binding used by tests and bench.py; it mirrors the reference's own interface nam
 There is no CPU fallback: every compute call goes through the HIP library and fails loudly
 when it is missing or when no GPU is present.
 """
-from .api import (BCE, BceError, ContextPool, RankFile, compress, compress_device, compress_many, decompress, decompress_device,  # noqa: F401
-                  library_path, load_library, scan, synth_rand, synth_text, stats, stats_of, archive_of, plane_stream, set_plane_mask, set_plane_stream)
+from .api import (BCE, BceError, ContextPool, RankFile, compress, compress_device, compress_many, decompress, decompress_device, decompress_to_device,  # noqa: F401
+                  library_path, load_library, scan, synth_rand, synth_text, stats, stats_of, archive_of, plane_stream, set_plane_mask, set_plane_stream,
+                  verify, verify_device)
 from .build import build as build_native  # noqa: F401
+
+
+_TENSOR_NAMES = ("compress_tensor", "decompress_tensor", "verify_tensor")
+
+
+def __getattr__(name):
+    # the torch plumbing (bce_amd/tensor.py) is imported when it is first asked for: the binding itself needs no torch
+    if name in _TENSOR_NAMES:
+        from . import tensor
+        return getattr(tensor, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -81,6 +81,9 @@ SYMBOLS = [
     ("bce_hip_scan", C.c_int, [C.c_void_p, _u8p, C.POINTER(C.c_double)]),
     ("bce_hip_decompress", C.c_int, [_u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("bce_hip_decompress_device", C.c_int, [C.c_void_p, _u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("bce_hip_decompress_to_device", C.c_int, [C.c_void_p, _u8p, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("bce_hip_verify_device", C.c_int, [C.c_void_p, _u8p, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_uint64)]),
+    ("bce_hip_verify_host", C.c_int, [C.c_void_p, _u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(C.c_uint64)]),
     ("bce_hip_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     ("bce_hip_synth_text", None, [C.c_uint64, _u8p, C.c_size_t]),
     ("bce_hip_synth_rand", None, [C.c_uint64, _u8p, C.c_size_t]),
@@ -465,6 +468,61 @@ def decompress_device(archive, device=0, ctx=None, out=None):
         c.check(c.lib.bce_hip_decompress_device(c.h, a.ctypes.data, len(a), buf.ctypes.data, n.value, C.byref(n)),
                 "bce_hip_decompress_device")
         return buf.tobytes()
+    finally:
+        if own:
+            c.close()
+
+
+def decompress_to_device(archive, device_ptr, cap, device=0, ctx=None) -> int:
+    """The GPU-assisted decoder with the text left in device memory: archive (host bytes) -> the decoded bytes at
+    `device_ptr` (an int: `cap` bytes of the caller's memory on `device`, any alignment), the number of bytes returned.
+    Nothing of the text crosses to the host.  device_ptr=None only reports the size; cap too small raises (status -5)
+    with nothing written.  The library runs on a stream of its own: the memory must be ready when this is called
+    (synchronise the stream that produced it), and it is complete when the call returns."""
+    own = ctx is None
+    c = ctx or _Ctx(device)
+    try:
+        a = _as_u8(archive)
+        n = C.c_size_t()
+        ptr = None if device_ptr is None else int(device_ptr)
+        c.check(c.lib.bce_hip_decompress_to_device(c.h, a.ctypes.data, len(a), ptr, int(cap), C.byref(n)), "bce_hip_decompress_to_device")
+        return n.value
+    finally:
+        if own:
+            c.close()
+
+
+_NO_DIFF = (1 << 64) - 1
+
+
+def verify_device(archive, device_ptr, n, device=0, ctx=None):
+    """Does `archive` decode to the `n` bytes at `device_ptr` (device memory of `device`, any alignment)?  Decoded and
+    compared on the GPU; nothing of the text crosses to the host.  -> None when it does, else the first index at which
+    they differ (min(n, decoded size) when only the sizes differ).  Stream rule: as decompress_to_device."""
+    own = ctx is None
+    c = ctx or _Ctx(device)
+    try:
+        a = _as_u8(archive)
+        fd = C.c_uint64(_NO_DIFF)
+        ptr = None if device_ptr is None else int(device_ptr)
+        c.check(c.lib.bce_hip_verify_device(c.h, a.ctypes.data, len(a), ptr, int(n), C.byref(fd)), "bce_hip_verify_device")
+        return None if fd.value == _NO_DIFF else fd.value
+    finally:
+        if own:
+            c.close()
+
+
+def verify(archive, data, device=0, ctx=None):
+    """verify_device for host bytes: `data` is uploaded once and compared on the GPU with what `archive` decodes to.
+    -> None when equal, else the first differing index."""
+    own = ctx is None
+    c = ctx or _Ctx(device)
+    try:
+        a, d = _as_u8(archive), _as_u8(data)
+        fd = C.c_uint64(_NO_DIFF)
+        c.check(c.lib.bce_hip_verify_host(c.h, a.ctypes.data, len(a), d.ctypes.data if len(d) else None, len(d), C.byref(fd)),
+                "bce_hip_verify_host")
+        return None if fd.value == _NO_DIFF else fd.value
     finally:
         if own:
             c.close()

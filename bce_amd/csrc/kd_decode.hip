@@ -18,6 +18,9 @@
 // The archive format, the model and the coder arithmetic are the reference's; parity = decode(reference
 // archive) == input (tests/test_gpu_decode.py).  Inputs whose LF mapping is not one cycle (periodic inputs, on which
 // the reference's decoder fails) are unrolled from the cycle through row 0.
+// Where the text ends up is the caller's choice (DecDest): a host buffer (bce_hip_decompress_device), the caller's device
+// memory, written by the walk itself (bce_hip_decompress_to_device), or the context's buffer, compared there with the
+// original (bce_hip_verify_device / _host; kd_compare.hip).
 #include <sched.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -1757,6 +1760,20 @@ struct Events {
   ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
 };
 
+// Where a decode's text goes (decompress_device).  The inverse BWT's walk writes single bytes at any address, so the caller's
+// device memory is written directly: kDevice needs no text buffer of the context's at all.
+struct DecDest {
+  enum Kind { kHost, kDevice, kCompare } kind;
+  uint8_t *out;                  // kHost: the caller's host buffer, kDevice: the caller's device buffer (any alignment), of cap bytes
+  size_t cap;
+  // kCompare: the text stays in the context's own buffer and is compared there with orig_n bytes, which are on the device
+  // (orig_dev) or on the host (orig_host: uploaded into the BWT's buffer, idle once the walk has read it)
+  const uint8_t *orig_dev, *orig_host;
+  uint64_t orig_n;
+  uint64_t *first_diff;
+  bool own_text() const { return kind != kDevice; }            // the text lands in c->text
+};
+
 // What BCE_DEC_TIMING and BCE_ALLOC_TRACE report about the rounds
 struct DecStats {
   double t_q = 0, t_copy = 0, t_host = 0, t_c = 0;      // query pass, copy out, host decoders, children pass (and the rest)
@@ -1793,6 +1810,7 @@ struct Decode {
   bce_hip_ctx *c;
   const DecEnv env = dec_env();
   ArchiveHead &hd;
+  const DecDest &dest;
   const uint32_t n;
   const size_t rstride;                                        // of the boundary ranks R[8][n + 1]
   const uint32_t full_cap;                                     // the largest node list a decode can need
@@ -1828,8 +1846,8 @@ struct Decode {
   uint64_t probe_mbox0 = 0;
   bool probe_done, query_heavy = false;
 
-  Decode(bce_hip_ctx *ctx, ArchiveHead &h)
-      : c(ctx), hd(h), n(h.n), rstride((size_t)h.n + 1), full_cap(dec_full_capP(h.n)),
+  Decode(bce_hip_ctx *ctx, ArchiveHead &h, const DecDest &to)
+      : c(ctx), hd(h), dest(to), n(h.n), rstride((size_t)h.n + 1), full_cap(dec_full_capP(h.n)),
         pin_q(&ctx->dec_pin[0], &ctx->dec_pin_cap[0]), pin_e(&ctx->dec_pin[1], &ctx->dec_pin_cap[1]),
         pin_res(&ctx->dec_pin[2], &ctx->dec_pin_cap[2]), Qbuf(ctx->skey[0]), Ebuf(ctx->skey[1]), Rsbuf(ctx->sesc),
         budget(dec_budget(ctx)), host_tail_ok(!env.no_host_tail), tail_min((h.n >> 6) + (1u << 18)),
@@ -2450,7 +2468,7 @@ struct Decode {
     const size_t b4n = (size_t)n * 4, wb = (size_t)8 * plane_words(n) * 4;
     const uint64_t post = more(c->sa[0], std::max<size_t>(8 * rstride, b4n)) + more(c->sa[1], b4n) + more(c->key[0], std::max(wb, b4n)) +
                           more(c->key[1], std::max(wb, b4n)) + more(c->rank, b4n) + more(c->gran, (size_t)8 * plane_granules(n) * sizeof(Granule)) +
-                          more(c->bwt, n) + more(c->text, n);
+                          more(c->bwt, n) + (dest.own_text() ? more(c->text, n) : 0);
     size_t fr = 0, tot = 0;
     if (env.give_back || (hipMemGetInfo(&fr, &tot) == hipSuccess && fr < 2 * post)) {
       BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2495,7 +2513,7 @@ struct Decode {
     BCE_HIP_TRY(c, hipGetLastError());
     if (ferr) { snprintf(c->err, sizeof c->err, "decode: a mixed gap was never split"); return BCE_HIP_E_INTERNAL; }
     BCE_TRY(ensure(c, c->bwt, n));
-    BCE_TRY(ensure(c, c->text, n));
+    if (dest.own_text()) BCE_TRY(ensure(c, c->text, n));
     BCE_TRY(ensure(c, c->stat, 64));
     sample_mem();
     uint32_t *dz = c->stat.as<uint32_t>();
@@ -2507,7 +2525,10 @@ struct Decode {
   }
 
   // ---- inverse BWT ----
-  int inverse_bwt(uint8_t *out) {
+  // The text is written where the destination wants it: into the context's buffer and copied to the host from there (kHost),
+  // straight into the caller's device memory (kDevice), or into the context's buffer and compared there (kCompare).
+  int inverse_bwt() {
+    uint8_t *const text = dest.own_text() ? c->text.as<uint8_t>() : dest.out;
     const size_t b4 = (size_t)n * 4;
     const uint32_t gn = grid256(n);
     for (int i = 0; i < 2; ++i) { BCE_TRY(ensure(c, c->sa[i], b4)); BCE_TRY(ensure(c, c->key[i], b4)); }
@@ -2527,18 +2548,39 @@ struct Decode {
     uint8_t *V = reinterpret_cast<uint8_t *>(val[0]);
     uint64_t lc = 0;
     uint32_t walkers = 0;
-    BCE_TRY(lf_walk(c, lf, c->bwt.as<uint8_t>(), n, c->text.as<uint8_t>(), n, off, V, &lc, &walkers));
+    BCE_TRY(lf_walk(c, lf, c->bwt.as<uint8_t>(), n, text, n, off, V, &lc, &walkers));
     if (lc == 0 || lc > n || n % lc) { snprintf(c->err, sizeof c->err, "decode: LF cycle of length %llu in %u rows", (unsigned long long)lc, n); return BCE_HIP_E_INTERNAL; }
     const bool single_cycle = lc == n;
     // periodic input (the reference's decoder returns zeros here)
-    if (!single_cycle) hipLaunchKernelGGL(expand_cycle_kernel, dim3(gn), dim3(256), 0, c->stream, V, (uint32_t)lc, n, off, c->text.as<uint8_t>());
-    BCE_HIP_TRY(c, hipMemcpyAsync(out, c->text.p, n, hipMemcpyDeviceToHost, c->stream));
+    if (!single_cycle) hipLaunchKernelGGL(expand_cycle_kernel, dim3(gn), dim3(256), 0, c->stream, V, (uint32_t)lc, n, off, text);
+    if (dest.kind == DecDest::kHost) BCE_HIP_TRY(c, hipMemcpyAsync(dest.out, c->text.p, n, hipMemcpyDeviceToHost, c->stream));
     BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
     BCE_HIP_TRY(c, hipGetLastError());
+    if (dest.kind == DecDest::kDevice && env.timing) fprintf(stderr, "gpu decode: text left on the device (%u B written in place, no copy to the host)\n", n);
+    if (dest.kind == DecDest::kCompare) BCE_TRY(compare());
     if (env.timing) fprintf(stderr, "gpu decode: inverse BWT (%s, %u walkers) %.3f s\n", single_cycle ? "one cycle" : "periodic", walkers, now_s() - tp0);
     if (env.mem()) fprintf(stderr, "gpu decode: device memory in use over the whole decode (sampled after every allocation stage): %.1f GB at most\n", st.peak_used / 1e9);
     if (env.timing) fprintf(stderr, "gpu decode: this context so far: device allocations %u calls %.1f MB %.3f s, pinned (query / answer buffers) %u calls %.1f MB %.3f s\n",
                             c->alloc_calls, c->alloc_bytes / 1e6, c->alloc_s, c->pin_calls, c->pin_bytes / 1e6, c->pin_s);
+    return BCE_HIP_OK;
+  }
+
+  // ---- kCompare: the decoded text against the original, on the device (kd_compare.hip) ----
+  // The common prefix is compared; where the sizes differ and the prefix agrees, the first index one of them lacks differs.
+  int compare() {
+    const double tc0 = now_s();
+    const uint64_t m = std::min<uint64_t>(n, dest.orig_n);
+    const uint8_t *orig = dest.orig_dev;
+    if (!orig && m) {                                             // (the walk has read the BWT: its n bytes are free for the original)
+      BCE_HIP_TRY(c, hipMemcpyAsync(c->bwt.p, dest.orig_host, m, hipMemcpyHostToDevice, c->stream));
+      orig = c->bwt.as<uint8_t>();
+    }
+    uint64_t fd = UINT64_MAX;
+    BCE_TRY(kd_compare(c, c->text.as<uint8_t>(), orig, m, &fd));
+    if (fd == UINT64_MAX && dest.orig_n != n) fd = m;
+    *dest.first_diff = fd;
+    if (env.timing) fprintf(stderr, "gpu decode: text left on the device, compared there with %llu B %s: %.6f s\n", (unsigned long long)dest.orig_n,
+                            dest.orig_dev ? "of device memory" : "uploaded from the host", now_s() - tc0);
     return BCE_HIP_OK;
   }
 };
@@ -2552,22 +2594,28 @@ using namespace bce;
 
 // `bce -d` on the GPU: archive -> original bytes (see the header of this file).  The context is only used for its
 // device, stream and scratch buffers; any compression state in it is dropped.
-static int decompress_device(bce_hip_ctx *c, const uint8_t *archive, size_t len, uint8_t *out, size_t cap, size_t *out_len) {
+// The text goes where `dest` says (DecDest): to the caller's host buffer, to the caller's device memory, or nowhere -- compared
+// on the device with the original.  For the host destination the launches, copies and allocations are what they always were.
+static int decompress_device(bce_hip_ctx *c, const uint8_t *archive, size_t len, const DecDest &dest, size_t *out_len) {
   if (!c) return BCE_HIP_E_ARG;
   struct PartEnd { bce_hip_ctx *c; ~PartEnd() { c->dec_part = 0; } } part_end{c};
   if (!archive || !out_len) return BCE_HIP_E_ARG;
+  const bool cmp = dest.kind == DecDest::kCompare;
+  if (cmp && (!dest.first_diff || (dest.orig_n && !dest.orig_dev && !dest.orig_host))) return BCE_HIP_E_ARG;
   ArchiveHead hd;
   if (parse_archive(archive, len, hd, /*header_only=*/true) != 0) return BCE_HIP_E_ARG;
   *out_len = hd.n;
-  if (!out) return BCE_HIP_OK;
-  if (cap < hd.n) return BCE_HIP_E_OVERFLOW;
+  if (!cmp) {
+    if (!dest.out) return BCE_HIP_OK;
+    if (dest.cap < hd.n) return BCE_HIP_E_OVERFLOW;
+  }
   if (parse_archive(archive, len, hd, false) != 0) return BCE_HIP_E_ARG;
   BCE_HIP_TRY(c, hipSetDevice(c->device));
   c->coder->drain();
   c->stage = 0; c->enum_active = false; c->k1_valid = false;   // the scratch buffers below belong to the decoder now
   c->phase = 4;
   struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
-  Decode d(c, hd);
+  Decode d(c, hd, dest);
   c->dec_part = 1;
   BCE_TRY(d.setup(len));
   BCE_TRY(d.rounds());
@@ -2576,10 +2624,39 @@ static int decompress_device(bce_hip_ctx *c, const uint8_t *archive, size_t len,
   BCE_TRY(d.give_back());
   BCE_TRY(d.planes());
   c->dec_part = 3;                                              // (... and the boundary ranks, once access_kernel has read them)
-  return d.inverse_bwt(out);
+  return d.inverse_bwt();
 }
 
 extern "C" int bce_hip_decompress_device(bce_hip_ctx *c, const uint8_t *archive, size_t len, uint8_t *out, size_t cap,
                                          size_t *out_len) {
-  return bce_guarded(c, [&] { return decompress_device(c, archive, len, out, cap, out_len); });
+  return bce_guarded(c, [&] { return decompress_device(c, archive, len, DecDest{DecDest::kHost, out, cap, nullptr, nullptr, 0, nullptr}, out_len); });
+}
+
+// The same decode with the text left in the caller's DEVICE memory (of the context's device, any alignment, cap bytes): the walk
+// of the inverse BWT writes it there, nothing of it crosses to the host.
+extern "C" int bce_hip_decompress_to_device(bce_hip_ctx *c, const uint8_t *archive, size_t len, void *d_out, size_t cap,
+                                            size_t *out_len) {
+  return bce_guarded(c, [&] {
+    return decompress_device(c, archive, len, DecDest{DecDest::kDevice, static_cast<uint8_t *>(d_out), cap, nullptr, nullptr, 0, nullptr}, out_len);
+  });
+}
+
+// Decode and compare with the original on the device: *first_diff = UINT64_MAX (equal), the first index that differs, or
+// min(n, decoded size) when only the sizes differ.
+extern "C" int bce_hip_verify_device(bce_hip_ctx *c, const uint8_t *archive, size_t len, const void *d_original, size_t n,
+                                     uint64_t *first_diff) {
+  return bce_guarded(c, [&] {
+    if (n && !d_original) return (int)BCE_HIP_E_ARG;
+    size_t decoded = 0;
+    return decompress_device(c, archive, len, DecDest{DecDest::kCompare, nullptr, 0, static_cast<const uint8_t *>(d_original), nullptr, n, first_diff}, &decoded);
+  });
+}
+
+extern "C" int bce_hip_verify_host(bce_hip_ctx *c, const uint8_t *archive, size_t len, const uint8_t *original, size_t n,
+                                   uint64_t *first_diff) {
+  return bce_guarded(c, [&] {
+    if (n && !original) return (int)BCE_HIP_E_ARG;
+    size_t decoded = 0;
+    return decompress_device(c, archive, len, DecDest{DecDest::kCompare, nullptr, 0, nullptr, original, n, first_diff}, &decoded);
+  });
 }

@@ -1,5 +1,6 @@
 // main.cpp -- the `bce` command line, mirroring the reference's main() (bce.cpp:1376-1484):
 //   bce -c archive.bce file [config.bcc]    compress on the MI355X through libbcehip.so
+//   bce -t file archive.bce                 (extension) decode on the GPU and compare with "file" there; writes nothing
 // Banner, usage text, summary line, argument detection and exit codes follow the reference
 // (banner :1377-1379, -c :1403-1427, -d :1428-1472, usage :1473-1483).  -d uses the GPU-assisted decoder (kd_decode.hip), -ds the host decoder (decoder.cpp);
 // -s runs the enumeration on the GPU in scan mode and the ScanCoder optimisation on the host (scan_coder.cpp).
@@ -206,6 +207,89 @@ static int compress_blocks(const HostFile &data, uint32_t nblocks, const uint8_t
   return 0;
 }
 
+// The archives inside an archive file: (offset, length) of each -- one for a plain archive, the table's for a BCEM container.
+// false: a container whose table does not fit the file.
+static bool archive_blocks(const HostFile &adata, std::vector<std::pair<size_t, size_t>> &blocks) {
+  if (!is_container(adata)) { blocks.emplace_back(0, adata.size()); return true; }
+  const uint32_t ver = (uint32_t)get_le(adata.data() + 4, 4), nb = (uint32_t)get_le(adata.data() + 8, 4);
+  size_t pos = 12 + (size_t)nb * 16;
+  if (ver != 1 || pos > adata.size()) return false;
+  for (uint32_t b = 0; b < nb; ++b) {
+    const size_t alen = (size_t)get_le(adata.data() + 12 + (size_t)b * 16 + 8, 8);
+    if (alen > adata.size() - pos) return false;
+    blocks.emplace_back(pos, alen);
+    pos += alen;
+  }
+  return true;
+}
+
+// (A weak reference: this file is also linked, for the sanitizer run of `-ds` on hostile archives, into a CPU-only program beside
+//  "no device" stand-ins for just the entry points the older modes call.  With libbcehip.so it resolves like any other.)
+extern "C" int bce_hip_verify_host(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, const uint8_t *original, size_t n,
+                                   uint64_t *first_diff) __attribute__((weak));
+
+// exit status of `bce -t` when the archive decodes, but not to the file's bytes (every other failure keeps the status -d gives it)
+static const int kExitDiffers = 1;
+
+// `bce -t file archive.bce` (an extension): the archive is decoded on the GPU and compared THERE with the file, block by block for
+// a container (bce_hip_verify_host: the decoded text never comes back to the host).  Nothing is written.
+static int test_archive(const char *file_path, const char *archive_path) {
+  auto start = std::chrono::high_resolution_clock::now();
+  HostFile adata, data;
+  std::thread areader(read_whole_file, archive_path, &adata, (size_t)0);
+  std::thread freader(read_whole_file, file_path, &data, (size_t)0);
+  bce_hip_ctx *ctx = nullptr;
+  const int rc0 = bce_hip_create(&ctx, 0);
+  areader.join();
+  freader.join();
+  struct Destroy { bce_hip_ctx *&c; ~Destroy() { if (c) bce_hip_destroy(c); } } destroy{ctx};
+  if (adata.status == -1) { printf("Archive not found.\n"); return -1; }
+  if (adata.status != 0 || adata.size() == 0) { printf("Could not read Archive.\n"); return -2; }
+  if (data.status != 0) { printf("Error loading file\n"); return -1; }
+  if (rc0 != 0 || !bce_hip_verify_host) { printf("No usable HIP device: %s\n", bce_hip_strerror(rc0 ? rc0 : BCE_HIP_E_DEVICE)); return -3; }
+  std::vector<std::pair<size_t, size_t>> blocks;
+  if (!archive_blocks(adata, blocks)) { printf("Could not read Archive.\n"); return -2; }
+  // where each block's text begins in the whole file: from the blocks' own headers (a container's table must agree with them, as for -d)
+  std::vector<uint64_t> at(blocks.size() + 1, 0);
+  for (size_t b = 0; b < blocks.size(); ++b) {
+    size_t hn = 0;
+    const int hr = bce_hip_decompress(adata.data() + blocks[b].first, blocks[b].second, nullptr, 0, &hn);
+    if (hr != 0 && blocks.size() == 1) { printf("Decompression failed: %s\n", bce_hip_strerror(hr)); return -4; }
+    if (hr != 0 || (blocks.size() > 1 && (uint64_t)hn != get_le(adata.data() + 12 + b * 16, 8))) { printf("Could not read Archive.\n"); return -2; }
+    at[b + 1] = at[b] + hn;
+  }
+  const uint64_t total = at.back(), fsize = data.size();
+  uint64_t prog = 0;
+  if (blocks.size() == 1) bce_hip_set_progress(ctx, progress, &prog);
+  for (size_t b = 0; b < blocks.size(); ++b) {
+    const uint64_t lo = std::min(at[b], fsize), len = std::min(at[b + 1] - at[b], fsize - lo);   // the file's slice for this block
+    uint64_t fd = UINT64_MAX;
+    const int rc = bce_hip_verify_host(ctx, adata.data() + blocks[b].first, blocks[b].second, data.data() + lo, (size_t)len, &fd);
+    if (blocks.size() == 1) progress_end();
+    if (rc != 0) {
+      if (bce_hip_last_error(ctx)[0]) printf("%s\n", bce_hip_last_error(ctx));
+      printf("Decompression failed: %s\n", bce_hip_strerror(rc));
+      return -4;
+    }
+    if (fd == UINT64_MAX) continue;
+    if (fd < len) printf("Archive differs from file at byte %llu\n", (unsigned long long)(at[b] + fd));
+    else printf("Archive differs from file in size: the archive holds %llu B, the file %llu B (equal up to byte %llu)\n",
+                (unsigned long long)total, (unsigned long long)fsize, (unsigned long long)fsize);
+    fflush(stdout);
+    return kExitDiffers;
+  }
+  if (fsize != total) {                                             // (a longer file: every block agreed with its slice)
+    printf("Archive differs from file in size: the archive holds %llu B, the file %llu B (equal up to byte %llu)\n",
+           (unsigned long long)total, (unsigned long long)fsize, (unsigned long long)total);
+    return kExitDiffers;
+  }
+  std::chrono::duration<double> duration = std::chrono::high_resolution_clock::now() - start;
+  printf("Archive OK: %zu B -> %llu B in %.1f s\n", adata.size(), (unsigned long long)total, duration.count());
+  ctx = nullptr;                                                    // (left to fast_exit, like -d)
+  fast_exit(0);
+  return 0;
+}
+
 static int usage() {
   printf("Usage:\n");
   printf("  bce -c archive.bce file [config.bcc]\n");
@@ -216,6 +300,9 @@ static int usage() {
   printf("\n");
   printf("  bce -s config.bcc file\n");
   printf("   Scan \"file\" and generate a config file \"config.bcc\" to improve the AdaptiveCoder (uses a lot of memory)\n");
+  printf("\n");
+  printf("  bce -t file archive.bce\n");
+  printf("   Tests archive \"archive.bce\" against \"file\": decodes it on the GPU and compares there, writes nothing (extension; exit status 0 = equal, %d = differs)\n", kExitDiffers);
   printf("\n");
   printf("  bce -cN archive.bcem file [config.bcc]      (extension: N = 2..64 blocks, one container, all GPUs of the node; every block < 2^31 bytes)\n");
   return 0;
@@ -325,19 +412,7 @@ int main(int argc, char **argv) {
     // :1466): the plain host decoder (decoder.cpp), on purpose and by name -- there is no silent fallback.
     // A BCEM container (bce -cN, the sharded bench) is decoded block by block.
     std::vector<std::pair<size_t, size_t>> blocks;               // (offset, length) of each archive inside adata
-    if (is_container(adata)) {
-      const uint32_t ver = (uint32_t)get_le(adata.data() + 4, 4), nb = (uint32_t)get_le(adata.data() + 8, 4);
-      size_t pos = 12 + (size_t)nb * 16;
-      if (ver != 1 || pos > adata.size()) { printf("Could not read Archive.\n"); return -2; }
-      for (uint32_t b = 0; b < nb; ++b) {
-        const size_t alen = (size_t)get_le(adata.data() + 12 + (size_t)b * 16 + 8, 8);
-        if (alen > adata.size() - pos) { printf("Could not read Archive.\n"); return -2; }
-        blocks.emplace_back(pos, alen);
-        pos += alen;
-      }
-    } else {
-      blocks.emplace_back(0, adata.size());
-    }
+    if (!archive_blocks(adata, blocks)) { printf("Could not read Archive.\n"); return -2; }
     int rc = 0;
     // the output: plain memory, not value-initialised (a vector would write 10^8 zeroes first that the decoder overwrites)
     // (2 MB-aligned with huge pages asked for, and its pages faulted in by the kernel -- MADV_POPULATE_WRITE leaves the
@@ -477,6 +552,8 @@ int main(int argc, char **argv) {
     fast_exit(0);
     if (keep) bce_hip_destroy(keep);
     return 0;
+  } else if (argc == 4 && argv[1][0] == '-' && argv[1][1] == 't' && argv[1][2] == 0) {
+    return test_archive(argv[2], argv[3]);
   } else if (argc == 4 && argv[1][0] == '-' && argv[1][1] == 's') {
     // Scan (bce.cpp:1384-1402): enumeration on the GPU, ScanCoder optimisation on the host, 288-byte config out
     auto start = std::chrono::high_resolution_clock::now();

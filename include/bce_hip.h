@@ -179,7 +179,14 @@ int bce_hip_enum_model(bce_hip_ctx *ctx, uint32_t *out, uint64_t cap_records, ui
 int bce_hip_scan(bce_hip_ctx *ctx, uint8_t config288[BCE_HIP_CONFIG_BYTES], double result_bytes[9]);
 
 /* ---- decoder (SURVEY section 8f "next #1"): bce_hip_decompress = plain host C++ (`bce -ds`),
- *      bce_hip_decompress_device = the GPU-assisted decoder of kd_decode.hip (`bce -d`); same bytes ---------------- */
+ *      bce_hip_decompress_device = the GPU-assisted decoder of kd_decode.hip (`bce -d`); same bytes.
+ *      The GPU-assisted decoder has one body and three destinations for the text: the caller's host buffer
+ *      (bce_hip_decompress_device), the caller's device memory (bce_hip_decompress_to_device: the mirror of
+ *      bce_hip_compress_device, nothing of the text crosses to the host), or none -- compared on the device with the
+ *      original (bce_hip_verify_device / _host, `bce -t`: the format carries no checksum, so "decode it and compare" is
+ *      the integrity check there is).  The archive is a host pointer in all of them: the eight range decoders read it
+ *      on host threads.  All work runs on the context's own stream and is complete when the call returns; device
+ *      memory the caller passes in must be ready (its producer's stream synchronised) when the call is made. -------- */
 /* BCE::decode + unbwt::bytewise + inverse BWT + rotate (bce.cpp:1169-1233, 1043-1102): archive -> original bytes.
  * out == NULL: only report the decoded size in *out_len.  Needs no context and no GPU. */
 int bce_hip_decompress(const uint8_t *archive, size_t len, uint8_t *out, size_t cap, size_t *out_len);
@@ -188,6 +195,17 @@ int bce_hip_decompress(const uint8_t *archive, size_t len, uint8_t *out, size_t 
  * then plane fill, unbwt::bytewise as wavelet-matrix access and the inverse BWT on the device.  Uses the context's
  * device, stream and scratch buffers; a compression in progress in the same context is dropped. */
 int bce_hip_decompress_device(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, uint8_t *out, size_t cap, size_t *out_len);
+/* The same decode with the text left in DEVICE memory the caller owns (of the context's device; any alignment, e.g. a slice of a
+ * tensor): the inverse BWT writes its bytes straight to d_out[0, n), never beyond, and the context allocates no text buffer of its
+ * own.  d_out == NULL: only report the decoded size; cap < n: BCE_HIP_E_OVERFLOW, nothing written. */
+int bce_hip_decompress_to_device(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, void *d_out, size_t cap, size_t *out_len);
+/* Decode into the context's own buffer and compare there with the n bytes of the original (_device: device memory of the context's
+ * device, any alignment; _host: uploaded once into a scratch buffer of the context that is idle by then).  BCE_HIP_OK with
+ * *first_diff = UINT64_MAX: the archive decodes to exactly these n bytes; = i: the smallest index at which the two differ; the
+ * sizes differ and the common prefix agrees: min(n, decoded size).  An archive that does not parse or decode: the decoder's status,
+ * as bce_hip_decompress_device, *first_diff untouched. */
+int bce_hip_verify_device(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, const void *d_original, size_t n, uint64_t *first_diff);
+int bce_hip_verify_host(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, const uint8_t *original, size_t n, uint64_t *first_diff);
 
 /* ---- statistics of the last bce_hip_encode / bce_hip_compress ------------------------------------ */
 typedef struct bce_hip_stats {
