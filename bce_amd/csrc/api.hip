@@ -1,5 +1,5 @@
 // api.hip -- the C ABI of libbcehip.so (include/bce_hip.h): context lifetime, stage entry points and
-// the host-side driver of BCE::encode (bce.cpp:1117-1167).
+// the host-side driver of BCE::encode (bce.cpp:1117-1167): struct Enumeration, the round loop.
 #include <condition_variable>
 #include <functional>
 #include <mutex>
@@ -335,6 +335,268 @@ int flush_symbols(bce_hip_ctx *c, uint64_t nsym) {
   }
   return k3_reset_symbols(c);
 }
+// ---- the round loop of BCE::code (bce.cpp:1246-1371) as the host drives it --------------------------------
+// The enumeration's switches, read from the environment once per enumeration (not once per process: tests set them between two
+// compressions): BCE_HIP_SPLIT_SYMS, BCE_HIP_DFS_ENTER, BCE_HIP_NO_FLUSH_PREDICT, BCE_HIP_PLANE_TRACE.
+struct EnumEnv {
+  uint64_t split_limit = 1ull << 31;   // symbol records of one round from which it runs plane group by plane group (K4's limit)
+  uint32_t dfs_enter;                  // live nodes from which the depth-first tail is first tried
+  bool no_predict = getenv("BCE_HIP_NO_FLUSH_PREDICT") != nullptr, plane_trace = getenv("BCE_HIP_PLANE_TRACE") != nullptr;
+  explicit EnumEnv(const bce_hip_ctx *c) {
+    const char *s = getenv("BCE_HIP_SPLIT_SYMS"), *d = getenv("BCE_HIP_DFS_ENTER");
+    const uint64_t v = s ? strtoull(s, nullptr, 10) : 0;
+    if (v && v < split_limit) split_limit = v;
+    // (from 1 M live nodes down (512 K .. 8 M measured: 1 M is best on text, source code and executables) the tail starts with
+    //  workgroup-local rounds, k3_local_kernel; without them the walkers alone take over at 65 536)
+    dfs_enter = d ? (uint32_t)strtoul(d, nullptr, 10) : (c->dbg_no_local ? 65536u : (1u << 20));
+  }
+};
+
+// A round that finds the symbol buffer too small is a round thrown away: its count kernel has run in full, the rest of
+// the batch's launches return at once (8 launches of ~5 us) and the round runs again after the flush -- ~90 us per
+// flush, 1.2 ms of the 13 ms of text.  The host knows how many symbols the last rounds emitted and how much room is
+// left, so it flushes BEFORE a round that is unlikely to fit and never queues more rounds than the room allows
+// (an estimate: a round that does not fit after all still takes the old way).
+struct FlushPredictor {
+  uint64_t est_syms = 0;                           // symbols of a coming round, from the last rounds (0: unknown)
+  uint64_t recent_syms[8] = {0, 0, 0, 0, 0, 0, 0, 0}; uint32_t recent_at = 0;
+  // What the last eight rounds emitted, each (`re`: a batch's run table, one entry per round and plane): the bulk of the nodes
+  // moves from plane to plane with a period of eight rounds, and the symbols per round swing with it -- the largest of a
+  // period is what the next round may bring.  Ramp-up: the last round alone (the next doubles).
+  void record(const RunEntry *re, uint32_t rounds, bool decaying) {
+    for (uint32_t i = 0; i < rounds; ++i) {
+      uint64_t t = 0;
+      for (int p = 0; p < 8; ++p) t += re[(size_t)i * 8 + p].count;
+      recent_syms[recent_at++ & 7u] = t;
+    }
+    est_syms = 0;
+    if (decaying) { for (uint64_t v : recent_syms) est_syms = v > est_syms ? v : est_syms; }
+    else est_syms = recent_syms[(recent_at - 1u) & 7u];
+  }
+  // how many of `batch` rounds a buffer of `cap` records that holds `held` is likely to take (0: flush first)
+  uint32_t rounds_that_fit(uint32_t batch, uint64_t cap, uint64_t held, bool decaying) const {
+    if (!est_syms) return batch;
+    const uint64_t room = cap > held ? cap - held : 0;
+    uint64_t need = decaying ? est_syms + (est_syms >> 4) + 1024 : 2 * est_syms + 1024;   // (ramp-up: a round emits twice the last one's)
+    uint64_t acc = 0; uint32_t fit = 0;
+    while (fit < batch && acc + need <= room) { acc += need; if (!decaying) need *= 2; ++fit; }
+    if (!fit && !held) return batch;                       // (an empty buffer that is still too small grows the old way)
+    return fit;
+  }
+};
+
+// One enumeration: the state its steps share.  bce_hip_encode and bce_hip_scan run() it with their sink -- `sink(nsym)` takes the
+// symbol records buffered so far (the model flush of -c, the ScanCoders of -s) and leaves the buffer empty; bce_hip_enum_round runs
+// one batch of one round with it.  The rounds come wide in batches, one launch each, from the LDS tail kernel or depth-first.
+struct Enumeration {
+  enum class Kernels { kTail, kSmall, kWide };     // the LDS tail kernel, one launch per round (k3_small_kernel), wide rounds
+  struct Batch { Kernels how; uint32_t rounds; uint64_t nodes; bool growing; };   // rounds == 0: flush first; nodes, growing: what bounds the grid
+  // What a step leaves for the loop to do: the next batch (after a flush as well); round c->round again, the node lists or the
+  // symbol buffer having grown; the next batch behind a split round; nothing.  All but the last mean "look again" and say why.
+  enum class Next { kRounds, kSameRound, kSplitDone, kFinished };
+  static constexpr uint32_t kEarlyMax = 4;         // early small flushes: 1M, 2M, 4M, 8M records (0..5 measured: +3 % on text, neutral on random data)
+  bce_hip_ctx *c;
+  const std::function<int(uint64_t)> sink;
+  const EnumEnv env;
+  const uint32_t n;
+  EnumCtl ctl{};                                   // the control block as last read back (sym_total: 0 once the host has flushed)
+  uint64_t cur_nodes = 0;                          // nodes of round c->round
+  bool decaying = false;                           // past the ramp-up: the node count no longer doubles
+  bool have_ctl = false;                           // a round has ended: ctl says something
+  bool wide_once = false;                          // round c->round does not fit the one-launch kernel: the wide kernels run it
+  // depth-first tail: first attempt when the live set is small, a second one (if the first ran out of room) when tiny
+  int dfs_try = 0;
+  const uint32_t dfs_enter[2];
+  FlushPredictor predict;
+
+  Enumeration(bce_hip_ctx *ctx, std::function<int(uint64_t)> to)
+      : c(ctx), sink(std::move(to)), env(ctx), n(ctx->n), dfs_enter{env.dfs_enter, 2048u} {
+    for (int i = 0; i < 8; ++i) { const uint32_t Ci = c->zeros[(i + 7) & 7]; cur_nodes += (Ci && n - Ci) ? 1 : 0; }
+  }
+  bool finished() const { return ctl.done_round != 0xFFFFFFFFu; }
+  int flush() { BCE_TRY(sink(ctl.sym_total)); ctl.sym_total = 0; return BCE_HIP_OK; }   // (sym_total, the host copy: what the next batch starts from)
+  int grow_lists() { BCE_TRY(k3_grow_lists(c, ctl)); ctl.overflow = 0; return BCE_HIP_OK; }   // round c->round does not fit the node lists (nothing of it was written)
+  // K3's GPU time (stats.k3_ms): ev0 goes in front of the launches, ev1 behind them, and the time between is added once the host
+  // has waited for ev1 -- with the control block's copy, or alone.  What the host does between two such pairs is not in it.
+  int clock_start() { BCE_HIP_TRY(c, hipEventRecord(c->ev0, c->stream)); return BCE_HIP_OK; }
+  int clock_stop(bool read_ctl) {
+    BCE_HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    if (read_ctl) BCE_TRY(k3_sync_ctl(c, &ctl));
+    else BCE_HIP_TRY(c, hipEventSynchronize(c->ev1));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->stats.k3_ms += ms;
+    return BCE_HIP_OK;
+  }
+
+  int run() {
+    for (Next next = Next::kRounds; next != Next::kFinished;) {
+      BCE_TRY(gate_regain(c));                     // (lent to another context behind the last model flush)
+      next = Next::kRounds;
+      BCE_TRY(depth_first(&next));
+      if (next != Next::kFinished) BCE_TRY(batch(&next));
+    }
+    return BCE_HIP_OK;
+  }
+  // Few live nodes and almost everything visited: finish depth-first (k3_dfs.hip).  The walkers' symbols come after everything
+  // emitted so far, so flush that first.
+  int depth_first(Next *next) {
+    const bool tail = have_ctl && decaying && !ctl.need_flush && !finished() && dfs_try < 2 && ctl.next_nodes && ctl.next_nodes <= dfs_enter[dfs_try];
+    if (!tail || !(ctl.nodes_total >= 8ull * (n - 1) / 8 || c->round >= 1024u || c->dbg_tail_round)) return BCE_HIP_OK;
+    BCE_TRY(flush());
+    BCE_TRY(gate_regain(c));
+    bool dfs_done = false;
+    BCE_TRY(clock_start());
+    RoctxRange range("bce K3 tail (local rounds + walkers)");
+    BCE_TRY(k3_dfs_tail(c, ctl, dfs_enter[dfs_try], &dfs_done));
+    BCE_TRY(clock_stop(false));
+    if (!dfs_done) { ++dfs_try; return BCE_HIP_OK; }   // out of room (symbols / queue): carry on with rounds
+    BCE_TRY(k3_sync_ctl(c, &ctl));
+    *next = Next::kFinished;
+    return flush();
+  }
+  // The kernels of the next batch and how many rounds of them to queue.
+  Batch plan() {
+    if ((!c->dbg_no_tail || cur_nodes == 0) && cur_nodes <= K3_TAIL_ENTER)       // (no node at all, e.g. one byte repeated: only this kernel says "done" then)
+      // narrow phase: the persistent single-workgroup kernel loops over rounds on the device
+      // (while the depth-first tail may still take over, come back after 1024 rounds: an input that is one long run
+      //  or one table has this few nodes from the first round on, and its millions of rounds belong to the walkers)
+      return {Kernels::kTail, (dfs_try < 2 && !c->dbg_no_dfs) ? 1024u : K3_TAIL_MAXROUNDS, 0, false};
+    Batch b;
+    if (!c->dbg_no_small && !wide_once && cur_nodes <= K3_SMALL_NODES) {
+      // narrow rounds: one launch per round (k3_small_kernel); while the count still doubles, queue only as many
+      // rounds as stay within its range
+      b = {Kernels::kSmall, 64, cur_nodes, !decaying};
+      if (!decaying) { b.rounds = 1; while (b.rounds < 16 && (cur_nodes << (b.rounds + 1)) <= 2ull * K3_SMALL_NODES) ++b.rounds; }
+    } else {
+      // wide rounds: sync often (the round dominates); medium rounds: queue many per sync
+      wide_once = false;
+      b = {Kernels::kWide, cur_nodes > (1u << 22) ? 4u : (cur_nodes > (1u << 20) ? K3_BATCH_MID : (cur_nodes > (1u << 14) ? 16u : 64u)), decaying ? cur_nodes : 0, !decaying};
+    }
+    // ramp-up: the node count doubles per round; once a round or two reach the next early-flush size, stop there so
+    // that the coders get their first (small) batches as early as possible
+    if (!decaying && have_ctl && c->stats.flushes < kEarlyMax) {
+      const uint64_t want = (uint64_t)1 << (20 + c->stats.flushes);
+      uint64_t est = ctl.sym_total, nn = cur_nodes;
+      uint32_t cut = 0;
+      while (cut < b.rounds && est < want) { est += nn; nn *= 2; ++cut; }
+      b.rounds = cut ? cut : 1u;
+    }
+    if (!env.no_predict && have_ctl && !ctl.need_flush) b.rounds = predict.rounds_that_fit(b.rounds, c->sym_cap, ctl.sym_total, decaying);
+    return b;
+  }
+  // Queue a batch, wait for it and take in what it did: ctl, the rounds' runs, c->round, the predictor's counts.
+  int run_batch(const Batch &b) {
+    const uint32_t first = c->round;
+    RoctxRange range("bce K3 rounds");
+    BCE_TRY(clock_start());
+    switch (b.how) {
+      case Kernels::kTail: BCE_TRY(k3_tail(c, b.rounds)); break;
+      case Kernels::kSmall: BCE_TRY(k3_rounds_small(c, b.rounds, b.nodes, b.growing)); break;
+      case Kernels::kWide: BCE_TRY(k3_rounds(c, b.rounds, b.nodes)); break;
+    }
+    BCE_TRY(clock_stop(true));
+    if (ctl.stalled) return k3_stalled(c);         // (before skip_round is read: a stalled round does not set it)
+    uint32_t executed = ctl.tail_rounds;
+    if (b.how == Kernels::kTail) {
+      BCE_TRY(k3_fetch_tail_runs(c, executed));
+    } else {
+      const bool stopped = ctl.need_flush || ctl.overflow || (b.how == Kernels::kSmall && ctl.small_bail);
+      executed = stopped ? ctl.skip_round - first : b.rounds;
+      if (executed > b.rounds) return k3_bad_skip(c, ctl, first, b.rounds);
+      BCE_TRY(k3_fetch_runs(c, first, executed));
+      if (executed) predict.record(reinterpret_cast<const RunEntry *>(c->h_runs), executed, decaying);
+    }
+    c->round = first + executed;
+    return BCE_HIP_OK;
+  }
+  // One batch of rounds, and what its end asks for.
+  int batch(Next *next) {
+    const Batch b = plan();
+    if (!b.rounds) return flush();                 // (no room for the next round: flushed, look again)
+    BCE_TRY(run_batch(b));
+    if (b.how == Kernels::kSmall && ctl.small_bail) { BCE_TRY(k3_clear_small_bail(c)); wide_once = true; }
+    if (ctl.overflow) {                            // larger lists, the same round again
+      BCE_TRY(grow_lists());
+      have_ctl = true; cur_nodes = 0;
+      for (int p = 0; p < 8; ++p) cur_nodes += (uint64_t)ctl.cnt[c->round & 1u][p][0] + ctl.cnt[c->round & 1u][p][1];
+      *next = Next::kSameRound;
+      return BCE_HIP_OK;
+    }
+    round_ended(/*split=*/false);
+    if (ctl.need_flush && ctl.sym_total) return flush();   // (the batch stopped at a round whose symbols found no room: flushed, look again)
+    if (ctl.need_flush) {
+      // one round alone exceeds the symbol buffer: enlarge it and run the round again -- or, when the round emits more than
+      // one model flush can take (2^31 records: a high-entropy input of more than ~10^9 bytes), plane group by plane group
+      const uint64_t want = ctl.want_syms + (ctl.want_syms >> 3) + 1024;
+      if (want >= env.split_limit) return split_round(next);
+      *next = Next::kSameRound;
+      return k3_grow_symbols(c, want);
+    }
+    if (finished()) { *next = Next::kFinished; return flush(); }
+    // The host coders are the critical path from the first batch on: hand them small batches early (1M, 2M, 4M, 8M
+    // records) instead of waiting for the symbol buffer to fill, so that they are never idle while the GPU works on
+    // the next 16M.
+    if (c->stats.flushes < kEarlyMax && ctl.sym_total >= ((uint64_t)1 << (20 + c->stats.flushes))) BCE_TRY(flush());
+    return BCE_HIP_OK;
+  }
+  // Round c->round - 1 has ended, ctl is what it left: the next round's width, and whether the count still grows.
+  void round_ended(bool split) {
+    if (c->progress) c->progress(ctl.nodes_total, 8ull * n, c->progress_user);
+    if (env.plane_trace) {
+      fprintf(stderr, "round %u: %llu nodes next, k3 %.2f ms so far; per plane:", c->round, (unsigned long long)ctl.next_nodes, c->stats.k3_ms);
+      for (int p = 0; p < 8; ++p) fprintf(stderr, " %u", ctl.cnt[c->round & 1u][p][0] + ctl.cnt[c->round & 1u][p][1]);
+      fprintf(stderr, "\n");
+    }
+    decaying = ctl.next_nodes <= cur_nodes && c->round > 16;   // past the ramp-up: the node count no longer doubles
+    if (!split && c->dbg_tail_round && c->round >= c->dbg_tail_round) decaying = true;   // test knob 10: the tail starts while the count still grows (a split round never applied it)
+    have_ctl = true;
+    cur_nodes = ctl.next_nodes;
+  }
+  // One pass of a split round: the symbols of the planes in `mask`.
+  // (K3's event time covers the passes' launches only: the flushes between them wait for coder threads)
+  int split_pass(uint32_t mask, bool repeat) {
+    BCE_TRY(clock_start());
+    BCE_TRY(k3_clear_need_flush(c));
+    BCE_TRY(k3_round_masked(c, mask, repeat));
+    BCE_TRY(clock_stop(true));
+    return ctl.stalled ? k3_stalled(c) : (int)BCE_HIP_OK;
+  }
+  // A round whose symbols do not fit ONE model flush (K4 takes fewer than 2^31 records; BCE_HIP_SPLIT_SYMS lowers the limit for
+  // tests).  The planes' streams are independent, so the round is run once per GROUP of planes -- every pass classifies all
+  // nodes and writes all children (the same values to the same places: the parents' lists are not touched), records only its
+  // group's symbols (K3Args::pmask) and is flushed on its own; a plane's records of one round never exceed n/2 < 2^30.
+  // kSplitDone / kFinished: the round is done, its symbols flushed; kSameRound: its lists were too small and have been grown.
+  int split_round(Next *next) {
+    // pass 0, all planes, three launches: either the round fits after all (the one-launch rounds only know an upper bound), or
+    // the per-plane counts are in the control block afterwards
+    BCE_TRY(split_pass(0xFFu, false));
+    if (ctl.overflow) { *next = Next::kSameRound; return grow_lists(); }
+    if (!ctl.need_flush) {
+      BCE_TRY(k3_fetch_runs(c, c->round, 1));
+      BCE_TRY(flush());
+    } else {
+      uint64_t cnt[8], maxp = 0;
+      for (int q = 0; q < 8; ++q) { cnt[q] = ctl.ptot[q][2]; if (cnt[q] > maxp) maxp = cnt[q]; }
+      if (maxp + 1024 > c->sym_cap) BCE_TRY(k3_grow_symbols(c, maxp + 1024));      // (< 2^30 + 1025)
+      for (int q = 0; q < 8;) {
+        const bool repeat = q > 0;
+        uint32_t mask = 0; uint64_t acc = 0;
+        while (q < 8 && (mask == 0 || acc + cnt[q] <= c->sym_cap)) { mask |= 1u << q; acc += cnt[q]; ++q; }
+        BCE_TRY(split_pass(mask, repeat));
+        if (ctl.need_flush || ctl.overflow) { snprintf(c->err, sizeof c->err, "k3: pass of planes %#x of round %u does not fit (%llu symbols, room for %llu)", mask, c->round, (unsigned long long)acc, (unsigned long long)c->sym_cap); return BCE_HIP_E_INTERNAL; }
+        BCE_TRY(k3_fetch_runs(c, c->round, 1));
+        BCE_TRY(flush());
+        BCE_TRY(gate_regain(c));
+      }
+      c->stats.split_rounds += 1.0;
+    }
+    c->round += 1;
+    predict.est_syms = 0;                          // (the round's records went by the predictor)
+    round_ended(/*split=*/true);
+    *next = finished() ? Next::kFinished : Next::kSplitDone;
+    return BCE_HIP_OK;
+  }
+};
 
 }  // namespace
 
@@ -522,8 +784,7 @@ static int bwt_body(bce_hip_ctx *c, uint32_t *offset) {
   BCE_HIP_TRY(c, hipSetDevice(c->device));
   const double t0 = now_s();
   RoctxRange range("bce K1 rotation sort + BWT");
-  c->phase = 1;
-  struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
+  PhaseScope phase(c, 1);
   BCE_TRY(k1_bwt(c));
   c->stats.t_bwt = now_s() - t0;
   c->stage = 2;
@@ -556,8 +817,7 @@ int bce_hip_divbwt(bce_hip_ctx *c, const uint8_t *in, uint8_t *out, uint32_t n, 
   return bce_guarded(c, [&]() -> int {
     BCE_HIP_TRY(c, hipSetDevice(c->device));
     c->coder->drain();
-    c->phase = 1;
-    struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
+    PhaseScope phase(c, 1);
     return k1_divbwt(c, in, out, n, primary);
   });
 }
@@ -567,8 +827,7 @@ int bce_hip_inverse_bwt(bce_hip_ctx *c, const uint8_t *in, uint8_t *out, uint32_
   return bce_guarded(c, [&]() -> int {
     BCE_HIP_TRY(c, hipSetDevice(c->device));
     c->coder->drain();
-    c->phase = 5;
-    struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
+    PhaseScope phase(c, 5);
     return kd_inverse_bw_transform(c, in, out, n, primary);
   });
 }
@@ -580,8 +839,7 @@ static int planes_body(bce_hip_ctx *c, uint32_t zeros[8]) {
   BCE_HIP_TRY(c, hipSetDevice(c->device));
   const double t0 = now_s();
   RoctxRange range("bce K2 planes + rank directory");
-  c->phase = 2;
-  struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
+  PhaseScope phase(c, 2);
   BCE_TRY(k2_build_planes(c));
   c->stats.t_planes = now_s() - t0;
   c->stage = 3;
@@ -601,8 +859,7 @@ int bce_hip_rank1(bce_hip_ctx *c, int plane, const uint32_t *idx, uint32_t count
   if (!idx || !out || plane < 0 || plane > 7) return BCE_HIP_E_ARG;
   for (uint32_t i = 0; i < count; ++i) if (idx[i] > c->n) return BCE_HIP_E_ARG;
   BCE_HIP_TRY(c, hipSetDevice(c->device));
-  c->phase = 3;                                  // (it reads the planes: what goes back is what an enumeration beside them would give)
-  struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
+  PhaseScope phase(c, 3);                        // (it reads the planes: what goes back is what an enumeration beside them would give)
   return k2_rank1(c, plane, idx, count, out);
 }
 
@@ -610,8 +867,7 @@ int bce_hip_rank1(bce_hip_ctx *c, int plane, const uint32_t *idx, uint32_t count
 // (each call runs as phase 3, the enumeration's, and leaves phase 0 behind: between the calls other entry points run in this context)
 int bce_hip_enum_begin(bce_hip_ctx *c) {
   BCE_TRY(check_stage(c, 3));
-  c->phase = 3;
-  struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
+  PhaseScope phase(c, 3);
   BCE_HIP_TRY(c, hipSetDevice(c->device));
   BCE_TRY(k4_prepare(c));
   BCE_TRY(k3_begin(c));
@@ -627,25 +883,20 @@ int bce_hip_enum_nodes(bce_hip_ctx *c, int plane, uint32_t *out, uint32_t cap_no
 int bce_hip_enum_round(bce_hip_ctx *c, uint64_t *next_nodes) {
   if (!c || !c->enum_active) return BCE_HIP_E_STATE;
   BCE_HIP_TRY(c, hipSetDevice(c->device));
-  c->phase = 3;
-  struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
+  PhaseScope phase(c, 3);
   const uint32_t first = c->round;
-  if (c->dbg_step_small) BCE_TRY(k3_rounds_small(c, 1, K3_SMALL_NODES, false));   // test hook: step with the one-launch kernel
-  else BCE_TRY(k3_rounds(c, 1, 0));
-  EnumCtl ctl;
-  BCE_TRY(k3_sync_ctl(c, &ctl));
-  if (ctl.stalled) return k3_stalled(c);
-  if (ctl.overflow) {                              // larger lists, the same round again (as bce_hip_encode does)
-    BCE_TRY(k3_grow_lists(c, ctl));
-    if (c->dbg_step_small) BCE_TRY(k3_rounds_small(c, 1, K3_SMALL_NODES, false));
-    else BCE_TRY(k3_rounds(c, 1, 0));
-    BCE_TRY(k3_sync_ctl(c, &ctl));
-    if (ctl.overflow) return BCE_HIP_E_OVERFLOW;
+  Enumeration e(c, nullptr);                       // (no sink: the stepping interface never flushes)
+  // test hook (knob 5): step with the one-launch kernel
+  const Enumeration::Batch b = {c->dbg_step_small ? Enumeration::Kernels::kSmall : Enumeration::Kernels::kWide, 1, c->dbg_step_small ? K3_SMALL_NODES : 0u, false};
+  BCE_TRY(e.run_batch(b));
+  if (e.ctl.overflow) {                            // larger lists, the same round again (as bce_hip_encode does)
+    BCE_TRY(e.grow_lists());
+    BCE_TRY(e.run_batch(b));
+    if (e.ctl.overflow) return BCE_HIP_E_OVERFLOW;
   }
-  if (ctl.need_flush) return BCE_HIP_E_OVERFLOW;   // the stepping interface never flushes
-  BCE_TRY(k3_fetch_runs(c, first, 1));
+  if (e.ctl.need_flush) return BCE_HIP_E_OVERFLOW;
   c->round = first + 1;
-  if (next_nodes) *next_nodes = ctl.next_nodes;
+  if (next_nodes) *next_nodes = e.ctl.next_nodes;
   return BCE_HIP_OK;
 }
 
@@ -676,8 +927,7 @@ int bce_hip_enum_model(bce_hip_ctx *c, uint32_t *out, uint64_t cap_records, uint
   *count = ctl.sym_total;
   if (ctl.sym_total > cap_records) return BCE_HIP_E_OVERFLOW;
   c->coder->drain();
-  c->phase = 3;
-  struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
+  PhaseScope phase(c, 3);
   BCE_TRY(k4_flush(c, ctl.sym_total, c->slot[0]));
   for (uint64_t i = 0; i < ctl.sym_total; ++i) {
     const uint64_t o = c->slot[0].h_out[i];
@@ -689,13 +939,10 @@ int bce_hip_enum_model(bce_hip_ctx *c, uint32_t *out, uint64_t cap_records, uint
 
 // ---- BCE::encode ------------------------------------------------------------------------------------
 static int encode_body(bce_hip_ctx *c);
-static int enumerate_body(bce_hip_ctx *c, EnumCtl &ctl, const std::function<int(uint64_t)> &sink);
-static int split_round(bce_hip_ctx *c, EnumCtl &ctl, const std::function<int(uint64_t)> &sink, bool *executed);
 int bce_hip_encode(bce_hip_ctx *c) { return gate_on_error(c, bce_guarded(c, [&] { return encode_body(c); })); }
 static int encode_body(bce_hip_ctx *c) {
   BCE_TRY(check_stage(c, 3));
-  c->phase = 3;
-  struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
+  PhaseScope phase(c, 3);
   c->gate_wait_s = 0; c->gate_held_s = 0; c->gate_lent = false;
   const double t_enc0 = now_s();
   gate_acquire(c);
@@ -709,8 +956,8 @@ static int encode_body(bce_hip_ctx *c) {
   c->coder->begin(c->config, C, n);
   c->stats.symbols = 0; c->stats.flushes = 0; c->stats.t_model = 0; c->stats.t_model_kernels = 0; c->stats.t_coder = 0;
 
-  EnumCtl ctl;
-  BCE_TRY(enumerate_body(c, ctl, [&](uint64_t nsym) { return flush_symbols(c, nsym); }));
+  Enumeration e(c, [&](uint64_t nsym) { return flush_symbols(c, nsym); });
+  BCE_TRY(e.run());
   gate_release(c);                               // the GPU phase is over (the last flush and its copy are queued): next context
   c->gate_lent = false;
   static const bool gate_timing = getenv("BCE_HIP_GATE_TIMING") != nullptr;
@@ -723,8 +970,8 @@ static int encode_body(bce_hip_ctx *c) {
   }
   if (c->coder->failed()) { snprintf(c->err, sizeof c->err, "host allocation failed in a range-coder thread"); return BCE_HIP_E_NOMEM; }
   c->stats.t_coder_busy = c->coder->busy_seconds();
-  c->stats.rounds = ctl.done_round;
-  c->stats.nodes = ctl.nodes_total;
+  c->stats.rounds = e.ctl.done_round;
+  c->stats.nodes = e.ctl.nodes_total;
   c->coder->finish(c->config, n, c->offset);     // the archive is laid out by bce_hip_archive_copy, straight into the caller's buffer
   c->enum_active = false;
   c->stage = 4;
@@ -733,270 +980,6 @@ static int encode_body(bce_hip_ctx *c) {
     fprintf(stderr, "gate: ctx %p waited %.1f ms, held %.1f ms of %.1f ms from encode's start to its last flush queued (K3 %.1f ms, model %.1f ms, %llu flushes); coders' tail %.1f ms\n",
             (void *)c, c->gate_wait_s * 1e3, c->gate_held_s * 1e3, (t_gpu_done - t_enc0) * 1e3, c->stats.k3_ms, c->stats.t_model * 1e3,
             (unsigned long long)c->stats.flushes, (now_s() - t_gpu_done) * 1e3);
-  return BCE_HIP_OK;
-}
-
-// The round loop of BCE::code (bce.cpp:1246-1371) as the host drives it: wide rounds in batches, one-launch rounds, the
-// LDS tail kernel, the depth-first tail.  `sink(nsym)` takes the symbol records buffered so far (the model flush of -c,
-// the ScanCoders of -s) and leaves the buffer empty.
-// A round whose symbols do not fit ONE model flush (K4 takes fewer than 2^31 records; BCE_HIP_SPLIT_SYMS lowers the limit for
-// tests).  The planes' streams are independent, so the round is run once per GROUP of planes -- every pass classifies all
-// nodes and writes all children (the same values to the same places: the parents' lists are not touched), records only its
-// group's symbols (K3Args::pmask) and is flushed on its own; a plane's records of one round never exceed n/2 < 2^30.
-// *executed: the round is done (ctl = the control block after its last pass, its symbols flushed); false: its lists were too
-// small, they have been grown and the caller runs the round again.
-static int split_round(bce_hip_ctx *c, EnumCtl &ctl, const std::function<int(uint64_t)> &sink, bool *executed) {
-  *executed = false;
-  // (K3's event time covers the passes' launches only: the flushes between them wait for coder threads)
-  auto pass = [&](uint32_t mask, bool repeat) -> int {
-    BCE_HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    BCE_TRY(k3_clear_need_flush(c));
-    BCE_TRY(k3_round_masked(c, mask, repeat));
-    BCE_HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    BCE_TRY(k3_sync_ctl(c, &ctl));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->stats.k3_ms += ms;
-    return BCE_HIP_OK;
-  };
-  // pass 0, all planes, three launches: either the round fits after all (the one-launch rounds only know an upper bound), or
-  // the per-plane counts are in the control block afterwards
-  BCE_TRY(pass(0xFFu, false));
-  if (ctl.stalled) return k3_stalled(c);
-  if (ctl.overflow) { BCE_TRY(k3_grow_lists(c, ctl)); ctl.overflow = 0; return BCE_HIP_OK; }
-  if (!ctl.need_flush) {
-    BCE_TRY(k3_fetch_runs(c, c->round, 1));
-    BCE_TRY(sink(ctl.sym_total));
-    ctl.sym_total = 0;
-    *executed = true;
-    return BCE_HIP_OK;
-  }
-  uint64_t cnt[8], maxp = 0;
-  for (int q = 0; q < 8; ++q) { cnt[q] = ctl.ptot[q][2]; if (cnt[q] > maxp) maxp = cnt[q]; }
-  if (maxp + 1024 > c->sym_cap) BCE_TRY(k3_grow_symbols(c, maxp + 1024));      // (< 2^30 + 1025)
-  bool first = true;
-  for (int q = 0; q < 8;) {
-    uint32_t mask = 0;
-    uint64_t acc = 0;
-    while (q < 8 && (mask == 0 || acc + cnt[q] <= c->sym_cap)) { mask |= 1u << q; acc += cnt[q]; ++q; }
-    BCE_TRY(pass(mask, !first));
-    if (ctl.stalled) return k3_stalled(c);
-    if (ctl.need_flush || ctl.overflow) { snprintf(c->err, sizeof c->err, "k3: pass of planes %#x of round %u does not fit (%llu symbols, room for %llu)", mask, c->round, (unsigned long long)acc, (unsigned long long)c->sym_cap); return BCE_HIP_E_INTERNAL; }
-    BCE_TRY(k3_fetch_runs(c, c->round, 1));
-    BCE_TRY(sink(ctl.sym_total));
-    BCE_TRY(gate_regain(c));
-    ctl.sym_total = 0;
-    first = false;
-  }
-  c->stats.split_rounds += 1.0;
-  *executed = true;
-  return BCE_HIP_OK;
-}
-
-static int enumerate_body(bce_hip_ctx *c, EnumCtl &ctl, const std::function<int(uint64_t)> &sink) {
-  const uint32_t n = c->n;
-  uint64_t split_limit = 1ull << 31;
-  if (const char *e = getenv("BCE_HIP_SPLIT_SYMS")) { const uint64_t v = strtoull(e, nullptr, 10); if (v && v < split_limit) split_limit = v; }
-  uint64_t cur_nodes = 0;
-  for (int i = 0; i < 8; ++i) { const uint32_t Ci = c->zeros[(i + 7) & 7]; cur_nodes += (Ci && n - Ci) ? 1 : 0; }
-  bool decaying = false;
-  bool have_ctl = false, wide_once = false;
-  const uint32_t early_max = 4;                   // early small flushes: 1M, 2M, 4M, 8M records (0..5 measured: +3 % on text, neutral on random data)
-  // depth-first tail: first attempt when the live set is small, a second one (if the first ran out of room) when tiny
-  // (first attempt: from 1 M live nodes down (512 K .. 8 M measured: 1 M is best on text, source code and executables) the tail starts with workgroup-local rounds, k3_local_kernel; without them
-  //  the walkers alone take over at 65 536)
-  uint32_t kDfsEnter[2] = {c->dbg_no_local ? 65536u : (1u << 20), 2048u};
-  if (const char *e = getenv("BCE_HIP_DFS_ENTER")) kDfsEnter[0] = (uint32_t)strtoul(e, nullptr, 10);
-  int dfs_try = 0;
-  // A round that finds the symbol buffer too small is a round thrown away: its count kernel has run in full, the rest of
-  // the batch's launches return at once (8 launches of ~5 us) and the round runs again after the flush -- ~90 us per
-  // flush, 1.2 ms of the 13 ms of text.  The host knows how many symbols the last rounds emitted and how much room is
-  // left, so it flushes BEFORE a round that is unlikely to fit and never queues more rounds than the room allows
-  // (an estimate: a round that does not fit after all still takes the old way).
-  uint64_t est_syms = 0;                           // symbols of a coming round, from the last rounds (0: unknown)
-  uint64_t recent_syms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t recent_at = 0;
-  static const bool no_predict = getenv("BCE_HIP_NO_FLUSH_PREDICT") != nullptr;
-  auto rounds_that_fit = [&](uint32_t batch) -> uint32_t {  // 0: flush first
-    if (no_predict || !have_ctl || !est_syms || ctl.need_flush) return batch;
-    const uint64_t room = c->sym_cap > ctl.sym_total ? c->sym_cap - ctl.sym_total : 0;
-    uint64_t need = decaying ? est_syms + (est_syms >> 4) + 1024 : 2 * est_syms + 1024;   // (ramp-up: a round emits twice the last one's)
-    uint64_t acc = 0;
-    uint32_t fit = 0;
-    while (fit < batch && acc + need <= room) { acc += need; if (!decaying) need *= 2; ++fit; }
-    if (!fit && !ctl.sym_total) return batch;              // (an empty buffer that is still too small grows the old way)
-    return fit;
-  };
-  for (;;) {
-    BCE_TRY(gate_regain(c));                       // (lent to another context behind the last model flush)
-    if (have_ctl && decaying && !ctl.need_flush && ctl.done_round == 0xFFFFFFFFu) {
-      // few live nodes and almost everything visited: finish depth-first (k3_dfs.hip).  The walkers' symbols
-      // come after everything emitted so far, so flush that first.
-      const uint64_t all = 8ull * (n - 1);
-      if (dfs_try < 2 && ctl.next_nodes && ctl.next_nodes <= kDfsEnter[dfs_try] && (ctl.nodes_total >= all / 8 || c->round >= 1024u || c->dbg_tail_round)) {
-        BCE_TRY(sink(ctl.sym_total));
-        BCE_TRY(gate_regain(c));
-        ctl.sym_total = 0;
-        bool dfs_done = false;
-        BCE_HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-        RoctxRange range("bce K3 tail (local rounds + walkers)");
-        BCE_TRY(k3_dfs_tail(c, ctl, kDfsEnter[dfs_try], &dfs_done));
-        BCE_HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-        BCE_HIP_TRY(c, hipEventSynchronize(c->ev1));
-        { float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->stats.k3_ms += ms; }
-        if (dfs_done) {
-          BCE_TRY(k3_sync_ctl(c, &ctl));
-          BCE_TRY(sink(ctl.sym_total));
-          break;
-        }
-        ++dfs_try;                                // out of room (symbols / queue): carry on with rounds
-      }
-    }
-    const uint32_t first = c->round;
-    bool runs_fetched = false;
-    uint32_t executed = 0;
-    RoctxRange range("bce K3 rounds");
-    BCE_HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
-    if ((!c->dbg_no_tail || cur_nodes == 0) && cur_nodes <= K3_TAIL_ENTER) {       // (no node at all, e.g. one byte repeated: only this kernel says "done" then)
-      // narrow phase: the persistent single-workgroup kernel loops over rounds on the device
-      // (while the depth-first tail may still take over, come back after 1024 rounds: an input that is one long run
-      //  or one table has this few nodes from the first round on, and its millions of rounds belong to the walkers)
-      BCE_TRY(k3_tail(c, (dfs_try < 2 && !c->dbg_no_dfs) ? 1024u : K3_TAIL_MAXROUNDS));
-      BCE_HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-      BCE_TRY(k3_sync_ctl(c, &ctl));
-      if (ctl.stalled) return k3_stalled(c);        // (before skip_round is read: a stalled round does not set it)
-      executed = ctl.tail_rounds;
-      BCE_TRY(k3_fetch_tail_runs(c, executed));
-    } else if (!c->dbg_no_small && !wide_once && cur_nodes <= K3_SMALL_NODES) {
-      // narrow rounds: one launch per round (k3_small_kernel); while the count still doubles, queue only as many
-      // rounds as stay within its range
-      uint32_t batch = 64;
-      if (!decaying) {
-        batch = 1;
-        while (batch < 16 && (cur_nodes << (batch + 1)) <= 2ull * K3_SMALL_NODES) ++batch;
-        if (have_ctl && c->stats.flushes < early_max) {          // see the wide branch: stop at the next early-flush size
-          const uint64_t want = (uint64_t)1 << (20 + c->stats.flushes);
-          uint64_t est = ctl.sym_total, nn = cur_nodes;
-          uint32_t b = 0;
-          while (b < batch && est < want) { est += nn; nn *= 2; ++b; }
-          batch = b ? b : 1u;
-        }
-      }
-      {
-        const uint32_t fit = rounds_that_fit(batch);
-        if (!fit) { BCE_TRY(sink(ctl.sym_total)); ctl.sym_total = 0; continue; }
-        batch = fit;
-      }
-      BCE_TRY(k3_rounds_small(c, batch, cur_nodes, !decaying));
-      BCE_HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-      BCE_TRY(k3_sync_ctl(c, &ctl));
-      if (ctl.stalled) return k3_stalled(c);        // (before skip_round is read: a stalled round does not set it)
-      executed = (ctl.need_flush || ctl.small_bail || ctl.overflow) ? ctl.skip_round - first : batch;
-      if (executed > batch) return k3_bad_skip(c, ctl, first, batch);
-      BCE_TRY(k3_fetch_runs(c, first, executed));
-      runs_fetched = true;
-      if (ctl.small_bail) { BCE_TRY(k3_clear_small_bail(c)); wide_once = true; }
-    } else {
-      // wide rounds: sync often (the round dominates); medium rounds: queue many per sync
-      wide_once = false;
-      uint32_t batch = cur_nodes > (1u << 22) ? 4u : (cur_nodes > (1u << 20) ? K3_BATCH_MID : (cur_nodes > (1u << 14) ? 16u : 64u));
-      // ramp-up: the node count doubles per round; once a round or two reach the next early-flush size, stop there so
-      // that the coders get their first (small) batches as early as possible
-      if (!decaying && have_ctl && c->stats.flushes < early_max) {
-        const uint64_t want = (uint64_t)1 << (20 + c->stats.flushes);
-        uint64_t est = ctl.sym_total, nn = cur_nodes;
-        uint32_t b = 0;
-        while (b < batch && est < want) { est += nn; nn *= 2; ++b; }
-        batch = b ? b : 1u;
-      }
-      {
-        const uint32_t fit = rounds_that_fit(batch);
-        if (!fit) { BCE_TRY(sink(ctl.sym_total)); ctl.sym_total = 0; continue; }
-        batch = fit;
-      }
-      BCE_TRY(k3_rounds(c, batch, decaying ? cur_nodes : 0));
-      BCE_HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-      BCE_TRY(k3_sync_ctl(c, &ctl));
-      if (ctl.stalled) return k3_stalled(c);        // (before skip_round is read: a stalled round does not set it)
-      executed = (ctl.need_flush || ctl.overflow) ? ctl.skip_round - first : batch;
-      if (executed > batch) return k3_bad_skip(c, ctl, first, batch);
-      BCE_TRY(k3_fetch_runs(c, first, executed));
-      runs_fetched = true;
-    }
-    { float ms = 0; if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->stats.k3_ms += ms; }
-    c->round = first + executed;
-    if (executed && runs_fetched) {
-      // what the last eight rounds emitted, each (h_runs holds this batch's run table: one entry per round and plane): the
-      // bulk of the nodes moves from plane to plane with a period of eight rounds, and the symbols per round swing with
-      // it -- the largest of a period is what the next round may bring.  Ramp-up: the last round alone (the next doubles).
-      const RunEntry *re = reinterpret_cast<const RunEntry *>(c->h_runs);
-      for (uint32_t i = 0; i < executed; ++i) {
-        uint64_t t = 0;
-        for (int p = 0; p < 8; ++p) t += re[(size_t)i * 8 + p].count;
-        recent_syms[recent_at++ & 7u] = t;
-      }
-      est_syms = 0;
-      if (decaying) { for (uint64_t v : recent_syms) est_syms = v > est_syms ? v : est_syms; }
-      else est_syms = recent_syms[(recent_at - 1u) & 7u];
-    }
-    if (ctl.overflow) {
-      // the round c->round does not fit the node lists (nothing of it was written): larger lists, the same round again
-      BCE_TRY(k3_grow_lists(c, ctl));
-      ctl.overflow = 0;
-      have_ctl = true;
-      cur_nodes = 0;
-      for (int p = 0; p < 8; ++p) cur_nodes += (uint64_t)ctl.cnt[c->round & 1u][p][0] + ctl.cnt[c->round & 1u][p][1];
-      continue;
-    }
-    if (c->progress) c->progress(ctl.nodes_total, 8ull * n, c->progress_user);
-    {
-      static const bool plane_trace = getenv("BCE_HIP_PLANE_TRACE") != nullptr;
-      if (plane_trace) {
-        fprintf(stderr, "round %u: %llu nodes next, k3 %.2f ms so far; per plane:", c->round, (unsigned long long)ctl.next_nodes, c->stats.k3_ms);
-        for (int p = 0; p < 8; ++p) fprintf(stderr, " %u", ctl.cnt[c->round & 1u][p][0] + ctl.cnt[c->round & 1u][p][1]);
-        fprintf(stderr, "\n");
-      }
-    }
-    decaying = ctl.next_nodes <= cur_nodes && c->round > 16;   // past the ramp-up: the node count no longer doubles
-    if (c->dbg_tail_round && c->round >= c->dbg_tail_round) decaying = true;   // test knob 10: the tail starts while the count still grows
-    have_ctl = true;
-    cur_nodes = ctl.next_nodes;
-    const bool done = ctl.done_round != 0xFFFFFFFFu;
-    if (ctl.need_flush) {
-      if (ctl.sym_total == 0) {
-        // one round alone exceeds the symbol buffer: enlarge it and run the round again -- or, when the round emits more than
-        // one model flush can take (2^31 records: a high-entropy input of more than ~10^9 bytes), plane group by plane group
-        uint64_t want = ctl.want_syms + (ctl.want_syms >> 3) + 1024;
-        if (want >= split_limit) {
-          bool executed_round = false;
-          BCE_TRY(split_round(c, ctl, sink, &executed_round));
-          if (!executed_round) continue;           // (the lists were too small for it: grown, the round comes again)
-          c->round += 1;
-          est_syms = 0;
-          if (c->progress) c->progress(ctl.nodes_total, 8ull * n, c->progress_user);
-          decaying = ctl.next_nodes <= cur_nodes && c->round > 16;
-          cur_nodes = ctl.next_nodes;
-          if (ctl.done_round != 0xFFFFFFFFu) break;
-          continue;
-        }
-        BCE_TRY(k3_grow_symbols(c, want));
-        continue;
-      }
-      BCE_TRY(sink(ctl.sym_total));
-      ctl.sym_total = 0;                         // (the host copy: what the next batch starts from)
-      continue;
-    }
-    if (done) {
-      BCE_TRY(sink(ctl.sym_total));
-      break;
-    }
-    // The host coders are the critical path from the first batch on: hand them small batches early (1M, 2M, 4M, 8M
-    // records) instead of waiting for the symbol buffer to fill, so that they are never idle while the GPU works on
-    // the next 16M.
-    if (c->stats.flushes < early_max && ctl.sym_total >= ((uint64_t)1 << (20 + c->stats.flushes))) {
-      BCE_TRY(sink(ctl.sym_total));
-      ctl.sym_total = 0;                         // the host copy is consulted again at the top of the loop
-    }
-  }
   return BCE_HIP_OK;
 }
 
@@ -1017,8 +1000,8 @@ static int scan_body(bce_hip_ctx *c, uint8_t *config288, double *result_bytes) {
   BCE_HIP_TRY(c, hipSetDevice(c->device));
   c->coder->drain();
   c->scan_mode = true;
-  c->phase = 3;
-  struct Reset { bce_hip_ctx *c; ~Reset() { c->scan_mode = false; c->phase = 0; } } reset{c};
+  PhaseScope phase(c, 3);
+  struct Reset { bce_hip_ctx *c; ~Reset() { c->scan_mode = false; } } reset{c};
   BCE_TRY(k4_prepare(c));
   BCE_TRY(k3_begin(c));
   c->stats.t_coder = 0;
@@ -1055,11 +1038,11 @@ static int scan_body(bce_hip_ctx *c, uint8_t *config288, double *result_bytes) {
     }
     return k3_reset_symbols(c);
   };
-  EnumCtl ctl;
   c->stats.flushes = 0; c->stats.symbols = 0;
-  BCE_TRY(enumerate_body(c, ctl, [&](uint64_t nsym) { c->stats.flushes++; c->stats.symbols += nsym; return consume(nsym); }));
-  c->stats.rounds = ctl.done_round;
-  c->stats.nodes = ctl.nodes_total;
+  Enumeration e(c, [&](uint64_t nsym) { c->stats.flushes++; c->stats.symbols += nsym; return consume(nsym); });
+  BCE_TRY(e.run());
+  c->stats.rounds = e.ctl.done_round;
+  c->stats.nodes = e.ctl.nodes_total;
   c->enum_active = false;
   uint8_t init[9][32];
   memset(init, 0, sizeof init);                            // ScanCoder::init_ is a zero-initialised static (:834)

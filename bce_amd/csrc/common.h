@@ -363,6 +363,17 @@ inline int bce_guarded(bce_hip_ctx *c, F &&body) {
   catch (...) { if (c) snprintf(c->err, sizeof c->err, "unknown exception"); return BCE_HIP_E_INTERNAL; }
 }
 
+// The phase of an entry point (bce_hip_ctx::phase) for as long as it runs: every way out of it, error returns included, leaves
+// phase 0 behind (a phase left standing would make a later ctx_trim give back buffers that are in use).
+struct PhaseScope {
+  PhaseScope(bce_hip_ctx *c, int phase) : c_(c) { c_->phase = phase; }
+  ~PhaseScope() { c_->phase = 0; }
+  PhaseScope(const PhaseScope &) = delete;
+  PhaseScope &operator=(const PhaseScope &) = delete;
+ private:
+  bce_hip_ctx *c_;
+};
+
 // roctx ranges around the kernel families (the reference's M_TIME stage lines, bce.cpp:886-891,974-979,1159-1164, as
 // profiler markers: rocprofv3 --marker-trace shows K1 / K2 / K3 batches / K4 flushes on the host timeline).  The marker
 // library is looked up at run time -- librocprofiler-sdk-roctx.so, else libroctx64.so -- and absent = no-op.
@@ -396,11 +407,11 @@ int k2_build_planes(bce_hip_ctx *c);                // k2_planes.hip
 int k2_get_plane_bits(bce_hip_ctx *c, int plane, uint8_t *out);
 int k2_rank1(bce_hip_ctx *c, int plane, const uint32_t *idx, uint32_t count, uint32_t *out);
 int k3_begin(bce_hip_ctx *c);                       // k3_enumerate.hip
-int k3_rounds(bce_hip_ctx *c, uint32_t count, uint64_t nodes_hint);
+int k3_rounds(bce_hip_ctx *c, uint32_t count, uint64_t nodes_hint);   // queue `count` rounds from c->round (no sync)
 int k3_rounds_small(bce_hip_ctx *c, uint32_t count, uint64_t cur_nodes, bool growing);   // one launch per round, narrow rounds
 int k3_round_masked(bce_hip_ctx *c, uint32_t mask, bool repeat);   // one round, three launches, symbols of the planes in `mask` only
 int k3_clear_need_flush(bce_hip_ctx *c);
-int k3_clear_small_bail(bce_hip_ctx *c);   // queue `count` rounds from c->round (no sync)
+int k3_clear_small_bail(bce_hip_ctx *c);   // after a one-launch round bailed out: small_bail = 0, so that later launches run again
 int k3_dfs_tail(bce_hip_ctx *c, const EnumCtl &ctl, uint32_t enter, bool *done);   // k3_dfs.hip: finish the enumeration depth-first
 int k3_tail(bce_hip_ctx *c, uint32_t max_rounds = K3_TAIL_MAXROUNDS);   // queue the persistent narrow-round kernel from c->round (no sync)
 int k3_fetch_tail_runs(bce_hip_ctx *c, uint32_t rounds);
@@ -415,7 +426,7 @@ uint64_t k3_symbol_capacity(const bce_hip_ctx *c, uint32_t n);   // records betw
 void k4_prepin(bce_hip_ctx *c, uint32_t n);         // start pinning the flush slots' host staging for an input of n bytes (threads)
 void k4_prepin_join(bce_hip_ctx *c, bool drop);     // wait for those threads (drop: free what they pinned and nobody adopted)
 int k4_flush(bce_hip_ctx *c, uint64_t nsym, FlushSlot &slot);         // synchronous: outputs are in slot.h_out on return
-int k4_flush_async(bce_hip_ctx *c, uint64_t nsym, FlushSlot &slot);   // outputs are in slot.h_out once slot.ev_copy has fired   // sort + replay + D2H into the slot (synchronous)
+int k4_flush_async(bce_hip_ctx *c, uint64_t nsym, FlushSlot &slot);   // sort + replay + D2H into the slot, all queued: outputs are in slot.h_out once slot.ev_copy has fired
 
 // radix sort (radix_sort.hip): stable LSD sort of (key,val) u32 pairs on key bits [first_bit, first_bit+bits).
 // Result is left in key[res]/val[res]; returns res (0 or 1) through *res.

@@ -2613,8 +2613,7 @@ static int decompress_device(bce_hip_ctx *c, const uint8_t *archive, size_t len,
   BCE_HIP_TRY(c, hipSetDevice(c->device));
   c->coder->drain();
   c->stage = 0; c->enum_active = false; c->k1_valid = false;   // the scratch buffers below belong to the decoder now
-  c->phase = 4;
-  struct PhaseEnd { bce_hip_ctx *c; ~PhaseEnd() { c->phase = 0; } } phase_end{c};
+  PhaseScope phase(c, 4);
   Decode d(c, hd, dest);
   c->dec_part = 1;
   BCE_TRY(d.setup(len));
