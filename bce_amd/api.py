@@ -27,6 +27,14 @@ class BceError(RuntimeError):
         super().__init__("%s failed: status %d (%s)%s" % (where, status, _strerror(status), (" -- " + detail) if detail else ""))
 
 
+class ChecksumError(BceError):
+    """A block of a version-2 container decoded to bytes whose CRC-32 is not the table's."""
+
+    def __init__(self, block, expected, actual):
+        self.status, self.block, self.expected, self.actual = -6, block, expected, actual
+        RuntimeError.__init__(self, "Checksum mismatch in block %d: table %08X, decoded %08X" % (block, expected, actual))
+
+
 class Stats(C.Structure):
     _fields_ = [("n", C.c_uint64), ("nodes", C.c_uint64), ("symbols", C.c_uint64), ("rounds", C.c_uint32),
                 ("sort_rounds", C.c_uint32), ("flushes", C.c_uint32), ("spine_levels", C.c_uint32),
@@ -84,6 +92,12 @@ SYMBOLS = [
     ("bce_hip_decompress_to_device", C.c_int, [C.c_void_p, _u8p, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("bce_hip_verify_device", C.c_int, [C.c_void_p, _u8p, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_uint64)]),
     ("bce_hip_verify_host", C.c_int, [C.c_void_p, _u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    ("bce_hip_crc32", C.c_uint32, [C.c_uint32, _u8p, C.c_size_t]),
+    ("bce_hip_crc32_combine", C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
+    ("bce_hip_crc32_device", C.c_int, [C.c_void_p, _vp, C.c_size_t, C.POINTER(C.c_uint32)]),
+    ("bce_hip_input_crc32", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    ("bce_hip_decode_crc32", C.c_int, [C.c_void_p, _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
+    ("bce_hip_decompress_device_crc32", C.c_int, [C.c_void_p, _u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
     ("bce_hip_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     ("bce_hip_synth_text", None, [C.c_uint64, _u8p, C.c_size_t]),
     ("bce_hip_synth_rand", None, [C.c_uint64, _u8p, C.c_size_t]),
@@ -371,9 +385,11 @@ class ContextPool:
     def __exit__(self, *exc):
         self.close()
 
-    def compress_many(self, inputs, config=None, on_device=False, with_stats=False, symbol_capacity=0):
+    def compress_many(self, inputs, config=None, on_device=False, with_stats=False, symbol_capacity=0, with_crc=False):
         """Independent inputs (files, or the blocks of `bce -cN`) -> their archives, in order; each is the archive
-        `compress` gives for the same input.  `inputs`: buffers, or (device_ptr, n) pairs with on_device=True."""
+        `compress` gives for the same input.  `inputs`: buffers, or (device_ptr, n) pairs with on_device=True.
+        with_crc: every result is a tuple that ends with the CRC-32 of the input, taken on the device between the load and
+        the encoding (bce_hip_input_crc32): (archive, crc) or (archive, stats, crc)."""
         import threading
         inputs = list(inputs)
         results = [None] * len(inputs)
@@ -396,8 +412,12 @@ class ContextPool:
                         rf = RankFile(n=n, device_ptr=ptr, ctx=c)
                     else:
                         rf = RankFile(inputs[i], ctx=c)
+                    crc = input_crc32(c) if with_crc else None
                     arch = BCE(config, symbol_capacity).encode(rf)
-                    results[i] = (arch, stats(rf)) if with_stats else arch
+                    res = (arch, stats(rf)) if with_stats else (arch,)
+                    if with_crc:
+                        res += (crc,)
+                    results[i] = res if len(res) > 1 else arch
             except Exception as e:  # the other workers stop at their next input
                 with lock:
                     errors.append(e)
@@ -414,10 +434,11 @@ class ContextPool:
         return results
 
 
-def compress_many(inputs, config=None, device=0, contexts=2, on_device=False, with_stats=False, symbol_capacity=0):
+def compress_many(inputs, config=None, device=0, contexts=2, on_device=False, with_stats=False, symbol_capacity=0, with_crc=False):
     """ContextPool.compress_many with a pool of its own."""
     with ContextPool(contexts, device) as pool:
-        return pool.compress_many(inputs, config=config, on_device=on_device, with_stats=with_stats, symbol_capacity=symbol_capacity)
+        return pool.compress_many(inputs, config=config, on_device=on_device, with_stats=with_stats, symbol_capacity=symbol_capacity,
+                                  with_crc=with_crc)
 
 
 def scan(data, device=0):
@@ -445,6 +466,16 @@ def decompress(archive) -> bytes:
     if rc != 0:
         raise BceError(rc, "bce_hip_decompress")
     return out.tobytes()
+
+
+def decoded_size(archive) -> int:
+    """The number of bytes `archive` decodes to, from its header alone (no GPU, nothing decoded)."""
+    a = _as_u8(archive)
+    n = C.c_size_t()
+    rc = load_library().bce_hip_decompress(a.ctypes.data if len(a) else None, len(a), None, 0, C.byref(n))
+    if rc != 0:
+        raise BceError(rc, "bce_hip_decompress")
+    return n.value
 
 
 def decompress_device(archive, device=0, ctx=None, out=None):
@@ -523,6 +554,53 @@ def verify(archive, data, device=0, ctx=None):
         c.check(c.lib.bce_hip_verify_host(c.h, a.ctypes.data, len(a), d.ctypes.data if len(d) else None, len(d), C.byref(fd)),
                 "bce_hip_verify_host")
         return None if fd.value == _NO_DIFF else fd.value
+    finally:
+        if own:
+            c.close()
+
+
+def crc32(data, crc=0) -> int:
+    """CRC-32 of host bytes as zlib.crc32 computes it (bce_hip_crc32: the library's own routine, no GPU)."""
+    a = _as_u8(data)
+    return load_library().bce_hip_crc32(int(crc) & 0xFFFFFFFF, a.ctypes.data if len(a) else None, len(a))
+
+
+def crc32_combine(crc_a, crc_b, len_b) -> int:
+    """CRC-32 of A || B from the CRC-32s of A and B and the length of B (bce_hip_crc32_combine; no GPU)."""
+    return load_library().bce_hip_crc32_combine(int(crc_a) & 0xFFFFFFFF, int(crc_b) & 0xFFFFFFFF, int(len_b))
+
+
+def crc32_device(ptr, n, device=0, ctx=None) -> int:
+    """CRC-32 of the `n` bytes at device pointer `ptr` (memory of `device`, any alignment, any n), computed on the GPU
+    (kd_crc32.hip).  Stream rule: as decompress_to_device."""
+    own = ctx is None
+    c = ctx or _Ctx(device)
+    try:
+        v = C.c_uint32()
+        c.check(c.lib.bce_hip_crc32_device(c.h, None if ptr is None else int(ptr), int(n), C.byref(v)), "bce_hip_crc32_device")
+        return v.value
+    finally:
+        if own:
+            c.close()
+
+
+def input_crc32(ctx) -> int:
+    """CRC-32 of the input context `ctx` holds (after a load, for as long as it keeps the bytes: bce_hip_input_crc32)."""
+    v = C.c_uint32()
+    ctx.check(ctx.lib.bce_hip_input_crc32(ctx.h, C.byref(v)), "bce_hip_input_crc32")
+    return v.value
+
+
+def decode_crc32(archive, device=0, ctx=None):
+    """Decode `archive` on the GPU into the context's own buffer and checksum it there -> (decoded bytes, CRC-32 of the
+    text).  Nothing of the text crosses to the host."""
+    own = ctx is None
+    c = ctx or _Ctx(device)
+    try:
+        a = _as_u8(archive)
+        n, v = C.c_size_t(), C.c_uint32()
+        c.check(c.lib.bce_hip_decode_crc32(c.h, a.ctypes.data, len(a), C.byref(n), C.byref(v)), "bce_hip_decode_crc32")
+        return n.value, v.value
     finally:
         if own:
             c.close()

@@ -5,37 +5,68 @@ the sharded path only.  A plain single-block `.bce` archive is NOT wrapped, so i
 
 layout (little-endian):  b"BCEM" | u32 version=1 | u32 nblocks | nblocks x (u64 raw_bytes, u64 archive_bytes) | archives...
 Every embedded archive is exactly what `bce -c` produces for that block alone (parity is per block).
+
+Version 2 (`bce -CN`, pack_blocks with `crcs`) is the checked container: the same archives behind a table of
+nblocks x (u64 raw_bytes, u64 archive_bytes, u32 crc32, u32 0), where crc32 is the CRC-32 of the block's TEXT as zlib.crc32
+computes it.  Whoever decodes a block can test it without the original (`bce -d`, `bce -ds`, `bce -t archive`,
+tensor.decompress_container_tensor, tensor.test_container); the CRC of the whole file follows from the blocks' by
+crc32_combine.  Version 1 stays readable and stays what `bce -cN` and pack_blocks without `crcs` write, byte for byte.
 """
 import struct
 
 MAGIC = b"BCEM"
 
 
-def pack_blocks(archives, raw_sizes):
+def pack_blocks(archives, raw_sizes, crcs=None):
+    """The container of `archives`; with `crcs` (the CRC-32 of every block's text) a version-2 one."""
     if len(archives) != len(raw_sizes):
         raise ValueError("one raw size per archive")
-    out = [MAGIC, struct.pack("<II", 1, len(archives))]
-    for a, r in zip(archives, raw_sizes):
-        out.append(struct.pack("<QQ", r, len(a)))
+    if crcs is None:
+        out = [MAGIC, struct.pack("<II", 1, len(archives))]
+        for a, r in zip(archives, raw_sizes):
+            out.append(struct.pack("<QQ", r, len(a)))
+    else:
+        if len(crcs) != len(archives):
+            raise ValueError("one CRC-32 per archive")
+        out = [MAGIC, struct.pack("<II", 2, len(archives))]
+        for a, r, c in zip(archives, raw_sizes, crcs):
+            out.append(struct.pack("<QQII", r, len(a), c & 0xFFFFFFFF, 0))
     out.extend(archives)
     return b"".join(out)
 
 
-def unpack_blocks(blob):
-    if blob[:4] != MAGIC:
+def block_table(blob):
+    """One entry per block: (raw_bytes, offset of the archive in `blob`, archive_bytes, crc32 or None for version 1).
+    ValueError: not a container, an unknown version, a table or an archive beyond the blob, a reserved word that is
+    not 0, bytes behind the last archive."""
+    if bytes(blob[:4]) != MAGIC or len(blob) < 12:
         raise ValueError("not a BCEM container")
     ver, nb = struct.unpack_from("<II", blob, 4)
-    if ver != 1:
+    if ver not in (1, 2):
         raise ValueError("unknown container version %d" % ver)
-    pos = 12
-    meta = []
-    for _ in range(nb):
-        meta.append(struct.unpack_from("<QQ", blob, pos))
-        pos += 16
-    archives = []
-    for _raw, alen in meta:
-        archives.append(bytes(blob[pos:pos + alen]))
+    entry = 16 if ver == 1 else 24
+    pos = 12 + nb * entry
+    if pos > len(blob):
+        raise ValueError("container table beyond the end")
+    table = []
+    for b in range(nb):
+        if ver == 1:
+            raw, alen = struct.unpack_from("<QQ", blob, 12 + b * entry)
+            crc = None
+        else:
+            raw, alen, crc, reserved = struct.unpack_from("<QQII", blob, 12 + b * entry)
+            if reserved != 0:
+                raise ValueError("reserved word of block %d is not 0" % b)
+        if alen > len(blob) - pos:
+            raise ValueError("archive of block %d beyond the end" % b)
+        table.append((raw, pos, alen, crc))
         pos += alen
     if pos != len(blob):
         raise ValueError("trailing bytes in container")
-    return archives, [m[0] for m in meta]
+    return table
+
+
+def unpack_blocks(blob):
+    """-> (archives, raw sizes) of a version-1 or version-2 container."""
+    table = block_table(blob)
+    return [bytes(blob[pos:pos + alen]) for _raw, pos, alen, _crc in table], [t[0] for t in table]

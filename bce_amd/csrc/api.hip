@@ -266,10 +266,12 @@ int set_input(bce_hip_ctx *c, const void *src, uint32_t n, hipMemcpyKind kind) {
 int set_input_body(bce_hip_ctx *c, const void *src, uint32_t n, hipMemcpyKind kind) {
   BCE_HIP_TRY(c, hipSetDevice(c->device));
   const double t0 = now_s();
+  c->text_loaded = false;
   BCE_TRY(ensure(c, c->text, n));
   BCE_HIP_TRY(c, hipMemcpyAsync(c->text.p, src, n, kind, c->stream));
   BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->n = n;
+  c->text_loaded = true;
   c->stage = 1;
   c->enum_active = false;
   memset(&c->stats, 0, sizeof c->stats);
@@ -672,7 +674,7 @@ void bce_hip_destroy(bce_hip_ctx *c) {
   DevBuf *bufs[] = {&c->text, &c->bwt, &c->sa[0], &c->sa[1], &c->key[0], &c->key[1], &c->rank, &c->k2, &c->nrk, &c->act[0], &c->act[1], &c->khi[0], &c->khi[1], &c->dl[0], &c->dl[1], &c->dl[2], &c->dl[3], &c->kflag, &c->actv[0], &c->actv[1],
                     &c->rs_hist, &c->blk, &c->ptmp[0], &c->ptmp[1], &c->gran, &c->nlist[0], &c->nlist[1], &c->ctl, &c->tilecnt,
                     &c->tileoff, &c->runs, &c->smwords, &c->k3tw, &c->k3grp, &c->truns, &c->skey[0], &c->skey[1], &c->sval[0], &c->sval[1], &c->sout,
-                    &c->sesc, &c->stat, &c->dcfg, &c->k4w, &c->scanrec, &c->dfs, &c->skey_alt, &c->sesc_alt, &c->rs_hist_k4};
+                    &c->sesc, &c->stat, &c->crc_tab, &c->dcfg, &c->k4w, &c->scanrec, &c->dfs, &c->skey_alt, &c->sesc_alt, &c->rs_hist_k4};
   for (DevBuf *b : bufs) release(*b);
   for (auto &par : c->dlist) for (DevBuf &b : par) release(b);
   k4_prepin_join(c, true);
@@ -798,6 +800,7 @@ int bce_hip_set_bwt(bce_hip_ctx *c, const uint8_t *bwt, uint32_t n, uint32_t off
   BCE_TRY(ensure(c, c->bwt, n));
   BCE_HIP_TRY(c, hipMemcpy(c->bwt.p, bwt, n, hipMemcpyHostToDevice));
   c->n = n; c->offset = offset; c->stage = 2; c->enum_active = false;
+  c->text_loaded = false;                        // (n is the injected BWT's now: whatever an earlier load left in `text` is not this input)
   c->k1_unique = false; c->k1_valid = false;     // no suffix array behind an injected BWT
   memset(&c->stats, 0, sizeof c->stats);
   c->stats.n = n;
@@ -1134,6 +1137,31 @@ int bce_hip_compress_device(bce_hip_ctx *c, const void *d_in, uint32_t n, uint8_
   if (c && d_in && n && n < 0x80000000u) k4_prepin(c, n);
   BCE_TRY(bce_hip_load_device(c, d_in, n));
   return compress_loaded(c, out, cap, out_len);
+}
+
+// ---- CRC-32 on the device (kd_crc32.hip) ---------------------------------------------------------------
+int bce_hip_crc32_device(bce_hip_ctx *c, const void *d, size_t n, uint32_t *crc) {
+  if (!c || !crc || (n && !d)) return BCE_HIP_E_ARG;
+  if (n == 0) { *crc = 0; return BCE_HIP_OK; }
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    uint32_t v = 0;
+    BCE_TRY(kd_crc32(c, static_cast<const uint8_t *>(d), n, &v));
+    *crc = v;
+    return BCE_HIP_OK;
+  });
+}
+
+int bce_hip_input_crc32(bce_hip_ctx *c, uint32_t *crc) {
+  if (!c || !crc) return BCE_HIP_E_ARG;
+  if (!c->text_loaded || c->stage < 1) { snprintf(c->err, sizeof c->err, "no loaded input in this context"); return BCE_HIP_E_STATE; }
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    uint32_t v = 0;
+    BCE_TRY(kd_crc32(c, c->text.as<uint8_t>(), c->n, &v));
+    *crc = v;
+    return BCE_HIP_OK;
+  });
 }
 
 int bce_hip_get_stats(const bce_hip_ctx *c, bce_hip_stats *out) {

@@ -202,6 +202,10 @@ struct bce_hip_ctx {
   bool scan_mode = false;                        // `bce -s`: K3 emits scan_pack words (bce_core.h) into scanrec
   bce::DevBuf scanrec;
   bce::DevBuf stat, dcfg, k4w;                   // K4 counters, device copy of PlaneCfg[8], per-window work arrays
+  bce::DevBuf crc_tab;                           // kd_crc32.hip: the step tables of a launch of crc_tab_grid workgroups, its constants, its result word
+  uint32_t crc_tab_grid = 0;                     // 0: no step tables uploaded
+  bool crc_const_ready = false;                  // its launch-independent constants are uploaded
+  bool text_loaded = false;                      // `text` holds the n bytes of the last bce_hip_load_* (bce_hip_input_crc32)
   uint32_t stat_off[8] = {0};
 
   // pinned host staging
@@ -403,6 +407,7 @@ int k1_bwt(bce_hip_ctx *c);                         // k1_bwt.hip
 int k1_divbwt(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n, uint32_t *pidx);   // the libdivsufsort seam
 int kd_inverse_bw_transform(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n, uint32_t idx);   // kd_decode.hip
 int kd_compare(bce_hip_ctx *c, const uint8_t *a, const uint8_t *b, uint64_t m, uint64_t *first_diff);   // kd_compare.hip: first differing byte of two device buffers
+int kd_crc32(bce_hip_ctx *c, const uint8_t *d, uint64_t n, uint32_t *crc);   // kd_crc32.hip: CRC-32 (zlib's) of a device buffer
 int k2_build_planes(bce_hip_ctx *c);                // k2_planes.hip
 int k2_get_plane_bits(bce_hip_ctx *c, int plane, uint8_t *out);
 int k2_rank1(bce_hip_ctx *c, int plane, const uint32_t *idx, uint32_t count, uint32_t *out);

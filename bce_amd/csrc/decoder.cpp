@@ -25,6 +25,7 @@
 #include "host_coder.h"
 
 #include "decoder_core.h"
+#include "crc32_gf2.h"
 
 namespace {
 
@@ -34,6 +35,47 @@ using bce::kUnknown;
 struct Triple { uint32_t s, x0, x1; };
 
 }  // namespace
+
+// ---- CRC-32 (zlib's, gzip's, PNG's) of host bytes: what `bce -ds` checks a version-2 container's blocks with ----
+// Slice by 8: T[k][v] = the raw CRC of byte v followed by k zero bytes = v x^(8 (k + 1)) mod P; eight message bytes, the
+// running value folded into the first four, give eight independent look-ups.
+namespace {
+struct CrcTables {
+  uint32_t t[8][256];
+  CrcTables() {
+    for (uint32_t v = 0; v < 256; ++v) {
+      uint32_t c = v;
+      for (int b = 0; b < 8; ++b) c = (c >> 1) ^ (bce::kCrcPoly & (0u - (c & 1u)));
+      t[0][v] = c;
+    }
+    for (int k = 1; k < 8; ++k)
+      for (uint32_t v = 0; v < 256; ++v) t[k][v] = (t[k - 1][v] >> 8) ^ t[0][t[k - 1][v] & 0xFFu];
+  }
+};
+}  // namespace
+extern "C" uint32_t bce_hip_crc32(uint32_t crc, const uint8_t *p, size_t n) {
+  static const CrcTables tab;
+  if (!p || n == 0) return crc;
+  uint32_t c = ~crc;
+  for (; n && (reinterpret_cast<uintptr_t>(p) & 7u); --n) c = (c >> 8) ^ tab.t[0][(c ^ *p++) & 0xFFu];
+  for (; n >= 8; n -= 8, p += 8) {
+    uint32_t lo, hi;
+    memcpy(&lo, p, 4);
+    memcpy(&hi, p + 4, 4);
+#if defined(__BYTE_ORDER__) && __BYTE_ORDER__ == __ORDER_BIG_ENDIAN__
+    lo = __builtin_bswap32(lo); hi = __builtin_bswap32(hi);
+#endif
+    lo ^= c;
+    c = tab.t[7][lo & 0xFFu] ^ tab.t[6][(lo >> 8) & 0xFFu] ^ tab.t[5][(lo >> 16) & 0xFFu] ^ tab.t[4][lo >> 24] ^
+        tab.t[3][hi & 0xFFu] ^ tab.t[2][(hi >> 8) & 0xFFu] ^ tab.t[1][(hi >> 16) & 0xFFu] ^ tab.t[0][hi >> 24];
+  }
+  for (; n; --n) c = (c >> 8) ^ tab.t[0][(c ^ *p++) & 0xFFu];
+  return ~c;
+}
+// crc(A || B) = crc(A) x^(8 |B|) + crc(B): init and final xor cancel between the two sides (crc32_gf2.h)
+extern "C" uint32_t bce_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
+  return bce::crc_mulmod(crc_a, bce::crc_xpow8(len_b)) ^ crc_b;
+}
 
 // Decode an archive produced by `bce -c`.  out == NULL: only report the decoded size in *out_len.
 static int decompress_body(const uint8_t *archive, size_t len, uint8_t *out, size_t cap, size_t *out_len);

@@ -1011,7 +1011,7 @@ int k1_divbwt(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n
   if (n == 0 || n >= 0x7FFFFFFFu) return BCE_HIP_E_ARG;
   const uint32_t m = n + 1u;
   // the context's compression state is gone -- before the first allocation, which may give back its planes and node lists
-  c->stage = 0; c->k1_valid = false; c->enum_active = false;
+  c->stage = 0; c->k1_valid = false; c->enum_active = false; c->text_loaded = false;
   BCE_TRY(ensure(c, c->text, m));
   BCE_TRY(ensure(c, c->bwt, m));
   uint8_t *T = c->text.as<uint8_t>();

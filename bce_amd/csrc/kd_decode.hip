@@ -1225,7 +1225,7 @@ int kd_inverse_bw_transform(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_ho
   const size_t b4 = (size_t)m_rows * 4;
   // the context's compression state is gone -- before the first allocation, which may give back its planes and node lists (ctx_trim,
   // phase 5: the caller's)
-  c->stage = 0; c->k1_valid = false; c->enum_active = false;
+  c->stage = 0; c->k1_valid = false; c->enum_active = false; c->text_loaded = false;
   BCE_TRY(ensure(c, c->text, m_rows));
   BCE_TRY(ensure(c, c->bwt, m_rows));
   BCE_TRY(ensure(c, c->ptmp[0], m_rows));
@@ -1763,7 +1763,7 @@ struct Events {
 // Where a decode's text goes (decompress_device).  The inverse BWT's walk writes single bytes at any address, so the caller's
 // device memory is written directly: kDevice needs no text buffer of the context's at all.
 struct DecDest {
-  enum Kind { kHost, kDevice, kCompare } kind;
+  enum Kind { kHost, kDevice, kCompare, kChecksum } kind;
   uint8_t *out;                  // kHost: the caller's host buffer, kDevice: the caller's device buffer (any alignment), of cap bytes
   size_t cap;
   // kCompare: the text stays in the context's own buffer and is compared there with orig_n bytes, which are on the device
@@ -1771,6 +1771,9 @@ struct DecDest {
   const uint8_t *orig_dev, *orig_host;
   uint64_t orig_n;
   uint64_t *first_diff;
+  // kChecksum: the text stays in the context's own buffer and only its CRC-32 is reported (kd_crc32.hip); kHost with `crc`: the
+  // same word beside the copy to the host -- taken from the context's buffer, on the device, before the copy is queued
+  uint32_t *crc;
   bool own_text() const { return kind != kDevice; }            // the text lands in c->text
 };
 
@@ -2553,6 +2556,7 @@ struct Decode {
     const bool single_cycle = lc == n;
     // periodic input (the reference's decoder returns zeros here)
     if (!single_cycle) hipLaunchKernelGGL(expand_cycle_kernel, dim3(gn), dim3(256), 0, c->stream, V, (uint32_t)lc, n, off, text);
+    if (dest.crc && dest.own_text()) BCE_TRY(checksum());
     if (dest.kind == DecDest::kHost) BCE_HIP_TRY(c, hipMemcpyAsync(dest.out, c->text.p, n, hipMemcpyDeviceToHost, c->stream));
     BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
     BCE_HIP_TRY(c, hipGetLastError());
@@ -2562,6 +2566,16 @@ struct Decode {
     if (env.mem()) fprintf(stderr, "gpu decode: device memory in use over the whole decode (sampled after every allocation stage): %.1f GB at most\n", st.peak_used / 1e9);
     if (env.timing) fprintf(stderr, "gpu decode: this context so far: device allocations %u calls %.1f MB %.3f s, pinned (query / answer buffers) %u calls %.1f MB %.3f s\n",
                             c->alloc_calls, c->alloc_bytes / 1e6, c->alloc_s, c->pin_calls, c->pin_bytes / 1e6, c->pin_s);
+    return BCE_HIP_OK;
+  }
+
+  // ---- kChecksum (and kHost with a checksum asked for): the CRC-32 of the decoded text, on the device (kd_crc32.hip) ----
+  int checksum() {
+    const double tc0 = now_s();
+    uint32_t v = 0;
+    BCE_TRY(kd_crc32(c, c->text.as<uint8_t>(), n, &v));
+    *dest.crc = v;
+    if (env.timing) fprintf(stderr, "gpu decode: CRC-32 of the %u B of text on the device: %.6f s\n", n, now_s() - tc0);
     return BCE_HIP_OK;
   }
 
@@ -2600,8 +2614,10 @@ static int decompress_device(bce_hip_ctx *c, const uint8_t *archive, size_t len,
   if (!c) return BCE_HIP_E_ARG;
   struct PartEnd { bce_hip_ctx *c; ~PartEnd() { c->dec_part = 0; } } part_end{c};
   if (!archive || !out_len) return BCE_HIP_E_ARG;
-  const bool cmp = dest.kind == DecDest::kCompare;
-  if (cmp && (!dest.first_diff || (dest.orig_n && !dest.orig_dev && !dest.orig_host))) return BCE_HIP_E_ARG;
+  const bool cmp = dest.kind == DecDest::kCompare || dest.kind == DecDest::kChecksum;   // (no buffer of the caller's)
+  if (dest.kind == DecDest::kChecksum && !dest.crc) return BCE_HIP_E_ARG;
+  if (dest.crc && !dest.own_text()) return BCE_HIP_E_ARG;      // (the checksum is taken from the context's buffer: kDevice has none)
+  if (dest.kind == DecDest::kCompare && (!dest.first_diff || (dest.orig_n && !dest.orig_dev && !dest.orig_host))) return BCE_HIP_E_ARG;
   ArchiveHead hd;
   if (parse_archive(archive, len, hd, /*header_only=*/true) != 0) return BCE_HIP_E_ARG;
   *out_len = hd.n;
@@ -2612,7 +2628,7 @@ static int decompress_device(bce_hip_ctx *c, const uint8_t *archive, size_t len,
   if (parse_archive(archive, len, hd, false) != 0) return BCE_HIP_E_ARG;
   BCE_HIP_TRY(c, hipSetDevice(c->device));
   c->coder->drain();
-  c->stage = 0; c->enum_active = false; c->k1_valid = false;   // the scratch buffers below belong to the decoder now
+  c->stage = 0; c->enum_active = false; c->k1_valid = false; c->text_loaded = false;   // the scratch buffers below belong to the decoder now
   PhaseScope phase(c, 4);
   Decode d(c, hd, dest);
   c->dec_part = 1;
@@ -2628,7 +2644,7 @@ static int decompress_device(bce_hip_ctx *c, const uint8_t *archive, size_t len,
 
 extern "C" int bce_hip_decompress_device(bce_hip_ctx *c, const uint8_t *archive, size_t len, uint8_t *out, size_t cap,
                                          size_t *out_len) {
-  return bce_guarded(c, [&] { return decompress_device(c, archive, len, DecDest{DecDest::kHost, out, cap, nullptr, nullptr, 0, nullptr}, out_len); });
+  return bce_guarded(c, [&] { return decompress_device(c, archive, len, DecDest{DecDest::kHost, out, cap, nullptr, nullptr, 0, nullptr, nullptr}, out_len); });
 }
 
 // The same decode with the text left in the caller's DEVICE memory (of the context's device, any alignment, cap bytes): the walk
@@ -2636,7 +2652,7 @@ extern "C" int bce_hip_decompress_device(bce_hip_ctx *c, const uint8_t *archive,
 extern "C" int bce_hip_decompress_to_device(bce_hip_ctx *c, const uint8_t *archive, size_t len, void *d_out, size_t cap,
                                             size_t *out_len) {
   return bce_guarded(c, [&] {
-    return decompress_device(c, archive, len, DecDest{DecDest::kDevice, static_cast<uint8_t *>(d_out), cap, nullptr, nullptr, 0, nullptr}, out_len);
+    return decompress_device(c, archive, len, DecDest{DecDest::kDevice, static_cast<uint8_t *>(d_out), cap, nullptr, nullptr, 0, nullptr, nullptr}, out_len);
   });
 }
 
@@ -2647,7 +2663,7 @@ extern "C" int bce_hip_verify_device(bce_hip_ctx *c, const uint8_t *archive, siz
   return bce_guarded(c, [&] {
     if (n && !d_original) return (int)BCE_HIP_E_ARG;
     size_t decoded = 0;
-    return decompress_device(c, archive, len, DecDest{DecDest::kCompare, nullptr, 0, static_cast<const uint8_t *>(d_original), nullptr, n, first_diff}, &decoded);
+    return decompress_device(c, archive, len, DecDest{DecDest::kCompare, nullptr, 0, static_cast<const uint8_t *>(d_original), nullptr, n, first_diff, nullptr}, &decoded);
   });
 }
 
@@ -2656,6 +2672,32 @@ extern "C" int bce_hip_verify_host(bce_hip_ctx *c, const uint8_t *archive, size_
   return bce_guarded(c, [&] {
     if (n && !original) return (int)BCE_HIP_E_ARG;
     size_t decoded = 0;
-    return decompress_device(c, archive, len, DecDest{DecDest::kCompare, nullptr, 0, nullptr, original, n, first_diff}, &decoded);
+    return decompress_device(c, archive, len, DecDest{DecDest::kCompare, nullptr, 0, nullptr, original, n, first_diff, nullptr}, &decoded);
+  });
+}
+
+// bce_hip_decompress_device that also reports the CRC-32 of the text: computed on the device from the context's buffer, before the
+// copy to the host is queued (`bce -d` on a version-2 container).  out == NULL: only the size, *crc untouched.
+extern "C" int bce_hip_decompress_device_crc32(bce_hip_ctx *c, const uint8_t *archive, size_t len, uint8_t *out, size_t cap,
+                                               size_t *out_len, uint32_t *crc) {
+  if (!c || !crc) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&] {
+    uint32_t v = 0;
+    const int rc = decompress_device(c, archive, len, DecDest{DecDest::kHost, out, cap, nullptr, nullptr, 0, nullptr, &v}, out_len);
+    if (rc == BCE_HIP_OK && out) *crc = v;
+    return rc;
+  });
+}
+
+// Decode into the context's own buffer and report the size and the CRC-32 of the text: nothing of it goes to the host, no second
+// buffer is held (`bce -t archive` on a version-2 container).
+extern "C" int bce_hip_decode_crc32(bce_hip_ctx *c, const uint8_t *archive, size_t len, size_t *decoded, uint32_t *crc) {
+  if (!c || !crc || !decoded) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&] {
+    uint32_t v = 0;
+    size_t n = 0;
+    const int rc = decompress_device(c, archive, len, DecDest{DecDest::kChecksum, nullptr, 0, nullptr, nullptr, 0, nullptr, &v}, &n);
+    if (rc == BCE_HIP_OK) { *decoded = n; *crc = v; }
+    return rc;
   });
 }

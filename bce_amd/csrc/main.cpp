@@ -1,6 +1,8 @@
 // main.cpp -- the `bce` command line, mirroring the reference's main() (bce.cpp:1376-1484):
 //   bce -c archive.bce file [config.bcc]    compress on the MI355X through libbcehip.so
 //   bce -t file archive.bce                 (extension) decode on the GPU and compare with "file" there; writes nothing
+//   bce -CN archive.bcem file [config.bcc]  (extension) as -cN, N = 1..64, with the CRC-32 of every block's text in the container
+//   bce -t archive.bcem                     (extension) decode such a container on the GPU and test it against its own CRC-32s
 // Banner, usage text, summary line, argument detection and exit codes follow the reference
 // (banner :1377-1379, -c :1403-1427, -d :1428-1472, usage :1473-1483).  -d uses the GPU-assisted decoder (kd_decode.hip), -ds the host decoder (decoder.cpp);
 // -s runs the enumeration on the GPU in scan mode and the ScanCoder optimisation on the host (scan_coder.cpp).
@@ -98,15 +100,34 @@ static void fast_exit(int code) {
 // embedded archive is exactly what `bce -c` writes for that block alone.  Same layout as bce_amd/container.py
 // (the 8-GPU path of bench.py gathers its blocks into it).  A plain archive cannot start with "BCEM": that would
 // be a header of 0x4342 words.
+// Version 2 (`bce -CN`): the same with table entries of (u64 raw_bytes, u64 archive_bytes, u32 CRC-32 of the block's text,
+// u32 0) -- the archives are version 1's, and whoever decodes one can test it without the original.
 static bool is_container(const HostFile &a) { return a.size() >= 12 && memcmp(a.data(), "BCEM", 4) == 0; }
 static void put_u32(std::vector<uint8_t> &v, uint32_t x) { for (int i = 0; i < 4; ++i) v.push_back((uint8_t)(x >> (8 * i))); }
 static void put_u64(std::vector<uint8_t> &v, uint64_t x) { for (int i = 0; i < 8; ++i) v.push_back((uint8_t)(x >> (8 * i))); }
 static uint64_t get_le(const uint8_t *p, int bytes) { uint64_t x = 0; for (int i = 0; i < bytes; ++i) x |= (uint64_t)p[i] << (8 * i); return x; }
+// the table of a container that archive_blocks has accepted: version, entry b's raw size and (version 2) CRC-32
+static uint32_t container_version(const HostFile &a) { return is_container(a) ? (uint32_t)get_le(a.data() + 4, 4) : 0; }
+static size_t table_entry_bytes(uint32_t version) { return version == 2 ? 24 : 16; }
+static uint64_t table_raw(const HostFile &a, size_t b) { return get_le(a.data() + 12 + b * table_entry_bytes(container_version(a)), 8); }
+static uint32_t table_crc(const HostFile &a, size_t b) { return (uint32_t)get_le(a.data() + 12 + b * 24 + 16, 4); }
+
+// (Weak references: this file is also linked, for the sanitizer run of `-ds` on hostile archives, into a CPU-only program beside
+//  "no device" stand-ins for just the entry points the older modes call.  With libbcehip.so they resolve like any other.)
+extern "C" int bce_hip_verify_host(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, const uint8_t *original, size_t n,
+                                   uint64_t *first_diff) __attribute__((weak));
+extern "C" int bce_hip_input_crc32(bce_hip_ctx *ctx, uint32_t *crc) __attribute__((weak));
+extern "C" int bce_hip_decode_crc32(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, size_t *decoded, uint32_t *crc) __attribute__((weak));
+extern "C" int bce_hip_decompress_device_crc32(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, uint8_t *out, size_t cap,
+                                               size_t *out_len, uint32_t *crc) __attribute__((weak));
 
 // `bce -cN`: N contiguous blocks over the GPUs of the node.  With more blocks than GPUs every device gets up to four
 // gated contexts (bce_hip_set_gated), one host thread each: their GPU phases take turns while the coder threads of the
 // context that has just left the GPU finish its block.  Blocks are handed out in order to whichever context is free.
-static int compress_blocks(const HostFile &data, uint32_t nblocks, const uint8_t *config, std::vector<uint8_t> &out) {
+// with_crc (`-CN`): a version-2 container -- every block's CRC-32 comes from the context that compressed it, which still holds
+// the block's bytes on the device (bce_hip_input_crc32).
+static int compress_blocks(const HostFile &data, uint32_t nblocks, const uint8_t *config, bool with_crc, std::vector<uint8_t> &out) {
+  if (with_crc && !bce_hip_input_crc32) return BCE_HIP_E_DEVICE;
   std::vector<bce_hip_ctx *> ctx;
   int ndev = 0;
   for (int dev = 0; dev < 64; ++dev) {
@@ -146,7 +167,8 @@ static int compress_blocks(const HostFile &data, uint32_t nblocks, const uint8_t
   const char *test_nomem = getenv("BCE_CLI_TEST_NOMEM_BLOCK");      // (test hook: this block's first attempt "runs out of memory"; "all": every block's)
   const bool test_all = test_nomem && strcmp(test_nomem, "all") == 0;
   const long test_block = test_nomem && !test_all ? atol(test_nomem) : -1;
-  std::vector<char> done(nblocks, 0);                               // block b's archive is in arch[b]
+  std::vector<char> done(nblocks, 0);                               // block b's archive is in arch[b] (and, with_crc, its CRC-32 in crcs[b])
+  std::vector<uint32_t> crcs(nblocks, 0);
   std::vector<std::thread> th;
   for (size_t d = 0; d < ctx.size(); ++d)
     th.emplace_back([&, d] {
@@ -157,6 +179,7 @@ static int compress_blocks(const HostFile &data, uint32_t nblocks, const uint8_t
         int rc = (test_all || (long)b == test_block) ? BCE_HIP_E_NOMEM
                                          : bce_hip_compress(ctx[d], data.data() + lo[b], (uint32_t)(lo[b + 1] - lo[b]), nullptr, 0, &alen);
         if (rc == 0) { arch[b].resize(alen); rc = bce_hip_archive_copy(ctx[d], arch[b].data(), alen); }
+        if (rc == 0 && with_crc) rc = bce_hip_input_crc32(ctx[d], &crcs[b]);
         if (rc == 0) done[b] = 1;
         if (rc == BCE_HIP_E_NOMEM) {
           { std::lock_guard<std::mutex> lk(deferred_mu); deferred.push_back(b); }
@@ -190,7 +213,8 @@ static int compress_blocks(const HostFile &data, uint32_t nblocks, const uint8_t
       size_t alen = 0;
       rc = bce_hip_compress(c, data.data() + lo[b], (uint32_t)(lo[b + 1] - lo[b]), nullptr, 0, &alen);
       if (rc == 0) { arch[b].resize(alen); rc = bce_hip_archive_copy(c, arch[b].data(), alen); }
-      if (rc == 0) done[b] = 1;
+      if (rc == 0 && with_crc) rc = bce_hip_input_crc32(c, &crcs[b]);
+      if (rc == 0) done[b] = 1;                                     // (a block without its CRC is a block missing)
     }
     if (rc && c) printf("%s\n", bce_hip_last_error(c));
     if (c) bce_hip_destroy(c);
@@ -200,33 +224,34 @@ static int compress_blocks(const HostFile &data, uint32_t nblocks, const uint8_t
     if (!done[b] || arch[b].empty()) return BCE_HIP_E_INTERNAL;     // a container never goes out with a block missing
   out.clear();
   out.insert(out.end(), {'B', 'C', 'E', 'M'});
-  put_u32(out, 1);
+  put_u32(out, with_crc ? 2 : 1);
   put_u32(out, nblocks);
-  for (uint32_t b = 0; b < nblocks; ++b) { put_u64(out, lo[b + 1] - lo[b]); put_u64(out, arch[b].size()); }
+  for (uint32_t b = 0; b < nblocks; ++b) {
+    put_u64(out, lo[b + 1] - lo[b]);
+    put_u64(out, arch[b].size());
+    if (with_crc) { put_u32(out, crcs[b]); put_u32(out, 0); }
+  }
   for (uint32_t b = 0; b < nblocks; ++b) out.insert(out.end(), arch[b].begin(), arch[b].end());
   return 0;
 }
 
 // The archives inside an archive file: (offset, length) of each -- one for a plain archive, the table's for a BCEM container.
-// false: a container whose table does not fit the file.
+// false: a container of an unknown version, one whose table does not fit the file, or (version 2) with a reserved word that is not 0.
 static bool archive_blocks(const HostFile &adata, std::vector<std::pair<size_t, size_t>> &blocks) {
   if (!is_container(adata)) { blocks.emplace_back(0, adata.size()); return true; }
   const uint32_t ver = (uint32_t)get_le(adata.data() + 4, 4), nb = (uint32_t)get_le(adata.data() + 8, 4);
-  size_t pos = 12 + (size_t)nb * 16;
-  if (ver != 1 || pos > adata.size()) return false;
+  const size_t entry = table_entry_bytes(ver);
+  size_t pos = 12 + (size_t)nb * entry;
+  if ((ver != 1 && ver != 2) || pos > adata.size()) return false;
   for (uint32_t b = 0; b < nb; ++b) {
-    const size_t alen = (size_t)get_le(adata.data() + 12 + (size_t)b * 16 + 8, 8);
+    const size_t alen = (size_t)get_le(adata.data() + 12 + (size_t)b * entry + 8, 8);
+    if (ver == 2 && get_le(adata.data() + 12 + (size_t)b * entry + 20, 4) != 0) return false;
     if (alen > adata.size() - pos) return false;
     blocks.emplace_back(pos, alen);
     pos += alen;
   }
   return true;
 }
-
-// (A weak reference: this file is also linked, for the sanitizer run of `-ds` on hostile archives, into a CPU-only program beside
-//  "no device" stand-ins for just the entry points the older modes call.  With libbcehip.so it resolves like any other.)
-extern "C" int bce_hip_verify_host(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, const uint8_t *original, size_t n,
-                                   uint64_t *first_diff) __attribute__((weak));
 
 // exit status of `bce -t` when the archive decodes, but not to the file's bytes (every other failure keeps the status -d gives it)
 static const int kExitDiffers = 1;
@@ -255,7 +280,7 @@ static int test_archive(const char *file_path, const char *archive_path) {
     size_t hn = 0;
     const int hr = bce_hip_decompress(adata.data() + blocks[b].first, blocks[b].second, nullptr, 0, &hn);
     if (hr != 0 && blocks.size() == 1) { printf("Decompression failed: %s\n", bce_hip_strerror(hr)); return -4; }
-    if (hr != 0 || (blocks.size() > 1 && (uint64_t)hn != get_le(adata.data() + 12 + b * 16, 8))) { printf("Could not read Archive.\n"); return -2; }
+    if (hr != 0 || (blocks.size() > 1 && (uint64_t)hn != table_raw(adata, b))) { printf("Could not read Archive.\n"); return -2; }
     at[b + 1] = at[b] + hn;
   }
   const uint64_t total = at.back(), fsize = data.size();
@@ -290,6 +315,60 @@ static int test_archive(const char *file_path, const char *archive_path) {
   return 0;
 }
 
+static void print_mismatch(size_t block, uint32_t table, uint32_t decoded) {
+  printf("Checksum mismatch in block %zu: table %08X, decoded %08X\n", block, (unsigned)table, (unsigned)decoded);
+}
+
+// `bce -t archive.bcem` (an extension): a version-2 container tested against its own CRC-32s.  Every block is decoded on the GPU
+// into the context's buffer and checksummed there (bce_hip_decode_crc32): no file is read or uploaded, nothing of the text comes
+// back, nothing is written.  An archive without checksums gets its answer before any device is asked for.
+static const int kExitNoChecksum = 2;
+static int self_test_archive(const char *archive_path) {
+  auto start = std::chrono::high_resolution_clock::now();
+  HostFile adata;
+  read_whole_file(archive_path, &adata, (size_t)0);
+  if (adata.status == -1) { printf("Archive not found.\n"); return -1; }
+  if (adata.status != 0 || adata.size() == 0) { printf("Could not read Archive.\n"); return -2; }
+  if (container_version(adata) != 2) {
+    if (is_container(adata) && container_version(adata) != 1) { printf("Could not read Archive.\n"); return -2; }
+    printf("Archive carries no checksum: test it against the file (bce -t file archive)\n");
+    return kExitNoChecksum;
+  }
+  std::vector<std::pair<size_t, size_t>> blocks;
+  if (!archive_blocks(adata, blocks)) { printf("Could not read Archive.\n"); return -2; }
+  uint64_t total = 0;
+  for (size_t b = 0; b < blocks.size(); ++b) {                      // the table's sizes must be the blocks' own, as for -d
+    size_t hn = 0;
+    const uint64_t raw = table_raw(adata, b);
+    if (bce_hip_decompress(adata.data() + blocks[b].first, blocks[b].second, nullptr, 0, &hn) != 0 || raw < 1 || raw >= 0x80000000ull || (uint64_t)hn != raw) {
+      printf("Could not read Archive.\n");
+      return -2;
+    }
+    total += raw;
+  }
+  bce_hip_ctx *ctx = nullptr;
+  const int rc0 = bce_hip_create(&ctx, 0);
+  struct Destroy { bce_hip_ctx *&c; ~Destroy() { if (c) bce_hip_destroy(c); } } destroy{ctx};
+  if (rc0 != 0 || !bce_hip_decode_crc32) { printf("No usable HIP device: %s\n", bce_hip_strerror(rc0 ? rc0 : BCE_HIP_E_DEVICE)); return -3; }
+  for (size_t b = 0; b < blocks.size(); ++b) {
+    size_t n = 0;
+    uint32_t crc = 0;
+    int rc = bce_hip_decode_crc32(ctx, adata.data() + blocks[b].first, blocks[b].second, &n, &crc);
+    if (rc == 0 && (uint64_t)n != table_raw(adata, b)) rc = BCE_HIP_E_INTERNAL;
+    if (rc != 0) {
+      if (bce_hip_last_error(ctx)[0]) printf("%s\n", bce_hip_last_error(ctx));
+      printf("Decompression failed: %s\n", bce_hip_strerror(rc));
+      return -4;
+    }
+    if (crc != table_crc(adata, b)) { print_mismatch(b, table_crc(adata, b), crc); fflush(stdout); return kExitDiffers; }
+  }
+  std::chrono::duration<double> duration = std::chrono::high_resolution_clock::now() - start;
+  printf("Archive OK: %zu B -> %llu B in %.1f s\n", adata.size(), (unsigned long long)total, duration.count());
+  ctx = nullptr;                                                    // (left to fast_exit, like -d)
+  fast_exit(0);
+  return 0;
+}
+
 static int usage() {
   printf("Usage:\n");
   printf("  bce -c archive.bce file [config.bcc]\n");
@@ -305,6 +384,12 @@ static int usage() {
   printf("   Tests archive \"archive.bce\" against \"file\": decodes it on the GPU and compares there, writes nothing (extension; exit status 0 = equal, %d = differs)\n", kExitDiffers);
   printf("\n");
   printf("  bce -cN archive.bcem file [config.bcc]      (extension: N = 2..64 blocks, one container, all GPUs of the node; every block < 2^31 bytes)\n");
+  printf("\n");
+  printf("  bce -CN archive.bcem file [config.bcc]\n");
+  printf("   As -cN with N = 1..64, and the container holds the CRC-32 of every block: -d and -ds check what they decode (extension)\n");
+  printf("\n");
+  printf("  bce -t archive.bcem\n");
+  printf("   Tests a -CN archive against its own checksums: decodes it on the GPU, writes nothing (extension; exit status 0 = sound, %d = a block differs, %d = the archive carries no checksum)\n", kExitDiffers, kExitNoChecksum);
   return 0;
 }
 
@@ -313,17 +398,20 @@ int main(int argc, char **argv) {
   printf("Copyright (C) 2016  Christoph Diegelmann\n");
   printf("This is free software under GNU Lesser General Public License. See <http://www.gnu.org/licenses/lgpl>\n\n");
 
-  if ((argc == 4 || argc == 5) && argv[1][0] == '-' && argv[1][1] == 'c') {
+  if ((argc == 4 || argc == 5) && argv[1][0] == '-' && (argv[1][1] == 'c' || argv[1][1] == 'C')) {
     auto start = std::chrono::high_resolution_clock::now();
     HostFile data;
     // (-cN, the extension: every BLOCK obeys the reference's n < 2^31, the file may be N times that)
-    const uint32_t nb_arg = (uint32_t)atoi(argv[1] + 2);
-    const size_t file_limit = nb_arg >= 2 && nb_arg <= 64 ? (size_t)nb_arg * (kMaxInput - 1) + 1 : kMaxInput;
+    // (-CN: the same with checksums, from one block on -- `-C1` is the self-checking archive of an ordinary file)
+    const bool with_crc = argv[1][1] == 'C';
+    const uint32_t nb_arg = (uint32_t)atoi(argv[1] + 2), nb_min = with_crc ? 1u : 2u;
+    if (with_crc && (nb_arg < 1 || nb_arg > 64)) return usage();
+    const size_t file_limit = nb_arg >= nb_min && nb_arg <= 64 ? (size_t)nb_arg * (kMaxInput - 1) + 1 : kMaxInput;
     std::thread reader(read_whole_file, argv[3], &data, file_limit);  // File::File, bce.cpp:842-856 -- beside the runtime's start-up
     bce_hip_ctx *ctx = nullptr;
     uint64_t expect = 0;                                          // the file's size, if it says: what the context prepares for
     { struct stat st; if (stat(argv[3], &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) expect = (uint64_t)st.st_size; }
-    if (atoi(argv[1] + 2) >= 2) expect = 0;                       // (-cN: the blocks get contexts of their own)
+    if (nb_arg >= nb_min) expect = 0;                             // (-cN, -CN: the blocks get contexts of their own)
     int rc = bce_hip_create_sized(&ctx, 0, expect);
     if (rc != 0) {
       reader.join();
@@ -358,11 +446,16 @@ int main(int argc, char **argv) {
     }
     lap("file read");
     // `-cN` (N = 2..64, an extension): N blocks in a BCEM container, spread over the GPUs of the node
-    const uint32_t nblocks = (uint32_t)atoi(argv[1] + 2);
-    if (nblocks >= 2 && nblocks <= 64 && data.size() >= nblocks) {
+    const uint32_t nblocks = nb_arg;
+    if (with_crc && data.size() < nblocks) {                        // (never a plain archive in a checked one's place)
+      printf("Error loading file\n");
+      bce_hip_destroy(ctx);
+      return -1;
+    }
+    if (nblocks >= nb_min && nblocks <= 64 && data.size() >= nblocks) {
       bce_hip_destroy(ctx);
       std::vector<uint8_t> blob;
-      rc = compress_blocks(data, nblocks, cfgbuf.empty() ? nullptr : cfgbuf.data(), blob);
+      rc = compress_blocks(data, nblocks, cfgbuf.empty() ? nullptr : cfgbuf.data(), with_crc, blob);
       if (rc != 0) { printf("Compression failed: %s\n", bce_hip_strerror(rc)); return -4; }
       std::chrono::duration<double> duration = std::chrono::high_resolution_clock::now() - start;
       if (!write_file(argv[2], blob.data(), blob.size())) { printf("Could not write Archive.\n"); return -5; }
@@ -413,6 +506,7 @@ int main(int argc, char **argv) {
     // A BCEM container (bce -cN, the sharded bench) is decoded block by block.
     std::vector<std::pair<size_t, size_t>> blocks;               // (offset, length) of each archive inside adata
     if (!archive_blocks(adata, blocks)) { printf("Could not read Archive.\n"); return -2; }
+    const bool checked = container_version(adata) == 2;             // every block's CRC-32 is in the table: what is decoded is tested
     int rc = 0;
     // the output: plain memory, not value-initialised (a vector would write 10^8 zeroes first that the decoder overwrites)
     // (2 MB-aligned with huge pages asked for, and its pages faulted in by the kernel -- MADV_POPULATE_WRITE leaves the
@@ -434,7 +528,7 @@ int main(int argc, char **argv) {
     struct JoinOnExit { std::thread &t; ~JoinOnExit() { if (t.joinable()) t.join(); } } join_prefault{prefault};
     size_t out_size = 0;
     bce_hip_ctx *keep = nullptr;                                   // the one-block context: given back after the file is written
-    if (blocks.size() == 1) {
+    if (blocks.size() == 1 && !checked) {
       uint64_t prog = 0;
       bce_hip_ctx *ctx = ctx0;
       if (use_gpu) {
@@ -466,7 +560,7 @@ int main(int argc, char **argv) {
       // and the output is sized from the verified values only -- a wrapping or oversized table is "Could not read Archive".
       std::vector<size_t> at(blocks.size() + 1, 0);
       for (size_t b = 0; b < blocks.size(); ++b) {
-        const uint64_t raw = get_le(adata.data() + 12 + b * 16, 8);
+        const uint64_t raw = table_raw(adata, b);
         size_t hn = 0;
         const int hr = bce_hip_decompress(adata.data() + blocks[b].first, blocks[b].second, nullptr, 0, &hn);
         if (hr != 0 || raw < 1 || raw >= 0x80000000ull || (uint64_t)hn != raw || raw > SIZE_MAX - at[b]) {
@@ -499,13 +593,24 @@ int main(int argc, char **argv) {
       // as in compress_blocks: a context that runs out of device memory (blocks of a GB and more, two contexts per device) gives
       // its memory back and leaves its block to ONE context that has the device to itself at the end
       std::vector<char> done(blocks.size(), 0);
+      // a checked container: the CRC-32 of what block b decoded to -- on the device, from the decoder's own buffer, before the
+      // text is copied back (-d), or of the bytes in the output (-ds) -- against the table's; a block that differs ends the run
+      const int kMismatch = 1;                                      // (no bce_hip_status is positive)
+      std::vector<uint32_t> got(blocks.size(), 0);
+      std::vector<char> differs(blocks.size(), 0);
       auto decode_block = [&](bce_hip_ctx *c, size_t b) -> int {
         const uint8_t *ap = adata.data() + blocks[b].first;
         size_t n = 0;
         const size_t want = at[b + 1] - at[b];
-        int r = c ? bce_hip_decompress_device(c, ap, blocks[b].second, out.get() + at[b], want, &n)
-                  : bce_hip_decompress(ap, blocks[b].second, out.get() + at[b], want, &n);
+        int r;
+        if (c) r = checked ? bce_hip_decompress_device_crc32(c, ap, blocks[b].second, out.get() + at[b], want, &n, &got[b])
+                           : bce_hip_decompress_device(c, ap, blocks[b].second, out.get() + at[b], want, &n);
+        else {
+          r = bce_hip_decompress(ap, blocks[b].second, out.get() + at[b], want, &n);
+          if (r == 0 && checked && n == want) got[b] = bce_hip_crc32(0, out.get() + at[b], want);
+        }
         if (r == 0 && n != want) r = BCE_HIP_E_INTERNAL;         // the table and the block's own header disagree
+        if (r == 0 && checked && got[b] != table_crc(adata, b)) { differs[b] = 1; r = kMismatch; }
         return r;
       };
       std::vector<std::thread> th;
@@ -537,6 +642,11 @@ int main(int argc, char **argv) {
         if (c) bce_hip_destroy(c);
       }
       if (rc == 0) for (size_t b = 0; b < blocks.size(); ++b) if (!done[b]) rc = BCE_HIP_E_INTERNAL;
+      for (size_t b = 0; b < blocks.size(); ++b)
+        if (differs[b]) {                                           // (the lowest block that differs; the file is not written)
+          print_mismatch(b, table_crc(adata, b), got[b]);
+          return -4;
+        }
     }
     if (rc != 0) {
       printf("Decompression failed: %s\n", bce_hip_strerror(rc));
@@ -554,6 +664,8 @@ int main(int argc, char **argv) {
     return 0;
   } else if (argc == 4 && argv[1][0] == '-' && argv[1][1] == 't' && argv[1][2] == 0) {
     return test_archive(argv[2], argv[3]);
+  } else if (argc == 3 && argv[1][0] == '-' && argv[1][1] == 't' && argv[1][2] == 0) {
+    return self_test_archive(argv[2]);
   } else if (argc == 4 && argv[1][0] == '-' && argv[1][1] == 's') {
     // Scan (bce.cpp:1384-1402): enumeration on the GPU, ScanCoder optimisation on the host, 288-byte config out
     auto start = std::chrono::high_resolution_clock::now();

@@ -4,13 +4,18 @@
     u = decompress_tensor(arch, device="cuda:0")   # -> 1-D uint8 CUDA tensor; nothing of the text crosses to the host
     assert verify_tensor(arch, t) is None          # decoded and compared on the GPU
 
+    blob = compress_tensor_blocks(t)               # any size >= 1 (blocks below 2^31 each) -> a checked BCEM container (version 2)
+    u = decompress_container_tensor(blob)          # every block decoded into its slice and tested against its CRC-32 there
+    assert test_container(blob) is None            # ... or only tested: nothing is kept
+
 Stream rule.  The library runs on a stream of its own and knows nothing of torch's.  So every helper here synchronises
 the tensor's CURRENT torch stream on the tensor's device before the call -- whatever produced `t` / `out` there must be
 done -- and the call returns only when the library's stream is idle: the result may be used from any stream at once.
 A tensor produced on another, non-current stream has to be synchronised by the caller."""
 import torch
 
-from . import api
+from . import api, container
+from .sharding import block_range
 
 
 def _device_index(device):
@@ -76,3 +81,108 @@ def verify_tensor(archive, t, ctx=None):
     _check(t, "t")
     _ready(t)
     return api.verify_device(archive, t.data_ptr() if t.numel() else None, t.numel(), device=t.device.index, ctx=ctx)
+
+
+_MAX_BLOCK = (1 << 31) - 1          # a block obeys the reference's n < 2^31
+
+
+def compress_tensor_blocks(t, blocks=None, config=None, contexts=4, checksum=True):
+    """A 1-D uint8 CUDA tensor of ANY size >= 1 -> a BCEM container (host bytes): `blocks` contiguous blocks
+    (sharding.block_range; default: the fewest that keep every block below 2^31 bytes), each compressed from its slice in
+    HBM by a pool of `contexts` gated contexts of t's device.  checksum=True: a version-2 container with the CRC-32 of
+    every block, taken on the device by the context that compresses it; False: version 1, what `bce -cN` writes.
+    Synchronises t's current stream first."""
+    _check(t, "t")
+    n = t.numel()
+    if n == 0:
+        raise api.BceError(-1, "compress_tensor_blocks", "empty input")
+    if blocks is None:
+        blocks = (n + _MAX_BLOCK - 1) // _MAX_BLOCK
+    blocks = int(blocks)
+    if blocks < 1 or blocks > n or (n + blocks - 1) // blocks > _MAX_BLOCK:
+        raise ValueError("%d blocks do not split %d bytes into blocks of 1 .. 2^31 - 1 bytes" % (blocks, n))
+    _ready(t)
+    ranges = [block_range(n, blocks, b) for b in range(blocks)]
+    base = t.data_ptr()
+    with api.ContextPool(contexts, t.device.index) as pool:
+        res = pool.compress_many([(base + lo, hi - lo) for lo, hi in ranges], config=config, on_device=True, with_crc=checksum)
+    sizes = [hi - lo for lo, hi in ranges]
+    if checksum:
+        return container.pack_blocks([bytes(a) for a, _ in res], sizes, [c for _, c in res])
+    return container.pack_blocks([bytes(a) for a in res], sizes)
+
+
+def _blocks_of(blob):
+    """(table, checked): the blocks of a container, or the one block of a plain archive; every raw size is the one the
+    block's own header states (the CLI's rule: a lying table is refused before anything is written)."""
+    if bytes(blob[:4]) == container.MAGIC:
+        table = container.block_table(blob)
+    else:
+        table = [(api.decoded_size(blob), 0, len(blob), None)]
+    for b, (raw, pos, alen, _crc) in enumerate(table):
+        if raw < 1 or raw > _MAX_BLOCK or api.decoded_size(memoryview(blob)[pos:pos + alen]) != raw:
+            raise ValueError("block %d: the table's size is not the block's own" % b)
+    return table
+
+
+def decompress_container_tensor(blob, device="cuda:0", out=None, check=True):
+    """A BCEM container (either version) or a plain archive -> ONE 1-D uint8 tensor on the device: every block is decoded
+    straight into its slice (bce_hip_decompress_to_device), nothing of the text crosses to the host.  With `check`, a
+    version-2 container's blocks are tested there against the table's CRC-32 (bce_hip_crc32_device): ChecksumError
+    names the first block that differs -- the slices behind it have not been written.  `out`: as decompress_tensor."""
+    table = _blocks_of(blob)
+    total = sum(t[0] for t in table)
+    if out is not None:
+        _check(out, "out")
+        if out.numel() < total:
+            raise api.BceError(-5, "decompress_container_tensor", "out holds %d bytes, the container %d" % (out.numel(), total))
+        res = out[:total]
+    else:
+        res = torch.empty(total, dtype=torch.uint8, device=torch.device("cuda", _device_index(device)))
+    _ready(res)
+    view = memoryview(blob)
+    c = api._Ctx(res.device.index)
+    try:
+        at = 0
+        for b, (raw, pos, alen, crc) in enumerate(table):
+            ptr = res.data_ptr() + at
+            api.decompress_to_device(view[pos:pos + alen], ptr, raw, ctx=c)
+            if check and crc is not None:
+                got = api.crc32_device(ptr, raw, ctx=c)
+                if got != crc:
+                    raise api.ChecksumError(b, crc, got)
+            at += raw
+    finally:
+        c.close()
+    return res
+
+
+def test_container(blob, device="cuda:0", raise_on_refusal=False):
+    """Test a version-2 container against its own CRC-32s: every block is decoded on the GPU into the context's buffer and
+    checksummed there (bce_hip_decode_crc32); nothing is kept.  -> None when every block matches, else the index of the
+    first that does not -- or that the decoder refuses by itself (status -1: the block does not parse, -6: it decodes to
+    nonsense; -6 is also what a consistency failure of the decoder's own would give, so raise_on_refusal=True hands that
+    BceError, with the library's message, to the caller instead).  ValueError: nothing to check (a plain archive, a version-1 container)."""
+    if bytes(blob[:4]) != container.MAGIC:
+        raise ValueError("a plain archive carries no checksum: verify it against the original (verify_tensor)")
+    table = _blocks_of(blob)
+    if any(t[3] is None for t in table):
+        raise ValueError("a version-1 container carries no checksum: verify it against the original")
+    view = memoryview(blob)
+    c = api._Ctx(_device_index(device))
+    try:
+        for b, (raw, pos, alen, crc) in enumerate(table):
+            try:
+                n, got = api.decode_crc32(view[pos:pos + alen], ctx=c)
+            except api.BceError as e:
+                if e.status in (-1, -6) and not raise_on_refusal:   # the decoder itself refuses the block
+                    return b
+                raise
+            if n != raw or got != crc:
+                return b
+    finally:
+        c.close()
+    return None
+
+
+test_container.__test__ = False      # (a library function, not a test: its name starts with "test")

@@ -184,7 +184,7 @@ int bce_hip_scan(bce_hip_ctx *ctx, uint8_t config288[BCE_HIP_CONFIG_BYTES], doub
  *      (bce_hip_decompress_device), the caller's device memory (bce_hip_decompress_to_device: the mirror of
  *      bce_hip_compress_device, nothing of the text crosses to the host), or none -- compared on the device with the
  *      original (bce_hip_verify_device / _host, `bce -t`: the format carries no checksum, so "decode it and compare" is
- *      the integrity check there is).  The archive is a host pointer in all of them: the eight range decoders read it
+ *      the integrity check there is -- for a plain archive; a version-2 container carries CRC-32s, see the CRC-32 section below).  The archive is a host pointer in all of them: the eight range decoders read it
  *      on host threads.  All work runs on the context's own stream and is complete when the call returns; device
  *      memory the caller passes in must be ready (its producer's stream synchronised) when the call is made. -------- */
 /* BCE::decode + unbwt::bytewise + inverse BWT + rotate (bce.cpp:1169-1233, 1043-1102): archive -> original bytes.
@@ -206,6 +206,35 @@ int bce_hip_decompress_to_device(bce_hip_ctx *ctx, const uint8_t *archive, size_
  * as bce_hip_decompress_device, *first_diff untouched. */
 int bce_hip_verify_device(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, const void *d_original, size_t n, uint64_t *first_diff);
 int bce_hip_verify_host(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, const uint8_t *original, size_t n, uint64_t *first_diff);
+
+/* ---- extension: CRC-32 of texts, on the host and on the device (the blocks of a version-2 BCEM container) --------------
+ * A plain archive carries no checksum and must not: it is the reference's format.  The multi-block container is this project's
+ * own; its version 2 (`bce -CN`, bce_amd/container.py) holds the CRC-32 of every block's text -- as zlib, gzip and PNG compute it:
+ * reflected polynomial 0xEDB88320, init and final xor 0xFFFFFFFF -- so that an archive can be tested without the original. */
+/* zlib's calling shape: `crc` of the bytes so far (0 to start) -> crc of those bytes followed by p[0, n).  Host code, no context,
+ * no GPU. */
+uint32_t bce_hip_crc32(uint32_t crc, const uint8_t *p, size_t n);
+/* CRC-32 of A || B from the CRC-32s of A and of B and the length of B (any 64-bit length; the bytes are not needed): crc_a times
+ * x^(8 len_b) mod P by square and multiply, plus crc_b.  Gives a whole file's CRC from its blocks'.  Host code, no GPU. */
+uint32_t bce_hip_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+/* CRC-32 of n bytes of device memory of the context's device (any alignment, any n -- 2^32 and more included), computed there
+ * (kd_crc32.hip): one read of the bytes, one word comes back.  Stream rule of bce_hip_decompress_to_device: runs on the
+ * context's stream, complete on return; the memory must be ready when the call is made.  n == 0: *crc = 0, d ignored.  A null
+ * ctx or crc: BCE_HIP_E_ARG before any device call. */
+int bce_hip_crc32_device(bce_hip_ctx *ctx, const void *d, size_t n, uint32_t *crc);
+/* CRC-32 of the input the context holds, on the device.  Valid from bce_hip_load_host / _device on for as long as the context
+ * keeps the input's bytes: through bce_hip_bwt, bce_hip_build_planes, bce_hip_encode / _scan and after them (the depth-first tail
+ * of the enumeration reads the text, so no stage gives it back), until the next call that takes the buffer for something else --
+ * a load, bce_hip_set_bwt, bce_hip_divbwt, bce_hip_inverse_bwt or any decode in this context.  Otherwise BCE_HIP_E_STATE. */
+int bce_hip_input_crc32(bce_hip_ctx *ctx, uint32_t *crc);
+/* The GPU-assisted decode with the text left in the context's own buffer and only its size and CRC-32 reported: no second buffer
+ * is held and nothing of the text goes to the host (`bce -t archive`).  Archive errors as bce_hip_decompress_device, outputs
+ * untouched. */
+int bce_hip_decode_crc32(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, size_t *decoded, uint32_t *crc);
+/* bce_hip_decompress_device with the CRC-32 of the text beside it: taken on the device from the context's buffer before the copy
+ * to the host is queued (`bce -d` on a version-2 container).  out == NULL: only the size is reported, *crc untouched. */
+int bce_hip_decompress_device_crc32(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, uint8_t *out, size_t cap, size_t *out_len,
+                                    uint32_t *crc);
 
 /* ---- statistics of the last bce_hip_encode / bce_hip_compress ------------------------------------ */
 typedef struct bce_hip_stats {
