@@ -98,6 +98,10 @@ SYMBOLS = [
     ("bce_hip_input_crc32", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     ("bce_hip_decode_crc32", C.c_int, [C.c_void_p, _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
     ("bce_hip_decompress_device_crc32", C.c_int, [C.c_void_p, _u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
+    ("bce_hip_estimate", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)]),
+    ("bce_hip_estimate_host", C.c_int, [C.c_void_p, _u8p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)]),
+    ("bce_hip_estimate_device", C.c_int, [C.c_void_p, _vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)]),
+    ("bce_hip_cost_q24", C.c_uint32, [C.c_uint32, C.c_uint32]),
     ("bce_hip_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     ("bce_hip_synth_text", None, [C.c_uint64, _u8p, C.c_size_t]),
     ("bce_hip_synth_rand", None, [C.c_uint64, _u8p, C.c_size_t]),
@@ -333,6 +337,70 @@ def compress_device(device_ptr, n, config=None, device=0, ctx=None, out=None):
     finally:
         if own:
             c.close()
+
+
+class Estimate:
+    """What bce_hip_estimate reports: the size of the archive `compress` would make, and where its bits go.
+
+    .bytes           the archive's size in bytes (framing + the eight streams)
+    .plane_cost_q24  per plane, the bits its coder codes in unsigned Q24 fixed point (integer sums: exact, order-independent)
+    .plane_bits      the same as floats (Q24 sum / 2**24)
+    .plane_steps     per plane, the adaptive coder's calls (model records); their sum is stats(...)["symbols"]"""
+
+    __slots__ = ("bytes", "plane_cost_q24", "plane_steps")
+
+    def __init__(self, nbytes, plane_cost_q24, plane_steps):
+        self.bytes, self.plane_cost_q24, self.plane_steps = int(nbytes), [int(v) for v in plane_cost_q24], [int(v) for v in plane_steps]
+
+    @property
+    def plane_bits(self):
+        return [v / float(1 << 24) for v in self.plane_cost_q24]
+
+    def __repr__(self):
+        return "Estimate(bytes=%d, plane_bits=[%s])" % (self.bytes, ", ".join("%.1f" % b for b in self.plane_bits))
+
+
+def _estimate(c, config, call, where):
+    cfg = None if config is None else _as_u8(bytes(config))
+    if cfg is not None and len(cfg) != CONFIG_BYTES:
+        raise ValueError("Config not found or wrong size.")
+    c.check(c.lib.bce_hip_set_config(c.h, cfg.ctypes.data if cfg is not None else None), "bce_hip_set_config")
+    cost, steps, nbytes = (C.c_uint64 * 8)(), (C.c_uint64 * 8)(), C.c_size_t()
+    c.check(call(cost, steps, C.byref(nbytes)), where)
+    return Estimate(nbytes.value, list(cost), list(steps))
+
+
+def estimate(data, config=None, device=0, ctx=None) -> Estimate:
+    """The size `compress(data, config)` would give, without coding: K1..K4 run, the range coders do not
+    (bce_hip_estimate_host).  -> Estimate."""
+    a = _as_u8(data)
+    if len(a) == 0:
+        raise BceError(-1, "estimate", "empty input")
+    own = ctx is None
+    c = ctx or _Ctx(device)
+    try:
+        return _estimate(c, config, lambda *out: c.lib.bce_hip_estimate_host(c.h, a.ctypes.data, len(a), *out), "bce_hip_estimate_host")
+    finally:
+        if own:
+            c.close()
+
+
+def estimate_device(device_ptr, n, config=None, device=0, ctx=None) -> Estimate:
+    """The same with the input already resident in HBM (bce_hip_estimate_device); stream rule as decompress_to_device."""
+    own = ctx is None
+    c = ctx or _Ctx(device)
+    try:
+        ptr = None if device_ptr is None else int(device_ptr)
+        return _estimate(c, config, lambda *out: c.lib.bce_hip_estimate_device(c.h, ptr, int(n), *out), "bce_hip_estimate_device")
+    finally:
+        if own:
+            c.close()
+
+
+def cost_q24(freq, total) -> int:
+    """The cost of one range-coder step with probability freq / total: log2(total) - log2(freq) in unsigned Q24 fixed
+    point, the integer function the cost kernel runs (bce_hip_cost_q24; no GPU).  1 <= freq <= total < 2**32."""
+    return load_library().bce_hip_cost_q24(int(freq), int(total))
 
 
 def set_plane_mask(ctx, mask):

@@ -7,6 +7,7 @@
 #include <new>
 #include <utility>
 
+#include "bce_cost.h"
 #include "common.h"
 #include "host_coder.h"
 #include "scan_coder.h"
@@ -289,6 +290,16 @@ void account_slot(bce_hip_ctx *c, FlushSlot &slot) {
   slot.timed = false;
 }
 
+// A flush that runs beside the main stream (flush_seq moved on) reads skey[0] / sesc: the next rounds write the other pair, which
+// the flush BEFORE this one was the last to read.
+int flush_swap_buffers(bce_hip_ctx *c, uint32_t seq0) {
+  if (c->flush_seq == seq0) return BCE_HIP_OK;
+  std::swap(c->skey[0], c->skey_alt);
+  std::swap(c->sesc, c->sesc_alt);
+  if (seq0 > 0) BCE_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_k4_done[(seq0 - 1u) & 1u], 0));
+  return BCE_HIP_OK;
+}
+
 // Flush the model (K4) for the symbols buffered so far and hand the result to the coder threads.  Nothing here
 // waits for the GPU: the kernels are queued on the compute stream, the device-to-host copy on the copy stream,
 // and the coder threads wait for the copy's event before they touch the batch; the next rounds overlap both.
@@ -308,13 +319,7 @@ int flush_symbols(bce_hip_ctx *c, uint64_t nsym) {
     const uint32_t seq0 = c->flush_seq;
     RoctxRange range("bce K4 model flush");
     BCE_TRY(k4_flush_async(c, nsym, slot));
-    if (c->flush_seq != seq0) {
-      // the flush runs beside the main stream and reads skey[0] / sesc: the next rounds write the other pair, which
-      // the flush BEFORE this one was the last to read
-      std::swap(c->skey[0], c->skey_alt);
-      std::swap(c->sesc, c->sesc_alt);
-      if (seq0 > 0) BCE_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_k4_done[(seq0 - 1u) & 1u], 0));
-    }
+    BCE_TRY(flush_swap_buffers(c, seq0));
     // BCE_HIP_SYNC_FLUSH=1 (profiling): wait for the copy before queuing more rounds.  rocprofv3's kernel trace
     // serialises the copy stream's blit kernel with the compute stream and charges the 2.4 ms to the K3 kernel behind it.
     if (c->sync_flush) BCE_HIP_TRY(c, hipEventSynchronize(slot.ev_copy));
@@ -331,6 +336,26 @@ int flush_symbols(bce_hip_ctx *c, uint64_t nsym) {
       slot.batch.wait_ready = [once, ev]() { std::call_once(*once, [ev]() { (void)hipEventSynchronize(ev); }); };
     }
     c->coder->submit(&slot.batch);
+    c->stats.flushes++;
+    c->stats.symbols += nsym;
+    gate_lend(c);
+  }
+  return k3_reset_symbols(c);
+}
+// The sink of estimate mode (bce_hip_estimate): K4 as in flush_symbols, then the cost kernel on the records where they lie
+// (k4_cost.hip).  No device-to-host copy, no host staging, nothing for the coder threads; the slot only lends its events, and the
+// pinned run table, which are free again once its ev_copy -- behind the cost kernel here -- has fired.
+int flush_costs(bce_hip_ctx *c, uint64_t nsym) {
+  if (nsym) {
+    FlushSlot &slot = c->slot[c->slot_next];
+    c->slot_next = (c->slot_next + 1) % 3;
+    if (slot.timed) { BCE_HIP_TRY(c, hipEventSynchronize(slot.ev_copy)); account_slot(c, slot); }
+    const uint32_t seq0 = c->flush_seq;
+    RoctxRange range("bce K4 model flush + cost");
+    BCE_TRY(k4_flush_async(c, nsym, slot, /*copy_out=*/false));
+    BCE_TRY(k4_cost_async(c, nsym, slot));
+    BCE_TRY(flush_swap_buffers(c, seq0));
+    if (c->sync_flush) BCE_HIP_TRY(c, hipEventSynchronize(slot.ev_copy));
     c->stats.flushes++;
     c->stats.symbols += nsym;
     gate_lend(c);
@@ -674,7 +699,7 @@ void bce_hip_destroy(bce_hip_ctx *c) {
   DevBuf *bufs[] = {&c->text, &c->bwt, &c->sa[0], &c->sa[1], &c->key[0], &c->key[1], &c->rank, &c->k2, &c->nrk, &c->act[0], &c->act[1], &c->khi[0], &c->khi[1], &c->dl[0], &c->dl[1], &c->dl[2], &c->dl[3], &c->kflag, &c->actv[0], &c->actv[1],
                     &c->rs_hist, &c->blk, &c->ptmp[0], &c->ptmp[1], &c->gran, &c->nlist[0], &c->nlist[1], &c->ctl, &c->tilecnt,
                     &c->tileoff, &c->runs, &c->smwords, &c->k3tw, &c->k3grp, &c->truns, &c->skey[0], &c->skey[1], &c->sval[0], &c->sval[1], &c->sout,
-                    &c->sesc, &c->stat, &c->crc_tab, &c->dcfg, &c->k4w, &c->scanrec, &c->dfs, &c->skey_alt, &c->sesc_alt, &c->rs_hist_k4};
+                    &c->sesc, &c->stat, &c->crc_tab, &c->dcfg, &c->k4w, &c->scanrec, &c->dfs, &c->skey_alt, &c->sesc_alt, &c->rs_hist_k4, &c->cost_acc, &c->cost_runs};
   for (DevBuf *b : bufs) release(*b);
   for (auto &par : c->dlist) for (DevBuf &b : par) release(b);
   k4_prepin_join(c, true);
@@ -690,6 +715,7 @@ void bce_hip_destroy(bce_hip_ctx *c) {
     if (sl.ev_start) (void)hipEventDestroy(sl.ev_start);
     if (sl.ev_copy) (void)hipEventDestroy(sl.ev_copy);
     if (sl.ev_kend) (void)hipEventDestroy(sl.ev_kend);
+    if (sl.h_cost_runs) (void)hipHostFree(sl.h_cost_runs);
   }
   if (c->ev_k4) (void)hipEventDestroy(c->ev_k4);
   if (c->ev_k3_batch) (void)hipEventDestroy(c->ev_k3_batch);
@@ -1137,6 +1163,99 @@ int bce_hip_compress_device(bce_hip_ctx *c, const void *d_in, uint32_t n, uint8_
   if (c && d_in && n && n < 0x80000000u) k4_prepin(c, n);
   BCE_TRY(bce_hip_load_device(c, d_in, n));
   return compress_loaded(c, out, cap, out_len);
+}
+
+// ---- the archive's size without coding it (k4_cost.hip, bce_cost.h) ------------------------------------------------------
+uint32_t bce_hip_cost_q24(uint32_t freq, uint32_t total) {
+  if (freq == 0 || total < freq) return 0;
+  return bce::cost_q24(freq, total);
+}
+
+// What HostCoder::begin codes into plane p's stream before the first record: the preamble of its config row and C[p] with
+// range n + 1 -- uniform steps, cost L(k) each.
+static uint64_t begin_cost_q24(const uint8_t row[32], uint32_t n) {
+  uint64_t cost = 0;
+  uint32_t last = 0;
+  for (int b = 0; b < 32; ++b) {
+    cost += bce::cost_q24(1, 2);
+    if (row[b] != last) cost += bce::cost_q24(1, 6);
+    last = row[b];
+  }
+  return cost + bce::cost_q24(1, n + 1);
+}
+
+static int estimate_body(bce_hip_ctx *c, uint64_t *plane_cost, uint64_t *plane_steps, size_t *archive_bytes);
+int bce_hip_estimate(bce_hip_ctx *c, uint64_t plane_cost_q24[8], uint64_t plane_steps[8], size_t *archive_bytes) {
+  return gate_on_error(c, bce_guarded(c, [&] { return estimate_body(c, plane_cost_q24, plane_steps, archive_bytes); }));
+}
+static int estimate_body(bce_hip_ctx *c, uint64_t *plane_cost, uint64_t *plane_steps, size_t *archive_bytes) {
+  BCE_TRY(check_stage(c, 3));
+  PhaseScope phase(c, 3);
+  c->gate_wait_s = 0; c->gate_held_s = 0; c->gate_lent = false;
+  gate_acquire(c);
+  BCE_HIP_TRY(c, hipSetDevice(c->device));
+  const uint32_t n = c->n;
+  // the estimate is of the whole archive: the rounds record every plane's symbols, whatever bce_hip_set_plane_mask said (K3Args::pmask)
+  struct EstimateMode { bce_hip_ctx *c; ~EstimateMode() { c->estimate_mode = false; } } mode{c};
+  c->estimate_mode = true;
+  BCE_TRY(k4_prepare(c));
+  BCE_TRY(k3_begin(c));
+  BCE_TRY(k4_cost_begin(c));
+  c->stats.symbols = 0; c->stats.flushes = 0; c->stats.t_model = 0; c->stats.t_model_kernels = 0; c->stats.t_coder = 0;
+  c->stats.t_coder_busy = 0;
+
+  Enumeration e(c, [&](uint64_t nsym) { return flush_costs(c, nsym); });
+  BCE_TRY(e.run());
+  gate_release(c);
+  c->gate_lent = false;
+  uint64_t acc[16];
+  BCE_TRY(k4_cost_end(c, acc));                    // 128 bytes: everything queued has run
+  for (FlushSlot &sl : c->slot) account_slot(c, sl);
+  c->stats.rounds = e.ctl.done_round;
+  c->stats.nodes = e.ctl.nodes_total;
+  c->stats.t_enum = c->stats.k3_ms * 1e-3;
+  c->enum_active = false;                          // (the stage stays: an encode may follow, an archive made before is still there)
+
+  // plane p's stream: begin() + its records; the header coder main(-1) is run for real on the estimated stream sizes
+  // (HostCoder::rebuild_header), then 1 length word + header + streams (assemble).
+  uint64_t words[8], sum = 0;
+  for (int p = 0; p < 8; ++p) {
+    acc[p] += begin_cost_q24(c->config[p], n);
+    words[p] = bce::stream_words_q24(acc[p]);
+    sum += words[p];
+  }
+  if (plane_cost) memcpy(plane_cost, acc, 8 * sizeof(uint64_t));
+  if (plane_steps) memcpy(plane_steps, acc + 8, 8 * sizeof(uint64_t));
+  if (archive_bytes) {
+    if (sum > 0xFFFFFFFFull) { snprintf(c->err, sizeof c->err, "estimate: %llu stream words are more than the header can name", (unsigned long long)sum); return BCE_HIP_E_OVERFLOW; }
+    RangeCoder mainc;
+    mainc.preamble(c->config[8]);
+    mainc.setv(n);
+    mainc.uniform(c->offset, n + 1);
+    mainc.setv((uint32_t)sum);
+    uint64_t s = sum;
+    for (int i = 0; i < 7; ++i) { mainc.uniform((uint32_t)words[i], (uint32_t)s + 1); s -= words[i]; }
+    mainc.flush();
+    *archive_bytes = (size_t)(1 + mainc.data().size() + sum) * 2;
+  }
+  return BCE_HIP_OK;
+}
+
+static int estimate_loaded(bce_hip_ctx *c, uint64_t *plane_cost, uint64_t *plane_steps, size_t *archive_bytes) {
+  const double t0 = now_s();
+  BCE_TRY(bce_hip_bwt(c, nullptr));
+  BCE_TRY(bce_hip_build_planes(c, nullptr));
+  BCE_TRY(bce_hip_estimate(c, plane_cost, plane_steps, archive_bytes));
+  c->stats.t_total = now_s() - t0 + c->stats.t_load;
+  return BCE_HIP_OK;
+}
+int bce_hip_estimate_host(bce_hip_ctx *c, const uint8_t *in, uint32_t n, uint64_t plane_cost_q24[8], uint64_t plane_steps[8], size_t *archive_bytes) {
+  BCE_TRY(bce_hip_load_host(c, in, n));
+  return estimate_loaded(c, plane_cost_q24, plane_steps, archive_bytes);
+}
+int bce_hip_estimate_device(bce_hip_ctx *c, const void *d_in, uint32_t n, uint64_t plane_cost_q24[8], uint64_t plane_steps[8], size_t *archive_bytes) {
+  BCE_TRY(bce_hip_load_device(c, d_in, n));
+  return estimate_loaded(c, plane_cost_q24, plane_steps, archive_bytes);
 }
 
 // ---- CRC-32 on the device (kd_crc32.hip) ---------------------------------------------------------------

@@ -69,6 +69,9 @@ struct FlushSlot {
   uint64_t *pin_p = nullptr;
   size_t pin_cap = 0;
   double pin_s = 0;
+  // estimate mode (k4_cost.hip): the flush's run table on its way to the device, pinned; free again once ev_copy has fired
+  void *h_cost_runs = nullptr;
+  size_t h_cost_runs_cap = 0;
 };
 
 // ---- host memory registered with the runtime (hipHostRegister) ------------------------------------------------------------
@@ -199,9 +202,11 @@ struct bce_hip_ctx {
   bce::DevBuf skey[2], sval[2], sout, sesc;       // K3->K4: symbol keys (skey[0]) + escape words (sesc); sort ping-pong; outputs
   bce::DevBuf skey_alt, sesc_alt, rs_hist_k4;     // the other pair of symbol buffers (see k4_stream); K4's radix histograms
   uint64_t sym_cap = 0;
+  bool estimate_mode = false;                    // bce_hip_estimate is running: every plane's symbols are recorded, whatever the coder's plane mask
   bool scan_mode = false;                        // `bce -s`: K3 emits scan_pack words (bce_core.h) into scanrec
   bce::DevBuf scanrec;
   bce::DevBuf stat, dcfg, k4w;                   // K4 counters, device copy of PlaneCfg[8], per-window work arrays
+  bce::DevBuf cost_acc, cost_runs;               // k4_cost.hip: eight cost sums + eight record counts; the run table of the flush being summed
   bce::DevBuf crc_tab;                           // kd_crc32.hip: the step tables of a launch of crc_tab_grid workgroups, its constants, its result word
   uint32_t crc_tab_grid = 0;                     // 0: no step tables uploaded
   bool crc_const_ready = false;                  // its launch-independent constants are uploaded
@@ -431,7 +436,12 @@ uint64_t k3_symbol_capacity(const bce_hip_ctx *c, uint32_t n);   // records betw
 void k4_prepin(bce_hip_ctx *c, uint32_t n);         // start pinning the flush slots' host staging for an input of n bytes (threads)
 void k4_prepin_join(bce_hip_ctx *c, bool drop);     // wait for those threads (drop: free what they pinned and nobody adopted)
 int k4_flush(bce_hip_ctx *c, uint64_t nsym, FlushSlot &slot);         // synchronous: outputs are in slot.h_out on return
-int k4_flush_async(bce_hip_ctx *c, uint64_t nsym, FlushSlot &slot);   // sort + replay + D2H into the slot, all queued: outputs are in slot.h_out once slot.ev_copy has fired
+// sort + replay + D2H into the slot, all queued: outputs are in slot.h_out once slot.ev_copy has fired.  copy_out = false
+// (estimate mode): the records stay in `sout`, the slot needs no host staging and only lends its events.
+int k4_flush_async(bce_hip_ctx *c, uint64_t nsym, FlushSlot &slot, bool copy_out = true);
+int k4_cost_begin(bce_hip_ctx *c);                  // k4_cost.hip: the context's sums to zero
+int k4_cost_async(bce_hip_ctx *c, uint64_t nsym, FlushSlot &slot);   // behind k4_flush_async(.., false): add the flush's code lengths, per plane
+int k4_cost_end(bce_hip_ctx *c, uint64_t acc[16]);  // wait and read them: [0..7] Q24 cost sums, [8..15] record counts
 
 // radix sort (radix_sort.hip): stable LSD sort of (key,val) u32 pairs on key bits [first_bit, first_bit+bits).
 // Result is left in key[res]/val[res]; returns res (0 or 1) through *res.

@@ -930,7 +930,7 @@ K3Args k3_make_args(bce_hip_ctx *c, uint32_t round, uint32_t run_slot) {
     static const uint32_t v = e ? (uint32_t)strtoul(e, nullptr, 10) : K3_CAP32;
     a.cap32 = v < K3_CAP32 ? v : K3_CAP32;
   }
-  a.pmask = (c->scan_mode || !c->coder) ? 0xFFu : (c->coder->plane_mask & 0xFFu);
+  a.pmask = (c->scan_mode || c->estimate_mode || !c->coder) ? 0xFFu : (c->coder->plane_mask & 0xFFu);
   return a;
 }
 

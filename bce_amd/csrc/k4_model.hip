@@ -389,7 +389,7 @@ int k4_prepare(bce_hip_ctx *c) {
   return BCE_HIP_OK;
 }
 
-int k4_flush_async(bce_hip_ctx *c, uint64_t nsym64, FlushSlot &slot) {
+int k4_flush_async(bce_hip_ctx *c, uint64_t nsym64, FlushSlot &slot, bool copy_out) {
   if (nsym64 == 0) return BCE_HIP_OK;
   if (nsym64 >= (1ull << 31)) return BCE_HIP_E_OVERFLOW;
   const uint32_t nsym = (uint32_t)nsym64;
@@ -397,8 +397,8 @@ int k4_flush_async(bce_hip_ctx *c, uint64_t nsym64, FlushSlot &slot) {
   BCE_TRY(ensure(c, c->skey[1], b4));
   for (int i = 0; i < 2; ++i) BCE_TRY(ensure(c, c->sval[i], b4));
   BCE_TRY(ensure(c, c->sout, (size_t)nsym * 8 + 16));      // + slack: the copy-out moves 16-byte units
-  if (slot.pin_th.joinable()) slot.pin_th.join();                    // pinned ahead (k4_prepin): adopt it
-  if (slot.pin_p) {
+  if (copy_out && slot.pin_th.joinable()) slot.pin_th.join();        // pinned ahead (k4_prepin): adopt it
+  if (copy_out && slot.pin_p) {
     if (slot.pin_cap > slot.cap) {
       slot_free_host(slot, &c->reg_unmaps);
       slot.h_out = slot.pin_p; slot.cap = slot.pin_cap; slot.registered = true;
@@ -409,7 +409,7 @@ int k4_flush_async(bce_hip_ctx *c, uint64_t nsym64, FlushSlot &slot) {
     }
     slot.pin_p = nullptr; slot.pin_cap = 0;
   }
-  if (slot.cap < nsym) {
+  if (copy_out && slot.cap < nsym) {
     slot_free_host(slot, &c->reg_unmaps);
     size_t cap = (size_t)c->sym_cap > nsym ? (size_t)c->sym_cap : nsym;
     // A slot that has to grow in the middle of a compression (the symbol buffer grew: a high-entropy input of GBs has rounds of
@@ -523,6 +523,7 @@ int k4_flush_async(bce_hip_ctx *c, uint64_t nsym64, FlushSlot &slot) {
   BCE_HIP_TRY(c, hipEventRecord(c->ev_k4, ks));
   BCE_HIP_TRY(c, hipEventRecord(slot.ev_kend, ks));
   if (own) { BCE_HIP_TRY(c, hipEventRecord(c->ev_k4_done[c->flush_seq & 1u], ks)); ++c->flush_seq; }   // ... and have been read
+  if (!copy_out) { slot.timed = true; return BCE_HIP_OK; }             // (the caller records ev_copy behind what it queues on the records)
   BCE_HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->ev_k4, 0));
   BCE_HIP_TRY(c, hipMemcpyAsync(slot.h_out, c->sout.p, (size_t)nsym * 8, hipMemcpyDeviceToHost, c->copy_stream));
   BCE_HIP_TRY(c, hipEventRecord(slot.ev_copy, c->copy_stream));

@@ -120,6 +120,8 @@ extern "C" int bce_hip_input_crc32(bce_hip_ctx *ctx, uint32_t *crc) __attribute_
 extern "C" int bce_hip_decode_crc32(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, size_t *decoded, uint32_t *crc) __attribute__((weak));
 extern "C" int bce_hip_decompress_device_crc32(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, uint8_t *out, size_t cap,
                                                size_t *out_len, uint32_t *crc) __attribute__((weak));
+extern "C" int bce_hip_estimate_host(bce_hip_ctx *ctx, const uint8_t *in, uint32_t n, uint64_t plane_cost_q24[8], uint64_t plane_steps[8],
+                                     size_t *archive_bytes) __attribute__((weak));
 
 // `bce -cN`: N contiguous blocks over the GPUs of the node.  With more blocks than GPUs every device gets up to four
 // gated contexts (bce_hip_set_gated), one host thread each: their GPU phases take turns while the coder threads of the
@@ -369,6 +371,52 @@ static int self_test_archive(const char *archive_path) {
   return 0;
 }
 
+// load_config, bce.cpp:626-641: the 288 bytes of `path` into cfgbuf and into the context -- or, with the reference's message, the
+// defaults (cfgbuf left empty).
+static void read_config(const char *path, bce_hip_ctx *ctx, std::vector<uint8_t> &cfgbuf) {
+  std::ifstream cfg(path, std::ios::binary | std::ios::ate);
+  std::streamoff size = cfg ? (std::streamoff)cfg.tellg() : -1;
+  if (size != (std::streamoff)BCE_HIP_CONFIG_BYTES) {
+    printf("Config not found or wrong size.\n");
+  } else {
+    cfgbuf.resize(BCE_HIP_CONFIG_BYTES);
+    cfg.seekg(0, std::ios::beg);
+    if (!cfg.read(reinterpret_cast<char *>(cfgbuf.data()), size)) { printf("Could not read Config.\n"); cfgbuf.clear(); }
+    else if (bce_hip_set_config(ctx, cfgbuf.data()) != 0) { printf("Config rejected: %s\n", bce_hip_last_error(ctx)); cfgbuf.clear(); }
+  }
+}
+
+// `bce -e file [config.bcc]` (extension): the size `bce -c` would write, from the model's code lengths summed on the GPU
+// (bce_hip_estimate_host); the range coders do not run and nothing is written.
+static int estimate_file(const char *file, const char *config) {
+  HostFile data;
+  std::thread reader(read_whole_file, file, &data, kMaxInput);      // as -c: beside the runtime's start-up
+  bce_hip_ctx *ctx = nullptr;
+  const int rc0 = bce_hip_create(&ctx, 0);
+  reader.join();
+  if (rc0 != 0 || !bce_hip_estimate_host) {
+    printf("No usable HIP device: %s\n", bce_hip_strerror(rc0 ? rc0 : BCE_HIP_E_DEVICE));
+    if (ctx) bce_hip_destroy(ctx);
+    return -3;
+  }
+  std::vector<uint8_t> cfgbuf;
+  if (config) read_config(config, ctx, cfgbuf);
+  if (data.status != 0 || data.size() == 0 || data.size() >= kMaxInput) { printf("Error loading file\n"); bce_hip_destroy(ctx); return -1; }
+  uint64_t cost[8], steps[8], prog = 0;
+  size_t bytes = 0;
+  bce_hip_set_progress(ctx, progress, &prog);
+  const int rc = bce_hip_estimate_host(ctx, data.data(), (uint32_t)data.size(), cost, steps, &bytes);
+  progress_end();
+  if (rc != 0) { printf("Estimate failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); bce_hip_destroy(ctx); return -4; }
+  printf("Estimated size: %zu B (ratio %.4f)\n", bytes, (double)bytes / (double)data.size());
+  printf("Plane bits:");
+  for (int p = 0; p < 8; ++p) printf(" %.1f", (double)cost[p] / 16777216.0);
+  printf("\n");
+  fast_exit(0);
+  bce_hip_destroy(ctx);
+  return 0;
+}
+
 static int usage() {
   printf("Usage:\n");
   printf("  bce -c archive.bce file [config.bcc]\n");
@@ -390,6 +438,9 @@ static int usage() {
   printf("\n");
   printf("  bce -t archive.bcem\n");
   printf("   Tests a -CN archive against its own checksums: decodes it on the GPU, writes nothing (extension; exit status 0 = sound, %d = a block differs, %d = the archive carries no checksum)\n", kExitDiffers, kExitNoChecksum);
+  printf("\n");
+  printf("  bce -e file [config.bcc]\n");
+  printf("   Estimates the size -c would give for \"file\" [using config \"config.bcc\"]: the model's code lengths are summed on the GPU, nothing is coded or written (extension)\n");
   return 0;
 }
 
@@ -426,18 +477,7 @@ int main(int argc, char **argv) {
     // load_config, bce.cpp:626-641.  Read and validated ONCE (on the first context): `-c` and `-cN` apply the same 288
     // bytes or, with the same message, the defaults.
     std::vector<uint8_t> cfgbuf;
-    if (argc == 5) {
-      std::ifstream cfg(argv[4], std::ios::binary | std::ios::ate);
-      std::streamoff size = cfg ? (std::streamoff)cfg.tellg() : -1;
-      if (size != (std::streamoff)BCE_HIP_CONFIG_BYTES) {
-        printf("Config not found or wrong size.\n");
-      } else {
-        cfgbuf.resize(BCE_HIP_CONFIG_BYTES);
-        cfg.seekg(0, std::ios::beg);
-        if (!cfg.read(reinterpret_cast<char *>(cfgbuf.data()), size)) { printf("Could not read Config.\n"); cfgbuf.clear(); }
-        else if (bce_hip_set_config(ctx, cfgbuf.data()) != 0) { printf("Config rejected: %s\n", bce_hip_last_error(ctx)); cfgbuf.clear(); }
-      }
-    }
+    if (argc == 5) read_config(argv[4], ctx, cfgbuf);
     reader.join();
     if (data.status != 0 || data.size() == 0 || data.size() >= file_limit) {   // also covers the empty file, on which the reference crashes
       printf("Error loading file\n");
@@ -666,6 +706,8 @@ int main(int argc, char **argv) {
     return test_archive(argv[2], argv[3]);
   } else if (argc == 3 && argv[1][0] == '-' && argv[1][1] == 't' && argv[1][2] == 0) {
     return self_test_archive(argv[2]);
+  } else if ((argc == 3 || argc == 4) && argv[1][0] == '-' && argv[1][1] == 'e' && argv[1][2] == 0) {
+    return estimate_file(argv[2], argc == 4 ? argv[3] : nullptr);
   } else if (argc == 4 && argv[1][0] == '-' && argv[1][1] == 's') {
     // Scan (bce.cpp:1384-1402): enumeration on the GPU, ScanCoder optimisation on the host, 288-byte config out
     auto start = std::chrono::high_resolution_clock::now();

@@ -49,6 +49,16 @@ def compress_tensor(t, config=None, ctx=None):
     return arch
 
 
+def estimate_tensor(t, config=None, ctx=None):
+    """The size `compress_tensor(t, config)` would give, without coding (bce_hip_estimate_device) -> api.Estimate.
+    Synchronises t's current stream first; `ctx` (an api._Ctx of t's device) is reused if given."""
+    _check(t, "t")
+    if t.numel() == 0:
+        raise api.BceError(-1, "estimate_tensor", "empty input")
+    _ready(t)
+    return api.estimate_device(t.data_ptr(), t.numel(), config=config, device=t.device.index, ctx=ctx)
+
+
 def decompress_tensor(archive, device="cuda:0", out=None, ctx=None):
     """The GPU-assisted decoder with the text left on the device (bce_hip_decompress_to_device) -> a 1-D uint8 tensor there.
 

@@ -158,6 +158,36 @@ int bce_hip_compress(bce_hip_ctx *ctx, const uint8_t *in, uint32_t n, uint8_t *o
 /* same with the input already in HBM */
 int bce_hip_compress_device(bce_hip_ctx *ctx, const void *d_in, uint32_t n, uint8_t *out, size_t cap, size_t *out_len);
 
+/* ---- extension: the archive's size without coding it (k4_cost.hip) ---------------------------------------------------------
+ * BCE::encode (bce.cpp:1117-1167) with the range coders left out: K3 and K4 run as for bce_hip_encode, and where the host coders
+ * would take the model's (cum, freq, total) records (AdaptiveCoder::set's coder half, bce.cpp:520-529; the k > 31 escape's uniform
+ * bits, :507-510) a kernel adds up what each step costs, log2(total / freq) bits, per plane, where the records lie.  Nothing is
+ * copied to the host but 128 bytes at the end; no archive is made and none that the context holds is touched.
+ * Preconditions: those of bce_hip_encode (after bce_hip_build_planes; the config in force is the one bce_hip_set_config set).
+ * A later bce_hip_encode on the same context gives the archive it would have given without the estimate.  bce_hip_set_plane_mask
+ * is not looked at -- the estimate's rounds record every plane's symbols -- and stays as it was: the estimate is of the whole archive.  Any of the three outputs may be NULL.
+ *   plane_cost_q24[p]  bits, in unsigned Q24 fixed point (2^24 = one bit), of everything plane p's coder codes: the preamble of
+ *                      its config row and C[p] (bce.cpp:682-691, :1128) and every step of its records.  Integer sums of
+ *                      bce_hip_cost_q24: independent of how rounds and flushes are cut, the same from run to run.
+ *   plane_steps[p]     the adaptive coder's calls for plane p (coder_[p].set(...), bce.cpp:1302) = its model records; their sum
+ *                      is bce_hip_stats.symbols.  (A record with a k > 31 escape costs its uniform bits too, but counts once.)
+ *   *archive_bytes     2 x (1 + header words + the eight streams' words): a stream is the whole 16-bit words of its sum
+ *                      (shift_out, bce.cpp:655-661) plus the one word flush() adds (:610-615), which carries the rest; the
+ *                      header coder main(-1) (bce.cpp:1141-1150) is run on those sizes.  Measured against the real archive:
+ *                      DESIGN.md section 4.7.
+ * bce_hip_stats afterwards: as after bce_hip_encode, with t_coder = t_coder_busy = 0; t_model is K4 plus the cost kernel. */
+int bce_hip_estimate(bce_hip_ctx *ctx, uint64_t plane_cost_q24[8], uint64_t plane_steps[8], size_t *archive_bytes);
+/* load + BWT + planes + estimate in one call: main() -c branch (bce.cpp:1403-1427) up to the coders, like bce_hip_compress /
+ * bce_hip_compress_device.  A null ctx or input, n == 0 or n >= 2^31: BCE_HIP_E_ARG before any device call. */
+int bce_hip_estimate_host(bce_hip_ctx *ctx, const uint8_t *in, uint32_t n, uint64_t plane_cost_q24[8], uint64_t plane_steps[8],
+                          size_t *archive_bytes);
+int bce_hip_estimate_device(bce_hip_ctx *ctx, const void *d_in, uint32_t n, uint64_t plane_cost_q24[8], uint64_t plane_steps[8],
+                            size_t *archive_bytes);
+/* The cost of one range-coder step encode(cum, freq, total) (bce.cpp:520-529): L(total) - L(freq), L = log2 in unsigned Q24,
+ * integer arithmetic only (bce_amd/csrc/bce_cost.h: the function the kernel runs, compiled for the host).  1 <= freq <= total;
+ * anything else gives 0.  Uses no GPU. */
+uint32_t bce_hip_cost_q24(uint32_t freq, uint32_t total);
+
 /* ---- stepping interface for parity tests (BCE::code one round at a time) --------------------------- */
 /* begin: sets up the roots (bce.cpp:1237-1240).  round: runs one round over all 8 planes and
  * reports how many nodes the NEXT round holds.  nodes: copies plane p's current node list as
