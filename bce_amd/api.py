@@ -86,6 +86,8 @@ SYMBOLS = [
     ("bce_hip_enum_round", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("bce_hip_enum_symbols", C.c_int, [C.c_void_p, _u32p, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("bce_hip_enum_model", C.c_int, [C.c_void_p, _u32p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("bce_hip_model_begin", C.c_int, [C.c_void_p]),
+    ("bce_hip_model_flush", C.c_int, [C.c_void_p, _u32p, _u32p, C.c_uint64, _vp, C.POINTER(C.c_uint32)]),
     ("bce_hip_scan", C.c_int, [C.c_void_p, _u8p, C.POINTER(C.c_double)]),
     ("bce_hip_decompress", C.c_int, [_u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("bce_hip_decompress_device", C.c_int, [C.c_void_p, _u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -301,6 +303,39 @@ class BCE:
         cnt = C.c_uint64()
         rf._c.check(rf._c.lib.bce_hip_enum_model(rf._c.h, out.ctypes.data, cap, C.byref(cnt)), "bce_hip_enum_model")
         return out[:cnt.value].copy()
+
+
+class Model:
+    """Test hook: K4 (the adaptive model's kernels) alone, on symbol records of the caller's choosing (bce_hip_model_begin /
+    bce_hip_model_flush).  Needs no input; counters persist from flush to flush until the next begin()."""
+
+    def __init__(self, config=None, device=0, ctx=None):
+        if config is not None and len(config) != CONFIG_BYTES:
+            raise ValueError("Config not found or wrong size.")
+        self._own = ctx is None
+        self._c = ctx or _Ctx(device)
+        self.config = None if config is None else bytes(config)
+
+    def begin(self):
+        cfg = None if self.config is None else _as_u8(self.config)
+        self._c.check(self._c.lib.bce_hip_set_config(self._c.h, cfg.ctypes.data if cfg is not None else None), "bce_hip_set_config")
+        self._c.check(self._c.lib.bce_hip_model_begin(self._c.h), "bce_hip_model_begin")
+
+    def flush(self, key_words, esc_words):
+        """-> (the raw 64-bit model records, in the records' order; the long runs the flush queued)"""
+        kw = np.ascontiguousarray(key_words, dtype=np.uint32)
+        ew = np.ascontiguousarray(esc_words, dtype=np.uint32)
+        if kw.shape != ew.shape or kw.ndim != 1:
+            raise ValueError("key and escape words: two one-dimensional arrays of one length")
+        out = np.empty(len(kw), dtype=np.uint64)
+        nq = C.c_uint32()
+        self._c.check(self._c.lib.bce_hip_model_flush(self._c.h, kw.ctypes.data, ew.ctypes.data, len(kw), out.ctypes.data, C.byref(nq)),
+                      "bce_hip_model_flush")
+        return out, nq.value
+
+    def close(self):
+        if self._own:
+            self._c.close()
 
 
 def stats(rf: RankFile) -> dict:

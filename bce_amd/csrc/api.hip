@@ -966,6 +966,67 @@ int bce_hip_enum_model(bce_hip_ctx *c, uint32_t *out, uint64_t cap_records, uint
   return BCE_HIP_OK;
 }
 
+// ---- test hook: K4 alone, on records of the caller's choosing ------------------------------------------
+int bce_hip_model_begin(bce_hip_ctx *c) {
+  if (!c) return BCE_HIP_E_ARG;
+  BCE_HIP_TRY(c, hipSetDevice(c->device));
+  c->coder->drain();
+  PhaseScope phase(c, 3);
+  c->enum_active = false;                          // (the symbol buffers of a stepped enumeration are about to be overwritten)
+  c->model_hook = false;
+  BCE_TRY(k4_prepare(c));
+  c->model_hook = true;
+  return BCE_HIP_OK;
+}
+
+// Why a record is refused (nullptr: it is valid).  Everything k4_counters and the replay index with comes from the key word, so a
+// record that passes cannot reach outside the plane's counter array, whatever the caller sends.
+static const char *model_record_fault(const PlaneCfg cfg[8], uint32_t kw, uint32_t ew) {
+  if ((kw >> 26) >= 8u) return "plane >= 8";
+  const uint32_t k = key_k(kw), p = key_plane(kw), slot = key_slot(kw), nesc = esc_n(ew);
+  if (k < 2u || k > (uint32_t)kMaxK) return "k outside 2..31";
+  if (key_sym(kw) >= k) return "sym >= k";
+  if (slot < cfg[p].ctxoff[k] || slot - cfg[p].ctxoff[k] >= (1u << (2u * cfg[p].bits[k]))) return "slot outside the k's block";
+  if (nesc > 27u) return "nesc > 27";
+  if (nesc > 0u && k < 16u) return "escape bits with k < 16";
+  if (esc_bits(ew) >> nesc) return "escape bits beyond nesc";
+  return nullptr;
+}
+
+int bce_hip_model_flush(bce_hip_ctx *c, const uint32_t *key_words, const uint32_t *esc_words, uint64_t count, uint64_t *out_records,
+                        uint32_t *long_runs) {
+  if (!c) return BCE_HIP_E_ARG;
+  if (!c->model_hook) { snprintf(c->err, sizeof c->err, "bce_hip_model_flush without bce_hip_model_begin"); return BCE_HIP_E_STATE; }
+  if (long_runs) *long_runs = 0;
+  if (count == 0) return BCE_HIP_OK;
+  if (!key_words || !esc_words || !out_records || count >= (1ull << 31)) return BCE_HIP_E_ARG;
+  for (uint64_t i = 0; i < count; ++i)
+    if (const char *why = model_record_fault(c->cfg, key_words[i], esc_words[i])) {
+      snprintf(c->err, sizeof c->err, "model record %llu (key %#x, esc %#x): %s", (unsigned long long)i, key_words[i], esc_words[i], why);
+      return BCE_HIP_E_ARG;
+    }
+  BCE_HIP_TRY(c, hipSetDevice(c->device));
+  c->coder->drain();
+  PhaseScope phase(c, 3);
+  // the counters and the device's copy of the geometry are those of bce_hip_model_begin: a decode in between uses both buffers
+  // for its own ends, so the geometry goes up again (2 KB) and the counter array is checked to be the one k4_prepare sized
+  const uint32_t need = c->stat_off[7] + c->cfg[7].stat_bytes;        // (the planes' arrays lie in order: k4_prepare)
+  if (c->stat.cap < need || c->dcfg.cap < sizeof(PlaneCfg) * 8) return BCE_HIP_E_STATE;
+  BCE_HIP_TRY(c, hipMemcpyAsync(c->dcfg.p, c->cfg, sizeof(PlaneCfg) * 8, hipMemcpyHostToDevice, c->stream));
+  // where K3 leaves them: key words in skey[0], escape words in sesc
+  BCE_TRY(ensure(c, c->skey[0], (size_t)count * 4));
+  BCE_TRY(ensure(c, c->sesc, (size_t)count * 4));
+  BCE_HIP_TRY(c, hipMemcpyAsync(c->skey[0].p, key_words, (size_t)count * 4, hipMemcpyHostToDevice, c->stream));
+  BCE_HIP_TRY(c, hipMemcpyAsync(c->sesc.p, esc_words, (size_t)count * 4, hipMemcpyHostToDevice, c->stream));
+  BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  BCE_TRY(k4_flush(c, count, c->slot[0]));
+  memcpy(out_records, c->slot[0].h_out, (size_t)count * 8);
+  uint32_t nq = 0;
+  BCE_TRY(k4_long_runs(c, count, &nq));
+  if (long_runs) *long_runs = nq;
+  return BCE_HIP_OK;
+}
+
 // ---- BCE::encode ------------------------------------------------------------------------------------
 static int encode_body(bce_hip_ctx *c);
 int bce_hip_encode(bce_hip_ctx *c) { return gate_on_error(c, bce_guarded(c, [&] { return encode_body(c); })); }

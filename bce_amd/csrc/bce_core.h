@@ -255,7 +255,9 @@ BCE_HD uint32_t out_total(uint64_t o) { return (uint32_t)((o >> 21) & 0x1FFFu); 
 BCE_HD uint32_t out_esc_sentinel(uint64_t o) { return (uint32_t)(o >> 34); }     // 1 = no escape bits
 
 // One adaptive-model step on a slot's k byte counters (bce.cpp:512-518,529,531-533), the sequential
-// definition the K4 kernel is tested against.
+// definition the K4 kernels are tested against: tests/core_emul.cpp (emul_model) loops it over a record stream,
+// tests/test_model_cpu.py checks that loop against the rule written out in Python, and tests/test_gpu_model.py
+// compares k4_model.hip with it record by record (bce_hip_model_flush), on the streams of tests/model_cases.py.
 BCE_HD uint64_t model_step(uint8_t *ctr, uint32_t k, uint32_t s, uint32_t esc_word) {
   uint32_t l = 0;
   for (uint32_t i = 0; i < s; ++i) l += ctr[i];

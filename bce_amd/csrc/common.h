@@ -212,6 +212,7 @@ struct bce_hip_ctx {
   bool crc_const_ready = false;                  // its launch-independent constants are uploaded
   bool text_loaded = false;                      // `text` holds the n bytes of the last bce_hip_load_* (bce_hip_input_crc32)
   uint32_t stat_off[8] = {0};
+  bool model_hook = false;                       // bce_hip_model_begin ran: bce_hip_model_flush may follow
 
   // pinned host staging
   void *h_ctl = nullptr, *h_runs = nullptr;
@@ -439,6 +440,7 @@ int k4_flush(bce_hip_ctx *c, uint64_t nsym, FlushSlot &slot);         // synchro
 // sort + replay + D2H into the slot, all queued: outputs are in slot.h_out once slot.ev_copy has fired.  copy_out = false
 // (estimate mode): the records stay in `sout`, the slot needs no host staging and only lends its events.
 int k4_flush_async(bce_hip_ctx *c, uint64_t nsym, FlushSlot &slot, bool copy_out = true);
+int k4_long_runs(bce_hip_ctx *c, uint64_t nsym, uint32_t *count);    // test hook: long runs queued by the flush of nsym records that has just completed
 int k4_cost_begin(bce_hip_ctx *c);                  // k4_cost.hip: the context's sums to zero
 int k4_cost_async(bce_hip_ctx *c, uint64_t nsym, FlushSlot &slot);   // behind k4_flush_async(.., false): add the flush's code lengths, per plane
 int k4_cost_end(bce_hip_ctx *c, uint64_t acc[16]);  // wait and read them: [0..7] Q24 cost sums, [8..15] record counts

@@ -389,6 +389,29 @@ int k4_prepare(bce_hip_ctx *c) {
   return BCE_HIP_OK;
 }
 
+// per-window work arrays of a flush of nsym records, carved from one buffer (k4w): histT | stateW | winfo | queue | haltW | bitsW | qcount
+struct K4Work { size_t nwin, o_hist, o_state, o_info, o_queue, o_halt, o_bits, o_qc, bytes; };
+static K4Work k4_work(uint32_t nsym) {
+  K4Work w;
+  w.nwin = ((size_t)nsym + 63) / 64;
+  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  w.o_hist = 0; w.o_state = w.o_hist + w.nwin * 32; w.o_info = w.o_state + w.nwin * 32;
+  w.o_queue = up16(w.o_info + w.nwin * 4); w.o_halt = w.o_queue + (w.nwin / 4 + 2) * 8; w.o_bits = up16(w.o_halt + w.nwin);
+  w.o_qc = up16(w.o_bits + w.nwin * 8);
+  w.bytes = w.o_qc + 16;
+  return w;
+}
+
+// Test hook (bce_hip_model_flush): the long runs k4_window_kernel queued in the flush of nsym records that has just completed.
+int k4_long_runs(bce_hip_ctx *c, uint64_t nsym, uint32_t *count) {
+  *count = 0;
+  if (nsym == 0) return BCE_HIP_OK;
+  if (nsym >= (1ull << 31)) return BCE_HIP_E_OVERFLOW;
+  const K4Work wk = k4_work((uint32_t)nsym);
+  if (c->k4w.cap < wk.bytes) return BCE_HIP_E_STATE;
+  return read_back(c, count, c->k4w.as<uint8_t>() + wk.o_qc, sizeof *count);
+}
+
 int k4_flush_async(bce_hip_ctx *c, uint64_t nsym64, FlushSlot &slot, bool copy_out) {
   if (nsym64 == 0) return BCE_HIP_OK;
   if (nsym64 >= (1ull << 31)) return BCE_HIP_E_OVERFLOW;
@@ -465,13 +488,10 @@ int k4_flush_async(bce_hip_ctx *c, uint64_t nsym64, FlushSlot &slot, bool copy_o
   hipLaunchKernelGGL(k4_iota_kernel, dim3(grid), dim3(K4_T), 0, ks, nsym, val[0]);
   int res = 0;
   BCE_TRY(radix_sort_pairs_on(c, ks, own ? c->rs_hist_k4 : c->rs_hist, key, val, nsym, kSymRunShift, kSymRunBits, &res, 10));
-  // per-window work arrays, carved from one buffer: histT | stateW | winfo | queue | haltW | qcount
-  const size_t nwin = ((size_t)nsym + 63) / 64;
-  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  const size_t o_hist = 0, o_state = o_hist + nwin * 32, o_info = o_state + nwin * 32,
-               o_queue = up16(o_info + nwin * 4), o_halt = o_queue + (nwin / 4 + 2) * 8, o_bits = up16(o_halt + nwin),
-               o_qc = up16(o_bits + nwin * 8);
-  BCE_TRY(ensure(c, c->k4w, o_qc + 16));
+  const K4Work wk = k4_work(nsym);
+  const size_t nwin = wk.nwin, o_hist = wk.o_hist, o_state = wk.o_state, o_info = wk.o_info, o_queue = wk.o_queue, o_halt = wk.o_halt,
+               o_bits = wk.o_bits, o_qc = wk.o_qc;
+  BCE_TRY(ensure(c, c->k4w, wk.bytes));
   uint8_t *wbuf = c->k4w.as<uint8_t>();
   K4Args a;
   a.keys = key[res]; a.vals = val[res];

@@ -201,6 +201,21 @@ int bce_hip_enum_symbols(bce_hip_ctx *ctx, uint32_t *out, uint64_t cap_records, 
 /* run K4 on the symbols emitted so far: out[3*i+0..2] = cum, freq, total per record (same order) */
 int bce_hip_enum_model(bce_hip_ctx *ctx, uint32_t *out, uint64_t cap_records, uint64_t *count);
 
+/* Test hook: K4 (k4_model.hip) alone, on records of the caller's choosing instead of those K3 happens to emit.
+ * begin: the model of the config in force (bce_hip_set_config) with all counters zero; needs no loaded input and ends a stepped
+ * enumeration of the context.  flush: `count` symbol records in stream order -- key_words[i] / esc_words[i] as bce_core.h's
+ * pack_symbol lays them out: key [4:0] sym, [9:5] k, [25:10] slot, [28:26] plane; esc [26:0] escape bits, [31:27] nesc -- go where
+ * K3 would have left them and through the flush bce_hip_enum_model runs; out_records[i] = the raw 64-bit model record of record i
+ * (pack_model_out: cum, freq - 1, total, escape bits with their sentinel), *long_runs (may be NULL) = the runs of 256 and more
+ * records of one slot that this flush handed to the long-run kernels.  The counters stay for the next flush; count == 0 does
+ * nothing and succeeds.  Every record is checked on the host before any device work: plane < 8, 2 <= k <= 31, sym < k, the slot
+ * inside [ctxoff[k], ctxoff[k] + 4^bits[k]) of its plane's config row, nesc <= 27, nesc > 0 only with k >= 16, no escape bit at
+ * or above nesc; one that fails any of them: BCE_HIP_E_ARG, nothing uploaded, the counters untouched, the context usable.
+ * Without a begin: BCE_HIP_E_STATE. */
+int bce_hip_model_begin(bce_hip_ctx *ctx);
+int bce_hip_model_flush(bce_hip_ctx *ctx, const uint32_t *key_words, const uint32_t *esc_words, uint64_t count,
+                        uint64_t *out_records, uint32_t *long_runs);
+
 /* ---- config scan (SURVEY section 8f "next #2") ---------------------------------------------------------------- */
 /* main() -s branch (bce.cpp:1384-1402): BCE<ScanCoder<31>, noop>::encode + ScanCoder::save_config
  * (bce.cpp:726-834).  Call after bce_hip_build_planes: the enumeration runs on the GPU, the eight ScanCoders and

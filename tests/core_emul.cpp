@@ -130,6 +130,32 @@ extern "C" void emul_context(const uint8_t *row32, const uint32_t *kccs, uint32_
 }
 extern "C" uint32_t emul_small_quotient(uint32_t a, uint32_t b) { return small_quotient(a, b); }
 
+// K4's sequential definition: model_step (bce_core.h) over `count` records in stream order -- key / escape words as pack_symbol
+// lays them out -- on counter arrays laid out by plane_cfg_init: plane p's stat_bytes counters follow plane p - 1's in `state`
+// (emul_model_state_bytes of them, zero at the start; the caller keeps them between calls, as K4 keeps its counters between
+// flushes).  out[i] = the raw pack_model_out word.  Returns -1, or 1 + the index of the first record that does not fit the
+// config (nothing is written for it or behind it).
+extern "C" uint64_t emul_model_state_bytes(const uint8_t *config288) {
+  uint64_t total = 0;
+  for (int p = 0; p < 8; ++p) { PlaneCfg cfg; plane_cfg_init(cfg, config288 + 32 * p); total += cfg.stat_bytes; }
+  return total;
+}
+extern "C" int64_t emul_model(const uint8_t *config288, const uint32_t *key_words, const uint32_t *esc_words, uint64_t count,
+                              uint8_t *state, uint64_t state_bytes, uint64_t *out) {
+  PlaneCfg cfg[8];
+  uint64_t base[8], total = 0;
+  for (int p = 0; p < 8; ++p) { plane_cfg_init(cfg[p], config288 + 32 * p); base[p] = total; total += cfg[p].stat_bytes; }
+  if (state_bytes != total) return -1;
+  for (uint64_t i = 0; i < count; ++i) {
+    const uint32_t kw = key_words[i], k = key_k(kw), slot = key_slot(kw);
+    if ((kw >> 26) >= 8u || k < 2u || k > (uint32_t)kMaxK || key_sym(kw) >= k) return (int64_t)i + 1;
+    const PlaneCfg &c = cfg[key_plane(kw)];
+    if (slot < c.ctxoff[k] || slot - c.ctxoff[k] >= (1u << (2u * c.bits[k]))) return (int64_t)i + 1;
+    out[i] = model_step(state + base[key_plane(kw)] + c.off[k] + (uint64_t)(slot - c.ctxoff[k]) * k, k, key_sym(kw), esc_words[i]);
+  }
+  return 0;
+}
+
 // exhaustive-ish check of the reciprocal division used by the host coder: returns the number of mismatches
 extern "C" uint64_t emul_check_recip(uint64_t seed, uint64_t samples_per_divisor) {
   uint64_t bad = 0, st = seed ? seed : 1;
