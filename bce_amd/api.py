@@ -104,6 +104,9 @@ SYMBOLS = [
     ("bce_hip_estimate_host", C.c_int, [C.c_void_p, _u8p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)]),
     ("bce_hip_estimate_device", C.c_int, [C.c_void_p, _vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)]),
     ("bce_hip_cost_q24", C.c_uint32, [C.c_uint32, C.c_uint32]),
+    ("bce_hip_sort_pairs_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("bce_hip_sort_wide_device", C.c_int, [C.c_void_p, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("bce_hip_compare_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_size_t, C.POINTER(C.c_uint64)]),
     ("bce_hip_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     ("bce_hip_synth_text", None, [C.c_uint64, _u8p, C.c_size_t]),
     ("bce_hip_synth_rand", None, [C.c_uint64, _u8p, C.c_size_t]),
@@ -660,6 +663,28 @@ def verify(archive, data, device=0, ctx=None):
     finally:
         if own:
             c.close()
+
+
+def compare_device(ptr_a, ptr_b, n, ctx):
+    """Test hook (bce_hip_compare_device): the first index at which the `n` bytes at device pointers `ptr_a` and `ptr_b`
+    differ, None when they are equal.  Stream rule: as decompress_to_device."""
+    fd = C.c_uint64(0)
+    ctx.check(ctx.lib.bce_hip_compare_device(ctx.h, None if ptr_a is None else int(ptr_a), None if ptr_b is None else int(ptr_b),
+                                             int(n), C.byref(fd)), "bce_hip_compare_device")
+    return None if fd.value == _NO_DIFF else fd.value
+
+
+def sort_pairs_device(ptr_key, ptr_val, n, first_bit, bits, max_digit_bits, ctx):
+    """Test hook (bce_hip_sort_pairs_device): the stable radix sort of `n` (u32 key, u32 value) pairs in device memory, in
+    place, on key bits [first_bit, first_bit + bits).  Stream rule: as decompress_to_device."""
+    ctx.check(ctx.lib.bce_hip_sort_pairs_device(ctx.h, int(ptr_key), int(ptr_val), int(n), int(first_bit), int(bits), int(max_digit_bits)),
+              "bce_hip_sort_pairs_device")
+
+
+def sort_wide_device(ptr_lo, ptr_hi, ptr_val, n, bits, max_digit_bits, ctx):
+    """Test hook (bce_hip_sort_wide_device): the same with 64-bit keys in two u32 arrays (hi:lo), on key bits [0, bits)."""
+    ctx.check(ctx.lib.bce_hip_sort_wide_device(ctx.h, int(ptr_lo), int(ptr_hi), int(ptr_val), int(n), int(bits), int(max_digit_bits)),
+              "bce_hip_sort_wide_device")
 
 
 def crc32(data, crc=0) -> int:

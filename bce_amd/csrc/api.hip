@@ -699,7 +699,7 @@ void bce_hip_destroy(bce_hip_ctx *c) {
   DevBuf *bufs[] = {&c->text, &c->bwt, &c->sa[0], &c->sa[1], &c->key[0], &c->key[1], &c->rank, &c->k2, &c->nrk, &c->act[0], &c->act[1], &c->khi[0], &c->khi[1], &c->dl[0], &c->dl[1], &c->dl[2], &c->dl[3], &c->kflag, &c->actv[0], &c->actv[1],
                     &c->rs_hist, &c->blk, &c->ptmp[0], &c->ptmp[1], &c->gran, &c->nlist[0], &c->nlist[1], &c->ctl, &c->tilecnt,
                     &c->tileoff, &c->runs, &c->smwords, &c->k3tw, &c->k3grp, &c->truns, &c->skey[0], &c->skey[1], &c->sval[0], &c->sval[1], &c->sout,
-                    &c->sesc, &c->stat, &c->crc_tab, &c->dcfg, &c->k4w, &c->scanrec, &c->dfs, &c->skey_alt, &c->sesc_alt, &c->rs_hist_k4, &c->cost_acc, &c->cost_runs};
+                    &c->sesc, &c->stat, &c->crc_tab, &c->dcfg, &c->k4w, &c->scanrec, &c->dfs, &c->skey_alt, &c->sesc_alt, &c->rs_hist_k4, &c->cost_acc, &c->cost_runs, &c->cmp_res, &c->hook[0], &c->hook[1], &c->hook[2]};
   for (DevBuf *b : bufs) release(*b);
   for (auto &par : c->dlist) for (DevBuf &b : par) release(b);
   k4_prepin_join(c, true);
@@ -1340,6 +1340,65 @@ int bce_hip_input_crc32(bce_hip_ctx *c, uint32_t *crc) {
     uint32_t v = 0;
     BCE_TRY(kd_crc32(c, c->text.as<uint8_t>(), c->n, &v));
     *crc = v;
+    return BCE_HIP_OK;
+  });
+}
+
+// ---- test hooks: the shared primitives alone (radix_sort.hip, kd_compare.hip) ---------------------------------
+// The caller's arrays are one half of the sort's ping-pong, c->hook the other; a result that lands in the context's half is
+// copied back.  Phase 0: nothing of the context is given back to make room, and nothing but the sorter's histograms, the hook
+// buffers and the comparison's result word is written.
+int bce_hip_sort_pairs_device(bce_hip_ctx *c, void *d_key, void *d_val, uint32_t n, uint32_t first_bit, uint32_t bits, uint32_t max_digit_bits) {
+  if (!c || (uint64_t)first_bit + bits > 32 || (n && (!d_key || !d_val))) return BCE_HIP_E_ARG;
+  if (n <= 1) return BCE_HIP_OK;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)n * 4;
+    BCE_TRY(ensure(c, c->hook[0], bytes));
+    BCE_TRY(ensure(c, c->hook[1], bytes));
+    uint32_t *key[2] = {static_cast<uint32_t *>(d_key), c->hook[0].as<uint32_t>()};
+    uint32_t *val[2] = {static_cast<uint32_t *>(d_val), c->hook[1].as<uint32_t>()};
+    int res = 0;
+    BCE_TRY(radix_sort_pairs(c, key, val, n, first_bit, bits, &res, max_digit_bits));
+    if (res) {
+      BCE_HIP_TRY(c, hipMemcpyAsync(d_key, key[1], bytes, hipMemcpyDeviceToDevice, c->stream));
+      BCE_HIP_TRY(c, hipMemcpyAsync(d_val, val[1], bytes, hipMemcpyDeviceToDevice, c->stream));
+    }
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return BCE_HIP_OK;
+  });
+}
+
+int bce_hip_sort_wide_device(bce_hip_ctx *c, void *d_lo, void *d_hi, void *d_val, uint32_t n, uint32_t bits, uint32_t max_digit_bits) {
+  if (!c || bits > 64 || (n && (!d_lo || !d_hi || !d_val))) return BCE_HIP_E_ARG;
+  if (n <= 1) return BCE_HIP_OK;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)n * 4;
+    for (DevBuf &b : c->hook) BCE_TRY(ensure(c, b, bytes));
+    uint32_t *lo[2] = {static_cast<uint32_t *>(d_lo), c->hook[0].as<uint32_t>()};
+    uint32_t *hi[2] = {static_cast<uint32_t *>(d_hi), c->hook[1].as<uint32_t>()};
+    uint32_t *val[2] = {static_cast<uint32_t *>(d_val), c->hook[2].as<uint32_t>()};
+    int res = 0;
+    BCE_TRY(radix_sort_wide(c, lo, hi, val, n, bits, &res, max_digit_bits));
+    if (res) {
+      BCE_HIP_TRY(c, hipMemcpyAsync(d_lo, lo[1], bytes, hipMemcpyDeviceToDevice, c->stream));
+      BCE_HIP_TRY(c, hipMemcpyAsync(d_hi, hi[1], bytes, hipMemcpyDeviceToDevice, c->stream));
+      BCE_HIP_TRY(c, hipMemcpyAsync(d_val, val[1], bytes, hipMemcpyDeviceToDevice, c->stream));
+    }
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return BCE_HIP_OK;
+  });
+}
+
+int bce_hip_compare_device(bce_hip_ctx *c, const void *d_a, const void *d_b, size_t n, uint64_t *first_diff) {
+  if (!c || !first_diff || (n && (!d_a || !d_b))) return BCE_HIP_E_ARG;
+  if (n == 0) { *first_diff = UINT64_MAX; return BCE_HIP_OK; }
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    uint64_t v = UINT64_MAX;
+    BCE_TRY(kd_compare(c, static_cast<const uint8_t *>(d_a), static_cast<const uint8_t *>(d_b), n, &v));
+    *first_diff = v;
     return BCE_HIP_OK;
   });
 }

@@ -209,6 +209,8 @@ struct bce_hip_ctx {
   bce::DevBuf cost_acc, cost_runs;               // k4_cost.hip: eight cost sums + eight record counts; the run table of the flush being summed
   bce::DevBuf crc_tab;                           // kd_crc32.hip: the step tables of a launch of crc_tab_grid workgroups, its constants, its result word
   uint32_t crc_tab_grid = 0;                     // 0: no step tables uploaded
+  bce::DevBuf cmp_res;                           // kd_compare.hip: its result word (a buffer of its own, as kd_crc32.hip's: no stage's scratch is touched)
+  bce::DevBuf hook[3];                           // test hooks bce_hip_sort_pairs_device / _wide_device: the second halves of the sorts' ping-pong
   bool crc_const_ready = false;                  // its launch-independent constants are uploaded
   bool text_loaded = false;                      // `text` holds the n bytes of the last bce_hip_load_* (bce_hip_input_crc32)
   uint32_t stat_off[8] = {0};
@@ -446,7 +448,7 @@ int k4_cost_async(bce_hip_ctx *c, uint64_t nsym, FlushSlot &slot);   // behind k
 int k4_cost_end(bce_hip_ctx *c, uint64_t acc[16]);  // wait and read them: [0..7] Q24 cost sums, [8..15] record counts
 
 // radix sort (radix_sort.hip): stable LSD sort of (key,val) u32 pairs on key bits [first_bit, first_bit+bits).
-// Result is left in key[res]/val[res]; returns res (0 or 1) through *res.
+// Result is left in key[res]/val[res]; returns res (0 or 1) through *res.  first_bit + bits > 32: BCE_HIP_E_ARG.
 int radix_sort_pairs(bce_hip_ctx *c, uint32_t *key[2], uint32_t *val[2], uint32_t n, uint32_t first_bit, uint32_t bits, int *res,
                      uint32_t max_digit_bits = 8);
 int radix_sort_pairs_on(bce_hip_ctx *c, hipStream_t stream, DevBuf &hist, uint32_t *key[2], uint32_t *val[2], uint32_t n,

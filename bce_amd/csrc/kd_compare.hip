@@ -1,4 +1,4 @@
-// kd_compare.hip -- first differing byte of two device buffers (bce_hip_verify_device / _host, `bce -t`).
+// kd_compare.hip -- first differing byte of two device buffers (bce_hip_verify_device / _host, `bce -t`; alone: bce_hip_compare_device).
 //
 // The decoder leaves the text in HBM (kd_decode.hip); "does this archive decode to these bytes" is then one pass over
 // 2 m bytes that never leaves the device.  Memory-bound: every byte of both buffers is read once, nothing is written but
@@ -92,8 +92,10 @@ __global__ __launch_bounds__(CMP_T) void compare_kernel(const uint8_t *__restric
 int kd_compare(bce_hip_ctx *c, const uint8_t *a, const uint8_t *b, uint64_t m, uint64_t *first_diff) {
   *first_diff = kNoDiff;
   if (m == 0) return BCE_HIP_OK;
-  BCE_TRY(ensure(c, c->stat, 64));
-  unsigned long long *d_res = reinterpret_cast<unsigned long long *>(c->stat.as<uint8_t>() + 32);   // (behind the decoder's eight zero counts)
+  // (the result word lies in a buffer of its own: a call between two stages of a compression or between two model flushes --
+  //  bce_hip_compare_device is valid there -- must not touch the words other stages keep in c->stat, K4's model counters among them)
+  BCE_TRY(ensure(c, c->cmp_res, 8));
+  unsigned long long *d_res = c->cmp_res.as<unsigned long long>();
   BCE_HIP_TRY(c, hipMemsetAsync(d_res, 0xFF, 8, c->stream));
   const uint32_t head = (uint32_t)std::min<uint64_t>(m, (16u - (uint32_t)(reinterpret_cast<uintptr_t>(a) & 15u)) & 15u);
   const uint64_t units = (m - head) / 16;

@@ -458,6 +458,10 @@ int radix_sort_pairs(bce_hip_ctx *c, uint32_t *key[2], uint32_t *val[2], uint32_
 int radix_sort_pairs_on(bce_hip_ctx *c, hipStream_t stream, DevBuf &hbuf, uint32_t *key[2], uint32_t *val[2], uint32_t n,
                         uint32_t first_bit, uint32_t bits, int *res, uint32_t max_digit_bits) {
   *res = 0;
+  if ((uint64_t)first_bit + bits > 32) {         // (a shift of 32 and more is undefined in the kernels; no caller's window reaches it)
+    snprintf(c->err, sizeof c->err, "radix sort: key bits [%u, %u + %u) do not lie inside 32", first_bit, first_bit, bits);
+    return BCE_HIP_E_ARG;
+  }
   if (n <= 1 || bits == 0) return BCE_HIP_OK;
   if (max_digit_bits < 1 || max_digit_bits > (uint32_t)RS_MAXBITS) max_digit_bits = 8;
   const RsPlan pl = rs_plan(n);

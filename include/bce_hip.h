@@ -281,6 +281,27 @@ int bce_hip_decode_crc32(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, s
 int bce_hip_decompress_device_crc32(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, uint8_t *out, size_t cap, size_t *out_len,
                                     uint32_t *crc);
 
+/* ---- test hooks: the device primitives every stage rests on, alone (tests/test_gpu_sort.py, tests/test_gpu_compare.py) ----
+ * Stream rule of bce_hip_crc32_device for all three: the work runs on the context's stream and is complete on return; the caller's
+ * memory (device memory of the context's device) must be ready when the call is made.  Valid in any state of the context, between
+ * the stages of a compression and between two bce_hip_model_flush calls included: they write the caller's arrays, the sorter's
+ * histograms and buffers that only these hooks use, nothing that a stage keeps. */
+/* Test hook: radix_sort.hip's radix_sort_pairs -- the sort K1, the enumeration's tail, K4 and the decoder call -- on n (u32 key,
+ * u32 value) pairs of the caller's: stable LSD sort on key bits [first_bit, first_bit + bits), in place (the context holds the
+ * other halves of the ping-pong and copies the result back when it lands there); the key bits outside the window travel with their
+ * pair.  max_digit_bits = the widest digit of a pass, 1..10 (anything else counts as 8), as the callers pass it.
+ * first_bit + bits > 32, or n > 0 with a null pointer: BCE_HIP_E_ARG; n <= 1 or bits == 0: success, nothing touched. */
+int bce_hip_sort_pairs_device(bce_hip_ctx *ctx, void *d_key, void *d_val, uint32_t n, uint32_t first_bit, uint32_t bits,
+                              uint32_t max_digit_bits);
+/* Test hook: the same for radix_sort_wide (K1's first sort): 64-bit keys in two u32 arrays (hi:lo), sorted on key bits [0, bits).
+ * bits > 64, or n > 0 with a null pointer: BCE_HIP_E_ARG. */
+int bce_hip_sort_wide_device(bce_hip_ctx *ctx, void *d_lo, void *d_hi, void *d_val, uint32_t n, uint32_t bits,
+                             uint32_t max_digit_bits);
+/* Test hook: kd_compare.hip, the comparison behind bce_hip_verify_device / _host, on two buffers of the caller's, any alignment
+ * each: *first_diff = the smallest i < n with a[i] != b[i], UINT64_MAX when there is none (n == 0 included: pointers ignored).
+ * Reads [0, n) of both and nothing else.  A null ctx or first_diff, n > 0 with a null buffer: BCE_HIP_E_ARG. */
+int bce_hip_compare_device(bce_hip_ctx *ctx, const void *d_a, const void *d_b, size_t n, uint64_t *first_diff);
+
 /* ---- statistics of the last bce_hip_encode / bce_hip_compress ------------------------------------ */
 typedef struct bce_hip_stats {
   uint64_t n;            /* input bytes */
