@@ -107,6 +107,9 @@ SYMBOLS = [
     ("bce_hip_sort_pairs_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("bce_hip_sort_wide_device", C.c_int, [C.c_void_p, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("bce_hip_compare_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_size_t, C.POINTER(C.c_uint64)]),
+    ("bce_hip_count", C.c_int, [C.c_void_p, _u8p, _vp, C.c_uint32, _vp]),
+    ("bce_hip_count_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, _vp]),
+    ("bce_hip_input_bytes", C.c_int, [C.c_void_p, C.c_uint64, C.c_size_t, _u8p]),
     ("bce_hip_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     ("bce_hip_synth_text", None, [C.c_uint64, _u8p, C.c_size_t]),
     ("bce_hip_synth_rand", None, [C.c_uint64, _u8p, C.c_size_t]),
@@ -146,6 +149,37 @@ def _as_u8(data):
     return np.frombuffer(bytes(data), dtype=np.uint8)
 
 
+def _is_one_pattern(patterns):
+    return isinstance(patterns, (bytes, bytearray, memoryview, np.ndarray))
+
+
+def seam_count(head, tail, pattern) -> int:
+    """The occurrences of `pattern` (m bytes) in a circular text that straddle its end: those of the seam tail + head, where
+    `tail` is the text's last m - 1 bytes and `head` its first m - 1 (overlapping matches counted).  Every match inside the
+    2 (m - 1) bytes of the seam crosses their middle.  A cyclic count minus this is the linear count, for m <= n."""
+    seam, pattern = bytes(tail) + bytes(head), bytes(pattern)
+    found, at = 0, seam.find(pattern)
+    while at >= 0:
+        found += 1
+        at = seam.find(pattern, at + 1)
+    return found
+
+
+def linear_counts(cyclic, patterns, n, ends):
+    """Cyclic counts -> the counts an overlapping `bytes` scan of the n-byte text gives.  ends(k) -> (the text's first k bytes,
+    its last k), k <= n.  A pattern longer than the text occurs nowhere; otherwise the matches across the seam come off."""
+    out = np.array(cyclic, dtype=np.uint64)
+    longest = max([len(p) for p in patterns if len(p) <= n] + [1])
+    head, tail = ends(longest - 1)
+    for i, p in enumerate(patterns):
+        m = len(p)
+        if m > n:
+            out[i] = 0
+        elif m > 1:
+            out[i] -= seam_count(head[:m - 1], tail[len(tail) - (m - 1):], p)
+    return out
+
+
 class _Ctx:
     def __init__(self, device=0):
         self.lib = load_library()
@@ -181,6 +215,9 @@ class RankFile:
         self._c = ctx or _Ctx(device)
         lib = self._c.lib
         self._status = 0
+        self._text = None                        # the host input, when there is one: count() cuts the text's two ends from it
+        self._ends = (b"", b"")                  # of an input that came from device memory: its first and last bytes, as far as count() has fetched them
+        self._has_text = bwt is None
         if bwt is not None:                      # test hook: inject a BWT, skip K1
             a = _as_u8(bwt)
             self._c.check(lib.bce_hip_set_bwt(self._c.h, a.ctypes.data, len(a), int(offset)), "bce_hip_set_bwt")
@@ -196,6 +233,7 @@ class RankFile:
                     raise BceError(-1, "RankFile", "empty input")
                 self._c.check(lib.bce_hip_load_host(self._c.h, a.ctypes.data, len(a)), "bce_hip_load_host")
                 self._n = len(a)
+                self._text = a
             off = C.c_uint32()
             self._c.check(lib.bce_hip_bwt(self._c.h, C.byref(off)), "bce_hip_bwt")
             self._offset = off.value
@@ -229,6 +267,49 @@ class RankFile:
         out = np.empty(len(idx), dtype=np.uint32)
         self._c.check(self._c.lib.bce_hip_rank1(self._c.h, plane, idx.ctypes.data, len(idx), out.ctypes.data), "bce_hip_rank1")
         return out
+
+    def _text_ends(self, k):
+        """(the first k bytes of the text, its last k), k <= n: from the host input, or 2 k bytes fetched from the context's copy."""
+        if self._text is not None:
+            return self._text[:k].tobytes(), self._text[self._n - k:].tobytes()
+        if k > len(self._ends[0]):
+            head, tail = np.empty(k, dtype=np.uint8), np.empty(k, dtype=np.uint8)
+            self._c.check(self._c.lib.bce_hip_input_bytes(self._c.h, 0, k, head.ctypes.data), "bce_hip_input_bytes")
+            self._c.check(self._c.lib.bce_hip_input_bytes(self._c.h, self._n - k, k, tail.ctypes.data), "bce_hip_input_bytes")
+            self._ends = (head.tobytes(), tail.tobytes())
+        head, tail = self._ends
+        return head[:k], tail[len(tail) - k:]
+
+    def count(self, patterns, cyclic=False):
+        """How often byte strings occur in the text, counted on the GPU from the planes (bce_hip_count: backward search, the text
+        is not read).  `patterns`: one bytes-like -> an int; a sequence of them -> a numpy uint64 array.
+        cyclic=False: the count an overlapping scan of the text gives (what bytes.count would, if it counted overlapping
+        matches); 0 for a pattern longer than the text; an empty pattern raises ValueError.
+        cyclic=True: the matches in the circular text, those that run across its end included -- defined for every length (the
+        empty pattern: n).  The only count a RankFile built from an injected BWT can give: it has no text for the correction."""
+        one = _is_one_pattern(patterns)
+        pats = [_as_u8(patterns)] if one else [_as_u8(p) for p in patterns]
+        if not cyclic:
+            if not self._has_text:
+                raise ValueError("a RankFile built from an injected BWT holds no text: only cyclic=True counts are defined")
+            if any(len(p) == 0 for p in pats):
+                raise ValueError("an empty pattern has no linear count (cyclic=True: n)")
+        out = np.zeros(len(pats), dtype=np.uint64)
+        if pats:
+            offsets = np.zeros(len(pats) + 1, dtype=np.uint64)
+            offsets[1:] = np.cumsum([len(p) for p in pats], dtype=np.uint64)
+            flat = np.concatenate(pats) if int(offsets[-1]) else np.zeros(1, dtype=np.uint8)
+            self._c.check(self._c.lib.bce_hip_count(self._c.h, flat.ctypes.data, offsets.ctypes.data, len(pats), out.ctypes.data), "bce_hip_count")
+            if not cyclic:
+                out = linear_counts(out, pats, self._n, self._text_ends)
+        return int(out[0]) if one else out
+
+    def count_device(self, patterns_ptr, offsets_ptr, npat, counts_ptr):
+        """bce_hip_count_device: the cyclic counts of `npat` patterns that lie concatenated in device memory (int pointers: the
+        bytes, npat + 1 uint64 offsets, npat uint64 counts out).  Stream rule: as decompress_to_device."""
+        self._c.check(self._c.lib.bce_hip_count_device(self._c.h, None if patterns_ptr is None else int(patterns_ptr),
+                                                       None if offsets_ptr is None else int(offsets_ptr), int(npat),
+                                                       None if counts_ptr is None else int(counts_ptr)), "bce_hip_count_device")
 
     def close(self):
         self._c.close()
@@ -359,6 +440,17 @@ def compress(data, config=None, device=0, ctx=None) -> bytes:
     rf = RankFile(data, device=device, ctx=ctx)
     try:
         return BCE(config).encode(rf)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def count(data, patterns, device=0, ctx=None):
+    """How often `patterns` (one bytes-like -> int, a sequence -> numpy uint64 array) occur in `data`, overlapping matches
+    counted: K1 and K2 index the data on the GPU, RankFile.count asks the index."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.count(patterns)
     finally:
         if ctx is None:
             rf.close()

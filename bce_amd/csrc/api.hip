@@ -699,7 +699,7 @@ void bce_hip_destroy(bce_hip_ctx *c) {
   DevBuf *bufs[] = {&c->text, &c->bwt, &c->sa[0], &c->sa[1], &c->key[0], &c->key[1], &c->rank, &c->k2, &c->nrk, &c->act[0], &c->act[1], &c->khi[0], &c->khi[1], &c->dl[0], &c->dl[1], &c->dl[2], &c->dl[3], &c->kflag, &c->actv[0], &c->actv[1],
                     &c->rs_hist, &c->blk, &c->ptmp[0], &c->ptmp[1], &c->gran, &c->nlist[0], &c->nlist[1], &c->ctl, &c->tilecnt,
                     &c->tileoff, &c->runs, &c->smwords, &c->k3tw, &c->k3grp, &c->truns, &c->skey[0], &c->skey[1], &c->sval[0], &c->sval[1], &c->sout,
-                    &c->sesc, &c->stat, &c->crc_tab, &c->dcfg, &c->k4w, &c->scanrec, &c->dfs, &c->skey_alt, &c->sesc_alt, &c->rs_hist_k4, &c->cost_acc, &c->cost_runs, &c->cmp_res, &c->hook[0], &c->hook[1], &c->hook[2]};
+                    &c->sesc, &c->stat, &c->crc_tab, &c->dcfg, &c->k4w, &c->scanrec, &c->dfs, &c->skey_alt, &c->sesc_alt, &c->rs_hist_k4, &c->cost_acc, &c->cost_runs, &c->cmp_res, &c->cnt_res, &c->cnt_pat, &c->cnt_off, &c->cnt_out, &c->hook[0], &c->hook[1], &c->hook[2]};
   for (DevBuf *b : bufs) release(*b);
   for (auto &par : c->dlist) for (DevBuf &b : par) release(b);
   k4_prepin_join(c, true);
@@ -1401,6 +1401,63 @@ int bce_hip_compare_device(bce_hip_ctx *c, const void *d_a, const void *d_b, siz
     *first_diff = v;
     return BCE_HIP_OK;
   });
+}
+
+// ---- pattern counts from the planes (kd_count.hip) ---------------------------------------------------------
+// Phase 3, as bce_hip_rank1: the planes are read, so what an allocation may give back is what an enumeration beside them would.
+// Nothing a stage keeps is written: the staging buffers and the flag word are the count's own.
+static int count_state(bce_hip_ctx *c) {
+  if (c->stage >= 3) return BCE_HIP_OK;
+  snprintf(c->err, sizeof c->err, "count: the context holds no planes (stage %d; bce_hip_build_planes first)", c->stage);
+  return BCE_HIP_E_STATE;
+}
+
+int bce_hip_count(bce_hip_ctx *c, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint64_t *counts) {
+  if (!c) return BCE_HIP_E_ARG;
+  if (npat == 0) return BCE_HIP_OK;
+  BCE_TRY(count_state(c));
+  if (!offsets || !counts) return BCE_HIP_E_ARG;
+  for (uint32_t p = 0; p < npat; ++p)
+    if (offsets[p + 1] < offsets[p]) { snprintf(c->err, sizeof c->err, "count: pattern offsets decrease at %u", p); return BCE_HIP_E_ARG; }
+  const uint64_t bytes = offsets[npat];
+  if (bytes && !patterns) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope phase(c, 3);
+    const size_t off_bytes = ((size_t)npat + 1) * 8, out_bytes = (size_t)npat * 8;
+    BCE_TRY(ensure(c, c->cnt_pat, bytes ? (size_t)bytes : 1));
+    BCE_TRY(ensure(c, c->cnt_off, off_bytes));
+    BCE_TRY(ensure(c, c->cnt_out, out_bytes));
+    if (bytes) BCE_HIP_TRY(c, hipMemcpyAsync(c->cnt_pat.p, patterns, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+    BCE_HIP_TRY(c, hipMemcpyAsync(c->cnt_off.p, offsets, off_bytes, hipMemcpyHostToDevice, c->stream));
+    BCE_TRY(kd_count(c, c->cnt_pat.as<uint8_t>(), c->cnt_off.as<uint64_t>(), npat, c->cnt_out.as<uint64_t>()));
+    BCE_HIP_TRY(c, hipMemcpyAsync(counts, c->cnt_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return BCE_HIP_OK;
+  });
+}
+
+int bce_hip_count_device(bce_hip_ctx *c, const void *d_patterns, const void *d_offsets, uint32_t npat, void *d_counts) {
+  if (!c) return BCE_HIP_E_ARG;
+  if (npat == 0) return BCE_HIP_OK;
+  BCE_TRY(count_state(c));
+  if (!d_patterns || !d_offsets || !d_counts) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope phase(c, 3);
+    return kd_count(c, static_cast<const uint8_t *>(d_patterns), static_cast<const uint64_t *>(d_offsets), npat, static_cast<uint64_t *>(d_counts));
+  });
+}
+
+int bce_hip_input_bytes(bce_hip_ctx *c, uint64_t pos, size_t len, uint8_t *out) {
+  if (!c || (len && !out)) return BCE_HIP_E_ARG;
+  if (!c->text_loaded || c->stage < 1) { snprintf(c->err, sizeof c->err, "no loaded input in this context"); return BCE_HIP_E_STATE; }
+  if (pos > c->n || len > c->n - pos) return BCE_HIP_E_ARG;
+  if (len == 0) return BCE_HIP_OK;
+  BCE_HIP_TRY(c, hipSetDevice(c->device));
+  BCE_HIP_TRY(c, hipMemcpyAsync(out, c->text.as<uint8_t>() + pos, len, hipMemcpyDeviceToHost, c->stream));
+  BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return BCE_HIP_OK;
 }
 
 int bce_hip_get_stats(const bce_hip_ctx *c, bce_hip_stats *out) {

@@ -210,6 +210,8 @@ struct bce_hip_ctx {
   bce::DevBuf crc_tab;                           // kd_crc32.hip: the step tables of a launch of crc_tab_grid workgroups, its constants, its result word
   uint32_t crc_tab_grid = 0;                     // 0: no step tables uploaded
   bce::DevBuf cmp_res;                           // kd_compare.hip: its result word (a buffer of its own, as kd_crc32.hip's: no stage's scratch is touched)
+  bce::DevBuf cnt_res;                           // kd_count.hip: its flag word (a buffer of its own, as cmp_res)
+  bce::DevBuf cnt_pat, cnt_off, cnt_out;         // bce_hip_count: the patterns, their offsets and the counts of a call with host buffers, staged (grow-only)
   bce::DevBuf hook[3];                           // test hooks bce_hip_sort_pairs_device / _wide_device: the second halves of the sorts' ping-pong
   bool crc_const_ready = false;                  // its launch-independent constants are uploaded
   bool text_loaded = false;                      // `text` holds the n bytes of the last bce_hip_load_* (bce_hip_input_crc32)
@@ -416,6 +418,8 @@ int k1_divbwt(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n
 int kd_inverse_bw_transform(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n, uint32_t idx);   // kd_decode.hip
 int kd_compare(bce_hip_ctx *c, const uint8_t *a, const uint8_t *b, uint64_t m, uint64_t *first_diff);   // kd_compare.hip: first differing byte of two device buffers
 int kd_crc32(bce_hip_ctx *c, const uint8_t *d, uint64_t n, uint32_t *crc);   // kd_crc32.hip: CRC-32 (zlib's) of a device buffer
+// kd_count.hip: d_out[p] = occurrences of d_pat[d_off[p], d_off[p + 1]) in the circular text of the context's planes (device arrays)
+int kd_count(bce_hip_ctx *c, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, uint64_t *d_out);
 int k2_build_planes(bce_hip_ctx *c);                // k2_planes.hip
 int k2_get_plane_bits(bce_hip_ctx *c, int plane, uint8_t *out);
 int k2_rank1(bce_hip_ctx *c, int plane, const uint32_t *idx, uint32_t count, uint32_t *out);

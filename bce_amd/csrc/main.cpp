@@ -3,6 +3,8 @@
 //   bce -t file archive.bce                 (extension) decode on the GPU and compare with "file" there; writes nothing
 //   bce -CN archive.bcem file [config.bcc]  (extension) as -cN, N = 1..64, with the CRC-32 of every block's text in the container
 //   bce -t archive.bcem                     (extension) decode such a container on the GPU and test it against its own CRC-32s
+//   bce -g PATTERN file                     (extension) how often the bytes of PATTERN occur in "file", counted on the GPU from its BWT planes
+//   bce -gd PATTERN archive                 (extension) the same in what an archive or container holds
 // Banner, usage text, summary line, argument detection and exit codes follow the reference
 // (banner :1377-1379, -c :1403-1427, -d :1428-1472, usage :1473-1483).  -d uses the GPU-assisted decoder (kd_decode.hip), -ds the host decoder (decoder.cpp);
 // -s runs the enumeration on the GPU in scan mode and the ScanCoder optimisation on the host (scan_coder.cpp).
@@ -122,6 +124,8 @@ extern "C" int bce_hip_decompress_device_crc32(bce_hip_ctx *ctx, const uint8_t *
                                                size_t *out_len, uint32_t *crc) __attribute__((weak));
 extern "C" int bce_hip_estimate_host(bce_hip_ctx *ctx, const uint8_t *in, uint32_t n, uint64_t plane_cost_q24[8], uint64_t plane_steps[8],
                                      size_t *archive_bytes) __attribute__((weak));
+
+extern "C" int bce_hip_count(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint64_t *counts) __attribute__((weak));
 
 // `bce -cN`: N contiguous blocks over the GPUs of the node.  With more blocks than GPUs every device gets up to four
 // gated contexts (bce_hip_set_gated), one host thread each: their GPU phases take turns while the coder threads of the
@@ -417,6 +421,83 @@ static int estimate_file(const char *file, const char *config) {
   return 0;
 }
 
+// `bce -g PATTERN file` / `bce -gd PATTERN archive` (extensions): how often the literal bytes of PATTERN occur in the file, or in
+// what the archive (a plain one, or a BCEM container of either version) decodes to -- overlapping matches counted, as a scan of the
+// text would find them.  K1 and K2 index the text on the GPU and backward search on the planes counts the matches in the circular
+// text (bce_hip_count); those that run across the end of the text are found here, in its last and first m - 1 bytes, and come off.
+// An archive's blocks are decoded by the GPU-assisted decoder, one after the other, a version-2 container's against their CRC-32s.
+static uint64_t seam_matches(const uint8_t *t, size_t n, const uint8_t *pat, size_t m) {
+  std::vector<uint8_t> seam(t + n - (m - 1), t + n);
+  seam.insert(seam.end(), t, t + (m - 1));
+  uint64_t found = 0;
+  for (size_t s = 0; s + m <= seam.size(); ++s) found += memcmp(seam.data() + s, pat, m) == 0;
+  return found;
+}
+static int count_pattern(const char *pattern, const char *path, bool in_archive) {
+  const size_t m = strlen(pattern);
+  const uint8_t *pat = reinterpret_cast<const uint8_t *>(pattern);
+  HostFile file;
+  std::thread reader(read_whole_file, path, &file, in_archive ? (size_t)0 : kMaxInput);   // beside the runtime's start-up
+  bce_hip_ctx *ctx = nullptr;
+  const int rc0 = bce_hip_create(&ctx, 0);
+  reader.join();
+  struct Destroy { bce_hip_ctx *&c; ~Destroy() { if (c) bce_hip_destroy(c); } } destroy{ctx};
+  if (in_archive && file.status == -1) { printf("Archive not found.\n"); return -1; }
+  if (in_archive && (file.status != 0 || file.size() == 0)) { printf("Could not read Archive.\n"); return -2; }
+  if (!in_archive && (file.status != 0 || file.size() == 0 || file.size() >= kMaxInput)) { printf("Error loading file\n"); return -1; }
+  if (rc0 != 0 || !bce_hip_count) { printf("No usable HIP device: %s\n", bce_hip_strerror(rc0 ? rc0 : BCE_HIP_E_DEVICE)); return -3; }
+  const uint8_t *text = file.data();
+  size_t n = file.size();
+  std::vector<uint8_t> decoded;
+  if (in_archive) {
+    std::vector<std::pair<size_t, size_t>> blocks;
+    if (!archive_blocks(file, blocks)) { printf("Could not read Archive.\n"); return -2; }
+    const bool checked = container_version(file) == 2;
+    std::vector<size_t> at(blocks.size() + 1, 0);
+    for (size_t b = 0; b < blocks.size(); ++b) {                    // sizes from the blocks' own headers, which a container's table must name (as -d)
+      size_t hn = 0;
+      const int hr = bce_hip_decompress(file.data() + blocks[b].first, blocks[b].second, nullptr, 0, &hn);
+      if (hr != 0 && blocks.size() == 1 && !is_container(file)) { printf("Decompression failed: %s\n", bce_hip_strerror(hr)); return -4; }
+      if (hr != 0 || hn < 1 || hn >= kMaxInput || (is_container(file) && (uint64_t)hn != table_raw(file, b))) { printf("Could not read Archive.\n"); return -2; }
+      at[b + 1] = at[b] + hn;
+      if (at[b + 1] >= kMaxInput) { printf("The archive holds 2^31 bytes or more: one index covers one text below that\n"); return -2; }
+    }
+    if (checked && !bce_hip_decompress_device_crc32) { printf("No usable HIP device: %s\n", bce_hip_strerror(BCE_HIP_E_DEVICE)); return -3; }
+    decoded.resize(at.back());
+    for (size_t b = 0; b < blocks.size(); ++b) {
+      const uint8_t *ap = file.data() + blocks[b].first;
+      const size_t want = at[b + 1] - at[b];
+      size_t got = 0;
+      uint32_t crc = 0;
+      int rc = checked ? bce_hip_decompress_device_crc32(ctx, ap, blocks[b].second, decoded.data() + at[b], want, &got, &crc)
+                       : bce_hip_decompress_device(ctx, ap, blocks[b].second, decoded.data() + at[b], want, &got);
+      if (rc == 0 && got != want) rc = BCE_HIP_E_INTERNAL;
+      if (rc != 0) {
+        if (bce_hip_last_error(ctx)[0]) printf("%s\n", bce_hip_last_error(ctx));
+        printf("Decompression failed: %s\n", bce_hip_strerror(rc));
+        return -4;
+      }
+      if (checked && crc != table_crc(file, b)) { print_mismatch(b, table_crc(file, b), crc); return -4; }
+    }
+    text = decoded.data();
+    n = decoded.size();
+  }
+  uint64_t count = 0;
+  if (m <= n) {                                                     // (a longer pattern occurs nowhere in the text, only around it)
+    const uint64_t offsets[2] = {0, m};
+    int rc = bce_hip_load_host(ctx, text, (uint32_t)n);
+    if (rc == 0) rc = bce_hip_bwt(ctx, nullptr);
+    if (rc == 0) rc = bce_hip_build_planes(ctx, nullptr);
+    if (rc == 0) rc = bce_hip_count(ctx, pat, offsets, 1, &count);
+    if (rc != 0) { printf("Count failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); return -4; }
+    count -= seam_matches(text, n, pat, m);
+  }
+  printf("%llu occurrences\n", (unsigned long long)count);
+  ctx = nullptr;                                                    // (left to fast_exit, like -d)
+  fast_exit(0);
+  return 0;
+}
+
 static int usage() {
   printf("Usage:\n");
   printf("  bce -c archive.bce file [config.bcc]\n");
@@ -441,6 +522,12 @@ static int usage() {
   printf("\n");
   printf("  bce -e file [config.bcc]\n");
   printf("   Estimates the size -c would give for \"file\" [using config \"config.bcc\"]: the model's code lengths are summed on the GPU, nothing is coded or written (extension)\n");
+  printf("\n");
+  printf("  bce -g PATTERN file\n");
+  printf("   Counts how often the bytes of PATTERN occur in \"file\", overlapping matches included: the file is indexed on the GPU and the count comes from the index (extension)\n");
+  printf("\n");
+  printf("  bce -gd PATTERN archive.bce\n");
+  printf("   The same count in what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
   return 0;
 }
 
@@ -708,6 +795,8 @@ int main(int argc, char **argv) {
     return self_test_archive(argv[2]);
   } else if ((argc == 3 || argc == 4) && argv[1][0] == '-' && argv[1][1] == 'e' && argv[1][2] == 0) {
     return estimate_file(argv[2], argc == 4 ? argv[3] : nullptr);
+  } else if (argc == 4 && argv[2][0] != 0 && (strcmp(argv[1], "-g") == 0 || strcmp(argv[1], "-gd") == 0)) {
+    return count_pattern(argv[2], argv[3], argv[1][2] == 'd');
   } else if (argc == 4 && argv[1][0] == '-' && argv[1][1] == 's') {
     // Scan (bce.cpp:1384-1402): enumeration on the GPU, ScanCoder optimisation on the host, 288-byte config out
     auto start = std::chrono::high_resolution_clock::now();

@@ -18,6 +18,9 @@ from . import api, container
 from .sharding import block_range
 
 
+_MAX_BLOCK = (1 << 31) - 1          # a block obeys the reference's n < 2^31
+
+
 def _device_index(device):
     d = torch.device(device)
     if d.type != "cuda":
@@ -59,6 +62,38 @@ def estimate_tensor(t, config=None, ctx=None):
     return api.estimate_device(t.data_ptr(), t.numel(), config=config, device=t.device.index, ctx=ctx)
 
 
+def count_tensor(t, patterns, ctx=None):
+    """How often `patterns` (one bytes-like -> int, a sequence -> numpy uint64 array) occur in the 1-D uint8 CUDA tensor `t` (or
+    slice, any offset), overlapping matches counted: indexed where it lies (K1, K2) and counted from the index
+    (api.RankFile.count); of the text only the few bytes at its two ends that the longest pattern asks for reach the host.
+    Synchronises t's current stream first; `ctx` (an api._Ctx of t's device) is reused if given."""
+    _check(t, "t")
+    n = t.numel()
+    if n == 0:
+        raise api.BceError(-1, "count_tensor", "empty input")
+    if n > _MAX_BLOCK:
+        raise ValueError("one index covers one text of less than 2^31 bytes, not %d" % n)
+    _ready(t)
+    own = ctx is None
+    c = ctx or api._Ctx(t.device.index)
+    try:
+        return api.RankFile(n=n, device_ptr=t.data_ptr(), ctx=c).count(patterns)
+    finally:
+        if own:
+            c.close()
+
+
+def count_in_archive(blob, patterns, device="cuda:0"):
+    """count_tensor on what an archive holds: a plain archive or a BCEM container of either version is decoded into ONE tensor
+    on the device (decompress_container_tensor: a version-2 container's blocks are tested against their CRC-32 there), indexed
+    and counted there -- matches across block boundaries included.  A container of 2^31 bytes or more: ValueError (one index
+    covers one text), before anything is decoded."""
+    total = sum(t[0] for t in _blocks_of(blob))
+    if total > _MAX_BLOCK:
+        raise ValueError("the archive holds %d bytes: one index covers one text of less than 2^31" % total)
+    return count_tensor(decompress_container_tensor(blob, device=device), patterns)
+
+
 def decompress_tensor(archive, device="cuda:0", out=None, ctx=None):
     """The GPU-assisted decoder with the text left on the device (bce_hip_decompress_to_device) -> a 1-D uint8 tensor there.
 
@@ -91,9 +126,6 @@ def verify_tensor(archive, t, ctx=None):
     _check(t, "t")
     _ready(t)
     return api.verify_device(archive, t.data_ptr() if t.numel() else None, t.numel(), device=t.device.index, ctx=ctx)
-
-
-_MAX_BLOCK = (1 << 31) - 1          # a block obeys the reference's n < 2^31
 
 
 def compress_tensor_blocks(t, blocks=None, config=None, contexts=4, checksum=True):

@@ -281,6 +281,29 @@ int bce_hip_decode_crc32(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, s
 int bce_hip_decompress_device_crc32(bce_hip_ctx *ctx, const uint8_t *archive, size_t len, uint8_t *out, size_t cap, size_t *out_len,
                                     uint32_t *crc);
 
+/* ---- extension: how often byte strings occur in the input, from the planes (kd_count.hip, fm_step.h) -------------------------
+ * After bce_hip_build_planes the context holds a counting index of its input: the BWT of all cyclic rotations as a wavelet matrix
+ * with a rank directory.  Backward search on it -- one last-to-first step per pattern byte, eight rank levels each -- counts the
+ * rotations that start with a pattern: the CYCLIC count, the i in [0, n) with P[k] == T[(i + k) mod n] for all k < m.  Defined for
+ * every length: the empty pattern occurs n times, a pattern longer than the text wraps around it.  (The count `bytes.count` would
+ * give if it counted overlapping matches is this minus the occurrences that straddle the end of the text; bce_amd/api.py:
+ * RankFile.count.)  npat patterns arrive concatenated: pattern p is patterns[offsets[p], offsets[p + 1]), npat + 1 offsets,
+ * non-decreasing; counts[p] receives its count.
+ * Valid from bce_hip_build_planes on for as long as the planes stand (through bce_hip_encode / _estimate / _scan and after them;
+ * until the next load, bce_hip_set_bwt or decode); otherwise BCE_HIP_E_STATE with a bce_hip_last_error text.  Neither call changes
+ * the context's compression state: an encode after a count gives the archive it would have given.  npat == 0: success, nothing
+ * touched.  A null ctx, a null array with npat > 0, offsets that decrease: BCE_HIP_E_ARG. */
+int bce_hip_count(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint64_t *counts);
+/* The same with all three arrays in device memory of the context's device (offsets and counts 8-byte aligned).  Stream rule of
+ * bce_hip_decompress_to_device: runs on the context's stream, complete on return; the memory must be ready when the call is made.
+ * Decreasing offsets are found by the kernel (BCE_HIP_E_ARG after it has run; the counts are then undefined); that every offset
+ * lies inside the patterns' buffer is the caller's to keep. */
+int bce_hip_count_device(bce_hip_ctx *ctx, const void *d_patterns, const void *d_offsets, uint32_t npat, void *d_counts);
+/* len bytes of the input the context holds, from position pos, to the host (the few bytes at the two ends of the text that turn a
+ * cyclic count into a linear one, when the input came from device memory).  Valid as bce_hip_input_crc32; pos + len > n:
+ * BCE_HIP_E_ARG. */
+int bce_hip_input_bytes(bce_hip_ctx *ctx, uint64_t pos, size_t len, uint8_t *out);
+
 /* ---- test hooks: the device primitives every stage rests on, alone (tests/test_gpu_sort.py, tests/test_gpu_compare.py) ----
  * Stream rule of bce_hip_crc32_device for all three: the work runs on the context's stream and is complete on return; the caller's
  * memory (device memory of the context's device) must be ready when the call is made.  Valid in any state of the context, between
