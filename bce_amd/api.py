@@ -110,6 +110,8 @@ SYMBOLS = [
     ("bce_hip_count", C.c_int, [C.c_void_p, _u8p, _vp, C.c_uint32, _vp]),
     ("bce_hip_count_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, _vp]),
     ("bce_hip_input_bytes", C.c_int, [C.c_void_p, C.c_uint64, C.c_size_t, _u8p]),
+    ("bce_hip_locate", C.c_int, [C.c_void_p, _u8p, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("bce_hip_locate_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("bce_hip_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     ("bce_hip_synth_text", None, [C.c_uint64, _u8p, C.c_size_t]),
     ("bce_hip_synth_rand", None, [C.c_uint64, _u8p, C.c_size_t]),
@@ -147,6 +149,15 @@ def _as_u8(data):
     if isinstance(data, np.ndarray):
         return np.ascontiguousarray(data, dtype=np.uint8)
     return np.frombuffer(bytes(data), dtype=np.uint8)
+
+
+LOCATE_LINEAR = 1                               # BCE_HIP_LOCATE_LINEAR
+E_OVERFLOW = -5                                 # BCE_HIP_E_OVERFLOW
+
+
+def _positions_buffer(total):
+    """Host room for `total` located positions (RankFile.locate makes it only after the sizing call has passed max_hits)."""
+    return np.empty(max(total, 1), dtype=np.uint32)
 
 
 def _is_one_pattern(patterns):
@@ -311,6 +322,55 @@ class RankFile:
                                                        None if offsets_ptr is None else int(offsets_ptr), int(npat),
                                                        None if counts_ptr is None else int(counts_ptr)), "bce_hip_count_device")
 
+    def locate(self, patterns, cyclic=False, limit=None, max_hits=1 << 26):
+        """Where byte strings occur in the text: their byte offsets, ascending, gathered on the GPU from K1's suffix array at the
+        rows backward search ends at (bce_hip_locate; the text is not read).  `patterns`: one bytes-like -> one numpy uint32 array;
+        a sequence of them -> a list of arrays, in input order.
+        cyclic=False: the hits an overlapping scan of the text finds (as many as count() says); none for a pattern longer than the
+        text; an empty pattern raises ValueError.  cyclic=True: the hits in the circular text, those that run across its end
+        included, defined for every length (the empty pattern: every position).  A RankFile built from an injected BWT has no
+        suffix array: cyclic=False raises ValueError as count() does, cyclic=True BceError.
+        A sizing call comes first: more than `max_hits` hits in all -> ValueError naming the total, before any room for positions
+        is made.  `limit` keeps the first `limit` hits of each pattern in text order; it bounds the result, NOT the work (every
+        hit is gathered and sorted first) nor what max_hits is compared with.  The sizing call and the full call each run the
+        search (and, cyclic=False, the pass that counts the hits across the end): a request searches twice and gathers once."""
+        one = _is_one_pattern(patterns)
+        pats = [_as_u8(patterns)] if one else [_as_u8(p) for p in patterns]
+        if not cyclic:
+            if not self._has_text:
+                raise ValueError("a RankFile built from an injected BWT holds no text: only cyclic=True hits are defined")
+            if any(len(p) == 0 for p in pats):
+                raise ValueError("an empty pattern has no linear hits (cyclic=True: every position)")
+        if limit is not None and limit < 0:
+            raise ValueError("limit must not be negative")
+        if not pats:
+            return []
+        lib, flags = self._c.lib, 0 if cyclic else LOCATE_LINEAR
+        offsets = np.zeros(len(pats) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([len(p) for p in pats], dtype=np.uint64)
+        flat = np.concatenate(pats) if int(offsets[-1]) else np.zeros(1, dtype=np.uint8)
+        hits, total = np.zeros(len(pats) + 1, dtype=np.uint64), C.c_uint64(0)
+        rc = lib.bce_hip_locate(self._c.h, flat.ctypes.data, offsets.ctypes.data, len(pats), flags, hits.ctypes.data, None, 0, C.byref(total))
+        if rc in (0, E_OVERFLOW) and total.value > max_hits:        # (a batch beyond the call's row limit is sized exactly too)
+            raise ValueError("%d hits in all, more than max_hits = %d" % (total.value, max_hits))
+        self._c.check(rc, "bce_hip_locate")
+        pos = _positions_buffer(total.value)
+        self._c.check(lib.bce_hip_locate(self._c.h, flat.ctypes.data, offsets.ctypes.data, len(pats), flags, hits.ctypes.data, pos.ctypes.data,
+                                         total.value, C.byref(total)), "bce_hip_locate")
+        out = [pos[int(hits[i]):int(hits[i + 1])][:limit].copy() for i in range(len(pats))]
+        return out[0] if one else out
+
+    def locate_device(self, patterns_ptr, offsets_ptr, npat, hit_offsets_ptr, positions_ptr, cap, cyclic=False) -> int:
+        """bce_hip_locate_device: the hits of `npat` patterns that lie concatenated in device memory (int pointers: the bytes,
+        npat + 1 uint64 offsets; out: npat + 1 uint64 hit offsets, up to `cap` uint32 positions) -> the total.  positions_ptr None
+        with cap 0 only sizes; a total above cap raises BceError (BCE_HIP_E_OVERFLOW) with the hit offsets written and the
+        positions untouched.  Stream rule: as count_device."""
+        total = C.c_uint64(0)
+        ptr = lambda v: None if v is None else int(v)  # noqa: E731
+        self._c.check(self._c.lib.bce_hip_locate_device(self._c.h, ptr(patterns_ptr), ptr(offsets_ptr), int(npat), 0 if cyclic else LOCATE_LINEAR,
+                                                        ptr(hit_offsets_ptr), ptr(positions_ptr), int(cap), C.byref(total)), "bce_hip_locate_device")
+        return total.value
+
     def close(self):
         self._c.close()
 
@@ -451,6 +511,17 @@ def count(data, patterns, device=0, ctx=None):
     rf = RankFile(data, device=device, ctx=ctx)
     try:
         return rf.count(patterns)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def locate(data, patterns, cyclic=False, limit=None, max_hits=1 << 26, device=0, ctx=None):
+    """Where `patterns` occur in `data` (one bytes-like -> a numpy uint32 array of ascending byte offsets, a sequence -> a list of
+    them): K1 and K2 index the data on the GPU, RankFile.locate asks the index and K1's suffix array."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.locate(patterns, cyclic=cyclic, limit=limit, max_hits=max_hits)
     finally:
         if ctx is None:
             rf.close()

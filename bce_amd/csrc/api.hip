@@ -699,7 +699,8 @@ void bce_hip_destroy(bce_hip_ctx *c) {
   DevBuf *bufs[] = {&c->text, &c->bwt, &c->sa[0], &c->sa[1], &c->key[0], &c->key[1], &c->rank, &c->k2, &c->nrk, &c->act[0], &c->act[1], &c->khi[0], &c->khi[1], &c->dl[0], &c->dl[1], &c->dl[2], &c->dl[3], &c->kflag, &c->actv[0], &c->actv[1],
                     &c->rs_hist, &c->blk, &c->ptmp[0], &c->ptmp[1], &c->gran, &c->nlist[0], &c->nlist[1], &c->ctl, &c->tilecnt,
                     &c->tileoff, &c->runs, &c->smwords, &c->k3tw, &c->k3grp, &c->truns, &c->skey[0], &c->skey[1], &c->sval[0], &c->sval[1], &c->sout,
-                    &c->sesc, &c->stat, &c->crc_tab, &c->dcfg, &c->k4w, &c->scanrec, &c->dfs, &c->skey_alt, &c->sesc_alt, &c->rs_hist_k4, &c->cost_acc, &c->cost_runs, &c->cmp_res, &c->cnt_res, &c->cnt_pat, &c->cnt_off, &c->cnt_out, &c->hook[0], &c->hook[1], &c->hook[2]};
+                    &c->sesc, &c->stat, &c->crc_tab, &c->dcfg, &c->k4w, &c->scanrec, &c->dfs, &c->skey_alt, &c->sesc_alt, &c->rs_hist_k4, &c->cost_acc, &c->cost_runs, &c->cmp_res, &c->cnt_res, &c->cnt_pat, &c->cnt_off, &c->cnt_out, &c->loc_res, &c->loc_lo, &c->loc_cnt, &c->loc_drop, &c->loc_start, &c->loc_lin, &c->loc_bsum,
+                    &c->loc_key[0], &c->loc_key[1], &c->loc_val[0], &c->loc_val[1], &c->loc_pat, &c->loc_off, &c->loc_hits, &c->loc_pos, &c->hook[0], &c->hook[1], &c->hook[2]};
   for (DevBuf *b : bufs) release(*b);
   for (auto &par : c->dlist) for (DevBuf &b : par) release(b);
   k4_prepin_join(c, true);
@@ -1406,9 +1407,9 @@ int bce_hip_compare_device(bce_hip_ctx *c, const void *d_a, const void *d_b, siz
 // ---- pattern counts from the planes (kd_count.hip) ---------------------------------------------------------
 // Phase 3, as bce_hip_rank1: the planes are read, so what an allocation may give back is what an enumeration beside them would.
 // Nothing a stage keeps is written: the staging buffers and the flag word are the count's own.
-static int count_state(bce_hip_ctx *c) {
+static int count_state(bce_hip_ctx *c, const char *what = "count") {
   if (c->stage >= 3) return BCE_HIP_OK;
-  snprintf(c->err, sizeof c->err, "count: the context holds no planes (stage %d; bce_hip_build_planes first)", c->stage);
+  snprintf(c->err, sizeof c->err, "%s: the context holds no planes (stage %d; bce_hip_build_planes first)", what, c->stage);
   return BCE_HIP_E_STATE;
 }
 
@@ -1458,6 +1459,95 @@ int bce_hip_input_bytes(bce_hip_ctx *c, uint64_t pos, size_t len, uint8_t *out) 
   BCE_HIP_TRY(c, hipMemcpyAsync(out, c->text.as<uint8_t>() + pos, len, hipMemcpyDeviceToHost, c->stream));
   BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
   return BCE_HIP_OK;
+}
+
+// ---- pattern positions from the planes and K1's suffix array (kd_locate.hip) -----------------------------------------------
+// Phase 3 as the count: ctx_trim keeps sa[sa_res] there, for the depth-first tail.  Nothing after K1 writes that array until the
+// next load or decode (K3's tail, the encoder, the estimate, the scan, the count and the sort hooks only read it or never name
+// it), so it stands for as long as k1_valid does.  A text of one byte has no array: its only rotation starts at 0.
+static int locate_state(bce_hip_ctx *c, const uint32_t **sa) {
+  BCE_TRY(count_state(c, "locate"));
+  *sa = nullptr;
+  if (c->k1_valid && c->sa[c->sa_res].p && c->sa[c->sa_res].cap >= (size_t)c->n * 4) { *sa = c->sa[c->sa_res].as<uint32_t>(); return BCE_HIP_OK; }
+  if (c->n == 1 && c->text_loaded) return BCE_HIP_OK;
+  snprintf(c->err, sizeof c->err, c->text_loaded ? "locate: the suffix array of this input is gone" : "locate: there is no suffix array behind an injected BWT");
+  return BCE_HIP_E_STATE;
+}
+
+// The overflow protocol, once for both entry points.  d_*: device arrays; h_hits / h_pos: where a call with host buffers wants the
+// offsets and positions (then d_pos is staged in loc_pos once the total is known).  hit offsets and *total are out before the
+// first reason to refuse; the positions are touched only when all of them fit.
+static int locate_run(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, bool linear, uint64_t *d_hits,
+                      uint64_t *h_hits, uint32_t *d_pos, uint32_t *h_pos, bool sizing, uint64_t cap, uint64_t *total) {
+  uint64_t rows = 0, hits = 0;
+  const int rc = kd_locate_size(c, sa, d_pat, d_off, npat, linear, d_hits, &rows, &hits);
+  if (rc != BCE_HIP_OK && rc != BCE_HIP_E_OVERFLOW) return rc;
+  if (h_hits) {
+    BCE_HIP_TRY(c, hipMemcpyAsync(h_hits, d_hits, ((size_t)npat + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  *total = hits;
+  if (rc != BCE_HIP_OK || sizing) return rc;
+  if (hits > cap) { snprintf(c->err, sizeof c->err, "locate: %llu hits, room for %llu", (unsigned long long)hits, (unsigned long long)cap); return BCE_HIP_E_OVERFLOW; }
+  if (hits == 0) return BCE_HIP_OK;
+  if (h_pos) {
+    BCE_TRY(ensure(c, c->loc_pos, (size_t)hits * 4));
+    d_pos = c->loc_pos.as<uint32_t>();
+  }
+  BCE_TRY(kd_locate_fill(c, sa, d_off, npat, linear, rows, hits, d_pos));
+  if (h_pos) {
+    BCE_HIP_TRY(c, hipMemcpyAsync(h_pos, d_pos, (size_t)hits * 4, hipMemcpyDeviceToHost, c->stream));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return BCE_HIP_OK;
+}
+
+int bce_hip_locate(bce_hip_ctx *c, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t flags, uint64_t *hit_offsets,
+                   uint32_t *positions, uint64_t cap, uint64_t *total) {
+  if (!c || !total || (flags & ~BCE_HIP_LOCATE_LINEAR)) return BCE_HIP_E_ARG;
+  *total = 0;
+  if (npat == 0) { if (hit_offsets) hit_offsets[0] = 0; return BCE_HIP_OK; }
+  const uint32_t *sa = nullptr;
+  BCE_TRY(locate_state(c, &sa));
+  if (!offsets || !hit_offsets || (!positions && cap)) return BCE_HIP_E_ARG;
+  for (uint32_t p = 0; p < npat; ++p)
+    if (offsets[p + 1] < offsets[p]) { snprintf(c->err, sizeof c->err, "locate: pattern offsets decrease at %u", p); return BCE_HIP_E_ARG; }
+  const uint64_t bytes = offsets[npat];
+  if (bytes && !patterns) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope phase(c, 3);
+    const size_t off_bytes = ((size_t)npat + 1) * 8;
+    BCE_TRY(ensure(c, c->loc_pat, bytes ? (size_t)bytes : 1));
+    BCE_TRY(ensure(c, c->loc_off, off_bytes));
+    BCE_TRY(ensure(c, c->loc_hits, off_bytes));
+    if (bytes) BCE_HIP_TRY(c, hipMemcpyAsync(c->loc_pat.p, patterns, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
+    BCE_HIP_TRY(c, hipMemcpyAsync(c->loc_off.p, offsets, off_bytes, hipMemcpyHostToDevice, c->stream));
+    return locate_run(c, sa, c->loc_pat.as<uint8_t>(), c->loc_off.as<uint64_t>(), npat, flags & BCE_HIP_LOCATE_LINEAR, c->loc_hits.as<uint64_t>(),
+                      hit_offsets, nullptr, positions, !positions, cap, total);
+  });
+}
+
+int bce_hip_locate_device(bce_hip_ctx *c, const void *d_patterns, const void *d_offsets, uint32_t npat, uint32_t flags, void *d_hit_offsets,
+                          void *d_positions, uint64_t cap, uint64_t *total) {
+  if (!c || !total || (flags & ~BCE_HIP_LOCATE_LINEAR)) return BCE_HIP_E_ARG;
+  *total = 0;
+  if (npat == 0) {
+    if (!d_hit_offsets) return BCE_HIP_OK;
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    BCE_HIP_TRY(c, hipMemsetAsync(d_hit_offsets, 0, 8, c->stream));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return BCE_HIP_OK;
+  }
+  const uint32_t *sa = nullptr;
+  BCE_TRY(locate_state(c, &sa));
+  if (!d_patterns || !d_offsets || !d_hit_offsets || (!d_positions && cap)) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope phase(c, 3);
+    return locate_run(c, sa, static_cast<const uint8_t *>(d_patterns), static_cast<const uint64_t *>(d_offsets), npat, flags & BCE_HIP_LOCATE_LINEAR,
+                      static_cast<uint64_t *>(d_hit_offsets), nullptr, static_cast<uint32_t *>(d_positions), nullptr, !d_positions, cap, total);
+  });
 }
 
 int bce_hip_get_stats(const bce_hip_ctx *c, bce_hip_stats *out) {

@@ -212,6 +212,10 @@ struct bce_hip_ctx {
   bce::DevBuf cmp_res;                           // kd_compare.hip: its result word (a buffer of its own, as kd_crc32.hip's: no stage's scratch is touched)
   bce::DevBuf cnt_res;                           // kd_count.hip: its flag word (a buffer of its own, as cmp_res)
   bce::DevBuf cnt_pat, cnt_off, cnt_out;         // bce_hip_count: the patterns, their offsets and the counts of a call with host buffers, staged (grow-only)
+  bce::DevBuf loc_res;                           // kd_locate.hip: its flag word and scan total (a buffer of its own, as cnt_res)
+  bce::DevBuf loc_lo, loc_cnt, loc_drop, loc_start, loc_lin, loc_bsum;   // per pattern: the interval's first row, its rows, those across the text's end; the two CSR offset arrays; the scan's block sums
+  bce::DevBuf loc_key[2], loc_val[2];            // (position, pattern) of every row: both halves of the sorts' ping-pong
+  bce::DevBuf loc_pat, loc_off, loc_hits, loc_pos;   // bce_hip_locate: the arrays of a call with host buffers, staged (all grow-only)
   bce::DevBuf hook[3];                           // test hooks bce_hip_sort_pairs_device / _wide_device: the second halves of the sorts' ping-pong
   bool crc_const_ready = false;                  // its launch-independent constants are uploaded
   bool text_loaded = false;                      // `text` holds the n bytes of the last bce_hip_load_* (bce_hip_input_crc32)
@@ -420,6 +424,12 @@ int kd_compare(bce_hip_ctx *c, const uint8_t *a, const uint8_t *b, uint64_t m, u
 int kd_crc32(bce_hip_ctx *c, const uint8_t *d, uint64_t n, uint32_t *crc);   // kd_crc32.hip: CRC-32 (zlib's) of a device buffer
 // kd_count.hip: d_out[p] = occurrences of d_pat[d_off[p], d_off[p + 1]) in the circular text of the context's planes (device arrays)
 int kd_count(bce_hip_ctx *c, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, uint64_t *d_out);
+// kd_locate.hip: the positions of the same occurrences, CSR.  _size: d_hits[npat + 1], their total and the batch's cyclic rows;
+// _fill, straight after it: d_pos[total].  sa: K1's suffix array, null for n == 1.
+int kd_locate_size(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, bool linear,
+                   uint64_t *d_hits, uint64_t *rows, uint64_t *total);
+int kd_locate_fill(bce_hip_ctx *c, const uint32_t *sa, const uint64_t *d_off, uint32_t npat, bool linear, uint64_t rows, uint64_t total,
+                   uint32_t *d_pos);
 int k2_build_planes(bce_hip_ctx *c);                // k2_planes.hip
 int k2_get_plane_bits(bce_hip_ctx *c, int plane, uint8_t *out);
 int k2_rank1(bce_hip_ctx *c, int plane, const uint32_t *idx, uint32_t count, uint32_t *out);

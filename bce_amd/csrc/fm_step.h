@@ -1,5 +1,6 @@
-// fm_step.h -- backward search on the K2 planes: the step kd_count.hip runs per pattern byte, shared with the host
-// (tests/count_emul.cpp runs the same lines on planes it builds naively), the way bce_cost.h and bce_core.h are shared.
+// fm_step.h -- backward search on the K2 planes: the step kd_count.hip and kd_locate.hip run per pattern byte, and the row
+// arithmetic of a located batch, shared with the host (tests/count_emul.cpp and tests/locate_emul.cpp run the same lines on planes
+// they build naively), the way bce_cost.h and bce_core.h are shared.
 //
 // K2 partitions the BWT stably by bit 0, then bit 1, ... bit 7, zeros first (k2_planes.hip): an LSD radix sort, so after the
 // eight levels the bytes stand sorted by value, equal bytes in BWT order.  Following a position i in [0, n] down the levels for
@@ -26,13 +27,41 @@ BCE_HD void fm_step(uint32_t c, const uint32_t zeros[8], uint32_t &lo, uint32_t 
   }
 }
 
-// Occurrences of pat[0, m) in the circular text of n bytes whose planes rank2 serves: the i in [0, n) with
-// pat[k] == T[(i + k) mod n] for all k.  Any m: the empty pattern occurs n times, m > n wraps around.
+// The rows [lo, hi) of the sorted rotations that start with pat[0, m), in the circular text of n bytes whose planes rank2
+// serves.  Any m: the empty pattern owns all n rows, m > n wraps around.  The next byte is fetched before the current byte's
+// eight levels, off their chain.  An empty interval stops the search; lo is then whatever the last step left.
+template <class Rank2>
+BCE_HD void fm_range(const uint8_t *pat, uint64_t m, uint32_t n, const uint32_t zeros[8], uint32_t &lo, uint32_t &hi, Rank2 &&rank2) {
+  lo = 0; hi = n;
+  uint32_t c = m ? pat[m - 1] : 0u;
+  for (uint64_t k = m; k > 0 && lo < hi; --k) {
+    const uint32_t next = k > 1 ? pat[k - 2] : 0u;
+    fm_step(c, zeros, lo, hi, rank2);
+    c = next;
+  }
+}
+
+// Occurrences of pat[0, m) in that text: the i in [0, n) with pat[k] == T[(i + k) mod n] for all k.
 template <class Rank2>
 BCE_HD uint32_t fm_count(const uint8_t *pat, uint64_t m, uint32_t n, const uint32_t zeros[8], Rank2 &&rank2) {
-  uint32_t lo = 0, hi = n;
-  for (uint64_t k = m; k > 0 && lo < hi; --k) fm_step(pat[k - 1], zeros, lo, hi, rank2);
+  uint32_t lo, hi;
+  fm_range(pat, m, n, zeros, lo, hi, rank2);
   return hi - lo;
 }
+
+// ---- locating (kd_locate.hip): the occurrences are the suffix array's entries sa[lo, hi) ---------------------------------------
+// A batch's rows stand pattern after pattern: pattern p owns rows [start[p], start[p + 1]), start[0] = 0, non-decreasing,
+// npat + 1 words.  The pattern that owns row r < start[npat]: the last p with start[p] <= r (empty patterns between are skipped).
+BCE_HD uint32_t fm_row_pattern(const uint64_t *start, uint32_t npat, uint64_t r) {
+  uint32_t a = 0, b = npat;                          // start[a] <= r < start[b]
+  while (b - a > 1) {
+    const uint32_t mid = a + (b - a) / 2;
+    if (start[mid] <= r) a = mid; else b = mid;
+  }
+  return a;
+}
+
+// Does the cyclic hit at pos < n lie inside the text, pos + m <= n?  (A pattern longer than the text never does.)
+BCE_HD bool fm_linear_hit(uint32_t pos, uint64_t m, uint32_t n) { return m <= n && pos <= n - (uint32_t)m; }
 
 }  // namespace bce

@@ -5,6 +5,7 @@
 //   bce -t archive.bcem                     (extension) decode such a container on the GPU and test it against its own CRC-32s
 //   bce -g PATTERN file                     (extension) how often the bytes of PATTERN occur in "file", counted on the GPU from its BWT planes
 //   bce -gd PATTERN archive                 (extension) the same in what an archive or container holds
+//   bce -gl PATTERN file, -gld PATTERN archive   (extension) where they occur: the byte offsets, gathered on the GPU from K1's suffix array
 // Banner, usage text, summary line, argument detection and exit codes follow the reference
 // (banner :1377-1379, -c :1403-1427, -d :1428-1472, usage :1473-1483).  -d uses the GPU-assisted decoder (kd_decode.hip), -ds the host decoder (decoder.cpp);
 // -s runs the enumeration on the GPU in scan mode and the ScanCoder optimisation on the host (scan_coder.cpp).
@@ -126,6 +127,8 @@ extern "C" int bce_hip_estimate_host(bce_hip_ctx *ctx, const uint8_t *in, uint32
                                      size_t *archive_bytes) __attribute__((weak));
 
 extern "C" int bce_hip_count(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint64_t *counts) __attribute__((weak));
+extern "C" int bce_hip_locate(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t flags, uint64_t *hit_offsets,
+                              uint32_t *positions, uint64_t cap, uint64_t *total) __attribute__((weak));
 
 // `bce -cN`: N contiguous blocks over the GPUs of the node.  With more blocks than GPUs every device gets up to four
 // gated contexts (bce_hip_set_gated), one host thread each: their GPU phases take turns while the coder threads of the
@@ -426,6 +429,8 @@ static int estimate_file(const char *file, const char *config) {
 // text would find them.  K1 and K2 index the text on the GPU and backward search on the planes counts the matches in the circular
 // text (bce_hip_count); those that run across the end of the text are found here, in its last and first m - 1 bytes, and come off.
 // An archive's blocks are decoded by the GPU-assisted decoder, one after the other, a version-2 container's against their CRC-32s.
+// `-gl` / `-gld` (locate): the same files, answers and exit codes; the matches' byte offsets, one per line, ascending, come before
+// the count line.  They are the linear hits of bce_hip_locate: gathered from K1's suffix array and filtered on the GPU.
 static uint64_t seam_matches(const uint8_t *t, size_t n, const uint8_t *pat, size_t m) {
   std::vector<uint8_t> seam(t + n - (m - 1), t + n);
   seam.insert(seam.end(), t, t + (m - 1));
@@ -433,7 +438,7 @@ static uint64_t seam_matches(const uint8_t *t, size_t n, const uint8_t *pat, siz
   for (size_t s = 0; s + m <= seam.size(); ++s) found += memcmp(seam.data() + s, pat, m) == 0;
   return found;
 }
-static int count_pattern(const char *pattern, const char *path, bool in_archive) {
+static int count_pattern(const char *pattern, const char *path, bool in_archive, bool locate) {
   const size_t m = strlen(pattern);
   const uint8_t *pat = reinterpret_cast<const uint8_t *>(pattern);
   HostFile file;
@@ -445,7 +450,7 @@ static int count_pattern(const char *pattern, const char *path, bool in_archive)
   if (in_archive && file.status == -1) { printf("Archive not found.\n"); return -1; }
   if (in_archive && (file.status != 0 || file.size() == 0)) { printf("Could not read Archive.\n"); return -2; }
   if (!in_archive && (file.status != 0 || file.size() == 0 || file.size() >= kMaxInput)) { printf("Error loading file\n"); return -1; }
-  if (rc0 != 0 || !bce_hip_count) { printf("No usable HIP device: %s\n", bce_hip_strerror(rc0 ? rc0 : BCE_HIP_E_DEVICE)); return -3; }
+  if (rc0 != 0 || !bce_hip_count || (locate && !bce_hip_locate)) { printf("No usable HIP device: %s\n", bce_hip_strerror(rc0 ? rc0 : BCE_HIP_E_DEVICE)); return -3; }
   const uint8_t *text = file.data();
   size_t n = file.size();
   std::vector<uint8_t> decoded;
@@ -483,15 +488,27 @@ static int count_pattern(const char *pattern, const char *path, bool in_archive)
     n = decoded.size();
   }
   uint64_t count = 0;
+  std::vector<uint32_t> where;
   if (m <= n) {                                                     // (a longer pattern occurs nowhere in the text, only around it)
     const uint64_t offsets[2] = {0, m};
     int rc = bce_hip_load_host(ctx, text, (uint32_t)n);
     if (rc == 0) rc = bce_hip_bwt(ctx, nullptr);
     if (rc == 0) rc = bce_hip_build_planes(ctx, nullptr);
-    if (rc == 0) rc = bce_hip_count(ctx, pat, offsets, 1, &count);
-    if (rc != 0) { printf("Count failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); return -4; }
-    count -= seam_matches(text, n, pat, m);
+    if (locate) {
+      uint64_t hits[2] = {0, 0};
+      if (rc == 0) rc = bce_hip_locate(ctx, pat, offsets, 1, BCE_HIP_LOCATE_LINEAR, hits, nullptr, 0, &count);   // how many
+      if (rc == 0 && count) {
+        where.resize(count);
+        rc = bce_hip_locate(ctx, pat, offsets, 1, BCE_HIP_LOCATE_LINEAR, hits, where.data(), count, &count);
+      }
+      if (rc != 0) { printf("Locate failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); return -4; }
+    } else {
+      if (rc == 0) rc = bce_hip_count(ctx, pat, offsets, 1, &count);
+      if (rc != 0) { printf("Count failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); return -4; }
+      count -= seam_matches(text, n, pat, m);
+    }
   }
+  for (uint32_t at : where) printf("%u\n", at);
   printf("%llu occurrences\n", (unsigned long long)count);
   ctx = nullptr;                                                    // (left to fast_exit, like -d)
   fast_exit(0);
@@ -528,6 +545,12 @@ static int usage() {
   printf("\n");
   printf("  bce -gd PATTERN archive.bce\n");
   printf("   The same count in what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
+  printf("\n");
+  printf("  bce -gl PATTERN file\n");
+  printf("   Prints where the bytes of PATTERN occur in \"file\": the byte offsets, one per line, ascending, then the count; they come from the index and the suffix array on the GPU (extension)\n");
+  printf("\n");
+  printf("  bce -gld PATTERN archive.bce\n");
+  printf("   The same offsets in what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
   return 0;
 }
 
@@ -796,7 +819,9 @@ int main(int argc, char **argv) {
   } else if ((argc == 3 || argc == 4) && argv[1][0] == '-' && argv[1][1] == 'e' && argv[1][2] == 0) {
     return estimate_file(argv[2], argc == 4 ? argv[3] : nullptr);
   } else if (argc == 4 && argv[2][0] != 0 && (strcmp(argv[1], "-g") == 0 || strcmp(argv[1], "-gd") == 0)) {
-    return count_pattern(argv[2], argv[3], argv[1][2] == 'd');
+    return count_pattern(argv[2], argv[3], argv[1][2] == 'd', false);
+  } else if (argc == 4 && argv[2][0] != 0 && (strcmp(argv[1], "-gl") == 0 || strcmp(argv[1], "-gld") == 0)) {
+    return count_pattern(argv[2], argv[3], argv[1][3] == 'd', true);
   } else if (argc == 4 && argv[1][0] == '-' && argv[1][1] == 's') {
     // Scan (bce.cpp:1384-1402): enumeration on the GPU, ScanCoder optimisation on the host, 288-byte config out
     auto start = std::chrono::high_resolution_clock::now();

@@ -12,6 +12,7 @@ Stream rule.  The library runs on a stream of its own and knows nothing of torch
 the tensor's CURRENT torch stream on the tensor's device before the call -- whatever produced `t` / `out` there must be
 done -- and the call returns only when the library's stream is idle: the result may be used from any stream at once.
 A tensor produced on another, non-current stream has to be synchronised by the caller."""
+import numpy as np
 import torch
 
 from . import api, container
@@ -92,6 +93,54 @@ def count_in_archive(blob, patterns, device="cuda:0"):
     if total > _MAX_BLOCK:
         raise ValueError("the archive holds %d bytes: one index covers one text of less than 2^31" % total)
     return count_tensor(decompress_container_tensor(blob, device=device), patterns)
+
+
+def locate_tensor(t, patterns, cyclic=False, ctx=None):
+    """Where `patterns` (one bytes-like or a sequence of them) occur in the 1-D uint8 CUDA tensor `t` (or slice, any offset) ->
+    (offsets, positions), both tensors on t's device: int64[npat + 1] and int32[total] (positions are below 2^31).  Pattern p owns
+    positions[offsets[p]:offsets[p + 1]], ascending byte offsets into t.  cyclic: as api.RankFile.locate (False: an empty pattern
+    raises ValueError).  The text is indexed where it lies and the hits are gathered, filtered and ordered there
+    (bce_hip_locate_device, a sizing call first); of the answer only its total reaches the host.
+    Synchronises t's current stream first; `ctx` (an api._Ctx of t's device) is reused if given."""
+    _check(t, "t")
+    n = t.numel()
+    if n == 0:
+        raise api.BceError(-1, "locate_tensor", "empty input")
+    if n > _MAX_BLOCK:
+        raise ValueError("one index covers one text of less than 2^31 bytes, not %d" % n)
+    pats = [api._as_u8(patterns)] if api._is_one_pattern(patterns) else [api._as_u8(p) for p in patterns]
+    if not cyclic and any(len(p) == 0 for p in pats):
+        raise ValueError("an empty pattern has no linear hits (cyclic=True: every position)")
+    offsets = torch.zeros(len(pats) + 1, dtype=torch.int64, device=t.device)
+    if not pats:
+        return offsets, torch.empty(0, dtype=torch.int32, device=t.device)
+    lens = np.zeros(len(pats) + 1, dtype=np.int64)
+    lens[1:] = np.cumsum([len(p) for p in pats], dtype=np.int64)
+    flat = np.concatenate(pats) if int(lens[-1]) else np.zeros(1, dtype=np.uint8)
+    d_pat, d_off = torch.from_numpy(flat).to(t.device), torch.from_numpy(lens).to(t.device)
+    _ready(t)
+    own = ctx is None
+    c = ctx or api._Ctx(t.device.index)
+    try:
+        rf = api.RankFile(n=n, device_ptr=t.data_ptr(), ctx=c)
+        total = rf.locate_device(d_pat.data_ptr(), d_off.data_ptr(), len(pats), offsets.data_ptr(), None, 0, cyclic=cyclic)
+        positions = torch.empty(total, dtype=torch.int32, device=t.device)
+        if total:
+            torch.cuda.current_stream(t.device).synchronize()        # (the allocator may hand out memory a queued kernel still uses)
+            rf.locate_device(d_pat.data_ptr(), d_off.data_ptr(), len(pats), offsets.data_ptr(), positions.data_ptr(), total, cyclic=cyclic)
+        return offsets, positions
+    finally:
+        if own:
+            c.close()
+
+
+def locate_in_archive(blob, patterns, cyclic=False, device="cuda:0"):
+    """locate_tensor on what an archive holds, decoded as count_in_archive decodes it: into ONE tensor on the device, so the
+    offsets run over the concatenated blocks and hits across block boundaries are found.  -> (offsets, positions) on `device`."""
+    total = sum(t[0] for t in _blocks_of(blob))
+    if total > _MAX_BLOCK:
+        raise ValueError("the archive holds %d bytes: one index covers one text of less than 2^31" % total)
+    return locate_tensor(decompress_container_tensor(blob, device=device), patterns, cyclic=cyclic)
 
 
 def decompress_tensor(archive, device="cuda:0", out=None, ctx=None):

@@ -304,6 +304,35 @@ int bce_hip_count_device(bce_hip_ctx *ctx, const void *d_patterns, const void *d
  * BCE_HIP_E_ARG. */
 int bce_hip_input_bytes(bce_hip_ctx *ctx, uint64_t pos, size_t len, uint8_t *out);
 
+/* ---- extension: WHERE byte strings occur in the input, from the planes and K1's suffix array (kd_locate.hip, fm_step.h) --------
+ * Backward search ends at an interval [lo, hi) of the sorted rotations, and bce_hip_bwt leaves their order -- the suffix array,
+ * 4 n bytes the depth-first tail of the enumeration needs anyway -- in device memory: the occurrences are sa[lo .. hi).  No samples.
+ *   cyclic hits (flags == 0): the i in [0, n) with P[k] == T[(i + k) mod n] for all k < m: the set bce_hip_count counts.  Defined
+ *     for m == 0 (every i) and m > n; in a periodic text every tied rotation is a hit.
+ *   linear hits (BCE_HIP_LOCATE_LINEAR): those with i + m <= n, what an overlapping scan of the text finds; none for m > n.  The
+ *     filter runs on the device.
+ * Patterns arrive as for bce_hip_count.  The answer is CSR: hit_offsets[npat + 1], hit_offsets[0] == 0, pattern p owns
+ * positions[hit_offsets[p] .. hit_offsets[p + 1]), ascending; hit_offsets is exact in both modes (its differences are the counts)
+ * and *total (a host value) is its last word.
+ * Overflow protocol: hit_offsets and *total are written whenever the call gets as far as the search.  positions == NULL with
+ * cap == 0 is a sizing call and succeeds.  total > cap: BCE_HIP_E_OVERFLOW, hit_offsets and *total valid, no byte of positions
+ * written.  One call gathers at most 2^31 - 1 cyclic rows (the sum of the patterns' cyclic counts, also in linear mode): beyond
+ * that BCE_HIP_E_OVERFLOW with hit_offsets and *total exact, whatever cap is -- split the batch.
+ * Valid while the planes stand (bce_hip_count's rule) AND the suffix array does: from bce_hip_build_planes after bce_hip_bwt,
+ * through bce_hip_encode / _estimate / _scan / _count and after them, until the next load or decode.  After bce_hip_set_bwt:
+ * BCE_HIP_E_STATE, "no suffix array behind an injected BWT".  Neither call changes the compression state.  npat == 0: success,
+ * *total = 0, hit_offsets[0] = 0 where given.  A null ctx or total, a null array with npat > 0 (positions may be NULL only with
+ * cap == 0), flag bits other than BCE_HIP_LOCATE_LINEAR, offsets that decrease: BCE_HIP_E_ARG.  Order of the checks, as for
+ * bce_hip_count: ctx, total and flags first, then npat == 0, then the context's state (BCE_HIP_E_STATE wins over a null array), then
+ * the arrays.  A sizing call and the full call that follows it each run the search. */
+#define BCE_HIP_LOCATE_LINEAR 1u
+int bce_hip_locate(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t flags,
+                   uint64_t *hit_offsets, uint32_t *positions, uint64_t cap, uint64_t *total);
+/* The same with patterns, offsets, hit offsets and positions in device memory of the context's device (8-byte and 4-byte words
+ * aligned as such); total stays a host pointer.  Stream rule and the kernel's offset check: as bce_hip_count_device. */
+int bce_hip_locate_device(bce_hip_ctx *ctx, const void *d_patterns, const void *d_offsets, uint32_t npat, uint32_t flags,
+                          void *d_hit_offsets, void *d_positions, uint64_t cap, uint64_t *total);
+
 /* ---- test hooks: the device primitives every stage rests on, alone (tests/test_gpu_sort.py, tests/test_gpu_compare.py) ----
  * Stream rule of bce_hip_crc32_device for all three: the work runs on the context's stream and is complete on return; the caller's
  * memory (device memory of the context's device) must be ready when the call is made.  Valid in any state of the context, between
