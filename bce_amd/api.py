@@ -107,6 +107,8 @@ SYMBOLS = [
     ("bce_hip_sort_pairs_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("bce_hip_sort_wide_device", C.c_int, [C.c_void_p, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("bce_hip_compare_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_size_t, C.POINTER(C.c_uint64)]),
+    ("bce_hip_planes_from_ranks_device", C.c_int, [C.c_void_p, _vp, C.c_uint32, _vp, _vp, _vp]),
+    ("bce_hip_unbwt_device", C.c_int, [C.c_void_p, _vp, C.c_uint32, C.c_uint32, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("bce_hip_count", C.c_int, [C.c_void_p, _u8p, _vp, C.c_uint32, _vp]),
     ("bce_hip_count_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, _vp]),
     ("bce_hip_input_bytes", C.c_int, [C.c_void_p, C.c_uint64, C.c_size_t, _u8p]),
@@ -835,6 +837,25 @@ def compare_device(ptr_a, ptr_b, n, ctx):
     ctx.check(ctx.lib.bce_hip_compare_device(ctx.h, None if ptr_a is None else int(ptr_a), None if ptr_b is None else int(ptr_b),
                                              int(n), C.byref(fd)), "bce_hip_compare_device")
     return None if fd.value == _NO_DIFF else fd.value
+
+
+def _ptr(p):
+    return None if p is None else int(p)
+
+
+def planes_from_ranks_device(ptr_R, n, ptr_bwt, ctx, ptr_words=None, ptr_rankw=None):
+    """Test hook (bce_hip_planes_from_ranks_device): the decoder's planes stage -- boundary ranks u32 [8][n + 1] at device pointer
+    `ptr_R` (0xFFFFFFFF = unknown) -> the n BWT bytes at `ptr_bwt`, and the plane words / word ranks (u32 [8][(n + 31) // 32 + 3]
+    each) where asked for.  -> the status (0, or a negative BCE_HIP_E_* that the caller asserts); ctx.error() has the message."""
+    return ctx.lib.bce_hip_planes_from_ranks_device(ctx.h, _ptr(ptr_R), int(n), _ptr(ptr_bwt), _ptr(ptr_words), _ptr(ptr_rankw))
+
+
+def unbwt_device(ptr_bwt, n, offset, ptr_out, ctx):
+    """Test hook (bce_hip_unbwt_device): the decoder's inverse BWT of the n bytes at device pointer `ptr_bwt` into `ptr_out`, text
+    position i at (i + offset) % n.  -> (status, LF cycle length, walkers)."""
+    lc, m = C.c_uint64(0), C.c_uint32(0)
+    rc = ctx.lib.bce_hip_unbwt_device(ctx.h, _ptr(ptr_bwt), int(n), int(offset), _ptr(ptr_out), C.byref(lc), C.byref(m))
+    return rc, lc.value, m.value
 
 
 def sort_pairs_device(ptr_key, ptr_val, n, first_bit, bits, max_digit_bits, ctx):

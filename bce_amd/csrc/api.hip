@@ -1404,6 +1404,30 @@ int bce_hip_compare_device(bce_hip_ctx *c, const void *d_a, const void *d_b, siz
   });
 }
 
+// ---- test hooks: the decoder's back end alone (kd_decode.hip) ---------------------------------------------------
+// Phase 4 as a decode's: the context's compression state is dropped, the buffers written are the ones a decode's planes() and
+// inverse_bwt() write.
+int bce_hip_planes_from_ranks_device(bce_hip_ctx *c, const void *d_R, uint32_t n, void *d_bwt_out, void *d_words_out, void *d_rankw_out) {
+  if (!c || !d_R || !d_bwt_out || n == 0 || n >= 0x7FFFFFFFu) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    c->coder->drain();
+    PhaseScope phase(c, 4);
+    return kd_planes_from_ranks(c, static_cast<const uint32_t *>(d_R), n, static_cast<uint8_t *>(d_bwt_out),
+                                static_cast<uint32_t *>(d_words_out), static_cast<uint32_t *>(d_rankw_out));
+  });
+}
+
+int bce_hip_unbwt_device(bce_hip_ctx *c, const void *d_bwt, uint32_t n, uint32_t offset, void *d_out, uint64_t *cycle_len, uint32_t *walkers) {
+  if (!c || !d_bwt || !d_out || n == 0 || n >= 0x7FFFFFFFu) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    c->coder->drain();
+    PhaseScope phase(c, 4);
+    return kd_unbwt(c, static_cast<const uint8_t *>(d_bwt), n, offset, static_cast<uint8_t *>(d_out), cycle_len, walkers);
+  });
+}
+
 // ---- pattern counts from the planes (kd_count.hip) ---------------------------------------------------------
 // Phase 3, as bce_hip_rank1: the planes are read, so what an allocation may give back is what an enumeration beside them would.
 // Nothing a stage keeps is written: the staging buffers and the flag word are the count's own.

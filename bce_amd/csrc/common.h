@@ -420,6 +420,9 @@ inline uint32_t ceil_log2(uint32_t v) { uint32_t b = 0; while ((1ull << b) < v) 
 int k1_bwt(bce_hip_ctx *c);                         // k1_bwt.hip
 int k1_divbwt(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n, uint32_t *pidx);   // the libdivsufsort seam
 int kd_inverse_bw_transform(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n, uint32_t idx);   // kd_decode.hip
+// kd_decode.hip, test hooks: the decoder's planes() and inverse_bwt() stages on arrays of the caller's in device memory
+int kd_planes_from_ranks(bce_hip_ctx *c, const uint32_t *d_R, uint32_t n, uint8_t *d_bwt, uint32_t *d_words, uint32_t *d_rankw);
+int kd_unbwt(bce_hip_ctx *c, const uint8_t *d_bwt, uint32_t n, uint32_t offset, uint8_t *d_out, uint64_t *cycle, uint32_t *walkers);
 int kd_compare(bce_hip_ctx *c, const uint8_t *a, const uint8_t *b, uint64_t m, uint64_t *first_diff);   // kd_compare.hip: first differing byte of two device buffers
 int kd_crc32(bce_hip_ctx *c, const uint8_t *d, uint64_t n, uint32_t *crc);   // kd_crc32.hip: CRC-32 (zlib's) of a device buffer
 // kd_count.hip: d_out[p] = occurrences of d_pat[d_off[p], d_off[p + 1]) in the circular text of the context's planes (device arrays)

@@ -1808,6 +1808,85 @@ struct RoundPlan {
 uint32_t plane_words(uint32_t n) { return (uint32_t)(((uint64_t)n + 31) / 32) + 3; }   // of a plane's bits, with slack
 uint32_t plane_granules(uint32_t n) { return (uint32_t)((uint64_t)n / 96) + 2; }
 
+// ---- R -> planes -> granules -> BWT bytes (Decode::planes; alone: kd_planes_from_ranks) ----
+// R: the boundary ranks [8][n + 1] in device memory, zeros[p] = n - R[p][n].  The bytes land in c->bwt; the plane words and word
+// ranks stay in c->key[0] / c->key[1] (*words, *rankw: [8][plane_words(n)]) until the inverse BWT sorts there.  own_text: the
+// context's text buffer is made ready beside the BWT's.  sample_mem(): called after each allocation stage.
+template <class Sample>
+int planes_stage(bce_hip_ctx *c, const uint32_t *R, uint32_t n, const uint32_t zeros[8], bool own_text, Sample &&sample_mem,
+                 const uint32_t **words = nullptr, const uint32_t **rankw = nullptr) {
+  const size_t rstride = (size_t)n + 1;
+  FillArgs f;
+  f.R = R; f.n = n;
+  f.chunks = (uint32_t)(((uint64_t)n + 1 + FG_CHUNK - 1) / FG_CHUNK);
+  f.nwords = plane_words(n);
+  const uint32_t ngran = plane_granules(n);
+  BCE_TRY(ensure(c, c->blk, (size_t)8 * f.chunks * 4 + 64));
+  f.cmax = c->blk.as<uint32_t>();
+  f.err = f.cmax + (size_t)8 * f.chunks;
+  BCE_TRY(ensure(c, c->sa[0], 8 * rstride));                   // gap types
+  f.type = c->sa[0].as<uint8_t>();
+  BCE_TRY(ensure(c, c->key[0], (size_t)8 * f.nwords * 4));
+  BCE_TRY(ensure(c, c->key[1], (size_t)8 * f.nwords * 4));
+  f.words = c->key[0].as<uint32_t>();
+  f.rankw = c->key[1].as<uint32_t>();
+  if (words) *words = f.words;
+  if (rankw) *rankw = f.rankw;
+  BCE_TRY(ensure(c, c->gran, (size_t)8 * ngran * sizeof(Granule)));
+  sample_mem();
+  BCE_HIP_TRY(c, hipMemsetAsync(f.err, 0, 4, c->stream));
+  BCE_HIP_TRY(c, hipMemsetAsync(f.words, 0, (size_t)8 * f.nwords * 4, c->stream));
+  BCE_HIP_TRY(c, hipMemsetAsync(f.rankw, 0, (size_t)8 * f.nwords * 4, c->stream));
+  hipLaunchKernelGGL(fill_chunkmax_kernel, dim3(f.chunks, 8), dim3(FG_T), 0, c->stream, f);
+  hipLaunchKernelGGL(fill_chunkscan_kernel, dim3(8), dim3(1024), 0, c->stream, f);
+  hipLaunchKernelGGL((fill_kernel<0>), dim3(f.chunks, 8), dim3(FG_T), 0, c->stream, f);
+  hipLaunchKernelGGL((fill_kernel<1>), dim3(f.chunks, 8), dim3(FG_T), 0, c->stream, f);
+  const uint32_t gb = (ngran + 255) / 256;
+  hipLaunchKernelGGL(gran_from_words_kernel, dim3(gb < 4096 ? gb : 4096, 8), dim3(256), 0, c->stream, f, c->gran.as<Granule>(), ngran);
+  uint32_t ferr = 0;
+  BCE_TRY(read_back(c, &ferr, f.err, 4));
+  BCE_HIP_TRY(c, hipGetLastError());
+  if (ferr) { snprintf(c->err, sizeof c->err, "decode: a mixed gap was never split"); return BCE_HIP_E_INTERNAL; }
+  BCE_TRY(ensure(c, c->bwt, n));
+  if (own_text) BCE_TRY(ensure(c, c->text, n));
+  BCE_TRY(ensure(c, c->stat, 64));
+  sample_mem();
+  uint32_t *dz = c->stat.as<uint32_t>();
+  BCE_HIP_TRY(c, hipMemcpyAsync(dz, zeros, 32, hipMemcpyHostToDevice, c->stream));
+  BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  hipLaunchKernelGGL(access_kernel, dim3(grid256(n)), dim3(256), 0, c->stream, c->gran.as<Granule>(), ngran, n, dz, c->bwt.as<uint8_t>());
+  return BCE_HIP_OK;
+}
+
+// ---- inverse BWT (Decode::inverse_bwt; alone: kd_unbwt) ----
+// The n bytes of c->bwt -> the text, position i at text[(i + off) % n] (off < n; device memory, any alignment).  One cycle through
+// all n rows for a primitive input; a shorter cycle (length lc, the input's period pattern in BWT terms) otherwise, written once
+// into V (the sort's value buffers are free again) and then unrolled.  *lc, *walkers: as lf_walk reports them, set on the
+// error return as well (no cycle through row 0 of a length that divides n: nothing is written to `text`).
+template <class Sample>
+int unbwt_stage(bce_hip_ctx *c, uint32_t n, uint32_t off, uint8_t *text, Sample &&sample_mem, uint64_t *lc, uint32_t *walkers) {
+  const size_t b4 = (size_t)n * 4;
+  const uint32_t gn = grid256(n);
+  for (int i = 0; i < 2; ++i) { BCE_TRY(ensure(c, c->sa[i], b4)); BCE_TRY(ensure(c, c->key[i], b4)); }
+  BCE_TRY(ensure(c, c->rank, b4));
+  sample_mem();
+  uint32_t *key[2] = {c->key[0].as<uint32_t>(), c->key[1].as<uint32_t>()};
+  uint32_t *val[2] = {c->sa[0].as<uint32_t>(), c->sa[1].as<uint32_t>()};
+  uint32_t *lf = c->rank.as<uint32_t>();
+  hipLaunchKernelGGL(lf_keys_kernel, dim3(gn), dim3(256), 0, c->stream, c->bwt.as<uint8_t>(), n, key[0], val[0]);
+  int res = 0;
+  BCE_TRY(radix_sort_pairs(c, key, val, n, 0, 8, &res, 8));
+  sample_mem();                                                 // (the sort's histograms)
+  hipLaunchKernelGGL(lf_scatter_kernel, dim3(gn), dim3(256), 0, c->stream, val[res], n, lf);
+  uint8_t *V = reinterpret_cast<uint8_t *>(val[0]);
+  *lc = 0; *walkers = 0;
+  BCE_TRY(lf_walk(c, lf, c->bwt.as<uint8_t>(), n, text, n, off, V, lc, walkers));
+  if (*lc == 0 || *lc > n || n % *lc) { snprintf(c->err, sizeof c->err, "decode: LF cycle of length %llu in %u rows", (unsigned long long)*lc, n); return BCE_HIP_E_INTERNAL; }
+  // periodic input (the reference's decoder returns zeros here)
+  if (*lc != n) hipLaunchKernelGGL(expand_cycle_kernel, dim3(gn), dim3(256), 0, c->stream, V, (uint32_t)*lc, n, off, text);
+  return BCE_HIP_OK;
+}
+
 // One decode: the state its stages share.  decompress_device runs the stages in order.
 struct Decode {
   bce_hip_ctx *c;
@@ -2486,43 +2565,7 @@ struct Decode {
 
   // ---- R -> planes -> granules -> BWT bytes ----
   int planes() {
-    FillArgs f;
-    f.R = a.R; f.n = n;
-    f.chunks = (uint32_t)(((uint64_t)n + 1 + FG_CHUNK - 1) / FG_CHUNK);
-    f.nwords = plane_words(n);
-    const uint32_t ngran = plane_granules(n);
-    BCE_TRY(ensure(c, c->blk, (size_t)8 * f.chunks * 4 + 64));
-    f.cmax = c->blk.as<uint32_t>();
-    f.err = f.cmax + (size_t)8 * f.chunks;
-    BCE_TRY(ensure(c, c->sa[0], 8 * rstride));                   // gap types
-    f.type = c->sa[0].as<uint8_t>();
-    BCE_TRY(ensure(c, c->key[0], (size_t)8 * f.nwords * 4));
-    BCE_TRY(ensure(c, c->key[1], (size_t)8 * f.nwords * 4));
-    f.words = c->key[0].as<uint32_t>();
-    f.rankw = c->key[1].as<uint32_t>();
-    BCE_TRY(ensure(c, c->gran, (size_t)8 * ngran * sizeof(Granule)));
-    sample_mem();
-    BCE_HIP_TRY(c, hipMemsetAsync(f.err, 0, 4, c->stream));
-    BCE_HIP_TRY(c, hipMemsetAsync(f.words, 0, (size_t)8 * f.nwords * 4, c->stream));
-    BCE_HIP_TRY(c, hipMemsetAsync(f.rankw, 0, (size_t)8 * f.nwords * 4, c->stream));
-    hipLaunchKernelGGL(fill_chunkmax_kernel, dim3(f.chunks, 8), dim3(FG_T), 0, c->stream, f);
-    hipLaunchKernelGGL(fill_chunkscan_kernel, dim3(8), dim3(1024), 0, c->stream, f);
-    hipLaunchKernelGGL((fill_kernel<0>), dim3(f.chunks, 8), dim3(FG_T), 0, c->stream, f);
-    hipLaunchKernelGGL((fill_kernel<1>), dim3(f.chunks, 8), dim3(FG_T), 0, c->stream, f);
-    const uint32_t gb = (ngran + 255) / 256;
-    hipLaunchKernelGGL(gran_from_words_kernel, dim3(gb < 4096 ? gb : 4096, 8), dim3(256), 0, c->stream, f, c->gran.as<Granule>(), ngran);
-    uint32_t ferr = 0;
-    BCE_TRY(read_back(c, &ferr, f.err, 4));
-    BCE_HIP_TRY(c, hipGetLastError());
-    if (ferr) { snprintf(c->err, sizeof c->err, "decode: a mixed gap was never split"); return BCE_HIP_E_INTERNAL; }
-    BCE_TRY(ensure(c, c->bwt, n));
-    if (dest.own_text()) BCE_TRY(ensure(c, c->text, n));
-    BCE_TRY(ensure(c, c->stat, 64));
-    sample_mem();
-    uint32_t *dz = c->stat.as<uint32_t>();
-    BCE_HIP_TRY(c, hipMemcpyAsync(dz, a.zeros, 32, hipMemcpyHostToDevice, c->stream));
-    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    hipLaunchKernelGGL(access_kernel, dim3(grid256(n)), dim3(256), 0, c->stream, c->gran.as<Granule>(), ngran, n, dz, c->bwt.as<uint8_t>());
+    BCE_TRY(planes_stage(c, a.R, n, a.zeros, dest.own_text(), [this] { sample_mem(); }));
     if (env.timing) { BCE_HIP_TRY(c, hipStreamSynchronize(c->stream)); fprintf(stderr, "gpu decode: planes + unbwt %.3f s\n", now_s() - tp0); tp0 = now_s(); }
     return BCE_HIP_OK;
   }
@@ -2532,30 +2575,10 @@ struct Decode {
   // straight into the caller's device memory (kDevice), or into the context's buffer and compared there (kCompare).
   int inverse_bwt() {
     uint8_t *const text = dest.own_text() ? c->text.as<uint8_t>() : dest.out;
-    const size_t b4 = (size_t)n * 4;
-    const uint32_t gn = grid256(n);
-    for (int i = 0; i < 2; ++i) { BCE_TRY(ensure(c, c->sa[i], b4)); BCE_TRY(ensure(c, c->key[i], b4)); }
-    BCE_TRY(ensure(c, c->rank, b4));
-    sample_mem();
-    uint32_t *key[2] = {c->key[0].as<uint32_t>(), c->key[1].as<uint32_t>()};
-    uint32_t *val[2] = {c->sa[0].as<uint32_t>(), c->sa[1].as<uint32_t>()};
-    uint32_t *lf = c->rank.as<uint32_t>();
-    hipLaunchKernelGGL(lf_keys_kernel, dim3(gn), dim3(256), 0, c->stream, c->bwt.as<uint8_t>(), n, key[0], val[0]);
-    int res = 0;
-    BCE_TRY(radix_sort_pairs(c, key, val, n, 0, 8, &res, 8));
-    sample_mem();                                                 // (the sort's histograms)
-    hipLaunchKernelGGL(lf_scatter_kernel, dim3(gn), dim3(256), 0, c->stream, val[res], n, lf);
-    // one cycle through all n rows for a primitive input; a shorter cycle (length lc, the input's period pattern in BWT terms)
-    // otherwise, written once into V (the sort's value buffers are free again) and then unrolled
-    const uint32_t off = hd.offset % n;
-    uint8_t *V = reinterpret_cast<uint8_t *>(val[0]);
     uint64_t lc = 0;
     uint32_t walkers = 0;
-    BCE_TRY(lf_walk(c, lf, c->bwt.as<uint8_t>(), n, text, n, off, V, &lc, &walkers));
-    if (lc == 0 || lc > n || n % lc) { snprintf(c->err, sizeof c->err, "decode: LF cycle of length %llu in %u rows", (unsigned long long)lc, n); return BCE_HIP_E_INTERNAL; }
+    BCE_TRY(unbwt_stage(c, n, hd.offset % n, text, [this] { sample_mem(); }, &lc, &walkers));
     const bool single_cycle = lc == n;
-    // periodic input (the reference's decoder returns zeros here)
-    if (!single_cycle) hipLaunchKernelGGL(expand_cycle_kernel, dim3(gn), dim3(256), 0, c->stream, V, (uint32_t)lc, n, off, text);
     if (dest.crc && dest.own_text()) BCE_TRY(checksum());
     if (dest.kind == DecDest::kHost) BCE_HIP_TRY(c, hipMemcpyAsync(dest.out, c->text.p, n, hipMemcpyDeviceToHost, c->stream));
     BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2601,6 +2624,50 @@ struct Decode {
 
 
 }  // namespace
+
+// ---- test hooks: the back end alone (bce_hip_planes_from_ranks_device, bce_hip_unbwt_device) ----
+// The stages above on arrays of the caller's, in a context whose compression state is dropped as a decode drops it; the context's
+// buffers are the decoder's own, so a later encode or decode finds them as after a decode.
+int kd_planes_from_ranks(bce_hip_ctx *c, const uint32_t *d_R, uint32_t n, uint8_t *d_bwt, uint32_t *d_words, uint32_t *d_rankw) {
+  const size_t rstride = (size_t)n + 1;
+  uint32_t zeros[8];
+  for (int p = 0; p < 8; ++p) {                                  // the two ends of every plane are known: R[p][0] = 0, R[p][n] = its ones
+    uint32_t r0 = 0, rn = 0;
+    BCE_TRY(read_back(c, &r0, d_R + (size_t)p * rstride, 4));
+    BCE_TRY(read_back(c, &rn, d_R + (size_t)p * rstride + n, 4));
+    if (r0 != 0 || rn > n) { snprintf(c->err, sizeof c->err, "planes from ranks: R[%d][0] = %u, R[%d][n] = %u with n = %u", p, r0, p, rn, n); return BCE_HIP_E_ARG; }
+    zeros[p] = n - rn;
+  }
+  c->stage = 0; c->enum_active = false; c->k1_valid = false; c->text_loaded = false;
+  struct PartEnd { bce_hip_ctx *c; ~PartEnd() { c->dec_part = 0; } } part_end{c};
+  c->dec_part = 2;
+  const uint32_t *words = nullptr, *rankw = nullptr;
+  BCE_TRY(planes_stage(c, d_R, n, zeros, false, [] {}, &words, &rankw));
+  const size_t wb = (size_t)8 * plane_words(n) * 4;
+  if (d_words) BCE_HIP_TRY(c, hipMemcpyAsync(d_words, words, wb, hipMemcpyDeviceToDevice, c->stream));
+  if (d_rankw) BCE_HIP_TRY(c, hipMemcpyAsync(d_rankw, rankw, wb, hipMemcpyDeviceToDevice, c->stream));
+  BCE_HIP_TRY(c, hipMemcpyAsync(d_bwt, c->bwt.p, n, hipMemcpyDeviceToDevice, c->stream));
+  BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  BCE_HIP_TRY(c, hipGetLastError());
+  return BCE_HIP_OK;
+}
+
+int kd_unbwt(bce_hip_ctx *c, const uint8_t *d_bwt, uint32_t n, uint32_t offset, uint8_t *d_out, uint64_t *cycle, uint32_t *walkers) {
+  c->stage = 0; c->enum_active = false; c->k1_valid = false; c->text_loaded = false;
+  struct PartEnd { bce_hip_ctx *c; ~PartEnd() { c->dec_part = 0; } } part_end{c};
+  c->dec_part = 3;
+  BCE_TRY(ensure(c, c->bwt, n));
+  BCE_HIP_TRY(c, hipMemcpyAsync(c->bwt.p, d_bwt, n, hipMemcpyDeviceToDevice, c->stream));
+  uint64_t lc = 0;
+  uint32_t m = 0;
+  const int rc = unbwt_stage(c, n, offset % n, d_out, [] {}, &lc, &m);
+  if (cycle) *cycle = lc;
+  if (walkers) *walkers = m;
+  if (rc != BCE_HIP_OK) { (void)hipStreamSynchronize(c->stream); return rc; }   // (nothing of the caller's is in flight on return)
+  BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  BCE_HIP_TRY(c, hipGetLastError());
+  return BCE_HIP_OK;
+}
 
 }  // namespace bce
 

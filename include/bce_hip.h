@@ -354,6 +354,33 @@ int bce_hip_sort_wide_device(bce_hip_ctx *ctx, void *d_lo, void *d_hi, void *d_v
  * Reads [0, n) of both and nothing else.  A null ctx or first_diff, n > 0 with a null buffer: BCE_HIP_E_ARG. */
 int bce_hip_compare_device(bce_hip_ctx *ctx, const void *d_a, const void *d_b, size_t n, uint64_t *first_diff);
 
+/* ---- test hooks: the back end of the GPU decoder alone (kd_decode.hip; tests/test_gpu_unbwt.py) ----
+ * The two stages a decode runs after its last round, on arrays of the caller's in device memory of the context's device, with the
+ * launches and launch geometry of a decode (the decoder calls the same two functions).  Stream rule of the hooks above.  Unlike
+ * them these two are a decode as far as the context goes: whatever compression state it holds is dropped (as by any decode) and
+ * the decoder's scratch buffers are written, so they are valid wherever a decode is, and an encode or decode that follows finds
+ * the context as after a decode.  n == 0, n >= 2^31 - 1 or a null ctx / required pointer: BCE_HIP_E_ARG, before any device work. */
+/* Test hook: boundary ranks -> plane words and word ranks -> rank granules -> BWT bytes (fill_*_kernel, gran_from_words_kernel,
+ * access_kernel).  d_R: u32 [8][n + 1], R[p][i] = the ones of plane p in front of position i where known, 0xFFFFFFFF where not.
+ * R[p][0] (which must be 0) and R[p][n] must be known -- anything else, or R[p][n] > n: BCE_HIP_E_ARG, read from the device before
+ * anything is launched -- and between two neighbouring known indices a plane must be constant.  The planes' zero counts are taken
+ * from the array as the decoder takes them from the archive's header, zeros[p] = n - R[p][n].  A gap that is neither all zeros nor
+ * all ones, or a rank that decreases: BCE_HIP_E_INTERNAL, "decode: a mixed gap was never split", with no output written.
+ * d_bwt_out: the n bytes.  d_words_out, d_rankw_out (each may be NULL): u32 [8][W], W = (n + 31) / 32 + 3 -- the plane bits LSB
+ * first and the rank at each word's first position, zero in the words wholly past n (the rank of the word that starts AT n
+ * is kept). */
+int bce_hip_planes_from_ranks_device(bce_hip_ctx *ctx, const void *d_R, uint32_t n, void *d_bwt_out, void *d_words_out,
+                                     void *d_rankw_out);
+/* Test hook: the inverse BWT (lf_keys_kernel, one 8-bit radix pass, lf_scatter_kernel, the concurrent walkers of lf_walk, and
+ * expand_cycle_kernel for a periodic text) of the n bytes at d_bwt into d_out (any alignment; it may not overlap d_bwt): text
+ * position i lands at d_out[(i + offset) % n].  `offset` is reduced modulo n here, as the decoder reduces the archive's.
+ * *cycle_len (may be NULL): the length of the LF cycle through row 0 -- n for a primitive text, the period's share for a periodic
+ * one; *walkers (may be NULL): the walkers launched, ((n - 1) >> sh) + 1.  Both are set on BCE_HIP_E_INTERNAL as well: "decode: LF
+ * cycle of length L in n rows" -- L does not divide n, or is 0 (a walker's segment met twice) -- and then nothing of d_out is
+ * written. */
+int bce_hip_unbwt_device(bce_hip_ctx *ctx, const void *d_bwt, uint32_t n, uint32_t offset, void *d_out, uint64_t *cycle_len,
+                         uint32_t *walkers);
+
 /* ---- statistics of the last bce_hip_encode / bce_hip_compress ------------------------------------ */
 typedef struct bce_hip_stats {
   uint64_t n;            /* input bytes */

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle
+import unbwt_ref
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -102,7 +103,14 @@ def test_bad_arguments(seam):
     assert seam.divbwt(a.ctypes.data, a.ctypes.data, None, 0) == 0
     assert seam.inverse_bw_transform(a.ctypes.data, a.ctypes.data, None, 8, 0) == -1
     assert seam.inverse_bw_transform(a.ctypes.data, a.ctypes.data, None, 8, 9) == -1
-    # bytes that are no BWT for this index: several LF cycles
+    # bytes that are no BWT for this index: several LF cycles, says the plain reference -- so -1, and nothing written
     bad = np.frombuffer(b"abababab", dtype=np.uint8).copy()
-    out = np.empty_like(bad)
-    assert seam.inverse_bw_transform(bad.ctypes.data, out.ctypes.data, None, 8, 1) in (-1, 0)
+    out = np.full(8, 0xA5, dtype=np.uint8)
+    assert unbwt_ref.seam_inverse(bad, 1) is None
+    assert seam.inverse_bw_transform(bad.ctypes.data, out.ctypes.data, None, 8, 1) == -1
+    assert (out == 0xA5).all()
+    # ... and for its own index one cycle: 0, and the text
+    u, p = oracle.divbwt(b"abababab")
+    good = np.frombuffer(u, dtype=np.uint8).copy()
+    assert unbwt_ref.seam_inverse(good, p).tobytes() == b"abababab"
+    assert seam.inverse_bw_transform(good.ctypes.data, out.ctypes.data, None, 8, p) == 0 and out.tobytes() == b"abababab"
