@@ -114,6 +114,10 @@ SYMBOLS = [
     ("bce_hip_input_bytes", C.c_int, [C.c_void_p, C.c_uint64, C.c_size_t, _u8p]),
     ("bce_hip_locate", C.c_int, [C.c_void_p, _u8p, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("bce_hip_locate_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("bce_hip_match", C.c_int, [C.c_void_p, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp]),
+    ("bce_hip_match_device", C.c_int, [C.c_void_p, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp]),
+    ("bce_hip_coverage", C.c_int, [C.c_void_p, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    ("bce_hip_coverage_device", C.c_int, [C.c_void_p, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     ("bce_hip_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     ("bce_hip_synth_text", None, [C.c_uint64, _u8p, C.c_size_t]),
     ("bce_hip_synth_rand", None, [C.c_uint64, _u8p, C.c_size_t]),
@@ -154,6 +158,8 @@ def _as_u8(data):
 
 
 LOCATE_LINEAR = 1                               # BCE_HIP_LOCATE_LINEAR
+MATCH_LINEAR = 1                                # BCE_HIP_MATCH_LINEAR
+MATCH_MAX_LEN = 4096                            # BCE_HIP_MATCH_MAX_LEN: a work bound per end position, not a format limit
 E_OVERFLOW = -5                                 # BCE_HIP_E_OVERFLOW
 
 
@@ -373,6 +379,52 @@ class RankFile:
                                                         ptr(hit_offsets_ptr), ptr(positions_ptr), int(cap), C.byref(total)), "bce_hip_locate_device")
         return total.value
 
+    def _match_flags(self, cyclic, what):
+        if not cyclic and not self._has_text:
+            raise ValueError("a RankFile built from an injected BWT holds no text: only cyclic=True %s are defined" % what)
+        return 0 if cyclic else MATCH_LINEAR
+
+    def match(self, query, max_len, cyclic=False, positions=True):
+        """The matching statistics of `query` (a bytes-like, a second buffer) against the text, from the index on the GPU
+        (bce_hip_match: backward search from every end position, one lane each) -> (lens, pos), numpy uint32 arrays as long as the
+        query.  lens[i]: the length of the longest string that ends at query[i] and occurs in the text, at most min(max_len, i + 1);
+        max_len (1 .. 4096) bounds the work per position, a match cut short there is reported as max_len.  pos[i]: where one such
+        occurrence starts in the text (which one is not specified), 0xFFFFFFFF where lens[i] == 0; positions=False -> pos is None.
+        cyclic=False: occurrences inside the text, pos[i] + lens[i] <= n.  cyclic=True: in the circular text, those across its end
+        included -- without positions the only answer a RankFile built from an injected BWT can give (cyclic=False there:
+        ValueError, as count(); positions there: BceError, there is no suffix array)."""
+        flags = self._match_flags(cyclic, "matches")
+        q = _as_u8(query)
+        lens = np.zeros(len(q), dtype=np.uint32)
+        pos = np.full(len(q), 0xFFFFFFFF, dtype=np.uint32) if positions else None
+        self._c.check(self._c.lib.bce_hip_match(self._c.h, q.ctypes.data if len(q) else None, len(q), int(max_len), flags,
+                                                lens.ctypes.data if len(q) else None, pos.ctypes.data if positions and len(q) else None), "bce_hip_match")
+        return lens, pos
+
+    def match_device(self, query_ptr, q, max_len, lens_ptr, pos_ptr, cyclic=False):
+        """bce_hip_match_device: the same for a query of `q` bytes that lies in device memory (int pointers: the bytes; out: q uint32
+        lengths and, unless pos_ptr is None, q uint32 positions).  Stream rule: as count_device."""
+        ptr = lambda v: None if v is None else int(v)  # noqa: E731
+        self._c.check(self._c.lib.bce_hip_match_device(self._c.h, ptr(query_ptr), int(q), int(max_len), self._match_flags(cyclic, "matches"),
+                                                       ptr(lens_ptr), ptr(pos_ptr)), "bce_hip_match_device")
+
+    def coverage(self, query, min_len, cyclic=False) -> int:
+        """How many bytes of `query` lie in strings of min_len bytes or more (1 .. 4096) that occur in the text: the size of the
+        union of all such matches (bce_hip_coverage: searched and reduced on the GPU, 8 bytes come back).  cyclic: as match()."""
+        flags = self._match_flags(cyclic, "coverage figures")
+        q = _as_u8(query)
+        out = C.c_uint64(0)
+        self._c.check(self._c.lib.bce_hip_coverage(self._c.h, q.ctypes.data if len(q) else None, len(q), int(min_len), flags, C.byref(out)),
+                      "bce_hip_coverage")
+        return out.value
+
+    def coverage_device(self, query_ptr, q, min_len, cyclic=False) -> int:
+        """bce_hip_coverage_device: coverage() of a query of `q` bytes in device memory (an int pointer).  Stream rule: as count_device."""
+        out = C.c_uint64(0)
+        self._c.check(self._c.lib.bce_hip_coverage_device(self._c.h, None if query_ptr is None else int(query_ptr), int(q), int(min_len),
+                                                          self._match_flags(cyclic, "coverage figures"), C.byref(out)), "bce_hip_coverage_device")
+        return out.value
+
     def close(self):
         self._c.close()
 
@@ -524,6 +576,27 @@ def locate(data, patterns, cyclic=False, limit=None, max_hits=1 << 26, device=0,
     rf = RankFile(data, device=device, ctx=ctx)
     try:
         return rf.locate(patterns, cyclic=cyclic, limit=limit, max_hits=max_hits)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def match(data, query, max_len, cyclic=False, positions=True, device=0, ctx=None):
+    """The matching statistics of `query` against `data` -> (lens, pos) as RankFile.match: K1 and K2 index the data on the GPU,
+    every end position of the query is searched in the index."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.match(query, max_len, cyclic=cyclic, positions=positions)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def coverage(data, query, min_len, cyclic=False, device=0, ctx=None) -> int:
+    """How many bytes of `query` lie in strings of min_len bytes or more that occur in `data` (RankFile.coverage)."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.coverage(query, min_len, cyclic=cyclic)
     finally:
         if ctx is None:
             rf.close()

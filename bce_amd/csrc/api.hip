@@ -700,7 +700,7 @@ void bce_hip_destroy(bce_hip_ctx *c) {
                     &c->rs_hist, &c->blk, &c->ptmp[0], &c->ptmp[1], &c->gran, &c->nlist[0], &c->nlist[1], &c->ctl, &c->tilecnt,
                     &c->tileoff, &c->runs, &c->smwords, &c->k3tw, &c->k3grp, &c->truns, &c->skey[0], &c->skey[1], &c->sval[0], &c->sval[1], &c->sout,
                     &c->sesc, &c->stat, &c->crc_tab, &c->dcfg, &c->k4w, &c->scanrec, &c->dfs, &c->skey_alt, &c->sesc_alt, &c->rs_hist_k4, &c->cost_acc, &c->cost_runs, &c->cmp_res, &c->cnt_res, &c->cnt_pat, &c->cnt_off, &c->cnt_out, &c->loc_res, &c->loc_lo, &c->loc_cnt, &c->loc_drop, &c->loc_start, &c->loc_lin, &c->loc_bsum,
-                    &c->loc_key[0], &c->loc_key[1], &c->loc_val[0], &c->loc_val[1], &c->loc_pat, &c->loc_off, &c->loc_hits, &c->loc_pos, &c->hook[0], &c->hook[1], &c->hook[2]};
+                    &c->loc_key[0], &c->loc_key[1], &c->loc_val[0], &c->loc_val[1], &c->loc_pat, &c->loc_off, &c->loc_hits, &c->loc_pos, &c->mat_res, &c->mat_bsum, &c->mat_qry, &c->mat_len, &c->mat_pos, &c->hook[0], &c->hook[1], &c->hook[2]};
   for (DevBuf *b : bufs) release(*b);
   for (auto &par : c->dlist) for (DevBuf &b : par) release(b);
   k4_prepin_join(c, true);
@@ -1489,12 +1489,12 @@ int bce_hip_input_bytes(bce_hip_ctx *c, uint64_t pos, size_t len, uint8_t *out) 
 // Phase 3 as the count: ctx_trim keeps sa[sa_res] there, for the depth-first tail.  Nothing after K1 writes that array until the
 // next load or decode (K3's tail, the encoder, the estimate, the scan, the count and the sort hooks only read it or never name
 // it), so it stands for as long as k1_valid does.  A text of one byte has no array: its only rotation starts at 0.
-static int locate_state(bce_hip_ctx *c, const uint32_t **sa) {
-  BCE_TRY(count_state(c, "locate"));
+static int locate_state(bce_hip_ctx *c, const uint32_t **sa, const char *what = "locate") {
+  BCE_TRY(count_state(c, what));
   *sa = nullptr;
   if (c->k1_valid && c->sa[c->sa_res].p && c->sa[c->sa_res].cap >= (size_t)c->n * 4) { *sa = c->sa[c->sa_res].as<uint32_t>(); return BCE_HIP_OK; }
   if (c->n == 1 && c->text_loaded) return BCE_HIP_OK;
-  snprintf(c->err, sizeof c->err, c->text_loaded ? "locate: the suffix array of this input is gone" : "locate: there is no suffix array behind an injected BWT");
+  snprintf(c->err, sizeof c->err, c->text_loaded ? "%s: the suffix array of this input is gone" : "%s: there is no suffix array behind an injected BWT", what);
   return BCE_HIP_E_STATE;
 }
 
@@ -1571,6 +1571,105 @@ int bce_hip_locate_device(bce_hip_ctx *c, const void *d_patterns, const void *d_
     PhaseScope phase(c, 3);
     return locate_run(c, sa, static_cast<const uint8_t *>(d_patterns), static_cast<const uint64_t *>(d_offsets), npat, flags & BCE_HIP_LOCATE_LINEAR,
                       static_cast<uint64_t *>(d_hit_offsets), nullptr, static_cast<uint32_t *>(d_positions), nullptr, !d_positions, cap, total);
+  });
+}
+
+// ---- the longest matches of a second buffer in the text (kd_match.hip) -----------------------------------------------------------
+// Phase 3 with the count's rule.  Cyclic lengths alone need the planes only, so they work behind an injected BWT; positions, and
+// everything in linear mode, read sa[sa_res] by locate_state's rule -- read: nothing here writes that array, the planes or any
+// stage's scratch.  The arguments are judged before the state, the state before the arrays, as for the locate.
+static int match_args(bce_hip_ctx *c, uint64_t q, uint32_t max_len, uint32_t flags) {
+  if (!c || (flags & ~BCE_HIP_MATCH_LINEAR)) return BCE_HIP_E_ARG;
+  if (max_len < 1 || max_len > BCE_HIP_MATCH_MAX_LEN) {
+    snprintf(c->err, sizeof c->err, "match: a length bound of %u, outside 1 .. %u", max_len, BCE_HIP_MATCH_MAX_LEN);
+    return BCE_HIP_E_ARG;
+  }
+  if (q > 0x7FFFFFFFull) { snprintf(c->err, sizeof c->err, "match: a query of 2^31 bytes or more"); return BCE_HIP_E_ARG; }
+  return BCE_HIP_OK;
+}
+static int match_state(bce_hip_ctx *c, bool need_sa, const uint32_t **sa) {
+  *sa = nullptr;
+  return need_sa ? locate_state(c, sa, "match") : count_state(c, "match");
+}
+
+int bce_hip_match(bce_hip_ctx *c, const uint8_t *query, uint64_t q, uint32_t max_len, uint32_t flags, uint32_t *len_out, uint32_t *pos_out) {
+  BCE_TRY(match_args(c, q, max_len, flags));
+  if (q == 0) return BCE_HIP_OK;
+  const uint32_t *sa = nullptr;
+  BCE_TRY(match_state(c, (flags & BCE_HIP_MATCH_LINEAR) || pos_out, &sa));
+  if (!query || !len_out) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope phase(c, 3);
+    const size_t words = (size_t)q * 4;
+    BCE_TRY(ensure(c, c->mat_qry, (size_t)q));
+    BCE_TRY(ensure(c, c->mat_len, words));
+    if (pos_out) BCE_TRY(ensure(c, c->mat_pos, words));
+    BCE_HIP_TRY(c, hipMemcpyAsync(c->mat_qry.p, query, (size_t)q, hipMemcpyHostToDevice, c->stream));
+    BCE_TRY(kd_match(c, sa, c->mat_qry.as<uint8_t>(), (uint32_t)q, max_len, flags & BCE_HIP_MATCH_LINEAR, c->mat_len.as<uint32_t>(),
+                     pos_out ? c->mat_pos.as<uint32_t>() : nullptr));
+    BCE_HIP_TRY(c, hipMemcpyAsync(len_out, c->mat_len.p, words, hipMemcpyDeviceToHost, c->stream));
+    if (pos_out) BCE_HIP_TRY(c, hipMemcpyAsync(pos_out, c->mat_pos.p, words, hipMemcpyDeviceToHost, c->stream));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    BCE_HIP_TRY(c, hipGetLastError());
+    return BCE_HIP_OK;
+  });
+}
+
+int bce_hip_match_device(bce_hip_ctx *c, const void *d_query, uint64_t q, uint32_t max_len, uint32_t flags, void *d_len, void *d_pos) {
+  BCE_TRY(match_args(c, q, max_len, flags));
+  if (q == 0) return BCE_HIP_OK;
+  const uint32_t *sa = nullptr;
+  BCE_TRY(match_state(c, (flags & BCE_HIP_MATCH_LINEAR) || d_pos, &sa));
+  if (!d_query || !d_len) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope phase(c, 3);
+    BCE_TRY(kd_match(c, sa, static_cast<const uint8_t *>(d_query), (uint32_t)q, max_len, flags & BCE_HIP_MATCH_LINEAR,
+                     static_cast<uint32_t *>(d_len), static_cast<uint32_t *>(d_pos)));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    BCE_HIP_TRY(c, hipGetLastError());
+    return BCE_HIP_OK;
+  });
+}
+
+// The search with max_len = min_len (the windows of min_len bytes that end inside a longer match cover it: DESIGN.md 4.10), then
+// the reduction; of the answer only the result word reaches the host.
+static int coverage_run(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_query, uint32_t q, uint32_t min_len, bool linear, uint64_t *covered) {
+  BCE_TRY(ensure(c, c->mat_len, (size_t)q * 4));
+  BCE_TRY(kd_match(c, sa, d_query, q, min_len, linear, c->mat_len.as<uint32_t>(), nullptr));
+  return kd_coverage(c, c->mat_len.as<uint32_t>(), q, min_len, covered);
+}
+
+int bce_hip_coverage(bce_hip_ctx *c, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t flags, uint64_t *covered) {
+  if (!covered) return BCE_HIP_E_ARG;
+  BCE_TRY(match_args(c, q, min_len, flags));
+  *covered = 0;
+  if (q == 0) return BCE_HIP_OK;
+  const uint32_t *sa = nullptr;
+  BCE_TRY(match_state(c, flags & BCE_HIP_MATCH_LINEAR, &sa));
+  if (!query) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope phase(c, 3);
+    BCE_TRY(ensure(c, c->mat_qry, (size_t)q));
+    BCE_HIP_TRY(c, hipMemcpyAsync(c->mat_qry.p, query, (size_t)q, hipMemcpyHostToDevice, c->stream));
+    return coverage_run(c, sa, c->mat_qry.as<uint8_t>(), (uint32_t)q, min_len, flags & BCE_HIP_MATCH_LINEAR, covered);
+  });
+}
+
+int bce_hip_coverage_device(bce_hip_ctx *c, const void *d_query, uint64_t q, uint32_t min_len, uint32_t flags, uint64_t *covered) {
+  if (!covered) return BCE_HIP_E_ARG;
+  BCE_TRY(match_args(c, q, min_len, flags));
+  *covered = 0;
+  if (q == 0) return BCE_HIP_OK;
+  const uint32_t *sa = nullptr;
+  BCE_TRY(match_state(c, flags & BCE_HIP_MATCH_LINEAR, &sa));
+  if (!d_query) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope phase(c, 3);
+    return coverage_run(c, sa, static_cast<const uint8_t *>(d_query), (uint32_t)q, min_len, flags & BCE_HIP_MATCH_LINEAR, covered);
   });
 }
 

@@ -216,6 +216,9 @@ struct bce_hip_ctx {
   bce::DevBuf loc_lo, loc_cnt, loc_drop, loc_start, loc_lin, loc_bsum;   // per pattern: the interval's first row, its rows, those across the text's end; the two CSR offset arrays; the scan's block sums
   bce::DevBuf loc_key[2], loc_val[2];            // (position, pattern) of every row: both halves of the sorts' ping-pong
   bce::DevBuf loc_pat, loc_off, loc_hits, loc_pos;   // bce_hip_locate: the arrays of a call with host buffers, staged (all grow-only)
+  bce::DevBuf mat_res;                           // kd_match.hip: the coverage's result word (a buffer of its own, as loc_res)
+  bce::DevBuf mat_bsum;                          // the coverage scan's block maxima and block counts
+  bce::DevBuf mat_qry, mat_len, mat_pos;         // bce_hip_match / _coverage: the query of a call with a host buffer, the lengths and the positions, staged (all grow-only)
   bce::DevBuf hook[3];                           // test hooks bce_hip_sort_pairs_device / _wide_device: the second halves of the sorts' ping-pong
   bool crc_const_ready = false;                  // its launch-independent constants are uploaded
   bool text_loaded = false;                      // `text` holds the n bytes of the last bce_hip_load_* (bce_hip_input_crc32)
@@ -433,6 +436,11 @@ int kd_locate_size(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, con
                    uint64_t *d_hits, uint64_t *rows, uint64_t *total);
 int kd_locate_fill(bce_hip_ctx *c, const uint32_t *sa, const uint64_t *d_off, uint32_t npat, bool linear, uint64_t rows, uint64_t total,
                    uint32_t *d_pos);
+// kd_match.hip: d_len[i] (and d_pos[i], unless null) of the longest string that ends at d_query[i] and occurs in the text, at most
+// max_len bytes; queued, the caller waits.  kd_coverage: the bytes of the query inside matches of min_len or more, from such lengths.
+int kd_match(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_query, uint32_t q, uint32_t max_len, bool linear, uint32_t *d_len,
+             uint32_t *d_pos);
+int kd_coverage(bce_hip_ctx *c, const uint32_t *d_len, uint32_t q, uint32_t min_len, uint64_t *covered);
 int k2_build_planes(bce_hip_ctx *c);                // k2_planes.hip
 int k2_get_plane_bits(bce_hip_ctx *c, int plane, uint8_t *out);
 int k2_rank1(bce_hip_ctx *c, int plane, const uint32_t *idx, uint32_t count, uint32_t *out);

@@ -1,4 +1,4 @@
-// fm_step.h -- backward search on the K2 planes: the step kd_count.hip and kd_locate.hip run per pattern byte, and the row
+// fm_step.h -- backward search on the K2 planes: the step kd_count.hip, kd_locate.hip and kd_match.hip run per byte, and the row
 // arithmetic of a located batch, shared with the host (tests/count_emul.cpp and tests/locate_emul.cpp run the same lines on planes
 // they build naively), the way bce_cost.h and bce_core.h are shared.
 //
@@ -63,5 +63,56 @@ BCE_HD uint32_t fm_row_pattern(const uint64_t *start, uint32_t npat, uint64_t r)
 
 // Does the cyclic hit at pos < n lie inside the text, pos + m <= n?  (A pattern longer than the text never does.)
 BCE_HD bool fm_linear_hit(uint32_t pos, uint64_t m, uint32_t n) { return m <= n && pos <= n - (uint32_t)m; }
+
+// ---- matching statistics (kd_match.hip): the longest string that ends at q[i] and occurs in the text ------------------------------
+// len = the largest l <= min(L, i + 1) for which q[i - l + 1 .. i] occurs, found by extending to the left one byte at a time from
+// the empty match: the strings that end at i are suffixes of one another, so the first length that fails ends the search.  row = a
+// row of the sorted rotations whose rotation starts with that match (0 when len == 0): the caller reads the position from it.
+// The byte to the left is fetched before the current byte's eight levels, off their chain, as in fm_range.
+//   Cyclic: "occurs" as in fm_count; the search goes on while the interval [lo, hi) is not empty, and row = lo.
+//   Linear: an occurrence must start at a p with p + l <= n.  At length l only the l - 1 rotations that start at n - l + 1 .. n - 1
+//     run across the end of the text, so an interval of l rows or more holds a row inside the text and nothing is read.  A
+//     narrower one has fewer than l entries of the suffix array, neighbouring words: sa(r) reads them in turn until one passes
+//     fm_linear_hit -- the witness; if none does, the previous length stands.  An interval of one row whose start w is known needs
+//     no read: the step leaves the rotation that starts one byte earlier, at w - 1 (w == 0: it would start at the text's last
+//     byte and run across the end).  l > n never matches.  With want_row, a final length whose witness is not known (its interval
+//     was wide) looks for it among the interval's first len rows, where there must be one.
+// sa(r) is called with lo <= r < hi <= n only, and never for a text of one byte (which has no array: its rotation starts at 0).
+template <bool Linear, class Rank2, class Sa>
+BCE_HD void fm_match_end(const uint8_t *q, uint64_t i, uint32_t L, uint32_t n, const uint32_t zeros[8], bool want_row, uint32_t &len,
+                         uint32_t &row, Rank2 &&rank2, Sa &&sa) {
+  uint32_t maxl = i + 1 < (uint64_t)L ? (uint32_t)(i + 1) : L;
+  if (Linear && maxl > n) maxl = n;
+  uint32_t lo = 0, hi = n;                             // the rotations that start with the match of len bytes
+  uint32_t w = 0;                                      // Linear, known: the rotation of `row` starts at w, w + len <= n
+  bool known = false;
+  len = 0; row = 0;
+  uint32_t c = q[i];
+  while (len < maxl) {
+    const uint32_t l = len + 1;
+    const uint32_t next = l < maxl ? q[i - l] : 0u;
+    const bool single = Linear && known && hi - lo == 1u;
+    if (single && w == 0) break;
+    uint32_t a = lo, b = hi;
+    fm_step(c, zeros, a, b, rank2);
+    if (a >= b) break;
+    if (Linear) {
+      if (single) { w -= 1u; row = a; }
+      else if (b - a >= l) known = false;
+      else {
+        uint32_t r = a, p = sa(r);
+        while (!fm_linear_hit(p, l, n) && ++r < b) p = sa(r);
+        if (r == b) break;
+        known = true; w = p; row = r;
+      }
+    }
+    lo = a; hi = b; len = l; c = next;
+  }
+  if (!Linear) row = lo;
+  else if (!known) {
+    row = lo;
+    if (want_row && len) while (row + 1u < hi && !fm_linear_hit(sa(row), len, n)) ++row;
+  }
+}
 
 }  // namespace bce

@@ -6,6 +6,7 @@
 //   bce -g PATTERN file                     (extension) how often the bytes of PATTERN occur in "file", counted on the GPU from its BWT planes
 //   bce -gd PATTERN archive                 (extension) the same in what an archive or container holds
 //   bce -gl PATTERN file, -gld PATTERN archive   (extension) where they occur: the byte offsets, gathered on the GPU from K1's suffix array
+//   bce -gm MINLEN file query_file, -gmd MINLEN archive query_file   (extension) how much of a second file lies in strings of MINLEN bytes or more that occur in the first
 // Banner, usage text, summary line, argument detection and exit codes follow the reference
 // (banner :1377-1379, -c :1403-1427, -d :1428-1472, usage :1473-1483).  -d uses the GPU-assisted decoder (kd_decode.hip), -ds the host decoder (decoder.cpp);
 // -s runs the enumeration on the GPU in scan mode and the ScanCoder optimisation on the host (scan_coder.cpp).
@@ -129,6 +130,7 @@ extern "C" int bce_hip_estimate_host(bce_hip_ctx *ctx, const uint8_t *in, uint32
 extern "C" int bce_hip_count(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint64_t *counts) __attribute__((weak));
 extern "C" int bce_hip_locate(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t flags, uint64_t *hit_offsets,
                               uint32_t *positions, uint64_t cap, uint64_t *total) __attribute__((weak));
+extern "C" int bce_hip_coverage(bce_hip_ctx *ctx, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t flags, uint64_t *covered) __attribute__((weak));
 
 // `bce -cN`: N contiguous blocks over the GPUs of the node.  With more blocks than GPUs every device gets up to four
 // gated contexts (bce_hip_set_gated), one host thread each: their GPU phases take turns while the coder threads of the
@@ -431,6 +433,9 @@ static int estimate_file(const char *file, const char *config) {
 // An archive's blocks are decoded by the GPU-assisted decoder, one after the other, a version-2 container's against their CRC-32s.
 // `-gl` / `-gld` (locate): the same files, answers and exit codes; the matches' byte offsets, one per line, ascending, come before
 // the count line.  They are the linear hits of bce_hip_locate: gathered from K1's suffix array and filtered on the GPU.
+// `-gm MINLEN file query_file` / `-gmd MINLEN archive query_file` (coverage): the file or archive is read, judged, decoded and indexed
+// in the same way; query_file is a plain file, judged with the words of -g's.  One line: how many of its bytes lie in strings of
+// MINLEN bytes or more that occur in the indexed text (bce_hip_coverage, linear matches: searched and reduced on the GPU).
 static uint64_t seam_matches(const uint8_t *t, size_t n, const uint8_t *pat, size_t m) {
   std::vector<uint8_t> seam(t + n - (m - 1), t + n);
   seam.insert(seam.end(), t, t + (m - 1));
@@ -438,19 +443,26 @@ static uint64_t seam_matches(const uint8_t *t, size_t n, const uint8_t *pat, siz
   for (size_t s = 0; s + m <= seam.size(); ++s) found += memcmp(seam.data() + s, pat, m) == 0;
   return found;
 }
-static int count_pattern(const char *pattern, const char *path, bool in_archive, bool locate) {
+enum GrepMode { kGrepCount, kGrepLocate, kGrepCoverage };
+static int count_pattern(const char *pattern, const char *path, bool in_archive, GrepMode mode, const char *query_path = nullptr, uint32_t min_len = 0) {
+  const bool locate = mode == kGrepLocate, coverage = mode == kGrepCoverage;
   const size_t m = strlen(pattern);
   const uint8_t *pat = reinterpret_cast<const uint8_t *>(pattern);
   HostFile file;
+  HostFile query;
   std::thread reader(read_whole_file, path, &file, in_archive ? (size_t)0 : kMaxInput);   // beside the runtime's start-up
+  std::thread query_reader;
+  if (coverage) query_reader = std::thread(read_whole_file, query_path, &query, kMaxInput);
   bce_hip_ctx *ctx = nullptr;
   const int rc0 = bce_hip_create(&ctx, 0);
   reader.join();
+  if (coverage) query_reader.join();
   struct Destroy { bce_hip_ctx *&c; ~Destroy() { if (c) bce_hip_destroy(c); } } destroy{ctx};
   if (in_archive && file.status == -1) { printf("Archive not found.\n"); return -1; }
   if (in_archive && (file.status != 0 || file.size() == 0)) { printf("Could not read Archive.\n"); return -2; }
   if (!in_archive && (file.status != 0 || file.size() == 0 || file.size() >= kMaxInput)) { printf("Error loading file\n"); return -1; }
-  if (rc0 != 0 || !bce_hip_count || (locate && !bce_hip_locate)) { printf("No usable HIP device: %s\n", bce_hip_strerror(rc0 ? rc0 : BCE_HIP_E_DEVICE)); return -3; }
+  if (coverage && (query.status != 0 || query.size() == 0 || query.size() >= kMaxInput)) { printf("Error loading file\n"); return -1; }
+  if (rc0 != 0 || !bce_hip_count || (locate && !bce_hip_locate) || (coverage && !bce_hip_coverage)) { printf("No usable HIP device: %s\n", bce_hip_strerror(rc0 ? rc0 : BCE_HIP_E_DEVICE)); return -3; }
   const uint8_t *text = file.data();
   size_t n = file.size();
   std::vector<uint8_t> decoded;
@@ -487,6 +499,19 @@ static int count_pattern(const char *pattern, const char *path, bool in_archive,
     text = decoded.data();
     n = decoded.size();
   }
+  if (coverage) {
+    uint64_t covered = 0;
+    int rc = bce_hip_load_host(ctx, text, (uint32_t)n);
+    if (rc == 0) rc = bce_hip_bwt(ctx, nullptr);
+    if (rc == 0) rc = bce_hip_build_planes(ctx, nullptr);
+    if (rc == 0) rc = bce_hip_coverage(ctx, query.data(), query.size(), min_len, BCE_HIP_MATCH_LINEAR, &covered);
+    if (rc != 0) { printf("Match failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); return -4; }
+    printf("%llu of %zu bytes (%.1f %%) of %s lie in strings of %u bytes or more that occur in %s\n", (unsigned long long)covered, query.size(),
+           100.0 * (double)covered / (double)query.size(), query_path, min_len, path);
+    ctx = nullptr;                                                    // (left to fast_exit, like -d)
+    fast_exit(0);
+    return 0;
+  }
   uint64_t count = 0;
   std::vector<uint32_t> where;
   if (m <= n) {                                                     // (a longer pattern occurs nowhere in the text, only around it)
@@ -513,6 +538,18 @@ static int count_pattern(const char *pattern, const char *path, bool in_archive,
   ctx = nullptr;                                                    // (left to fast_exit, like -d)
   fast_exit(0);
   return 0;
+}
+
+// MINLEN of -gm / -gmd: decimal digits only, 1 .. 4096 (BCE_HIP_MATCH_MAX_LEN); anything else: 0
+static uint32_t parse_min_len(const char *s) {
+  uint32_t v = 0;
+  if (!*s) return 0;
+  for (; *s; ++s) {
+    if (*s < '0' || *s > '9') return 0;
+    v = v * 10 + (uint32_t)(*s - '0');
+    if (v > BCE_HIP_MATCH_MAX_LEN) return 0;
+  }
+  return v;
 }
 
 static int usage() {
@@ -551,6 +588,12 @@ static int usage() {
   printf("\n");
   printf("  bce -gld PATTERN archive.bce\n");
   printf("   The same offsets in what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
+  printf("\n");
+  printf("  bce -gm MINLEN file query_file\n");
+  printf("   Prints how many bytes of \"query_file\" lie in strings of MINLEN (1..4096) bytes or more that occur in \"file\": the file is indexed on the GPU and every position of the query is searched in the index there (extension)\n");
+  printf("\n");
+  printf("  bce -gmd MINLEN archive.bce query_file\n");
+  printf("   The same figure against what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
   return 0;
 }
 
@@ -819,9 +862,11 @@ int main(int argc, char **argv) {
   } else if ((argc == 3 || argc == 4) && argv[1][0] == '-' && argv[1][1] == 'e' && argv[1][2] == 0) {
     return estimate_file(argv[2], argc == 4 ? argv[3] : nullptr);
   } else if (argc == 4 && argv[2][0] != 0 && (strcmp(argv[1], "-g") == 0 || strcmp(argv[1], "-gd") == 0)) {
-    return count_pattern(argv[2], argv[3], argv[1][2] == 'd', false);
+    return count_pattern(argv[2], argv[3], argv[1][2] == 'd', kGrepCount);
   } else if (argc == 4 && argv[2][0] != 0 && (strcmp(argv[1], "-gl") == 0 || strcmp(argv[1], "-gld") == 0)) {
-    return count_pattern(argv[2], argv[3], argv[1][3] == 'd', true);
+    return count_pattern(argv[2], argv[3], argv[1][3] == 'd', kGrepLocate);
+  } else if (argc == 5 && (strcmp(argv[1], "-gm") == 0 || strcmp(argv[1], "-gmd") == 0) && parse_min_len(argv[2]) != 0) {
+    return count_pattern("", argv[3], argv[1][3] == 'd', kGrepCoverage, argv[4], parse_min_len(argv[2]));
   } else if (argc == 4 && argv[1][0] == '-' && argv[1][1] == 's') {
     // Scan (bce.cpp:1384-1402): enumeration on the GPU, ScanCoder optimisation on the host, 288-byte config out
     auto start = std::chrono::high_resolution_clock::now();

@@ -143,6 +143,71 @@ def locate_in_archive(blob, patterns, cyclic=False, device="cuda:0"):
     return locate_tensor(decompress_container_tensor(blob, device=device), patterns, cyclic=cyclic)
 
 
+def _match_args(t, query, what):
+    _check(t, "t")
+    _check(query, "query")
+    if query.device != t.device:
+        raise ValueError("query must lie on t's device")
+    n = t.numel()
+    if n == 0:
+        raise api.BceError(-1, what, "empty input")
+    if n > _MAX_BLOCK:
+        raise ValueError("one index covers one text of less than 2^31 bytes, not %d" % n)
+    if query.numel() > _MAX_BLOCK:
+        raise ValueError("a query is less than 2^31 bytes, not %d" % query.numel())
+    return n
+
+
+def match_tensor(t, query, max_len, cyclic=False, positions=True, ctx=None):
+    """The matching statistics of the 1-D uint8 CUDA tensor `query` against the 1-D uint8 CUDA tensor `t` (slices at any offset,
+    same device) -> (lens, pos), int32 tensors on that device as long as the query: as api.RankFile.match, with positions of -1
+    (0xFFFFFFFF) where lens is 0, pos None with positions=False.  The text is indexed where it lies and the query searched where
+    it lies (bce_hip_match_device); nothing of either reaches the host.
+    Synchronises the current stream first; `ctx` (an api._Ctx of t's device) is reused if given."""
+    n = _match_args(t, query, "match_tensor")
+    q = query.numel()
+    lens = torch.zeros(q, dtype=torch.int32, device=t.device)
+    pos = torch.full((q,), -1, dtype=torch.int32, device=t.device) if positions else None
+    _ready(t)
+    own = ctx is None
+    c = ctx or api._Ctx(t.device.index)
+    try:
+        rf = api.RankFile(n=n, device_ptr=t.data_ptr(), ctx=c)
+        if q:
+            rf.match_device(query.data_ptr(), q, max_len, lens.data_ptr(), pos.data_ptr() if positions else None, cyclic=cyclic)
+        return lens, pos
+    finally:
+        if own:
+            c.close()
+
+
+def coverage_tensor(t, query, min_len, cyclic=False, ctx=None) -> int:
+    """How many bytes of the CUDA tensor `query` lie in strings of min_len bytes or more that occur in the CUDA tensor `t` (both 1-D
+    uint8, same device): api.RankFile.coverage with both buffers where they lie (bce_hip_coverage_device); 8 bytes reach the host.
+    Synchronises the current stream first; `ctx` (an api._Ctx of t's device) is reused if given."""
+    n = _match_args(t, query, "coverage_tensor")
+    _ready(t)
+    own = ctx is None
+    c = ctx or api._Ctx(t.device.index)
+    try:
+        rf = api.RankFile(n=n, device_ptr=t.data_ptr(), ctx=c)
+        return rf.coverage_device(query.data_ptr() if query.numel() else None, query.numel(), min_len, cyclic=cyclic)
+    finally:
+        if own:
+            c.close()
+
+
+def coverage_in_archive(blob, query, min_len, cyclic=False, device="cuda:0") -> int:
+    """coverage_tensor on what an archive holds, decoded as count_in_archive decodes it: into ONE tensor on the device, so matches
+    across block boundaries count.  `query`: a bytes-like (it is sent to the device) or a 1-D uint8 CUDA tensor there."""
+    total = sum(t[0] for t in _blocks_of(blob))
+    if total > _MAX_BLOCK:
+        raise ValueError("the archive holds %d bytes: one index covers one text of less than 2^31" % total)
+    if not isinstance(query, torch.Tensor):
+        query = torch.from_numpy(api._as_u8(query).copy()).to(device)
+    return coverage_tensor(decompress_container_tensor(blob, device=device), query, min_len, cyclic=cyclic)
+
+
 def decompress_tensor(archive, device="cuda:0", out=None, ctx=None):
     """The GPU-assisted decoder with the text left on the device (bce_hip_decompress_to_device) -> a 1-D uint8 tensor there.
 

@@ -333,6 +333,41 @@ int bce_hip_locate(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *of
 int bce_hip_locate_device(bce_hip_ctx *ctx, const void *d_patterns, const void *d_offsets, uint32_t npat, uint32_t flags,
                           void *d_hit_offsets, void *d_positions, uint64_t cap, uint64_t *total);
 
+/* ---- extension: the longest matches of a SECOND buffer in the input (kd_match.hip, fm_step.h) -----------------------------------
+ * The matching statistics of a query Q (q bytes, 1 <= q <= 2^31 - 1) against the text T (the n bytes the context indexed).  For
+ * every END position i in [0, q):
+ *   len[i]  the largest l with 0 <= l <= min(max_len, i + 1) such that Q[i - l + 1 .. i] occurs in T;
+ *   pos[i]  the start in T of ONE such occurrence (which one is not specified: the tied rotations of a periodic text stand in any
+ *           order), 0xFFFFFFFF where len[i] == 0.
+ *   cyclic (flags == 0): "occurs" in the circular text, as bce_hip_count defines it; l may exceed n on a periodic text.
+ *   linear (BCE_HIP_MATCH_LINEAR): an occurrence that starts at a p with p + l <= n, and pos[i] is such a p.
+ * In both modes len[i + 1] <= len[i] + 1, and a match that is cut short at max_len is reported as max_len.  max_len is a WORK bound
+ * per end position, 1 .. BCE_HIP_MATCH_MAX_LEN, not a limit of any format: a lane extends its match by at most that many bytes.
+ * Backward search from each end position, one lane each, with the step bce_hip_count runs; linear mode reads suffix-array entries
+ * only while an interval holds fewer rows than the match has bytes.
+ * pos_out may be NULL.  Cyclic lengths without positions need only the planes (they work after bce_hip_set_bwt); positions, and
+ * everything in linear mode, need the suffix array by bce_hip_locate's rule, otherwise BCE_HIP_E_STATE in its words.  Valid while
+ * the planes stand (bce_hip_count's rule); no call here changes the compression state: an encode after a match gives the archive
+ * of a fresh context.  q == 0: success, nothing launched.  A null ctx, a flag bit other than BCE_HIP_MATCH_LINEAR, a max_len
+ * outside 1 .. BCE_HIP_MATCH_MAX_LEN, q >= 2^31: BCE_HIP_E_ARG before any device call; then the state; then a null query or
+ * len_out: BCE_HIP_E_ARG. */
+#define BCE_HIP_MATCH_LINEAR 1u
+#define BCE_HIP_MATCH_MAX_LEN 4096u
+int bce_hip_match(bce_hip_ctx *ctx, const uint8_t *query, uint64_t q, uint32_t max_len, uint32_t flags, uint32_t *len_out,
+                  uint32_t *pos_out);
+/* The same with the query, the lengths and the positions (d_pos may be NULL) in device memory of the context's device, the two
+ * outputs 4-byte aligned.  Stream rule: as bce_hip_count_device. */
+int bce_hip_match_device(bce_hip_ctx *ctx, const void *d_query, uint64_t q, uint32_t max_len, uint32_t flags, void *d_len,
+                         void *d_pos);
+/* *covered = the number of j in [0, q) for which some i >= j has len[i] >= min_len and i - len[i] + 1 <= j: the size of the union of
+ * all matches of min_len bytes or more, i.e. how many bytes of the query lie in strings of at least min_len bytes that occur in
+ * the text.  The search runs with max_len = min_len (1 .. BCE_HIP_MATCH_MAX_LEN), which is enough: the windows of min_len bytes
+ * that end inside a longer match cover it.  Search and reduction run on the device; 8 bytes come back.  Modes, state and refusals
+ * as bce_hip_match without positions; a null covered: BCE_HIP_E_ARG; q == 0: *covered = 0. */
+int bce_hip_coverage(bce_hip_ctx *ctx, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t flags, uint64_t *covered);
+/* The same with the query in device memory; covered stays a host pointer. */
+int bce_hip_coverage_device(bce_hip_ctx *ctx, const void *d_query, uint64_t q, uint32_t min_len, uint32_t flags, uint64_t *covered);
+
 /* ---- test hooks: the device primitives every stage rests on, alone (tests/test_gpu_sort.py, tests/test_gpu_compare.py) ----
  * Stream rule of bce_hip_crc32_device for all three: the work runs on the context's stream and is complete on return; the caller's
  * memory (device memory of the context's device) must be ready when the call is made.  Valid in any state of the context, between
