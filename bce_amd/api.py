@@ -118,6 +118,10 @@ SYMBOLS = [
     ("bce_hip_match_device", C.c_int, [C.c_void_p, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp]),
     ("bce_hip_coverage", C.c_int, [C.c_void_p, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     ("bce_hip_coverage_device", C.c_int, [C.c_void_p, _vp, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    ("bce_hip_lcp", C.c_int, [C.c_void_p, C.c_uint32, _vp]),
+    ("bce_hip_lcp_device", C.c_int, [C.c_void_p, C.c_uint32, _vp]),
+    ("bce_hip_kgrams", C.c_int, [C.c_void_p, _vp, C.c_uint32, _vp]),
+    ("bce_hip_longest_repeat", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("bce_hip_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     ("bce_hip_synth_text", None, [C.c_uint64, _u8p, C.c_size_t]),
     ("bce_hip_synth_rand", None, [C.c_uint64, _u8p, C.c_size_t]),
@@ -160,6 +164,7 @@ def _as_u8(data):
 LOCATE_LINEAR = 1                               # BCE_HIP_LOCATE_LINEAR
 MATCH_LINEAR = 1                                # BCE_HIP_MATCH_LINEAR
 MATCH_MAX_LEN = 4096                            # BCE_HIP_MATCH_MAX_LEN: a work bound per end position, not a format limit
+KGRAMS_MAX = 64                                 # BCE_HIP_KGRAMS_MAX: values of k in one bce_hip_kgrams call
 E_OVERFLOW = -5                                 # BCE_HIP_E_OVERFLOW
 
 
@@ -197,6 +202,23 @@ def linear_counts(cyclic, patterns, n, ends):
         elif m > 1:
             out[i] -= seam_count(head[:m - 1], tail[len(tail) - (m - 1):], p)
     return out
+
+
+class KGram(C.Structure):
+    """bce_hip_kgram: the cyclic k-grams of a text for one k (RankFile.kgrams)."""
+    _fields_ = [("distinct", C.c_uint64), ("once", C.c_uint64), ("nlogn_q24", C.c_uint64), ("max_count", C.c_uint32), ("max_pos", C.c_uint32)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+    def __repr__(self):
+        return "KGram(%s)" % ", ".join("%s=%d" % kv for kv in self.as_dict().items())
+
+
+def entropy_from_sums(n, s_k, s_k1) -> float:
+    """H_k of the circular text of n bytes from S_k and S_(k+1) (KGram.nlogn_q24), in bits per byte: the double expression
+    `bce -gk` prints, max(0, S_k - S_(k+1)) / (n * 2^24)."""
+    return max(0, int(s_k) - int(s_k1)) / (int(n) * 16777216.0)
 
 
 class _Ctx:
@@ -425,6 +447,51 @@ class RankFile:
                                                           self._match_flags(cyclic, "coverage figures"), C.byref(out)), "bce_hip_coverage_device")
         return out.value
 
+    def lcp(self, max_len):
+        """The LCP array of the sorted rotations of the CIRCULAR text (bce_hip_lcp: one lane per row, on the GPU) -> a numpy uint32
+        array of n words: lcp[0] = 0, lcp[r] = the bytes on which the rotations in rows r - 1 and r agree, at most max_len
+        (1 .. 4096, a work bound).  Not capped at n: equal rotations of a periodic text give max_len.  Needs the suffix array and
+        the text: a RankFile built from an injected BWT raises BceError."""
+        out = np.zeros(self._n, dtype=np.uint32)
+        self._c.check(self._c.lib.bce_hip_lcp(self._c.h, int(max_len), out.ctypes.data), "bce_hip_lcp")
+        return out
+
+    def lcp_device(self, max_len, ptr):
+        """bce_hip_lcp_device: the same into n uint32 words of device memory (an int pointer).  Stream rule: as count_device."""
+        self._c.check(self._c.lib.bce_hip_lcp_device(self._c.h, int(max_len), None if ptr is None else int(ptr)), "bce_hip_lcp_device")
+
+    def kgrams(self, ks):
+        """The cyclic k-grams of the text (bce_hip_kgrams: one LCP pass, reduced on the GPU): one k -> a KGram record, a sequence
+        of up to 64 -> a list of them.  Fields: distinct (k-grams), once (those that occur once), nlogn_q24 (S_k, the sum of
+        N * log2(N) over them in Q24 integers), max_count (the most frequent one's occurrences), max_pos (where one of its
+        occurrences starts).  k: 0 .. 4096; k > n wraps around the text."""
+        one = isinstance(ks, (int, np.integer))
+        karr = np.array([ks] if one else list(ks), dtype=np.int64)
+        if len(karr) and (karr.min() < 0 or karr.max() > 0xFFFFFFFF):
+            raise ValueError("k is 0 .. %d" % MATCH_MAX_LEN)
+        karr = karr.astype(np.uint32)
+        out = (KGram * max(len(karr), 1))()
+        self._c.check(self._c.lib.bce_hip_kgrams(self._c.h, karr.ctypes.data if len(karr) else None, len(karr), C.addressof(out)), "bce_hip_kgrams")
+        recs = [out[i] for i in range(len(karr))]
+        return recs[0] if one else recs
+
+    def entropy_profile(self, K):
+        """[H_0 .. H_K], the order-k empirical entropies of the circular text in bits per byte, K <= 62: from kgrams(range(K + 2)),
+        H_k = max(0, S_k - S_(k+1)) / (n * 2^24)."""
+        K = int(K)
+        if K < 0 or K + 2 > KGRAMS_MAX:
+            raise ValueError("K is 0 .. %d" % (KGRAMS_MAX - 2))
+        recs = self.kgrams(range(K + 2))
+        return [entropy_from_sums(self._n, recs[k].nlogn_q24, recs[k + 1].nlogn_q24) for k in range(K + 1)]
+
+    def longest_repeat(self, max_len=MATCH_MAX_LEN):
+        """(len, pos_a, pos_b): the longest repeat of the circular text -- two rotations that agree on len bytes, len the largest
+        such number up to max_len (len == max_len: that many or more).  len == 0: no byte occurs twice, both positions are
+        0xFFFFFFFF."""
+        ln, a, b = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        self._c.check(self._c.lib.bce_hip_longest_repeat(self._c.h, int(max_len), C.byref(ln), C.byref(a), C.byref(b)), "bce_hip_longest_repeat")
+        return ln.value, a.value, b.value
+
     def close(self):
         self._c.close()
 
@@ -597,6 +664,37 @@ def coverage(data, query, min_len, cyclic=False, device=0, ctx=None) -> int:
     rf = RankFile(data, device=device, ctx=ctx)
     try:
         return rf.coverage(query, min_len, cyclic=cyclic)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def kgrams(data, ks, device=0, ctx=None):
+    """The cyclic k-grams of `data` (RankFile.kgrams): K1 and K2 index the data on the GPU, the LCP array of the sorted rotations is
+    built and reduced there."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.kgrams(ks)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def entropy_profile(data, K, device=0, ctx=None):
+    """[H_0 .. H_K] of the circular text `data`, in bits per byte (RankFile.entropy_profile)."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.entropy_profile(K)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def longest_repeat(data, max_len=MATCH_MAX_LEN, device=0, ctx=None):
+    """(len, pos_a, pos_b) of the longest repeat of the circular text `data` (RankFile.longest_repeat)."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.longest_repeat(max_len)
     finally:
         if ctx is None:
             rf.close()

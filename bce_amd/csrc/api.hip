@@ -700,7 +700,7 @@ void bce_hip_destroy(bce_hip_ctx *c) {
                     &c->rs_hist, &c->blk, &c->ptmp[0], &c->ptmp[1], &c->gran, &c->nlist[0], &c->nlist[1], &c->ctl, &c->tilecnt,
                     &c->tileoff, &c->runs, &c->smwords, &c->k3tw, &c->k3grp, &c->truns, &c->skey[0], &c->skey[1], &c->sval[0], &c->sval[1], &c->sout,
                     &c->sesc, &c->stat, &c->crc_tab, &c->dcfg, &c->k4w, &c->scanrec, &c->dfs, &c->skey_alt, &c->sesc_alt, &c->rs_hist_k4, &c->cost_acc, &c->cost_runs, &c->cmp_res, &c->cnt_res, &c->cnt_pat, &c->cnt_off, &c->cnt_out, &c->loc_res, &c->loc_lo, &c->loc_cnt, &c->loc_drop, &c->loc_start, &c->loc_lin, &c->loc_bsum,
-                    &c->loc_key[0], &c->loc_key[1], &c->loc_val[0], &c->loc_val[1], &c->loc_pat, &c->loc_off, &c->loc_hits, &c->loc_pos, &c->mat_res, &c->mat_bsum, &c->mat_qry, &c->mat_len, &c->mat_pos, &c->hook[0], &c->hook[1], &c->hook[2]};
+                    &c->loc_key[0], &c->loc_key[1], &c->loc_val[0], &c->loc_val[1], &c->loc_pat, &c->loc_off, &c->loc_hits, &c->loc_pos, &c->mat_res, &c->mat_bsum, &c->mat_qry, &c->mat_len, &c->mat_pos, &c->rep_res, &c->rep_bsum, &c->rep_lcp, &c->hook[0], &c->hook[1], &c->hook[2]};
   for (DevBuf *b : bufs) release(*b);
   for (auto &par : c->dlist) for (DevBuf &b : par) release(b);
   k4_prepin_join(c, true);
@@ -1670,6 +1670,98 @@ int bce_hip_coverage_device(bce_hip_ctx *c, const void *d_query, uint64_t q, uin
     BCE_HIP_TRY(c, hipSetDevice(c->device));
     PhaseScope phase(c, 3);
     return coverage_run(c, sa, static_cast<const uint8_t *>(d_query), (uint32_t)q, min_len, flags & BCE_HIP_MATCH_LINEAR, covered);
+  });
+}
+
+// ---- what the text holds by itself: the LCP array of the sorted rotations and its reductions (kd_lcp.hip) ---------------------------
+// Phase 3 with the locate's rule PLUS the text: both sa[sa_res] and `text` are read, neither is written, and no stage's scratch is
+// touched (the array, the block parts and the result words are rep_* buffers of the feature's own).  Nothing is kept from one call
+// to the next: every call runs its own LCP pass, so there is nothing that a load, bce_hip_set_bwt or a decode could leave stale.
+// The arguments are judged before the state, the state before the outputs, as for the match.
+static int repeat_bound(bce_hip_ctx *c, const char *what, uint32_t max_len) {
+  if (max_len >= 1 && max_len <= BCE_HIP_MATCH_MAX_LEN) return BCE_HIP_OK;
+  snprintf(c->err, sizeof c->err, "%s: a length bound of %u, outside 1 .. %u", what, max_len, BCE_HIP_MATCH_MAX_LEN);
+  return BCE_HIP_E_ARG;
+}
+static int repeat_state(bce_hip_ctx *c, const uint32_t **sa, const char *what) {
+  BCE_TRY(locate_state(c, sa, what));
+  if (c->text_loaded && c->text.p && c->text.cap >= (size_t)c->n) return BCE_HIP_OK;
+  snprintf(c->err, sizeof c->err, "%s: there is no suffix array behind an injected BWT", what);
+  return BCE_HIP_E_STATE;
+}
+
+int bce_hip_lcp(bce_hip_ctx *c, uint32_t max_len, uint32_t *lcp_out) {
+  if (!c) return BCE_HIP_E_ARG;
+  BCE_TRY(repeat_bound(c, "lcp", max_len));
+  const uint32_t *sa = nullptr;
+  BCE_TRY(repeat_state(c, &sa, "lcp"));
+  if (!lcp_out) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope phase(c, 3);
+    const size_t words = (size_t)c->n * 4;
+    BCE_TRY(ensure(c, c->rep_lcp, words));
+    BCE_TRY(kd_lcp(c, sa, max_len, c->rep_lcp.as<uint32_t>()));
+    BCE_HIP_TRY(c, hipMemcpyAsync(lcp_out, c->rep_lcp.p, words, hipMemcpyDeviceToHost, c->stream));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    BCE_HIP_TRY(c, hipGetLastError());
+    return BCE_HIP_OK;
+  });
+}
+
+int bce_hip_lcp_device(bce_hip_ctx *c, uint32_t max_len, void *d_lcp) {
+  if (!c) return BCE_HIP_E_ARG;
+  BCE_TRY(repeat_bound(c, "lcp", max_len));
+  const uint32_t *sa = nullptr;
+  BCE_TRY(repeat_state(c, &sa, "lcp"));
+  if (!d_lcp) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope phase(c, 3);
+    BCE_TRY(kd_lcp(c, sa, max_len, static_cast<uint32_t *>(d_lcp)));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    BCE_HIP_TRY(c, hipGetLastError());
+    return BCE_HIP_OK;
+  });
+}
+
+int bce_hip_kgrams(bce_hip_ctx *c, const uint32_t *ks, uint32_t nk, bce_hip_kgram *out) {
+  if (!c) return BCE_HIP_E_ARG;
+  if (nk > BCE_HIP_KGRAMS_MAX) { snprintf(c->err, sizeof c->err, "kgrams: %u values of k, more than %u", nk, BCE_HIP_KGRAMS_MAX); return BCE_HIP_E_ARG; }
+  if (nk == 0) return BCE_HIP_OK;
+  if (!ks) return BCE_HIP_E_ARG;
+  uint32_t bound = 1;                                                 // (k = 0 needs no array at all; the pass is bounded by 1 then)
+  for (uint32_t i = 0; i < nk; ++i) {
+    if (ks[i] > BCE_HIP_MATCH_MAX_LEN) { snprintf(c->err, sizeof c->err, "kgrams: k = %u, outside 0 .. %u", ks[i], BCE_HIP_MATCH_MAX_LEN); return BCE_HIP_E_ARG; }
+    if (ks[i] > bound) bound = ks[i];
+  }
+  const uint32_t *sa = nullptr;
+  BCE_TRY(repeat_state(c, &sa, "kgrams"));
+  if (!out) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope phase(c, 3);
+    BCE_TRY(ensure(c, c->rep_lcp, (size_t)c->n * 4));
+    BCE_TRY(kd_lcp(c, sa, bound, c->rep_lcp.as<uint32_t>()));
+    return kd_kgrams(c, sa, c->rep_lcp.as<uint32_t>(), ks, nk, out);
+  });
+}
+
+int bce_hip_longest_repeat(bce_hip_ctx *c, uint32_t max_len, uint32_t *len, uint32_t *pos_a, uint32_t *pos_b) {
+  if (!c) return BCE_HIP_E_ARG;
+  BCE_TRY(repeat_bound(c, "longest repeat", max_len));
+  const uint32_t *sa = nullptr;
+  BCE_TRY(repeat_state(c, &sa, "longest repeat"));
+  if (!len || !pos_a || !pos_b) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope phase(c, 3);
+    uint32_t res[3];
+    BCE_TRY(ensure(c, c->rep_lcp, (size_t)c->n * 4));
+    BCE_TRY(kd_lcp(c, sa, max_len, c->rep_lcp.as<uint32_t>()));
+    BCE_TRY(kd_longest_repeat(c, sa, c->rep_lcp.as<uint32_t>(), res));
+    *len = res[0]; *pos_a = res[1]; *pos_b = res[2];
+    return BCE_HIP_OK;
   });
 }
 

@@ -219,6 +219,9 @@ struct bce_hip_ctx {
   bce::DevBuf mat_res;                           // kd_match.hip: the coverage's result word (a buffer of its own, as loc_res)
   bce::DevBuf mat_bsum;                          // the coverage scan's block maxima and block counts
   bce::DevBuf mat_qry, mat_len, mat_pos;         // bce_hip_match / _coverage: the query of a call with a host buffer, the lengths and the positions, staged (all grow-only)
+  bce::DevBuf rep_res;                           // kd_lcp.hip: its result words, up to 64 k-gram records or the longest repeat's three (a buffer of its own, as mat_res)
+  bce::DevBuf rep_bsum;                          // the class and repeat reductions' per-block parts and maxima
+  bce::DevBuf rep_lcp;                           // the LCP array of a call that does not bring device memory for it: n words (grow-only, never kept as a cache)
   bce::DevBuf hook[3];                           // test hooks bce_hip_sort_pairs_device / _wide_device: the second halves of the sorts' ping-pong
   bool crc_const_ready = false;                  // its launch-independent constants are uploaded
   bool text_loaded = false;                      // `text` holds the n bytes of the last bce_hip_load_* (bce_hip_input_crc32)
@@ -441,6 +444,11 @@ int kd_locate_fill(bce_hip_ctx *c, const uint32_t *sa, const uint64_t *d_off, ui
 int kd_match(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_query, uint32_t q, uint32_t max_len, bool linear, uint32_t *d_len,
              uint32_t *d_pos);
 int kd_coverage(bce_hip_ctx *c, const uint32_t *d_len, uint32_t q, uint32_t min_len, uint64_t *covered);
+// kd_lcp.hip: the LCP array of the sorted rotations of the circular text, capped at max_len (queued, the caller waits); the records
+// of nk <= 64 values of k and the longest repeat, reduced from such an array (both wait: the result's way back)
+int kd_lcp(bce_hip_ctx *c, const uint32_t *sa, uint32_t max_len, uint32_t *d_lcp);
+int kd_kgrams(bce_hip_ctx *c, const uint32_t *sa, const uint32_t *d_lcp, const uint32_t *ks, uint32_t nk, bce_hip_kgram *out);
+int kd_longest_repeat(bce_hip_ctx *c, const uint32_t *sa, const uint32_t *d_lcp, uint32_t res[3]);
 int k2_build_planes(bce_hip_ctx *c);                // k2_planes.hip
 int k2_get_plane_bits(bce_hip_ctx *c, int plane, uint8_t *out);
 int k2_rank1(bce_hip_ctx *c, int plane, const uint32_t *idx, uint32_t count, uint32_t *out);

@@ -7,6 +7,7 @@
 //   bce -gd PATTERN archive                 (extension) the same in what an archive or container holds
 //   bce -gl PATTERN file, -gld PATTERN archive   (extension) where they occur: the byte offsets, gathered on the GPU from K1's suffix array
 //   bce -gm MINLEN file query_file, -gmd MINLEN archive query_file   (extension) how much of a second file lies in strings of MINLEN bytes or more that occur in the first
+//   bce -gk K file, -gkd K archive          (extension) the k-grams of the circular text for k = 0..K: how many, how many occur once, the most frequent, H_k; the longest repeat
 // Banner, usage text, summary line, argument detection and exit codes follow the reference
 // (banner :1377-1379, -c :1403-1427, -d :1428-1472, usage :1473-1483).  -d uses the GPU-assisted decoder (kd_decode.hip), -ds the host decoder (decoder.cpp);
 // -s runs the enumeration on the GPU in scan mode and the ScanCoder optimisation on the host (scan_coder.cpp).
@@ -131,6 +132,8 @@ extern "C" int bce_hip_count(bce_hip_ctx *ctx, const uint8_t *patterns, const ui
 extern "C" int bce_hip_locate(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t flags, uint64_t *hit_offsets,
                               uint32_t *positions, uint64_t cap, uint64_t *total) __attribute__((weak));
 extern "C" int bce_hip_coverage(bce_hip_ctx *ctx, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t flags, uint64_t *covered) __attribute__((weak));
+extern "C" int bce_hip_kgrams(bce_hip_ctx *ctx, const uint32_t *ks, uint32_t nk, bce_hip_kgram *out) __attribute__((weak));
+extern "C" int bce_hip_longest_repeat(bce_hip_ctx *ctx, uint32_t max_len, uint32_t *len, uint32_t *pos_a, uint32_t *pos_b) __attribute__((weak));
 
 // `bce -cN`: N contiguous blocks over the GPUs of the node.  With more blocks than GPUs every device gets up to four
 // gated contexts (bce_hip_set_gated), one host thread each: their GPU phases take turns while the coder threads of the
@@ -436,6 +439,10 @@ static int estimate_file(const char *file, const char *config) {
 // `-gm MINLEN file query_file` / `-gmd MINLEN archive query_file` (coverage): the file or archive is read, judged, decoded and indexed
 // in the same way; query_file is a plain file, judged with the words of -g's.  One line: how many of its bytes lie in strings of
 // MINLEN bytes or more that occur in the indexed text (bce_hip_coverage, linear matches: searched and reduced on the GPU).
+// `-gk K file` / `-gkd K archive` (k-grams): the file or archive is read, judged, decoded and indexed in the same way.  For k = 0..K
+// one line: the distinct k-grams of the CIRCULAR text, those that occur once, the occurrences of the most frequent one and the order-k
+// empirical entropy H_k = max(0, S_k - S_(k+1)) / (n 2^24) from the integer sums of bce_hip_kgrams; then the longest repeat
+// (bce_hip_longest_repeat at the bound 4096) and the text's size.  Two LCP passes, bounded by K + 1 and by 4096: nothing is cached.
 static uint64_t seam_matches(const uint8_t *t, size_t n, const uint8_t *pat, size_t m) {
   std::vector<uint8_t> seam(t + n - (m - 1), t + n);
   seam.insert(seam.end(), t, t + (m - 1));
@@ -443,9 +450,10 @@ static uint64_t seam_matches(const uint8_t *t, size_t n, const uint8_t *pat, siz
   for (size_t s = 0; s + m <= seam.size(); ++s) found += memcmp(seam.data() + s, pat, m) == 0;
   return found;
 }
-enum GrepMode { kGrepCount, kGrepLocate, kGrepCoverage };
+constexpr uint32_t kMaxKgramOrder = 32;                            // -gk / -gkd: the largest K
+enum GrepMode { kGrepCount, kGrepLocate, kGrepCoverage, kGrepKgrams };
 static int count_pattern(const char *pattern, const char *path, bool in_archive, GrepMode mode, const char *query_path = nullptr, uint32_t min_len = 0) {
-  const bool locate = mode == kGrepLocate, coverage = mode == kGrepCoverage;
+  const bool locate = mode == kGrepLocate, coverage = mode == kGrepCoverage, kgrams = mode == kGrepKgrams;
   const size_t m = strlen(pattern);
   const uint8_t *pat = reinterpret_cast<const uint8_t *>(pattern);
   HostFile file;
@@ -462,7 +470,7 @@ static int count_pattern(const char *pattern, const char *path, bool in_archive,
   if (in_archive && (file.status != 0 || file.size() == 0)) { printf("Could not read Archive.\n"); return -2; }
   if (!in_archive && (file.status != 0 || file.size() == 0 || file.size() >= kMaxInput)) { printf("Error loading file\n"); return -1; }
   if (coverage && (query.status != 0 || query.size() == 0 || query.size() >= kMaxInput)) { printf("Error loading file\n"); return -1; }
-  if (rc0 != 0 || !bce_hip_count || (locate && !bce_hip_locate) || (coverage && !bce_hip_coverage)) { printf("No usable HIP device: %s\n", bce_hip_strerror(rc0 ? rc0 : BCE_HIP_E_DEVICE)); return -3; }
+  if (rc0 != 0 || !bce_hip_count || (locate && !bce_hip_locate) || (coverage && !bce_hip_coverage) || (kgrams && (!bce_hip_kgrams || !bce_hip_longest_repeat))) { printf("No usable HIP device: %s\n", bce_hip_strerror(rc0 ? rc0 : BCE_HIP_E_DEVICE)); return -3; }
   const uint8_t *text = file.data();
   size_t n = file.size();
   std::vector<uint8_t> decoded;
@@ -512,6 +520,32 @@ static int count_pattern(const char *pattern, const char *path, bool in_archive,
     fast_exit(0);
     return 0;
   }
+  if (kgrams) {
+    const uint32_t K = min_len;                                       // (k = 0 .. K, and K + 1 for H_K)
+    uint32_t ks[kMaxKgramOrder + 2];
+    bce_hip_kgram rec[kMaxKgramOrder + 2];
+    for (uint32_t k = 0; k < K + 2; ++k) ks[k] = k;
+    uint32_t len = 0, pos_a = 0, pos_b = 0;
+    int rc = bce_hip_load_host(ctx, text, (uint32_t)n);
+    if (rc == 0) rc = bce_hip_bwt(ctx, nullptr);
+    if (rc == 0) rc = bce_hip_build_planes(ctx, nullptr);
+    if (rc == 0) rc = bce_hip_kgrams(ctx, ks, K + 2, rec);
+    if (rc == 0) rc = bce_hip_longest_repeat(ctx, BCE_HIP_MATCH_MAX_LEN, &len, &pos_a, &pos_b);
+    if (rc != 0) { printf("K-grams failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); return -4; }
+    printf("k-grams of the circular text: k distinct once most H_k\n");
+    for (uint32_t k = 0; k <= K; ++k) {
+      const uint64_t a = rec[k].nlogn_q24, b = rec[k + 1].nlogn_q24;
+      const double h = (double)(a > b ? a - b : 0) / ((double)n * 16777216.0);
+      printf("%u %llu %llu %u %.6f\n", k, (unsigned long long)rec[k].distinct, (unsigned long long)rec[k].once, rec[k].max_count, h);
+    }
+    if (len == 0) printf("longest repeat: none\n");
+    else if (len >= BCE_HIP_MATCH_MAX_LEN) printf("longest repeat: %u or more bytes at %u and %u\n", len, pos_a, pos_b);
+    else printf("longest repeat: %u bytes at %u and %u\n", len, pos_a, pos_b);
+    printf("%zu bytes\n", n);
+    ctx = nullptr;                                                    // (left to fast_exit, like -d)
+    fast_exit(0);
+    return 0;
+  }
   uint64_t count = 0;
   std::vector<uint32_t> where;
   if (m <= n) {                                                     // (a longer pattern occurs nowhere in the text, only around it)
@@ -550,6 +584,18 @@ static uint32_t parse_min_len(const char *s) {
     if (v > BCE_HIP_MATCH_MAX_LEN) return 0;
   }
   return v;
+}
+
+// K of -gk / -gkd: decimal digits only, 0 .. 32; anything else: -1
+static int parse_order(const char *s) {
+  uint32_t v = 0;
+  if (!*s) return -1;
+  for (; *s; ++s) {
+    if (*s < '0' || *s > '9') return -1;
+    v = v * 10 + (uint32_t)(*s - '0');
+    if (v > kMaxKgramOrder) return -1;
+  }
+  return (int)v;
 }
 
 static int usage() {
@@ -594,6 +640,12 @@ static int usage() {
   printf("\n");
   printf("  bce -gmd MINLEN archive.bce query_file\n");
   printf("   The same figure against what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
+  printf("\n");
+  printf("  bce -gk K file\n");
+  printf("   Prints for k = 0..K (K = 0..32) how many distinct k-grams the circular text of \"file\" has, how many occur once, how often the most frequent one occurs and the order-k entropy H_k in bits per byte, then its longest repeat: all reduced on the GPU from the LCP array of the sorted rotations (extension)\n");
+  printf("\n");
+  printf("  bce -gkd K archive.bce\n");
+  printf("   The same figures for what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
   return 0;
 }
 
@@ -867,6 +919,8 @@ int main(int argc, char **argv) {
     return count_pattern(argv[2], argv[3], argv[1][3] == 'd', kGrepLocate);
   } else if (argc == 5 && (strcmp(argv[1], "-gm") == 0 || strcmp(argv[1], "-gmd") == 0) && parse_min_len(argv[2]) != 0) {
     return count_pattern("", argv[3], argv[1][3] == 'd', kGrepCoverage, argv[4], parse_min_len(argv[2]));
+  } else if (argc == 4 && (strcmp(argv[1], "-gk") == 0 || strcmp(argv[1], "-gkd") == 0) && parse_order(argv[2]) >= 0) {
+    return count_pattern("", argv[3], argv[1][3] == 'd', kGrepKgrams, nullptr, (uint32_t)parse_order(argv[2]));
   } else if (argc == 4 && argv[1][0] == '-' && argv[1][1] == 's') {
     // Scan (bce.cpp:1384-1402): enumeration on the GPU, ScanCoder optimisation on the host, 288-byte config out
     auto start = std::chrono::high_resolution_clock::now();

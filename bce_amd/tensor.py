@@ -208,6 +208,56 @@ def coverage_in_archive(blob, query, min_len, cyclic=False, device="cuda:0") -> 
     return coverage_tensor(decompress_container_tensor(blob, device=device), query, min_len, cyclic=cyclic)
 
 
+def _indexed(t, what, ctx, use):
+    """use(RankFile of the 1-D uint8 CUDA tensor t, indexed where it lies) with a context of t's device."""
+    _check(t, "t")
+    n = t.numel()
+    if n == 0:
+        raise api.BceError(-1, what, "empty input")
+    if n > _MAX_BLOCK:
+        raise ValueError("one index covers one text of less than 2^31 bytes, not %d" % n)
+    _ready(t)
+    own = ctx is None
+    c = ctx or api._Ctx(t.device.index)
+    try:
+        return use(api.RankFile(n=n, device_ptr=t.data_ptr(), ctx=c))
+    finally:
+        if own:
+            c.close()
+
+
+def lcp_tensor(t, max_len, ctx=None):
+    """The LCP array of the sorted rotations of the circular text in the 1-D uint8 CUDA tensor `t` -> an int32 tensor of n words on
+    t's device (api.RankFile.lcp; the values are at most 4096).  The text is indexed where it lies and the array is written where
+    it stays (bce_hip_lcp_device); nothing reaches the host.
+    Synchronises t's current stream first; `ctx` (an api._Ctx of t's device) is reused if given."""
+    def use(rf):
+        out = torch.zeros(t.numel(), dtype=torch.int32, device=t.device)
+        torch.cuda.current_stream(t.device).synchronize()            # (the zero fill is done before the library's stream writes)
+        rf.lcp_device(max_len, out.data_ptr())
+        return out
+    return _indexed(t, "lcp_tensor", ctx, use)
+
+
+def kgrams_tensor(t, ks, ctx=None):
+    """api.RankFile.kgrams of the 1-D uint8 CUDA tensor `t`, indexed and reduced where it lies; 32 bytes per k reach the host."""
+    return _indexed(t, "kgrams_tensor", ctx, lambda rf: rf.kgrams(ks))
+
+
+def entropy_profile_tensor(t, K, ctx=None):
+    """[H_0 .. H_K] of the circular text in the 1-D uint8 CUDA tensor `t` (api.RankFile.entropy_profile)."""
+    return _indexed(t, "entropy_profile_tensor", ctx, lambda rf: rf.entropy_profile(K))
+
+
+def entropy_profile_in_archive(blob, K, device="cuda:0"):
+    """entropy_profile_tensor on what an archive holds, decoded as count_in_archive decodes it: into ONE tensor on the device, so
+    the profile is that of the concatenated blocks.  A container of 2^31 bytes or more: ValueError, before anything is decoded."""
+    total = sum(t[0] for t in _blocks_of(blob))
+    if total > _MAX_BLOCK:
+        raise ValueError("the archive holds %d bytes: one index covers one text of less than 2^31" % total)
+    return entropy_profile_tensor(decompress_container_tensor(blob, device=device), K)
+
+
 def decompress_tensor(archive, device="cuda:0", out=None, ctx=None):
     """The GPU-assisted decoder with the text left on the device (bce_hip_decompress_to_device) -> a 1-D uint8 tensor there.
 

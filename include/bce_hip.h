@@ -368,6 +368,49 @@ int bce_hip_coverage(bce_hip_ctx *ctx, const uint8_t *query, uint64_t q, uint32_
 /* The same with the query in device memory; covered stays a host pointer. */
 int bce_hip_coverage_device(bce_hip_ctx *ctx, const void *d_query, uint64_t q, uint32_t min_len, uint32_t flags, uint64_t *covered);
 
+/* ---- extension: what the input holds by ITSELF: LCP array, k-gram classes, longest repeat (kd_lcp.hip, lcp_step.h) -------------
+ * Everything here is about the CIRCULAR text, as bce_hip_count's cyclic mode and the coder see it: rotation a of the n bytes T is
+ * T[(a + j) mod n], j = 0, 1, ...  A linear variant is out of scope: the longest repeat of the linear text is not a maximum over
+ * adjacent rows (a middle row that starts near the text's end truncates the pairs with both of its neighbours), so it is no cheap
+ * by-product of this array.
+ *   lcp[0] = 0, and for 1 <= r < n lcp[r] = the largest l <= max_len with T[(sa[r-1] + j) mod n] == T[(sa[r] + j) mod n] for all
+ *   j < l, sa = the sorted rotations (what bce_hip_locate reads).  There is NO cap at n: two equal rotations of a periodic text
+ *   give max_len.  So the capped array is a function of the text alone -- rows tied to max_len bytes all carry max_len among
+ *   themselves, in whatever order the sort left them.  max_len is a WORK bound per row, 1 .. BCE_HIP_MATCH_MAX_LEN, not a limit of
+ *   any format; one lane per row compares eight bytes at a time, byte by byte across the text's end.
+ * State: the suffix array by bce_hip_locate's rule AND the loaded text (not behind bce_hip_set_bwt, not after a decode took the
+ * buffers): otherwise BCE_HIP_E_STATE in bce_hip_locate's words.  A text of one byte has no array: lcp = [0].  No call here
+ * changes the compression state or writes a stage's buffers, and nothing is cached from one call to the next: each call runs
+ * its own pass.  A null ctx, a max_len outside 1 .. BCE_HIP_MATCH_MAX_LEN: BCE_HIP_E_ARG before any device call; then the state;
+ * then a null output: BCE_HIP_E_ARG.  A refused call leaves its outputs untouched. */
+int bce_hip_lcp(bce_hip_ctx *ctx, uint32_t max_len, uint32_t *lcp_out);
+/* The same into n words of device memory of the context's device, 4-byte aligned.  Stream rule: as bce_hip_count_device. */
+int bce_hip_lcp_device(bce_hip_ctx *ctx, uint32_t max_len, void *d_lcp);
+/* The cyclic k-grams of the text, for nk <= BCE_HIP_KGRAMS_MAX values of k in 0 .. BCE_HIP_MATCH_MAX_LEN (host arrays), from ONE
+ * LCP pass bounded by the largest k (at least 1).  For a k, a class is a maximal run of rows [s, e) with lcp[r] >= k for
+ * s < r < e: the rotations that start with one k-gram w, e - s = N(w) its occurrences in the circular text (k > n wraps around;
+ * k = 0: one class of n rows).  Per k:
+ *   distinct   the classes, i.e. the distinct k-grams;       once       those that occur once;
+ *   nlogn_q24  S_k = the sum over the classes of N * L(N), L = the Q24 integer log2 of bce_hip_cost_q24 (L(N) = cost_q24(1, N)):
+ *              a uint64_t sum, exact and independent of the order, below n * L(n) < 2^60.  For the circular text the order-k
+ *              empirical entropy is n * H_k = S_k - S_(k+1), in units of 2^-24 bit;
+ *   max_count  the largest class;  max_pos  the start of a rotation of the lowest-row class that reaches it (sa[s]; which of the
+ *              tied rotations of a periodic text that is, is not specified).
+ * Reduced on the device, block-wise and without atomics; 32 bytes per k come back.  n == 1: every k gives {1, 1, 0, 1, 0}.
+ * nk == 0: success, nothing launched.  A null ctx, nk > BCE_HIP_KGRAMS_MAX, a null ks, a k above BCE_HIP_MATCH_MAX_LEN:
+ * BCE_HIP_E_ARG before any device call; then the state; then a null out: BCE_HIP_E_ARG. */
+#define BCE_HIP_KGRAMS_MAX 64u
+typedef struct bce_hip_kgram {
+  uint64_t distinct, once, nlogn_q24;
+  uint32_t max_count, max_pos;
+} bce_hip_kgram;
+int bce_hip_kgrams(bce_hip_ctx *ctx, const uint32_t *ks, uint32_t nk, bce_hip_kgram *out);
+/* The longest repeat of the circular text: *len = the largest lcp[r] at bound max_len, *pos_a = sa[r - 1] and *pos_b = sa[r] of
+ * the lowest row r that reaches it: two rotations that agree on *len bytes.  *len == max_len means "max_len bytes or more".
+ * *len == 0 (no byte occurs twice; n == 1 always): there is no pair, both positions are 0xFFFFFFFF.  State and refusals as
+ * bce_hip_lcp; all three outputs are required. */
+int bce_hip_longest_repeat(bce_hip_ctx *ctx, uint32_t max_len, uint32_t *len, uint32_t *pos_a, uint32_t *pos_b);
+
 /* ---- test hooks: the device primitives every stage rests on, alone (tests/test_gpu_sort.py, tests/test_gpu_compare.py) ----
  * Stream rule of bce_hip_crc32_device for all three: the work runs on the context's stream and is complete on return; the caller's
  * memory (device memory of the context's device) must be ready when the call is made.  Valid in any state of the context, between
