@@ -49,6 +49,19 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ParseInfo(C.Structure):
+    """bce_hip_parse_info: what a parse holds (RankFile.parse): nlits + copied == q, nops - ncopies literal runs."""
+    _fields_ = [("nops", C.c_uint64), ("nlits", C.c_uint64), ("ncopies", C.c_uint64), ("copied", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+class Op(C.Structure):
+    """bce_hip_op: src == OP_LITERAL: the next len bytes of the literal stream; else text[src : src + len]."""
+    _fields_ = [("len", C.c_uint32), ("src", C.c_uint32)]
+
+
 # every symbol include/bce_hip.h declares: (name, restype, argtypes)
 _u8p, _u32p, _vp = C.c_void_p, C.c_void_p, C.c_void_p
 SYMBOLS = [
@@ -124,6 +137,11 @@ SYMBOLS = [
     ("bce_hip_lcp_device", C.c_int, [C.c_void_p, C.c_uint32, _vp]),
     ("bce_hip_kgrams", C.c_int, [C.c_void_p, _vp, C.c_uint32, _vp]),
     ("bce_hip_longest_repeat", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("bce_hip_parse", C.c_int, [C.c_void_p, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _u8p, C.c_uint64, C.POINTER(ParseInfo)]),
+    ("bce_hip_parse_device", C.c_int, [C.c_void_p, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(ParseInfo)]),
+    ("bce_hip_patch", C.c_int, [C.c_void_p, _vp, C.c_uint64, _u8p, C.c_uint64, _u8p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("bce_hip_patch_device", C.c_int, [C.c_void_p, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("bce_hip_parse_of_lengths_device", C.c_int, [C.c_void_p, _vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(ParseInfo)]),
     ("bce_hip_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     ("bce_hip_synth_text", None, [C.c_uint64, _u8p, C.c_size_t]),
     ("bce_hip_synth_rand", None, [C.c_uint64, _u8p, C.c_size_t]),
@@ -168,6 +186,9 @@ MATCH_LINEAR = 1                                # BCE_HIP_MATCH_LINEAR
 MATCH_MAX_LEN = 4096                            # BCE_HIP_MATCH_MAX_LEN: a work bound per end position, not a format limit
 KGRAMS_MAX = 64                                 # BCE_HIP_KGRAMS_MAX: values of k in one bce_hip_kgrams call
 E_OVERFLOW = -5                                 # BCE_HIP_E_OVERFLOW
+OP_LITERAL = 0xFFFFFFFF                         # BCE_HIP_OP_LITERAL: bce_hip_op::src of a literal run
+PARSE_MAX_LEN = 256                             # the default length bound of a parse: the search costs up to q * max_len lane steps
+OP_DTYPE = np.dtype([("len", "<u4"), ("src", "<u4")])   # bce_hip_op as a numpy record
 
 
 def _positions_buffer(total):
@@ -254,7 +275,7 @@ class RankFile:
     `data` may be bytes / a numpy u8 array (host) or an int device pointer with `n` (input resident in HBM).
     """
 
-    def __init__(self, data=None, n=None, device=0, device_ptr=None, bwt=None, offset=None, ctx=None, build=True):
+    def __init__(self, data=None, n=None, device=0, device_ptr=None, bwt=None, offset=None, ctx=None, build=True, index=True):
         self._c = ctx or _Ctx(device)
         lib = self._c.lib
         self._status = 0
@@ -277,11 +298,13 @@ class RankFile:
                 self._c.check(lib.bce_hip_load_host(self._c.h, a.ctypes.data, len(a)), "bce_hip_load_host")
                 self._n = len(a)
                 self._text = a
-            off = C.c_uint32()
-            self._c.check(lib.bce_hip_bwt(self._c.h, C.byref(off)), "bce_hip_bwt")
-            self._offset = off.value
+            self._offset = None
+            if index:                            # (index=False: the text is loaded and nothing more -- all that patch() reads)
+                off = C.c_uint32()
+                self._c.check(lib.bce_hip_bwt(self._c.h, C.byref(off)), "bce_hip_bwt")
+                self._offset = off.value
         self.zeros = None
-        if build:
+        if build and index:
             z = (C.c_uint32 * 8)()
             self._c.check(lib.bce_hip_build_planes(self._c.h, z), "bce_hip_build_planes")
             self.zeros = list(z)
@@ -494,8 +517,62 @@ class RankFile:
         self._c.check(self._c.lib.bce_hip_longest_repeat(self._c.h, int(max_len), C.byref(ln), C.byref(a), C.byref(b)), "bce_hip_longest_repeat")
         return ln.value, a.value, b.value
 
+    def parse(self, query, min_len, max_len=PARSE_MAX_LEN):
+        """`query` (a bytes-like, a second buffer) written as copies out of the text plus the bytes that are new (bce_hip_parse: the
+        linear matching statistics at bound max_len, then from the query's end a copy of lens[e] bytes wherever lens[e] >= min_len,
+        else a literal byte; on the GPU) -> (ops, lits, info): ops a numpy record array (len, src) in query order, src == OP_LITERAL
+        for a run of literal bytes -- the next len bytes of lits (uint8) -- else text[src : src + len]; info a dict (nops, nlits,
+        ncopies, copied).  A sizing call, then the full call; each runs the search."""
+        q = _as_u8(query)
+        info = ParseInfo()
+        qp = q.ctypes.data if len(q) else None
+        self._c.check(self._c.lib.bce_hip_parse(self._c.h, qp, len(q), int(min_len), int(max_len), None, 0, None, 0, C.byref(info)), "bce_hip_parse")
+        ops, lits = np.zeros(info.nops, dtype=OP_DTYPE), np.zeros(info.nlits, dtype=np.uint8)
+        if len(q):
+            self._c.check(self._c.lib.bce_hip_parse(self._c.h, qp, len(q), int(min_len), int(max_len), ops.ctypes.data, len(ops),
+                                                    lits.ctypes.data if len(lits) else None, len(lits), C.byref(info)), "bce_hip_parse")
+        return ops, lits, info.as_dict()
+
+    def parse_device(self, query_ptr, q, min_len, max_len=PARSE_MAX_LEN, ops_ptr=None, ops_cap=0, lits_ptr=None, lits_cap=0):
+        """bce_hip_parse_device: the same for a query of `q` bytes in device memory, into `ops_cap` ops (8 bytes each, 4-byte
+        aligned) at ops_ptr and `lits_cap` bytes at lits_ptr (int pointers; both None with caps 0: a sizing call) -> the info dict.
+        More ops or literal bytes than room: BceError with status E_OVERFLOW, nothing written.  Stream rule: as count_device."""
+        info = ParseInfo()
+        self._c.check(self._c.lib.bce_hip_parse_device(self._c.h, _ptr(query_ptr), int(q), int(min_len), int(max_len), _ptr(ops_ptr), int(ops_cap),
+                                                       _ptr(lits_ptr), int(lits_cap), C.byref(info)), "bce_hip_parse_device")
+        return info.as_dict()
+
+    def patch(self, ops, lits):
+        """The bytes that `ops` (a record array as parse() gives, or an (nops, 2) uint32 array of (len, src)) and `lits` describe
+        over the text (bce_hip_patch: validated and copied on the GPU) -> a numpy uint8 array.  Any well-formed list is taken; one
+        that is not raises BceError (status -1) with the reason."""
+        ops, lits = _as_ops(ops), _as_u8(lits)
+        total = C.c_uint64(0)
+        args = (self._c.h, ops.ctypes.data if len(ops) else None, len(ops), lits.ctypes.data if len(lits) else None, len(lits))
+        self._c.check(self._c.lib.bce_hip_patch(*(args + (None, 0, C.byref(total)))), "bce_hip_patch")
+        out = np.zeros(total.value, dtype=np.uint8)
+        if total.value:
+            self._c.check(self._c.lib.bce_hip_patch(*(args + (out.ctypes.data, len(out), C.byref(total)))), "bce_hip_patch")
+        return out
+
+    def patch_device(self, ops_ptr, nops, lits_ptr, nlits, out_ptr=None, cap=0) -> int:
+        """bce_hip_patch_device: the same with the ops, the literal bytes and the result in device memory (int pointers; out_ptr
+        None with cap 0 validates and sizes) -> the result's bytes.  Stream rule: as count_device."""
+        total = C.c_uint64(0)
+        self._c.check(self._c.lib.bce_hip_patch_device(self._c.h, _ptr(ops_ptr), int(nops), _ptr(lits_ptr), int(nlits), _ptr(out_ptr), int(cap),
+                                                       C.byref(total)), "bce_hip_patch_device")
+        return total.value
+
     def close(self):
         self._c.close()
+
+
+def _as_ops(ops):
+    """ops as contiguous (len, src) pairs of little-endian uint32: a record array of OP_DTYPE, or anything of shape (nops, 2)."""
+    if isinstance(ops, np.ndarray) and ops.dtype == OP_DTYPE:
+        return np.ascontiguousarray(ops)
+    a = np.ascontiguousarray(np.asarray(ops, dtype=np.uint32).reshape(-1, 2))
+    return a.view(OP_DTYPE).reshape(-1)
 
 
 class BCE:
@@ -669,6 +746,70 @@ def coverage(data, query, min_len, cyclic=False, device=0, ctx=None) -> int:
     finally:
         if ctx is None:
             rf.close()
+
+
+def parse(data, query, min_len, max_len=PARSE_MAX_LEN, device=0, ctx=None):
+    """`query` as copies out of `data` plus literal bytes -> (ops, lits, info) as RankFile.parse: K1 and K2 index the data on the GPU."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.parse(query, min_len, max_len)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def patch(data, ops, lits, device=0, ctx=None):
+    """The bytes that `ops` and `lits` describe over `data` (RankFile.patch; the data is loaded, not indexed) -> a numpy uint8 array."""
+    rf = RankFile(data, device=device, ctx=ctx, build=False, index=False)
+    try:
+        return rf.patch(ops, lits)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def delta(base, new, min_len=16, max_len=PARSE_MAX_LEN, device=0, ctx=None) -> bytes:
+    """`new` as a delta against `base`: a "BCED" file (container.pack_delta) of the parse of `new` in the index of `base`, with the
+    CRC-32 of both sides -- the base's from the context that indexed it, on the GPU.  An empty base raises BceError."""
+    from . import container
+    rf = RankFile(base, device=device, ctx=ctx)
+    try:
+        ops, lits, _ = rf.parse(new, min_len, max_len)
+        return container.pack_delta(rf.size(), input_crc32(rf._c), len(_as_u8(new)), crc32(new), min_len, max_len, ops, lits)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def apply_delta(base, blob, device=0, ctx=None) -> bytes:
+    """What delta(base, ...) was made from, rebuilt from `base` and the delta file `blob`.  The file is read and judged before
+    anything goes to a device; a base of another size or CRC-32, or a result with another CRC-32: ChecksumError, nothing returned."""
+    from . import container
+    d = container.unpack_delta(blob)
+    base = _as_u8(base)
+    if len(base) != d["n"]:
+        raise ChecksumError(0, d["base_crc"], crc32(base))
+    rf = RankFile(base, device=device, ctx=ctx, build=False, index=False)
+    try:
+        have = input_crc32(rf._c)
+        if have != d["base_crc"]:
+            raise ChecksumError(0, d["base_crc"], have)
+        out = rf.patch(d["ops"], d["lits"])
+        if len(out) != d["q"] or crc32(out) != d["crc"]:
+            raise ChecksumError(0, d["crc"], crc32(out))
+        return out.tobytes()
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def parse_of_lengths_device(ptr_len, ptr_pos, ptr_query, q, min_len, ctx, ptr_ops=None, ops_cap=0, ptr_lits=None, lits_cap=0):
+    """Test hook (bce_hip_parse_of_lengths_device): the parse alone on `q` uint32 lengths (lens[i] <= i + 1), positions (ptr_pos may
+    be None: src = 0) and query bytes at device pointers -> (status, info dict); both outputs None with caps 0 sizes."""
+    info = ParseInfo()
+    rc = ctx.lib.bce_hip_parse_of_lengths_device(ctx.h, _ptr(ptr_len), _ptr(ptr_pos), _ptr(ptr_query), int(q), int(min_len), _ptr(ptr_ops), int(ops_cap),
+                                                 _ptr(ptr_lits), int(lits_cap), C.byref(info))
+    return rc, info.as_dict()
 
 
 def kgrams(data, ks, device=0, ctx=None):

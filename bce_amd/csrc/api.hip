@@ -9,6 +9,7 @@
 
 #include "bce_cost.h"
 #include "common.h"
+#include "parse_step.h"
 #include "host_coder.h"
 #include "scan_coder.h"
 
@@ -700,7 +701,7 @@ void bce_hip_destroy(bce_hip_ctx *c) {
                     &c->rs_hist, &c->blk, &c->ptmp[0], &c->ptmp[1], &c->gran, &c->nlist[0], &c->nlist[1], &c->ctl, &c->tilecnt,
                     &c->tileoff, &c->runs, &c->smwords, &c->k3tw, &c->k3grp, &c->truns, &c->skey[0], &c->skey[1], &c->sval[0], &c->sval[1], &c->sout,
                     &c->sesc, &c->stat, &c->crc_tab, &c->dcfg, &c->k4w, &c->scanrec, &c->dfs, &c->skey_alt, &c->sesc_alt, &c->rs_hist_k4, &c->cost_acc, &c->cost_runs, &c->cmp_res, &c->cnt_res, &c->cnt_pat, &c->cnt_off, &c->cnt_out, &c->loc_res, &c->loc_lo, &c->loc_cnt, &c->loc_drop, &c->loc_start, &c->loc_lin, &c->loc_bsum,
-                    &c->loc_key[0], &c->loc_key[1], &c->loc_val[0], &c->loc_val[1], &c->loc_pat, &c->loc_off, &c->loc_hits, &c->loc_pos, &c->mat_res, &c->mat_bsum, &c->mat_qry, &c->mat_len, &c->mat_pos, &c->rep_res, &c->rep_bsum, &c->rep_lcp, &c->hook[0], &c->hook[1], &c->hook[2]};
+                    &c->loc_key[0], &c->loc_key[1], &c->loc_val[0], &c->loc_val[1], &c->loc_pat, &c->loc_off, &c->loc_hits, &c->loc_pos, &c->mat_res, &c->mat_bsum, &c->mat_qry, &c->mat_len, &c->mat_pos, &c->rep_res, &c->rep_bsum, &c->rep_lcp, &c->par_res, &c->par_exit, &c->par_entry, &c->par_flag, &c->par_bsum, &c->par_bcnt, &c->par_hpre, &c->par_off, &c->par_loff, &c->par_ops, &c->par_lits, &c->par_out, &c->hook[0], &c->hook[1], &c->hook[2]};
   for (DevBuf *b : bufs) release(*b);
   for (auto &par : c->dlist) for (DevBuf &b : par) release(b);
   k4_prepin_join(c, true);
@@ -1790,6 +1791,145 @@ int bce_hip_longest_repeat(bce_hip_ctx *c, uint32_t max_len, uint32_t *len, uint
     BCE_TRY(kd_longest_repeat(c, sa, c->rep_lcp.as<uint32_t>(), c->n, res));
     *len = res[0]; *pos_a = res[1]; *pos_b = res[2];
     return BCE_HIP_OK;
+  });
+}
+
+// ---- a second buffer as a delta against the text: parse and patch (kd_parse.hip) ----------------------------------------------------
+// The parse: phase 3 with the match's rule and positions (locate_state).  The query of a call with a host buffer and the
+// statistics are staged in the match's mat_qry / mat_len / mat_pos; every other temporary is a par_* buffer of the feature's own,
+// and nothing a stage keeps is written.  The patch reads the text alone.  Arguments before the state, the state before the arrays.
+static int parse_args(bce_hip_ctx *c, uint64_t q, uint32_t min_len, uint32_t max_len, const void *ops, uint64_t ops_cap, const void *lits,
+                      uint64_t lits_cap, bce_hip_parse_info *info) {
+  if (!c || !info) return BCE_HIP_E_ARG;
+  if (min_len < 1 || min_len > max_len || max_len > BCE_HIP_MATCH_MAX_LEN) {
+    snprintf(c->err, sizeof c->err, "parse: bounds %u .. %u, outside 1 <= min_len <= max_len <= %u", min_len, max_len, BCE_HIP_MATCH_MAX_LEN);
+    return BCE_HIP_E_ARG;
+  }
+  if (q > 0x7FFFFFFFull) { snprintf(c->err, sizeof c->err, "parse: a query of 2^31 bytes or more"); return BCE_HIP_E_ARG; }
+  if ((!ops && ops_cap) || (!lits && lits_cap)) return BCE_HIP_E_ARG;
+  return BCE_HIP_OK;
+}
+
+int bce_hip_parse(bce_hip_ctx *c, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t max_len, bce_hip_op *ops, uint64_t ops_cap,
+                  uint8_t *lits, uint64_t lits_cap, bce_hip_parse_info *info) {
+  BCE_TRY(parse_args(c, q, min_len, max_len, ops, ops_cap, lits, lits_cap, info));
+  if (q == 0) { *info = bce_hip_parse_info{0, 0, 0, 0}; return BCE_HIP_OK; }
+  const uint32_t *sa = nullptr;
+  BCE_TRY(locate_state(c, &sa, "parse"));
+  if (!query) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope phase(c, 3);
+    const size_t words = (size_t)q * 4;
+    BCE_TRY(ensure(c, c->mat_qry, (size_t)q));
+    BCE_TRY(ensure(c, c->mat_len, words));
+    BCE_TRY(ensure(c, c->mat_pos, words));
+    BCE_HIP_TRY(c, hipMemcpyAsync(c->mat_qry.p, query, (size_t)q, hipMemcpyHostToDevice, c->stream));
+    BCE_TRY(kd_match(c, sa, c->mat_qry.as<uint8_t>(), (uint32_t)q, max_len, true, c->mat_len.as<uint32_t>(), c->mat_pos.as<uint32_t>()));
+    // sized first: the staging of the two outputs is as large as they are, and an overflow touches neither
+    BCE_TRY(kd_parse(c, c->mat_len.as<uint32_t>(), c->mat_pos.as<uint32_t>(), c->mat_qry.as<uint8_t>(), (uint32_t)q, min_len, true, nullptr, 0,
+                     nullptr, 0, info));
+    if (!ops && !lits) return BCE_HIP_OK;
+    BCE_TRY(ensure(c, c->par_ops, (size_t)info->nops * 8));
+    BCE_TRY(ensure(c, c->par_lits, info->nlits ? (size_t)info->nlits : 1));
+    BCE_TRY(kd_parse(c, c->mat_len.as<uint32_t>(), c->mat_pos.as<uint32_t>(), c->mat_qry.as<uint8_t>(), (uint32_t)q, min_len, false,
+                     c->par_ops.as<uint32_t>(), ops_cap, c->par_lits.as<uint8_t>(), lits_cap, info));
+    BCE_HIP_TRY(c, hipMemcpyAsync(ops, c->par_ops.p, (size_t)info->nops * 8, hipMemcpyDeviceToHost, c->stream));
+    if (info->nlits) BCE_HIP_TRY(c, hipMemcpyAsync(lits, c->par_lits.p, (size_t)info->nlits, hipMemcpyDeviceToHost, c->stream));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    BCE_HIP_TRY(c, hipGetLastError());
+    return BCE_HIP_OK;
+  });
+}
+
+int bce_hip_parse_device(bce_hip_ctx *c, const void *d_query, uint64_t q, uint32_t min_len, uint32_t max_len, void *d_ops, uint64_t ops_cap,
+                         void *d_lits, uint64_t lits_cap, bce_hip_parse_info *info) {
+  BCE_TRY(parse_args(c, q, min_len, max_len, d_ops, ops_cap, d_lits, lits_cap, info));
+  if (q == 0) { *info = bce_hip_parse_info{0, 0, 0, 0}; return BCE_HIP_OK; }
+  const uint32_t *sa = nullptr;
+  BCE_TRY(locate_state(c, &sa, "parse"));
+  if (!d_query) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope phase(c, 3);
+    const size_t words = (size_t)q * 4;
+    BCE_TRY(ensure(c, c->mat_len, words));
+    BCE_TRY(ensure(c, c->mat_pos, words));
+    const uint8_t *qry = static_cast<const uint8_t *>(d_query);
+    BCE_TRY(kd_match(c, sa, qry, (uint32_t)q, max_len, true, c->mat_len.as<uint32_t>(), c->mat_pos.as<uint32_t>()));
+    return kd_parse(c, c->mat_len.as<uint32_t>(), c->mat_pos.as<uint32_t>(), qry, (uint32_t)q, min_len, !d_ops && !d_lits,
+                    static_cast<uint32_t *>(d_ops), ops_cap, static_cast<uint8_t *>(d_lits), lits_cap, info);
+  });
+}
+
+int bce_hip_parse_of_lengths_device(bce_hip_ctx *c, const void *d_len, const void *d_pos, const void *d_query, uint64_t q, uint32_t min_len,
+                                    void *d_ops, uint64_t ops_cap, void *d_lits, uint64_t lits_cap, bce_hip_parse_info *info) {
+  BCE_TRY(parse_args(c, q, min_len, BCE_HIP_MATCH_MAX_LEN, d_ops, ops_cap, d_lits, lits_cap, info));
+  if (q == 0) { *info = bce_hip_parse_info{0, 0, 0, 0}; return BCE_HIP_OK; }
+  if (!d_len || !d_query) return BCE_HIP_E_ARG;
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    return kd_parse(c, static_cast<const uint32_t *>(d_len), static_cast<const uint32_t *>(d_pos), static_cast<const uint8_t *>(d_query), (uint32_t)q,
+                    min_len, !d_ops && !d_lits, static_cast<uint32_t *>(d_ops), ops_cap, static_cast<uint8_t *>(d_lits), lits_cap, info);
+  });
+}
+
+static int patch_args(bce_hip_ctx *c, const void *ops, uint64_t nops, const void *lits, uint64_t nlits, const void *out, uint64_t cap,
+                      uint64_t *out_len) {
+  if (!c || !out_len) return BCE_HIP_E_ARG;
+  if (nops > 0x7FFFFFFFull) { snprintf(c->err, sizeof c->err, "patch: 2^31 ops or more, a result of 2^31 bytes or more"); return BCE_HIP_E_ARG; }
+  if ((nops && !ops) || (nlits && !lits) || (cap && !out)) return BCE_HIP_E_ARG;
+  return BCE_HIP_OK;
+}
+static int patch_state(bce_hip_ctx *c) {
+  if (c->text_loaded && c->stage >= 1 && c->text.p && c->text.cap >= (size_t)c->n) return BCE_HIP_OK;
+  snprintf(c->err, sizeof c->err, "patch: no loaded input in this context");
+  return BCE_HIP_E_STATE;
+}
+// nops == 0: nothing to launch -- the empty result, and no literal byte may be left over
+static int patch_empty(bce_hip_ctx *c, uint64_t nlits, uint64_t *out_len) {
+  if (const char *why = bce::patch_list_bad(0, 0, 0, nlits)) { snprintf(c->err, sizeof c->err, "%s", why); return BCE_HIP_E_ARG; }
+  *out_len = 0;
+  return BCE_HIP_OK;
+}
+
+int bce_hip_patch(bce_hip_ctx *c, const bce_hip_op *ops, uint64_t nops, const uint8_t *lits, uint64_t nlits, uint8_t *out, uint64_t cap,
+                  uint64_t *out_len) {
+  BCE_TRY(patch_args(c, ops, nops, lits, nlits, out, cap, out_len));
+  BCE_TRY(patch_state(c));
+  if (nops == 0) return patch_empty(c, nlits, out_len);
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope phase(c, 3);
+    BCE_TRY(ensure(c, c->par_ops, (size_t)nops * 8));
+    BCE_TRY(ensure(c, c->par_lits, nlits ? (size_t)nlits : 1));
+    BCE_HIP_TRY(c, hipMemcpyAsync(c->par_ops.p, ops, (size_t)nops * 8, hipMemcpyHostToDevice, c->stream));
+    if (nlits) BCE_HIP_TRY(c, hipMemcpyAsync(c->par_lits.p, lits, (size_t)nlits, hipMemcpyHostToDevice, c->stream));
+    // validated and sized first: the staging of the result is as large as the result
+    uint64_t total = 0;
+    BCE_TRY(kd_patch(c, c->par_ops.as<uint32_t>(), (uint32_t)nops, c->par_lits.as<uint8_t>(), nlits, true, nullptr, 0, &total));
+    *out_len = total;
+    if (!out) return BCE_HIP_OK;
+    if (total > cap) { snprintf(c->err, sizeof c->err, "patch: %llu bytes, room for %llu", (unsigned long long)total, (unsigned long long)cap); return BCE_HIP_E_OVERFLOW; }
+    BCE_TRY(ensure(c, c->par_out, (size_t)total));
+    BCE_TRY(kd_patch(c, c->par_ops.as<uint32_t>(), (uint32_t)nops, c->par_lits.as<uint8_t>(), nlits, false, c->par_out.as<uint8_t>(), total, &total));
+    BCE_HIP_TRY(c, hipMemcpyAsync(out, c->par_out.p, (size_t)total, hipMemcpyDeviceToHost, c->stream));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    BCE_HIP_TRY(c, hipGetLastError());
+    return BCE_HIP_OK;
+  });
+}
+
+int bce_hip_patch_device(bce_hip_ctx *c, const void *d_ops, uint64_t nops, const void *d_lits, uint64_t nlits, void *d_out, uint64_t cap,
+                         uint64_t *out_len) {
+  BCE_TRY(patch_args(c, d_ops, nops, d_lits, nlits, d_out, cap, out_len));
+  BCE_TRY(patch_state(c));
+  if (nops == 0) return patch_empty(c, nlits, out_len);
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope phase(c, 3);
+    return kd_patch(c, static_cast<const uint32_t *>(d_ops), (uint32_t)nops, static_cast<const uint8_t *>(d_lits), nlits, !d_out,
+                    static_cast<uint8_t *>(d_out), cap, out_len);
   });
 }
 

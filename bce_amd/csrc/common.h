@@ -222,6 +222,12 @@ struct bce_hip_ctx {
   bce::DevBuf rep_res;                           // kd_lcp.hip: its result words, up to 64 k-gram records or the longest repeat's three (a buffer of its own, as mat_res)
   bce::DevBuf rep_bsum;                          // the class and repeat reductions' per-block parts and maxima
   bce::DevBuf rep_lcp;                           // the LCP array of a call that does not bring device memory for it: n words (grow-only, never kept as a cache)
+  bce::DevBuf par_res;                           // kd_parse.hip: the result words of the parse and of the patch (a buffer of its own, as mat_res)
+  bce::DevBuf par_exit, par_entry, par_flag;     // the parse: every position's exit from its block (+ 1), the blocks' entries, the flag byte per position
+  bce::DevBuf par_bsum, par_bcnt;                // the blocks' sums (parse: heads and literals packed; patch: lengths, literal lengths) and their counts / flag bits
+  bce::DevBuf par_hpre;                          // per op head: the literal bytes up to it
+  bce::DevBuf par_off, par_loff;                 // the patch: every op's offset in the output and in the literal bytes
+  bce::DevBuf par_ops, par_lits, par_out;        // bce_hip_parse / _patch with host buffers: the ops, the literal bytes and the result, staged (all grow-only)
   bce::DevBuf hook[3];                           // test hooks bce_hip_sort_pairs_device / _wide_device: the second halves of the sorts' ping-pong
   bool crc_const_ready = false;                  // its launch-independent constants are uploaded
   bool text_loaded = false;                      // `text` holds the n bytes of the last bce_hip_load_* (bce_hip_input_crc32)
@@ -449,6 +455,11 @@ int kd_coverage(bce_hip_ctx *c, const uint32_t *d_len, uint32_t q, uint32_t min_
 int kd_lcp(bce_hip_ctx *c, const uint32_t *sa, uint32_t max_len, uint32_t *d_lcp);
 int kd_kgrams(bce_hip_ctx *c, const uint32_t *sa, const uint32_t *d_lcp, uint32_t n, const uint32_t *ks, uint32_t nk, bce_hip_kgram *out);
 int kd_longest_repeat(bce_hip_ctx *c, const uint32_t *sa, const uint32_t *d_lcp, uint32_t n, uint32_t res[3]);
+// kd_parse.hip: the query as copies out of the text plus literal bytes, from its lengths and positions; and back.  Both wait.
+int kd_parse(bce_hip_ctx *c, const uint32_t *d_len, const uint32_t *d_pos, const uint8_t *d_query, uint32_t q, uint32_t min_len, bool sizing,
+             uint32_t *d_ops, uint64_t ops_cap, uint8_t *d_lits, uint64_t lits_cap, bce_hip_parse_info *info);
+int kd_patch(bce_hip_ctx *c, const uint32_t *d_ops, uint32_t nops, const uint8_t *d_lits, uint64_t nlits, bool sizing, uint8_t *d_out,
+             uint64_t cap, uint64_t *out_len);
 int k2_build_planes(bce_hip_ctx *c);                // k2_planes.hip
 int k2_get_plane_bits(bce_hip_ctx *c, int plane, uint8_t *out);
 int k2_rank1(bce_hip_ctx *c, int plane, const uint32_t *idx, uint32_t count, uint32_t *out);

@@ -7,6 +7,8 @@
 //   bce -gd PATTERN archive                 (extension) the same in what an archive or container holds
 //   bce -gl PATTERN file, -gld PATTERN archive   (extension) where they occur: the byte offsets, gathered on the GPU from K1's suffix array
 //   bce -gm MINLEN file query_file, -gmd MINLEN archive query_file   (extension) how much of a second file lies in strings of MINLEN bytes or more that occur in the first
+//   bce -gr MINLEN file query_file out.bcd, -grd ... archive ...   (extension) writes query_file as a delta against the first: copies out of it plus the new bytes
+//   bce -ga file in.bcd out_file, -gad archive in.bcd out_file     (extension) rebuilds a file from the first and a delta, both sides checked by CRC-32
 //   bce -gk K file, -gkd K archive          (extension) the k-grams of the circular text for k = 0..K: how many, how many occur once, the most frequent, H_k; the longest repeat
 // Banner, usage text, summary line, argument detection and exit codes follow the reference
 // (banner :1377-1379, -c :1403-1427, -d :1428-1472, usage :1473-1483).  -d uses the GPU-assisted decoder (kd_decode.hip), -ds the host decoder (decoder.cpp);
@@ -134,6 +136,10 @@ extern "C" int bce_hip_locate(bce_hip_ctx *ctx, const uint8_t *patterns, const u
 extern "C" int bce_hip_coverage(bce_hip_ctx *ctx, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t flags, uint64_t *covered) __attribute__((weak));
 extern "C" int bce_hip_kgrams(bce_hip_ctx *ctx, const uint32_t *ks, uint32_t nk, bce_hip_kgram *out) __attribute__((weak));
 extern "C" int bce_hip_longest_repeat(bce_hip_ctx *ctx, uint32_t max_len, uint32_t *len, uint32_t *pos_a, uint32_t *pos_b) __attribute__((weak));
+extern "C" int bce_hip_parse(bce_hip_ctx *ctx, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t max_len, bce_hip_op *ops, uint64_t ops_cap,
+                             uint8_t *lits, uint64_t lits_cap, bce_hip_parse_info *info) __attribute__((weak));
+extern "C" int bce_hip_patch(bce_hip_ctx *ctx, const bce_hip_op *ops, uint64_t nops, const uint8_t *lits, uint64_t nlits, uint8_t *out, uint64_t cap,
+                             uint64_t *out_len) __attribute__((weak));
 
 // `bce -cN`: N contiguous blocks over the GPUs of the node.  With more blocks than GPUs every device gets up to four
 // gated contexts (bce_hip_set_gated), one host thread each: their GPU phases take turns while the coder threads of the
@@ -451,9 +457,36 @@ static uint64_t seam_matches(const uint8_t *t, size_t n, const uint8_t *pat, siz
   return found;
 }
 constexpr uint32_t kMaxKgramOrder = 32;                            // -gk / -gkd: the largest K
-enum GrepMode { kGrepCount, kGrepLocate, kGrepCoverage, kGrepKgrams };
-static int count_pattern(const char *pattern, const char *path, bool in_archive, GrepMode mode, const char *query_path = nullptr, uint32_t min_len = 0) {
-  const bool locate = mode == kGrepLocate, coverage = mode == kGrepCoverage, kgrams = mode == kGrepKgrams;
+// `-gr MINLEN file query_file out.bcd` / `-grd` (delta): the file or archive is read, judged, decoded and indexed in the same way,
+// query_file judged as -gm's; the query is parsed on the GPU (bce_hip_parse at the bounds MINLEN and max(256, MINLEN)) and written
+// as a delta file.  `-ga file in.bcd out_file` / `-gad` (apply): in.bcd is read and judged as -d judges an archive, before the
+// device is missed; the base's size and CRC-32 (taken on the GPU) are checked before the patch, the result's after it, and a
+// mismatch on either side ends with kExitDiffers and writes nothing.
+// The delta file, little-endian: "BCED" | u32 version = 1 | u64 n | u32 crc32(base) | u64 q | u32 crc32(result) | u32 min_len |
+// u32 max_len | u64 nops | u64 nlits | nops x (u32 len, u32 src) | nlits bytes   (bce_amd/container.py: pack_delta / unpack_delta)
+constexpr size_t kDeltaHeader = 56;
+constexpr uint32_t kDeltaMaxLen = 256;                             // the length bound of -gr's search, where MINLEN is not above it
+struct DeltaHeader { uint64_t n, q, nops, nlits; uint32_t base_crc, crc, min_len, max_len; };
+template <class T> static T le_at(const uint8_t *p) { T v; memcpy(&v, p, sizeof v); return v; }
+// the magic, the version, sizes that add up to the file's length without overflow, a base and a result below 2^31 bytes
+static bool read_delta_header(const uint8_t *p, size_t len, DeltaHeader &h) {
+  if (len < kDeltaHeader || memcmp(p, "BCED", 4) != 0 || le_at<uint32_t>(p + 4) != 1) return false;
+  h.n = le_at<uint64_t>(p + 8); h.base_crc = le_at<uint32_t>(p + 16); h.q = le_at<uint64_t>(p + 20); h.crc = le_at<uint32_t>(p + 28);
+  h.min_len = le_at<uint32_t>(p + 32); h.max_len = le_at<uint32_t>(p + 36); h.nops = le_at<uint64_t>(p + 40); h.nlits = le_at<uint64_t>(p + 48);
+  const uint64_t room = len - kDeltaHeader;
+  if (h.nops > room / 8 || h.nlits != room - h.nops * 8) return false;
+  return h.q < kMaxInput && h.n < kMaxInput && (h.n != 0 || h.nops == 0);
+}
+static void write_delta_header(uint8_t *p, const DeltaHeader &h) {
+  const uint32_t ver = 1;
+  memcpy(p, "BCED", 4); memcpy(p + 4, &ver, 4); memcpy(p + 8, &h.n, 8); memcpy(p + 16, &h.base_crc, 4); memcpy(p + 20, &h.q, 8);
+  memcpy(p + 28, &h.crc, 4); memcpy(p + 32, &h.min_len, 4); memcpy(p + 36, &h.max_len, 4); memcpy(p + 40, &h.nops, 8); memcpy(p + 48, &h.nlits, 8);
+}
+enum GrepMode { kGrepCount, kGrepLocate, kGrepCoverage, kGrepKgrams, kGrepDelta, kGrepApply };
+static int count_pattern(const char *pattern, const char *path, bool in_archive, GrepMode mode, const char *query_path = nullptr, uint32_t min_len = 0,
+                         const char *out_path = nullptr) {
+  const bool locate = mode == kGrepLocate, kgrams = mode == kGrepKgrams, delta = mode == kGrepDelta, apply = mode == kGrepApply;
+  const bool coverage = mode == kGrepCoverage || delta || apply;      // (a second file is read)
   const size_t m = strlen(pattern);
   const uint8_t *pat = reinterpret_cast<const uint8_t *>(pattern);
   HostFile file;
@@ -469,8 +502,11 @@ static int count_pattern(const char *pattern, const char *path, bool in_archive,
   if (in_archive && file.status == -1) { printf("Archive not found.\n"); return -1; }
   if (in_archive && (file.status != 0 || file.size() == 0)) { printf("Could not read Archive.\n"); return -2; }
   if (!in_archive && (file.status != 0 || file.size() == 0 || file.size() >= kMaxInput)) { printf("Error loading file\n"); return -1; }
-  if (coverage && (query.status != 0 || query.size() == 0 || query.size() >= kMaxInput)) { printf("Error loading file\n"); return -1; }
-  if (rc0 != 0 || !bce_hip_count || (locate && !bce_hip_locate) || (coverage && !bce_hip_coverage) || (kgrams && (!bce_hip_kgrams || !bce_hip_longest_repeat))) { printf("No usable HIP device: %s\n", bce_hip_strerror(rc0 ? rc0 : BCE_HIP_E_DEVICE)); return -3; }
+  if (apply && query.status == -1) { printf("Archive not found.\n"); return -1; }
+  DeltaHeader dh{};
+  if (apply && (query.status != 0 || !read_delta_header(query.data(), query.size(), dh))) { printf("Could not read Archive.\n"); return -2; }
+  if (coverage && !apply && (query.status != 0 || query.size() == 0 || query.size() >= kMaxInput)) { printf("Error loading file\n"); return -1; }
+  if (rc0 != 0 || !bce_hip_count || (delta && (!bce_hip_parse || !bce_hip_input_crc32)) || (apply && (!bce_hip_patch || !bce_hip_input_crc32)) || (locate && !bce_hip_locate) || (coverage && !bce_hip_coverage) || (kgrams && (!bce_hip_kgrams || !bce_hip_longest_repeat))) { printf("No usable HIP device: %s\n", bce_hip_strerror(rc0 ? rc0 : BCE_HIP_E_DEVICE)); return -3; }
   const uint8_t *text = file.data();
   size_t n = file.size();
   std::vector<uint8_t> decoded;
@@ -506,6 +542,55 @@ static int count_pattern(const char *pattern, const char *path, bool in_archive,
     }
     text = decoded.data();
     n = decoded.size();
+  }
+  if (delta) {
+    const uint32_t max_len = min_len > kDeltaMaxLen ? min_len : kDeltaMaxLen;
+    bce_hip_parse_info info{};
+    DeltaHeader h{};
+    int rc = bce_hip_load_host(ctx, text, (uint32_t)n);
+    if (rc == 0) rc = bce_hip_bwt(ctx, nullptr);
+    if (rc == 0) rc = bce_hip_build_planes(ctx, nullptr);
+    if (rc == 0) rc = bce_hip_input_crc32(ctx, &h.base_crc);
+    if (rc == 0) rc = bce_hip_parse(ctx, query.data(), query.size(), min_len, max_len, nullptr, 0, nullptr, 0, &info);   // how much
+    std::vector<uint8_t> blob;
+    if (rc == 0) {
+      blob.resize(kDeltaHeader + info.nops * 8 + info.nlits);
+      rc = bce_hip_parse(ctx, query.data(), query.size(), min_len, max_len, reinterpret_cast<bce_hip_op *>(blob.data() + kDeltaHeader), info.nops,
+                         blob.data() + kDeltaHeader + info.nops * 8, info.nlits, &info);
+    }
+    if (rc != 0) { printf("Parse failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); return -4; }
+    h.n = n; h.q = query.size(); h.crc = bce_hip_crc32(0, query.data(), query.size()); h.min_len = min_len; h.max_len = max_len;
+    h.nops = info.nops; h.nlits = info.nlits;
+    write_delta_header(blob.data(), h);
+    if (!write_file(out_path, blob.data(), blob.size())) { printf("Could not write Archive.\n"); return -5; }
+    printf("%llu copies of %llu bytes, %llu literal bytes in %llu runs: %zu bytes of delta\n", (unsigned long long)info.ncopies,
+           (unsigned long long)info.copied, (unsigned long long)info.nlits, (unsigned long long)(info.nops - info.ncopies), blob.size());
+    ctx = nullptr;                                                    // (left to fast_exit, like -d)
+    fast_exit(0);
+    return 0;
+  }
+  if (apply) {
+    const bce_hip_op *ops = reinterpret_cast<const bce_hip_op *>(query.data() + kDeltaHeader);   // (56 bytes behind an allocation's start: aligned)
+    const uint8_t *lits = query.data() + kDeltaHeader + dh.nops * 8;
+    if (n != dh.n) { printf("The delta was made against %llu bytes, not %zu\n", (unsigned long long)dh.n, n); return kExitDiffers; }
+    uint32_t crc = 0;
+    int rc = bce_hip_load_host(ctx, text, (uint32_t)n);
+    if (rc == 0) rc = bce_hip_input_crc32(ctx, &crc);
+    if (rc != 0) { printf("Patch failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); return -4; }
+    if (crc != dh.base_crc) { printf("Checksum mismatch in the base: delta %08X, file %08X\n", dh.base_crc, crc); return kExitDiffers; }
+    uint64_t total = 0;
+    rc = bce_hip_patch(ctx, ops, dh.nops, lits, dh.nlits, nullptr, 0, &total);          // judged on the GPU, and how much
+    if (rc == BCE_HIP_E_ARG || (rc == 0 && total != dh.q)) { printf("Could not read Archive.\n"); return -2; }
+    std::vector<uint8_t> out((size_t)total);
+    if (rc == 0 && total) rc = bce_hip_patch(ctx, ops, dh.nops, lits, dh.nlits, out.data(), total, &total);
+    if (rc != 0) { printf("Patch failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); return -4; }
+    crc = bce_hip_crc32(0, out.data(), out.size());
+    if (crc != dh.crc) { printf("Checksum mismatch in the result: delta %08X, rebuilt %08X\n", dh.crc, crc); return kExitDiffers; }
+    if (!write_file(out_path, out.data(), out.size())) { printf("Could not write file.\n"); return -5; }
+    printf("Rebuilt %zu B from %zu B and a delta of %zu B\n", out.size(), n, query.size());
+    ctx = nullptr;                                                    // (left to fast_exit, like -d)
+    fast_exit(0);
+    return 0;
   }
   if (coverage) {
     uint64_t covered = 0;
@@ -646,6 +731,18 @@ static int usage() {
   printf("\n");
   printf("  bce -gkd K archive.bce\n");
   printf("   The same figures for what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
+  printf("\n");
+  printf("  bce -gr MINLEN file query_file out.bcd\n");
+  printf("   Writes \"query_file\" as a delta against \"file\" to \"out.bcd\": copies of MINLEN (1..4096) bytes or more out of \"file\", found in its index on the GPU and chosen there, plus the bytes that are new (extension)\n");
+  printf("\n");
+  printf("  bce -grd MINLEN archive.bce query_file out.bcd\n");
+  printf("   The same delta against what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU (extension)\n");
+  printf("\n");
+  printf("  bce -ga file in.bcd out_file\n");
+  printf("   Rebuilds \"out_file\" on the GPU from \"file\" and the delta \"in.bcd\"; the CRC-32 of \"file\" is checked before and that of the result after (extension; exit status %d = one of them differs, nothing written)\n", kExitDiffers);
+  printf("\n");
+  printf("  bce -gad archive.bce in.bcd out_file\n");
+  printf("   The same from what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU (extension)\n");
   return 0;
 }
 
@@ -919,6 +1016,10 @@ int main(int argc, char **argv) {
     return count_pattern(argv[2], argv[3], argv[1][3] == 'd', kGrepLocate);
   } else if (argc == 5 && (strcmp(argv[1], "-gm") == 0 || strcmp(argv[1], "-gmd") == 0) && parse_min_len(argv[2]) != 0) {
     return count_pattern("", argv[3], argv[1][3] == 'd', kGrepCoverage, argv[4], parse_min_len(argv[2]));
+  } else if (argc == 6 && (strcmp(argv[1], "-gr") == 0 || strcmp(argv[1], "-grd") == 0) && parse_min_len(argv[2]) != 0) {
+    return count_pattern("", argv[3], argv[1][3] == 'd', kGrepDelta, argv[4], parse_min_len(argv[2]), argv[5]);
+  } else if (argc == 5 && (strcmp(argv[1], "-ga") == 0 || strcmp(argv[1], "-gad") == 0)) {
+    return count_pattern("", argv[2], argv[1][3] == 'd', kGrepApply, argv[3], 0, argv[4]);
   } else if (argc == 4 && (strcmp(argv[1], "-gk") == 0 || strcmp(argv[1], "-gkd") == 0) && parse_order(argv[2]) >= 0) {
     return count_pattern("", argv[3], argv[1][3] == 'd', kGrepKgrams, nullptr, (uint32_t)parse_order(argv[2]));
   } else if (argc == 4 && argv[1][0] == '-' && argv[1][1] == 's') {

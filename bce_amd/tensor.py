@@ -197,6 +197,59 @@ def coverage_tensor(t, query, min_len, cyclic=False, ctx=None) -> int:
             c.close()
 
 
+def parse_tensor(t, query, min_len, max_len=api.PARSE_MAX_LEN, ctx=None):
+    """The 1-D uint8 CUDA tensor `query` as copies out of the 1-D uint8 CUDA tensor `t` plus literal bytes (api.RankFile.parse with
+    both buffers where they lie: bce_hip_parse_device, a sizing call and the full call) -> (ops, lits, info): ops an int32 tensor
+    (nops, 2) of (len, src) on that device, src == -1 (0xFFFFFFFF) for a run of literal bytes; lits a uint8 tensor; info a dict.
+    Nothing but info reaches the host.  Synchronises the current stream first; `ctx` (an api._Ctx of t's device) is reused if given."""
+    n = _match_args(t, query, "parse_tensor")
+    q = query.numel()
+    _ready(t)
+    own = ctx is None
+    c = ctx or api._Ctx(t.device.index)
+    try:
+        rf = api.RankFile(n=n, device_ptr=t.data_ptr(), ctx=c)
+        info = rf.parse_device(query.data_ptr() if q else None, q, min_len, max_len)
+        ops = torch.zeros((info["nops"], 2), dtype=torch.int32, device=t.device)
+        lits = torch.zeros(info["nlits"], dtype=torch.uint8, device=t.device)
+        if q:
+            torch.cuda.synchronize(t.device)
+            info = rf.parse_device(query.data_ptr(), q, min_len, max_len, ops.data_ptr(), info["nops"], lits.data_ptr() if info["nlits"] else None, info["nlits"])
+        return ops, lits, info
+    finally:
+        if own:
+            c.close()
+
+
+def patch_tensor(t, ops, lits, out=None, ctx=None):
+    """The bytes that `ops` (an int32 CUDA tensor (nops, 2) of (len, src)) and `lits` (a uint8 CUDA tensor) describe over the 1-D
+    uint8 CUDA tensor `t` (bce_hip_patch_device: validated, sized, then copied on the GPU) -> a uint8 tensor on that device: `out`
+    (its first bytes; it must be large enough) or a new one.  Only the result's length reaches the host."""
+    n = _match_args(t, lits, "patch_tensor")
+    if not isinstance(ops, torch.Tensor) or ops.dtype != torch.int32 or ops.dim() != 2 or ops.shape[1] != 2 or ops.device != t.device or not ops.is_contiguous():
+        raise ValueError("ops must be a contiguous int32 tensor (nops, 2) on t's device")
+    _ready(t)
+    own = ctx is None
+    c = ctx or api._Ctx(t.device.index)
+    try:
+        rf = api.RankFile(n=n, device_ptr=t.data_ptr(), ctx=c, build=False, index=False)
+        args = (ops.data_ptr() if ops.shape[0] else None, ops.shape[0], lits.data_ptr() if lits.numel() else None, lits.numel())
+        total = rf.patch_device(*args)
+        if out is None:
+            out = torch.zeros(total, dtype=torch.uint8, device=t.device)
+            torch.cuda.synchronize(t.device)
+        else:
+            _check(out, "out")
+            if out.device != t.device or out.numel() < total:
+                raise ValueError("out must hold %d bytes on t's device" % total)
+        if total:
+            rf.patch_device(*(args + (out.data_ptr(), out.numel())))
+        return out[:total]
+    finally:
+        if own:
+            c.close()
+
+
 def coverage_in_archive(blob, query, min_len, cyclic=False, device="cuda:0") -> int:
     """coverage_tensor on what an archive holds, decoded as count_in_archive decodes it: into ONE tensor on the device, so matches
     across block boundaries count.  `query`: a bytes-like (it is sent to the device) or a 1-D uint8 CUDA tensor there."""

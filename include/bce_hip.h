@@ -411,6 +411,65 @@ int bce_hip_kgrams(bce_hip_ctx *ctx, const uint32_t *ks, uint32_t nk, bce_hip_kg
  * bce_hip_lcp; all three outputs are required. */
 int bce_hip_longest_repeat(bce_hip_ctx *ctx, uint32_t max_len, uint32_t *len, uint32_t *pos_a, uint32_t *pos_b);
 
+/* ---- extension: a second buffer as a DELTA against the input: parse and patch (kd_parse.hip, parse_step.h) ----------------------
+ * T: the n bytes the context indexed.  Q: a query of q bytes, 0 <= q < 2^31.  1 <= min_len <= max_len <= BCE_HIP_MATCH_MAX_LEN.
+ * len[i], pos[i]: the LINEAR matching statistics of Q at bound max_len, exactly what bce_hip_match_device gives with
+ * BCE_HIP_MATCH_LINEAR and positions.  The parse is the chain
+ *     e = q - 1;  while e >= 0:  len[e] >= min_len ?  a copy of len[e] bytes from T[pos[e] ..], it covers Q[e - len[e] + 1 .. e], e -= len[e]
+ *                                                  :  the literal byte Q[e], e -= 1
+ * (from the right, because the index extends matches to the left: the lengths by END position are what exists).  The phrases
+ * come out in ascending query order, neighbouring literal bytes merged into one maximal run, as two streams: nops ops and nlits
+ * literal bytes in query order.  An op with src == BCE_HIP_OP_LITERAL stands for the next len bytes of the literal stream, any other
+ * for T[src .. src + len).  Which occurrence src names is not specified (as pos[i]); everything else about the output is unique.
+ * For min_len == 1 no parse of Q into substrings of T of at most max_len bytes and single literal bytes has fewer phrases, every
+ * literal byte counted as one; for a larger min_len that does not hold (a short copy may save a literal).
+ * The search costs up to q * max_len lane steps (a wave runs as long as its longest lane), so max_len is the caller's to choose.
+ * info (a host pointer, required) is written whenever the call gets as far as the chain: nlits + copied == q, nops - ncopies is the
+ * number of literal runs.  ops == NULL and lits == NULL with both caps 0: a sizing call, which succeeds.  Otherwise nops > ops_cap
+ * or nlits > lits_cap: BCE_HIP_E_OVERFLOW with info exact and no byte of either output written.  A sizing call and the full call
+ * that follows it each run the search.  State and refusals as bce_hip_match with positions (BCE_HIP_E_STATE in bce_hip_locate's
+ * words behind an injected BWT); no call here changes the compression state or writes a stage's buffers: an encode after a parse
+ * gives the archive of a fresh context.  q == 0: success, info all zero, nothing launched.  A null ctx or info, bounds outside
+ * 1 <= min_len <= max_len <= BCE_HIP_MATCH_MAX_LEN, q >= 2^31: BCE_HIP_E_ARG before any device call; then the state; then a null
+ * query, or a null output with a cap above 0: BCE_HIP_E_ARG. */
+#define BCE_HIP_OP_LITERAL 0xFFFFFFFFu
+typedef struct bce_hip_op {
+  uint32_t len, src;
+} bce_hip_op;
+typedef struct bce_hip_parse_info {
+  uint64_t nops, nlits, ncopies, copied;
+} bce_hip_parse_info;
+int bce_hip_parse(bce_hip_ctx *ctx, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t max_len, bce_hip_op *ops,
+                  uint64_t ops_cap, uint8_t *lits, uint64_t lits_cap, bce_hip_parse_info *info);
+/* The same with the query, the ops (4-byte aligned) and the literal bytes in device memory of the context's device; info stays a
+ * host pointer.  Stream rule: as bce_hip_count_device. */
+int bce_hip_parse_device(bce_hip_ctx *ctx, const void *d_query, uint64_t q, uint32_t min_len, uint32_t max_len, void *d_ops,
+                         uint64_t ops_cap, void *d_lits, uint64_t lits_cap, bce_hip_parse_info *info);
+/* The bytes that nops ops and nlits literal bytes describe over T, into out: ANY well-formed list, not only bce_hip_parse's; a
+ * copy's len may be anything from 1 to 2^31 - 1, copies may overlap and repeat.  Needs the loaded text only (no planes, no suffix
+ * array): valid from a load until a decode or bce_hip_set_bwt takes the text away, otherwise BCE_HIP_E_STATE.  A validation pass
+ * on the device comes first: an op with len == 0, a copy with src + len > n, literal lengths that do not add up to exactly nlits,
+ * a total of 2^31 bytes or more: BCE_HIP_E_ARG with the reason in bce_hip_last_error, nothing copied, out untouched.  Then
+ * *out_len = the total; total > cap: BCE_HIP_E_OVERFLOW, out untouched.  out == NULL with cap == 0 sizes and validates.  nops == 0:
+ * *out_len = 0 (nlits must be 0).  The copy is divided by output bytes, not by ops.  A null ctx or out_len, nops >= 2^31 (every
+ * op holds a byte), a null ops with nops > 0 or lits with nlits > 0, a null out with cap > 0: BCE_HIP_E_ARG before any device call. */
+int bce_hip_patch(bce_hip_ctx *ctx, const bce_hip_op *ops, uint64_t nops, const uint8_t *lits, uint64_t nlits, uint8_t *out,
+                  uint64_t cap, uint64_t *out_len);
+/* The same with the ops (4-byte aligned), the literal bytes and the result (any alignment) in device memory; out_len stays a host
+ * pointer.  d_out may not overlap the other two.  Stream rule: as bce_hip_count_device. */
+int bce_hip_patch_device(bce_hip_ctx *ctx, const void *d_ops, uint64_t nops, const void *d_lits, uint64_t nlits, void *d_out,
+                         uint64_t cap, uint64_t *out_len);
+/* Test hook (tests/test_gpu_parse_scans.py), valid in any state of the context: the parse alone -- bce_hip_parse_device without
+ * its search -- on q lengths, positions (d_pos may be NULL: every copy's src is 0) and query bytes of the caller's, with the launches
+ * and launch geometry of the real call (which runs the same function): blocks of 2048 positions, one workgroup that walks the
+ * blocks' sums 256 at a time.  It requires only d_len[i] <= i + 1, NOT lengths up to BCE_HIP_MATCH_MAX_LEN, so a jump can cross
+ * any number of blocks.  Writes only the feature's par_* buffers and the two outputs; sizing, overflow and info as bce_hip_parse.
+ * A null ctx or info, q >= 2^31, a min_len outside 1 .. BCE_HIP_MATCH_MAX_LEN, q > 0 with a null d_len or d_query, a null output
+ * with a cap above 0: BCE_HIP_E_ARG before any device call. */
+int bce_hip_parse_of_lengths_device(bce_hip_ctx *ctx, const void *d_len, const void *d_pos, const void *d_query, uint64_t q,
+                                    uint32_t min_len, void *d_ops, uint64_t ops_cap, void *d_lits, uint64_t lits_cap,
+                                    bce_hip_parse_info *info);
+
 /* ---- test hooks: the device primitives every stage rests on, alone (tests/test_gpu_sort.py, tests/test_gpu_compare.py) ----
  * Stream rule of bce_hip_crc32_device for all three: the work runs on the context's stream and is complete on return; the caller's
  * memory (device memory of the context's device) must be ready when the call is made.  Valid in any state of the context, between
