@@ -9,7 +9,6 @@
 
 #include "bce_cost.h"
 #include "common.h"
-#include "parse_step.h"
 #include "host_coder.h"
 #include "scan_coder.h"
 
@@ -700,9 +699,9 @@ void bce_hip_destroy(bce_hip_ctx *c) {
   DevBuf *bufs[] = {&c->text, &c->bwt, &c->sa[0], &c->sa[1], &c->key[0], &c->key[1], &c->rank, &c->k2, &c->nrk, &c->act[0], &c->act[1], &c->khi[0], &c->khi[1], &c->dl[0], &c->dl[1], &c->dl[2], &c->dl[3], &c->kflag, &c->actv[0], &c->actv[1],
                     &c->rs_hist, &c->blk, &c->ptmp[0], &c->ptmp[1], &c->gran, &c->nlist[0], &c->nlist[1], &c->ctl, &c->tilecnt,
                     &c->tileoff, &c->runs, &c->smwords, &c->k3tw, &c->k3grp, &c->truns, &c->skey[0], &c->skey[1], &c->sval[0], &c->sval[1], &c->sout,
-                    &c->sesc, &c->stat, &c->crc_tab, &c->dcfg, &c->k4w, &c->scanrec, &c->dfs, &c->skey_alt, &c->sesc_alt, &c->rs_hist_k4, &c->cost_acc, &c->cost_runs, &c->cmp_res, &c->cnt_res, &c->cnt_pat, &c->cnt_off, &c->cnt_out, &c->loc_res, &c->loc_lo, &c->loc_cnt, &c->loc_drop, &c->loc_start, &c->loc_lin, &c->loc_bsum,
-                    &c->loc_key[0], &c->loc_key[1], &c->loc_val[0], &c->loc_val[1], &c->loc_pat, &c->loc_off, &c->loc_hits, &c->loc_pos, &c->mat_res, &c->mat_bsum, &c->mat_qry, &c->mat_len, &c->mat_pos, &c->rep_res, &c->rep_bsum, &c->rep_lcp, &c->par_res, &c->par_exit, &c->par_entry, &c->par_flag, &c->par_bsum, &c->par_bcnt, &c->par_hpre, &c->par_off, &c->par_loff, &c->par_ops, &c->par_lits, &c->par_out, &c->hook[0], &c->hook[1], &c->hook[2]};
+                    &c->sesc, &c->stat, &c->crc_tab, &c->dcfg, &c->k4w, &c->scanrec, &c->dfs, &c->skey_alt, &c->sesc_alt, &c->rs_hist_k4, &c->cost_acc, &c->cost_runs, &c->cmp_res, &c->hook[0], &c->hook[1], &c->hook[2]};
   for (DevBuf *b : bufs) release(*b);
+  for (DevBuf &b : c->qbuf) release(b);
   for (auto &par : c->dlist) for (DevBuf &b : par) release(b);
   k4_prepin_join(c, true);
   if (c->h_ctl) (void)hipHostFree(c->h_ctl);
@@ -1346,6 +1345,17 @@ int bce_hip_input_crc32(bce_hip_ctx *c, uint32_t *crc) {
   });
 }
 
+int bce_hip_input_bytes(bce_hip_ctx *c, uint64_t pos, size_t len, uint8_t *out) {
+  if (!c || (len && !out)) return BCE_HIP_E_ARG;
+  if (!c->text_loaded || c->stage < 1) { snprintf(c->err, sizeof c->err, "no loaded input in this context"); return BCE_HIP_E_STATE; }
+  if (pos > c->n || len > c->n - pos) return BCE_HIP_E_ARG;
+  if (len == 0) return BCE_HIP_OK;
+  BCE_HIP_TRY(c, hipSetDevice(c->device));
+  BCE_HIP_TRY(c, hipMemcpyAsync(out, c->text.as<uint8_t>() + pos, len, hipMemcpyDeviceToHost, c->stream));
+  BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return BCE_HIP_OK;
+}
+
 // ---- test hooks: the shared primitives alone (radix_sort.hip, kd_compare.hip) ---------------------------------
 // The caller's arrays are one half of the sort's ping-pong, c->hook the other; a result that lands in the context's half is
 // copied back.  Phase 0: nothing of the context is given back to make room, and nothing but the sorter's histograms, the hook
@@ -1426,510 +1436,6 @@ int bce_hip_unbwt_device(bce_hip_ctx *c, const void *d_bwt, uint32_t n, uint32_t
     c->coder->drain();
     PhaseScope phase(c, 4);
     return kd_unbwt(c, static_cast<const uint8_t *>(d_bwt), n, offset, static_cast<uint8_t *>(d_out), cycle_len, walkers);
-  });
-}
-
-// ---- test hooks: the block scans of the index queries alone (kd_lcp.hip, kd_match.hip) ----------------------------
-// Phase 0, as the sort hooks: nothing of the context is given back to make room, and only the features' own rep_* / mat_* buffers
-// are written.  The LCP words are copied into rep_lcp first: the reductions load them sixteen bytes at a time from there.
-int bce_hip_lcp_reduce_device(bce_hip_ctx *c, const void *d_lcp, uint32_t n, const void *d_sa, const uint32_t *ks, uint32_t nk,
-                              bce_hip_kgram *out, uint32_t repeat3[3]) {
-  if (!c || !d_lcp || !d_sa || n == 0 || n > 0x7FFFFFFFu || nk > BCE_HIP_KGRAMS_MAX || (nk && (!ks || !out))) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    const size_t words = (size_t)n * 4;
-    BCE_TRY(ensure(c, c->rep_lcp, words));
-    BCE_HIP_TRY(c, hipMemcpyAsync(c->rep_lcp.p, d_lcp, words, hipMemcpyDeviceToDevice, c->stream));
-    const uint32_t *sa = static_cast<const uint32_t *>(d_sa);
-    if (nk) BCE_TRY(kd_kgrams(c, sa, c->rep_lcp.as<uint32_t>(), n, ks, nk, out));
-    if (repeat3) BCE_TRY(kd_longest_repeat(c, sa, c->rep_lcp.as<uint32_t>(), n, repeat3));
-    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    BCE_HIP_TRY(c, hipGetLastError());
-    return BCE_HIP_OK;
-  });
-}
-
-int bce_hip_coverage_of_lengths_device(bce_hip_ctx *c, const void *d_len, uint64_t q, uint32_t min_len, uint64_t *covered) {
-  if (!c || !covered || q > 0x7FFFFFFFull || min_len < 1 || min_len > BCE_HIP_MATCH_MAX_LEN || (q && !d_len)) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    return kd_coverage(c, static_cast<const uint32_t *>(d_len), (uint32_t)q, min_len, covered);
-  });
-}
-
-// ---- pattern counts from the planes (kd_count.hip) ---------------------------------------------------------
-// Phase 3, as bce_hip_rank1: the planes are read, so what an allocation may give back is what an enumeration beside them would.
-// Nothing a stage keeps is written: the staging buffers and the flag word are the count's own.
-static int count_state(bce_hip_ctx *c, const char *what = "count") {
-  if (c->stage >= 3) return BCE_HIP_OK;
-  snprintf(c->err, sizeof c->err, "%s: the context holds no planes (stage %d; bce_hip_build_planes first)", what, c->stage);
-  return BCE_HIP_E_STATE;
-}
-
-int bce_hip_count(bce_hip_ctx *c, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint64_t *counts) {
-  if (!c) return BCE_HIP_E_ARG;
-  if (npat == 0) return BCE_HIP_OK;
-  BCE_TRY(count_state(c));
-  if (!offsets || !counts) return BCE_HIP_E_ARG;
-  for (uint32_t p = 0; p < npat; ++p)
-    if (offsets[p + 1] < offsets[p]) { snprintf(c->err, sizeof c->err, "count: pattern offsets decrease at %u", p); return BCE_HIP_E_ARG; }
-  const uint64_t bytes = offsets[npat];
-  if (bytes && !patterns) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    PhaseScope phase(c, 3);
-    const size_t off_bytes = ((size_t)npat + 1) * 8, out_bytes = (size_t)npat * 8;
-    BCE_TRY(ensure(c, c->cnt_pat, bytes ? (size_t)bytes : 1));
-    BCE_TRY(ensure(c, c->cnt_off, off_bytes));
-    BCE_TRY(ensure(c, c->cnt_out, out_bytes));
-    if (bytes) BCE_HIP_TRY(c, hipMemcpyAsync(c->cnt_pat.p, patterns, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
-    BCE_HIP_TRY(c, hipMemcpyAsync(c->cnt_off.p, offsets, off_bytes, hipMemcpyHostToDevice, c->stream));
-    BCE_TRY(kd_count(c, c->cnt_pat.as<uint8_t>(), c->cnt_off.as<uint64_t>(), npat, c->cnt_out.as<uint64_t>()));
-    BCE_HIP_TRY(c, hipMemcpyAsync(counts, c->cnt_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
-    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return BCE_HIP_OK;
-  });
-}
-
-int bce_hip_count_device(bce_hip_ctx *c, const void *d_patterns, const void *d_offsets, uint32_t npat, void *d_counts) {
-  if (!c) return BCE_HIP_E_ARG;
-  if (npat == 0) return BCE_HIP_OK;
-  BCE_TRY(count_state(c));
-  if (!d_patterns || !d_offsets || !d_counts) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    PhaseScope phase(c, 3);
-    return kd_count(c, static_cast<const uint8_t *>(d_patterns), static_cast<const uint64_t *>(d_offsets), npat, static_cast<uint64_t *>(d_counts));
-  });
-}
-
-int bce_hip_input_bytes(bce_hip_ctx *c, uint64_t pos, size_t len, uint8_t *out) {
-  if (!c || (len && !out)) return BCE_HIP_E_ARG;
-  if (!c->text_loaded || c->stage < 1) { snprintf(c->err, sizeof c->err, "no loaded input in this context"); return BCE_HIP_E_STATE; }
-  if (pos > c->n || len > c->n - pos) return BCE_HIP_E_ARG;
-  if (len == 0) return BCE_HIP_OK;
-  BCE_HIP_TRY(c, hipSetDevice(c->device));
-  BCE_HIP_TRY(c, hipMemcpyAsync(out, c->text.as<uint8_t>() + pos, len, hipMemcpyDeviceToHost, c->stream));
-  BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return BCE_HIP_OK;
-}
-
-// ---- pattern positions from the planes and K1's suffix array (kd_locate.hip) -----------------------------------------------
-// Phase 3 as the count: ctx_trim keeps sa[sa_res] there, for the depth-first tail.  Nothing after K1 writes that array until the
-// next load or decode (K3's tail, the encoder, the estimate, the scan, the count and the sort hooks only read it or never name
-// it), so it stands for as long as k1_valid does.  A text of one byte has no array: its only rotation starts at 0.
-static int locate_state(bce_hip_ctx *c, const uint32_t **sa, const char *what = "locate") {
-  BCE_TRY(count_state(c, what));
-  *sa = nullptr;
-  if (c->k1_valid && c->sa[c->sa_res].p && c->sa[c->sa_res].cap >= (size_t)c->n * 4) { *sa = c->sa[c->sa_res].as<uint32_t>(); return BCE_HIP_OK; }
-  if (c->n == 1 && c->text_loaded) return BCE_HIP_OK;
-  snprintf(c->err, sizeof c->err, c->text_loaded ? "%s: the suffix array of this input is gone" : "%s: there is no suffix array behind an injected BWT", what);
-  return BCE_HIP_E_STATE;
-}
-
-// The overflow protocol, once for both entry points.  d_*: device arrays; h_hits / h_pos: where a call with host buffers wants the
-// offsets and positions (then d_pos is staged in loc_pos once the total is known).  hit offsets and *total are out before the
-// first reason to refuse; the positions are touched only when all of them fit.
-static int locate_run(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, bool linear, uint64_t *d_hits,
-                      uint64_t *h_hits, uint32_t *d_pos, uint32_t *h_pos, bool sizing, uint64_t cap, uint64_t *total) {
-  uint64_t rows = 0, hits = 0;
-  const int rc = kd_locate_size(c, sa, d_pat, d_off, npat, linear, d_hits, &rows, &hits);
-  if (rc != BCE_HIP_OK && rc != BCE_HIP_E_OVERFLOW) return rc;
-  if (h_hits) {
-    BCE_HIP_TRY(c, hipMemcpyAsync(h_hits, d_hits, ((size_t)npat + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  *total = hits;
-  if (rc != BCE_HIP_OK || sizing) return rc;
-  if (hits > cap) { snprintf(c->err, sizeof c->err, "locate: %llu hits, room for %llu", (unsigned long long)hits, (unsigned long long)cap); return BCE_HIP_E_OVERFLOW; }
-  if (hits == 0) return BCE_HIP_OK;
-  if (h_pos) {
-    BCE_TRY(ensure(c, c->loc_pos, (size_t)hits * 4));
-    d_pos = c->loc_pos.as<uint32_t>();
-  }
-  BCE_TRY(kd_locate_fill(c, sa, d_off, npat, linear, rows, hits, d_pos));
-  if (h_pos) {
-    BCE_HIP_TRY(c, hipMemcpyAsync(h_pos, d_pos, (size_t)hits * 4, hipMemcpyDeviceToHost, c->stream));
-    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  return BCE_HIP_OK;
-}
-
-int bce_hip_locate(bce_hip_ctx *c, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t flags, uint64_t *hit_offsets,
-                   uint32_t *positions, uint64_t cap, uint64_t *total) {
-  if (!c || !total || (flags & ~BCE_HIP_LOCATE_LINEAR)) return BCE_HIP_E_ARG;
-  *total = 0;
-  if (npat == 0) { if (hit_offsets) hit_offsets[0] = 0; return BCE_HIP_OK; }
-  const uint32_t *sa = nullptr;
-  BCE_TRY(locate_state(c, &sa));
-  if (!offsets || !hit_offsets || (!positions && cap)) return BCE_HIP_E_ARG;
-  for (uint32_t p = 0; p < npat; ++p)
-    if (offsets[p + 1] < offsets[p]) { snprintf(c->err, sizeof c->err, "locate: pattern offsets decrease at %u", p); return BCE_HIP_E_ARG; }
-  const uint64_t bytes = offsets[npat];
-  if (bytes && !patterns) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    PhaseScope phase(c, 3);
-    const size_t off_bytes = ((size_t)npat + 1) * 8;
-    BCE_TRY(ensure(c, c->loc_pat, bytes ? (size_t)bytes : 1));
-    BCE_TRY(ensure(c, c->loc_off, off_bytes));
-    BCE_TRY(ensure(c, c->loc_hits, off_bytes));
-    if (bytes) BCE_HIP_TRY(c, hipMemcpyAsync(c->loc_pat.p, patterns, (size_t)bytes, hipMemcpyHostToDevice, c->stream));
-    BCE_HIP_TRY(c, hipMemcpyAsync(c->loc_off.p, offsets, off_bytes, hipMemcpyHostToDevice, c->stream));
-    return locate_run(c, sa, c->loc_pat.as<uint8_t>(), c->loc_off.as<uint64_t>(), npat, flags & BCE_HIP_LOCATE_LINEAR, c->loc_hits.as<uint64_t>(),
-                      hit_offsets, nullptr, positions, !positions, cap, total);
-  });
-}
-
-int bce_hip_locate_device(bce_hip_ctx *c, const void *d_patterns, const void *d_offsets, uint32_t npat, uint32_t flags, void *d_hit_offsets,
-                          void *d_positions, uint64_t cap, uint64_t *total) {
-  if (!c || !total || (flags & ~BCE_HIP_LOCATE_LINEAR)) return BCE_HIP_E_ARG;
-  *total = 0;
-  if (npat == 0) {
-    if (!d_hit_offsets) return BCE_HIP_OK;
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    BCE_HIP_TRY(c, hipMemsetAsync(d_hit_offsets, 0, 8, c->stream));
-    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return BCE_HIP_OK;
-  }
-  const uint32_t *sa = nullptr;
-  BCE_TRY(locate_state(c, &sa));
-  if (!d_patterns || !d_offsets || !d_hit_offsets || (!d_positions && cap)) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    PhaseScope phase(c, 3);
-    return locate_run(c, sa, static_cast<const uint8_t *>(d_patterns), static_cast<const uint64_t *>(d_offsets), npat, flags & BCE_HIP_LOCATE_LINEAR,
-                      static_cast<uint64_t *>(d_hit_offsets), nullptr, static_cast<uint32_t *>(d_positions), nullptr, !d_positions, cap, total);
-  });
-}
-
-// ---- the longest matches of a second buffer in the text (kd_match.hip) -----------------------------------------------------------
-// Phase 3 with the count's rule.  Cyclic lengths alone need the planes only, so they work behind an injected BWT; positions, and
-// everything in linear mode, read sa[sa_res] by locate_state's rule -- read: nothing here writes that array, the planes or any
-// stage's scratch.  The arguments are judged before the state, the state before the arrays, as for the locate.
-static int match_args(bce_hip_ctx *c, uint64_t q, uint32_t max_len, uint32_t flags) {
-  if (!c || (flags & ~BCE_HIP_MATCH_LINEAR)) return BCE_HIP_E_ARG;
-  if (max_len < 1 || max_len > BCE_HIP_MATCH_MAX_LEN) {
-    snprintf(c->err, sizeof c->err, "match: a length bound of %u, outside 1 .. %u", max_len, BCE_HIP_MATCH_MAX_LEN);
-    return BCE_HIP_E_ARG;
-  }
-  if (q > 0x7FFFFFFFull) { snprintf(c->err, sizeof c->err, "match: a query of 2^31 bytes or more"); return BCE_HIP_E_ARG; }
-  return BCE_HIP_OK;
-}
-static int match_state(bce_hip_ctx *c, bool need_sa, const uint32_t **sa) {
-  *sa = nullptr;
-  return need_sa ? locate_state(c, sa, "match") : count_state(c, "match");
-}
-
-int bce_hip_match(bce_hip_ctx *c, const uint8_t *query, uint64_t q, uint32_t max_len, uint32_t flags, uint32_t *len_out, uint32_t *pos_out) {
-  BCE_TRY(match_args(c, q, max_len, flags));
-  if (q == 0) return BCE_HIP_OK;
-  const uint32_t *sa = nullptr;
-  BCE_TRY(match_state(c, (flags & BCE_HIP_MATCH_LINEAR) || pos_out, &sa));
-  if (!query || !len_out) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    PhaseScope phase(c, 3);
-    const size_t words = (size_t)q * 4;
-    BCE_TRY(ensure(c, c->mat_qry, (size_t)q));
-    BCE_TRY(ensure(c, c->mat_len, words));
-    if (pos_out) BCE_TRY(ensure(c, c->mat_pos, words));
-    BCE_HIP_TRY(c, hipMemcpyAsync(c->mat_qry.p, query, (size_t)q, hipMemcpyHostToDevice, c->stream));
-    BCE_TRY(kd_match(c, sa, c->mat_qry.as<uint8_t>(), (uint32_t)q, max_len, flags & BCE_HIP_MATCH_LINEAR, c->mat_len.as<uint32_t>(),
-                     pos_out ? c->mat_pos.as<uint32_t>() : nullptr));
-    BCE_HIP_TRY(c, hipMemcpyAsync(len_out, c->mat_len.p, words, hipMemcpyDeviceToHost, c->stream));
-    if (pos_out) BCE_HIP_TRY(c, hipMemcpyAsync(pos_out, c->mat_pos.p, words, hipMemcpyDeviceToHost, c->stream));
-    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    BCE_HIP_TRY(c, hipGetLastError());
-    return BCE_HIP_OK;
-  });
-}
-
-int bce_hip_match_device(bce_hip_ctx *c, const void *d_query, uint64_t q, uint32_t max_len, uint32_t flags, void *d_len, void *d_pos) {
-  BCE_TRY(match_args(c, q, max_len, flags));
-  if (q == 0) return BCE_HIP_OK;
-  const uint32_t *sa = nullptr;
-  BCE_TRY(match_state(c, (flags & BCE_HIP_MATCH_LINEAR) || d_pos, &sa));
-  if (!d_query || !d_len) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    PhaseScope phase(c, 3);
-    BCE_TRY(kd_match(c, sa, static_cast<const uint8_t *>(d_query), (uint32_t)q, max_len, flags & BCE_HIP_MATCH_LINEAR,
-                     static_cast<uint32_t *>(d_len), static_cast<uint32_t *>(d_pos)));
-    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    BCE_HIP_TRY(c, hipGetLastError());
-    return BCE_HIP_OK;
-  });
-}
-
-// The search with max_len = min_len (the windows of min_len bytes that end inside a longer match cover it: DESIGN.md 4.10), then
-// the reduction; of the answer only the result word reaches the host.
-static int coverage_run(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_query, uint32_t q, uint32_t min_len, bool linear, uint64_t *covered) {
-  BCE_TRY(ensure(c, c->mat_len, (size_t)q * 4));
-  BCE_TRY(kd_match(c, sa, d_query, q, min_len, linear, c->mat_len.as<uint32_t>(), nullptr));
-  return kd_coverage(c, c->mat_len.as<uint32_t>(), q, min_len, covered);
-}
-
-int bce_hip_coverage(bce_hip_ctx *c, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t flags, uint64_t *covered) {
-  if (!covered) return BCE_HIP_E_ARG;
-  BCE_TRY(match_args(c, q, min_len, flags));
-  *covered = 0;
-  if (q == 0) return BCE_HIP_OK;
-  const uint32_t *sa = nullptr;
-  BCE_TRY(match_state(c, flags & BCE_HIP_MATCH_LINEAR, &sa));
-  if (!query) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    PhaseScope phase(c, 3);
-    BCE_TRY(ensure(c, c->mat_qry, (size_t)q));
-    BCE_HIP_TRY(c, hipMemcpyAsync(c->mat_qry.p, query, (size_t)q, hipMemcpyHostToDevice, c->stream));
-    return coverage_run(c, sa, c->mat_qry.as<uint8_t>(), (uint32_t)q, min_len, flags & BCE_HIP_MATCH_LINEAR, covered);
-  });
-}
-
-int bce_hip_coverage_device(bce_hip_ctx *c, const void *d_query, uint64_t q, uint32_t min_len, uint32_t flags, uint64_t *covered) {
-  if (!covered) return BCE_HIP_E_ARG;
-  BCE_TRY(match_args(c, q, min_len, flags));
-  *covered = 0;
-  if (q == 0) return BCE_HIP_OK;
-  const uint32_t *sa = nullptr;
-  BCE_TRY(match_state(c, flags & BCE_HIP_MATCH_LINEAR, &sa));
-  if (!d_query) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    PhaseScope phase(c, 3);
-    return coverage_run(c, sa, static_cast<const uint8_t *>(d_query), (uint32_t)q, min_len, flags & BCE_HIP_MATCH_LINEAR, covered);
-  });
-}
-
-// ---- what the text holds by itself: the LCP array of the sorted rotations and its reductions (kd_lcp.hip) ---------------------------
-// Phase 3 with the locate's rule PLUS the text: both sa[sa_res] and `text` are read, neither is written, and no stage's scratch is
-// touched (the array, the block parts and the result words are rep_* buffers of the feature's own).  Nothing is kept from one call
-// to the next: every call runs its own LCP pass, so there is nothing that a load, bce_hip_set_bwt or a decode could leave stale.
-// The arguments are judged before the state, the state before the outputs, as for the match.
-static int repeat_bound(bce_hip_ctx *c, const char *what, uint32_t max_len) {
-  if (max_len >= 1 && max_len <= BCE_HIP_MATCH_MAX_LEN) return BCE_HIP_OK;
-  snprintf(c->err, sizeof c->err, "%s: a length bound of %u, outside 1 .. %u", what, max_len, BCE_HIP_MATCH_MAX_LEN);
-  return BCE_HIP_E_ARG;
-}
-static int repeat_state(bce_hip_ctx *c, const uint32_t **sa, const char *what) {
-  BCE_TRY(locate_state(c, sa, what));
-  if (c->text_loaded && c->text.p && c->text.cap >= (size_t)c->n) return BCE_HIP_OK;
-  snprintf(c->err, sizeof c->err, "%s: there is no suffix array behind an injected BWT", what);
-  return BCE_HIP_E_STATE;
-}
-
-int bce_hip_lcp(bce_hip_ctx *c, uint32_t max_len, uint32_t *lcp_out) {
-  if (!c) return BCE_HIP_E_ARG;
-  BCE_TRY(repeat_bound(c, "lcp", max_len));
-  const uint32_t *sa = nullptr;
-  BCE_TRY(repeat_state(c, &sa, "lcp"));
-  if (!lcp_out) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    PhaseScope phase(c, 3);
-    const size_t words = (size_t)c->n * 4;
-    BCE_TRY(ensure(c, c->rep_lcp, words));
-    BCE_TRY(kd_lcp(c, sa, max_len, c->rep_lcp.as<uint32_t>()));
-    BCE_HIP_TRY(c, hipMemcpyAsync(lcp_out, c->rep_lcp.p, words, hipMemcpyDeviceToHost, c->stream));
-    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    BCE_HIP_TRY(c, hipGetLastError());
-    return BCE_HIP_OK;
-  });
-}
-
-int bce_hip_lcp_device(bce_hip_ctx *c, uint32_t max_len, void *d_lcp) {
-  if (!c) return BCE_HIP_E_ARG;
-  BCE_TRY(repeat_bound(c, "lcp", max_len));
-  const uint32_t *sa = nullptr;
-  BCE_TRY(repeat_state(c, &sa, "lcp"));
-  if (!d_lcp) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    PhaseScope phase(c, 3);
-    BCE_TRY(kd_lcp(c, sa, max_len, static_cast<uint32_t *>(d_lcp)));
-    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    BCE_HIP_TRY(c, hipGetLastError());
-    return BCE_HIP_OK;
-  });
-}
-
-int bce_hip_kgrams(bce_hip_ctx *c, const uint32_t *ks, uint32_t nk, bce_hip_kgram *out) {
-  if (!c) return BCE_HIP_E_ARG;
-  if (nk > BCE_HIP_KGRAMS_MAX) { snprintf(c->err, sizeof c->err, "kgrams: %u values of k, more than %u", nk, BCE_HIP_KGRAMS_MAX); return BCE_HIP_E_ARG; }
-  if (nk == 0) return BCE_HIP_OK;
-  if (!ks) return BCE_HIP_E_ARG;
-  uint32_t bound = 1;                                                 // (k = 0 needs no array at all; the pass is bounded by 1 then)
-  for (uint32_t i = 0; i < nk; ++i) {
-    if (ks[i] > BCE_HIP_MATCH_MAX_LEN) { snprintf(c->err, sizeof c->err, "kgrams: k = %u, outside 0 .. %u", ks[i], BCE_HIP_MATCH_MAX_LEN); return BCE_HIP_E_ARG; }
-    if (ks[i] > bound) bound = ks[i];
-  }
-  const uint32_t *sa = nullptr;
-  BCE_TRY(repeat_state(c, &sa, "kgrams"));
-  if (!out) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    PhaseScope phase(c, 3);
-    BCE_TRY(ensure(c, c->rep_lcp, (size_t)c->n * 4));
-    BCE_TRY(kd_lcp(c, sa, bound, c->rep_lcp.as<uint32_t>()));
-    return kd_kgrams(c, sa, c->rep_lcp.as<uint32_t>(), c->n, ks, nk, out);
-  });
-}
-
-int bce_hip_longest_repeat(bce_hip_ctx *c, uint32_t max_len, uint32_t *len, uint32_t *pos_a, uint32_t *pos_b) {
-  if (!c) return BCE_HIP_E_ARG;
-  BCE_TRY(repeat_bound(c, "longest repeat", max_len));
-  const uint32_t *sa = nullptr;
-  BCE_TRY(repeat_state(c, &sa, "longest repeat"));
-  if (!len || !pos_a || !pos_b) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    PhaseScope phase(c, 3);
-    uint32_t res[3];
-    BCE_TRY(ensure(c, c->rep_lcp, (size_t)c->n * 4));
-    BCE_TRY(kd_lcp(c, sa, max_len, c->rep_lcp.as<uint32_t>()));
-    BCE_TRY(kd_longest_repeat(c, sa, c->rep_lcp.as<uint32_t>(), c->n, res));
-    *len = res[0]; *pos_a = res[1]; *pos_b = res[2];
-    return BCE_HIP_OK;
-  });
-}
-
-// ---- a second buffer as a delta against the text: parse and patch (kd_parse.hip) ----------------------------------------------------
-// The parse: phase 3 with the match's rule and positions (locate_state).  The query of a call with a host buffer and the
-// statistics are staged in the match's mat_qry / mat_len / mat_pos; every other temporary is a par_* buffer of the feature's own,
-// and nothing a stage keeps is written.  The patch reads the text alone.  Arguments before the state, the state before the arrays.
-static int parse_args(bce_hip_ctx *c, uint64_t q, uint32_t min_len, uint32_t max_len, const void *ops, uint64_t ops_cap, const void *lits,
-                      uint64_t lits_cap, bce_hip_parse_info *info) {
-  if (!c || !info) return BCE_HIP_E_ARG;
-  if (min_len < 1 || min_len > max_len || max_len > BCE_HIP_MATCH_MAX_LEN) {
-    snprintf(c->err, sizeof c->err, "parse: bounds %u .. %u, outside 1 <= min_len <= max_len <= %u", min_len, max_len, BCE_HIP_MATCH_MAX_LEN);
-    return BCE_HIP_E_ARG;
-  }
-  if (q > 0x7FFFFFFFull) { snprintf(c->err, sizeof c->err, "parse: a query of 2^31 bytes or more"); return BCE_HIP_E_ARG; }
-  if ((!ops && ops_cap) || (!lits && lits_cap)) return BCE_HIP_E_ARG;
-  return BCE_HIP_OK;
-}
-
-int bce_hip_parse(bce_hip_ctx *c, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t max_len, bce_hip_op *ops, uint64_t ops_cap,
-                  uint8_t *lits, uint64_t lits_cap, bce_hip_parse_info *info) {
-  BCE_TRY(parse_args(c, q, min_len, max_len, ops, ops_cap, lits, lits_cap, info));
-  if (q == 0) { *info = bce_hip_parse_info{0, 0, 0, 0}; return BCE_HIP_OK; }
-  const uint32_t *sa = nullptr;
-  BCE_TRY(locate_state(c, &sa, "parse"));
-  if (!query) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    PhaseScope phase(c, 3);
-    const size_t words = (size_t)q * 4;
-    BCE_TRY(ensure(c, c->mat_qry, (size_t)q));
-    BCE_TRY(ensure(c, c->mat_len, words));
-    BCE_TRY(ensure(c, c->mat_pos, words));
-    BCE_HIP_TRY(c, hipMemcpyAsync(c->mat_qry.p, query, (size_t)q, hipMemcpyHostToDevice, c->stream));
-    BCE_TRY(kd_match(c, sa, c->mat_qry.as<uint8_t>(), (uint32_t)q, max_len, true, c->mat_len.as<uint32_t>(), c->mat_pos.as<uint32_t>()));
-    // sized first: the staging of the two outputs is as large as they are, and an overflow touches neither
-    BCE_TRY(kd_parse(c, c->mat_len.as<uint32_t>(), c->mat_pos.as<uint32_t>(), c->mat_qry.as<uint8_t>(), (uint32_t)q, min_len, true, nullptr, 0,
-                     nullptr, 0, info));
-    if (!ops && !lits) return BCE_HIP_OK;
-    BCE_TRY(ensure(c, c->par_ops, (size_t)info->nops * 8));
-    BCE_TRY(ensure(c, c->par_lits, info->nlits ? (size_t)info->nlits : 1));
-    BCE_TRY(kd_parse(c, c->mat_len.as<uint32_t>(), c->mat_pos.as<uint32_t>(), c->mat_qry.as<uint8_t>(), (uint32_t)q, min_len, false,
-                     c->par_ops.as<uint32_t>(), ops_cap, c->par_lits.as<uint8_t>(), lits_cap, info));
-    BCE_HIP_TRY(c, hipMemcpyAsync(ops, c->par_ops.p, (size_t)info->nops * 8, hipMemcpyDeviceToHost, c->stream));
-    if (info->nlits) BCE_HIP_TRY(c, hipMemcpyAsync(lits, c->par_lits.p, (size_t)info->nlits, hipMemcpyDeviceToHost, c->stream));
-    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    BCE_HIP_TRY(c, hipGetLastError());
-    return BCE_HIP_OK;
-  });
-}
-
-int bce_hip_parse_device(bce_hip_ctx *c, const void *d_query, uint64_t q, uint32_t min_len, uint32_t max_len, void *d_ops, uint64_t ops_cap,
-                         void *d_lits, uint64_t lits_cap, bce_hip_parse_info *info) {
-  BCE_TRY(parse_args(c, q, min_len, max_len, d_ops, ops_cap, d_lits, lits_cap, info));
-  if (q == 0) { *info = bce_hip_parse_info{0, 0, 0, 0}; return BCE_HIP_OK; }
-  const uint32_t *sa = nullptr;
-  BCE_TRY(locate_state(c, &sa, "parse"));
-  if (!d_query) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    PhaseScope phase(c, 3);
-    const size_t words = (size_t)q * 4;
-    BCE_TRY(ensure(c, c->mat_len, words));
-    BCE_TRY(ensure(c, c->mat_pos, words));
-    const uint8_t *qry = static_cast<const uint8_t *>(d_query);
-    BCE_TRY(kd_match(c, sa, qry, (uint32_t)q, max_len, true, c->mat_len.as<uint32_t>(), c->mat_pos.as<uint32_t>()));
-    return kd_parse(c, c->mat_len.as<uint32_t>(), c->mat_pos.as<uint32_t>(), qry, (uint32_t)q, min_len, !d_ops && !d_lits,
-                    static_cast<uint32_t *>(d_ops), ops_cap, static_cast<uint8_t *>(d_lits), lits_cap, info);
-  });
-}
-
-int bce_hip_parse_of_lengths_device(bce_hip_ctx *c, const void *d_len, const void *d_pos, const void *d_query, uint64_t q, uint32_t min_len,
-                                    void *d_ops, uint64_t ops_cap, void *d_lits, uint64_t lits_cap, bce_hip_parse_info *info) {
-  BCE_TRY(parse_args(c, q, min_len, BCE_HIP_MATCH_MAX_LEN, d_ops, ops_cap, d_lits, lits_cap, info));
-  if (q == 0) { *info = bce_hip_parse_info{0, 0, 0, 0}; return BCE_HIP_OK; }
-  if (!d_len || !d_query) return BCE_HIP_E_ARG;
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    return kd_parse(c, static_cast<const uint32_t *>(d_len), static_cast<const uint32_t *>(d_pos), static_cast<const uint8_t *>(d_query), (uint32_t)q,
-                    min_len, !d_ops && !d_lits, static_cast<uint32_t *>(d_ops), ops_cap, static_cast<uint8_t *>(d_lits), lits_cap, info);
-  });
-}
-
-static int patch_args(bce_hip_ctx *c, const void *ops, uint64_t nops, const void *lits, uint64_t nlits, const void *out, uint64_t cap,
-                      uint64_t *out_len) {
-  if (!c || !out_len) return BCE_HIP_E_ARG;
-  if (nops > 0x7FFFFFFFull) { snprintf(c->err, sizeof c->err, "patch: 2^31 ops or more, a result of 2^31 bytes or more"); return BCE_HIP_E_ARG; }
-  if ((nops && !ops) || (nlits && !lits) || (cap && !out)) return BCE_HIP_E_ARG;
-  return BCE_HIP_OK;
-}
-static int patch_state(bce_hip_ctx *c) {
-  if (c->text_loaded && c->stage >= 1 && c->text.p && c->text.cap >= (size_t)c->n) return BCE_HIP_OK;
-  snprintf(c->err, sizeof c->err, "patch: no loaded input in this context");
-  return BCE_HIP_E_STATE;
-}
-// nops == 0: nothing to launch -- the empty result, and no literal byte may be left over
-static int patch_empty(bce_hip_ctx *c, uint64_t nlits, uint64_t *out_len) {
-  if (const char *why = bce::patch_list_bad(0, 0, 0, nlits)) { snprintf(c->err, sizeof c->err, "%s", why); return BCE_HIP_E_ARG; }
-  *out_len = 0;
-  return BCE_HIP_OK;
-}
-
-int bce_hip_patch(bce_hip_ctx *c, const bce_hip_op *ops, uint64_t nops, const uint8_t *lits, uint64_t nlits, uint8_t *out, uint64_t cap,
-                  uint64_t *out_len) {
-  BCE_TRY(patch_args(c, ops, nops, lits, nlits, out, cap, out_len));
-  BCE_TRY(patch_state(c));
-  if (nops == 0) return patch_empty(c, nlits, out_len);
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    PhaseScope phase(c, 3);
-    BCE_TRY(ensure(c, c->par_ops, (size_t)nops * 8));
-    BCE_TRY(ensure(c, c->par_lits, nlits ? (size_t)nlits : 1));
-    BCE_HIP_TRY(c, hipMemcpyAsync(c->par_ops.p, ops, (size_t)nops * 8, hipMemcpyHostToDevice, c->stream));
-    if (nlits) BCE_HIP_TRY(c, hipMemcpyAsync(c->par_lits.p, lits, (size_t)nlits, hipMemcpyHostToDevice, c->stream));
-    // validated and sized first: the staging of the result is as large as the result
-    uint64_t total = 0;
-    BCE_TRY(kd_patch(c, c->par_ops.as<uint32_t>(), (uint32_t)nops, c->par_lits.as<uint8_t>(), nlits, true, nullptr, 0, &total));
-    *out_len = total;
-    if (!out) return BCE_HIP_OK;
-    if (total > cap) { snprintf(c->err, sizeof c->err, "patch: %llu bytes, room for %llu", (unsigned long long)total, (unsigned long long)cap); return BCE_HIP_E_OVERFLOW; }
-    BCE_TRY(ensure(c, c->par_out, (size_t)total));
-    BCE_TRY(kd_patch(c, c->par_ops.as<uint32_t>(), (uint32_t)nops, c->par_lits.as<uint8_t>(), nlits, false, c->par_out.as<uint8_t>(), total, &total));
-    BCE_HIP_TRY(c, hipMemcpyAsync(out, c->par_out.p, (size_t)total, hipMemcpyDeviceToHost, c->stream));
-    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    BCE_HIP_TRY(c, hipGetLastError());
-    return BCE_HIP_OK;
-  });
-}
-
-int bce_hip_patch_device(bce_hip_ctx *c, const void *d_ops, uint64_t nops, const void *d_lits, uint64_t nlits, void *d_out, uint64_t cap,
-                         uint64_t *out_len) {
-  BCE_TRY(patch_args(c, d_ops, nops, d_lits, nlits, d_out, cap, out_len));
-  BCE_TRY(patch_state(c));
-  if (nops == 0) return patch_empty(c, nlits, out_len);
-  return bce_guarded(c, [&]() -> int {
-    BCE_HIP_TRY(c, hipSetDevice(c->device));
-    PhaseScope phase(c, 3);
-    return kd_patch(c, static_cast<const uint32_t *>(d_ops), (uint32_t)nops, static_cast<const uint8_t *>(d_lits), nlits, !d_out,
-                    static_cast<uint8_t *>(d_out), cap, out_len);
   });
 }
 

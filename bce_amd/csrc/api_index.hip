@@ -1,0 +1,458 @@
+// api_index.hip -- C ABI of the index queries (include/bce_hip.h): counts, positions, longest matches and coverage, the LCP array and
+// its reductions, parse and patch; and the two test hooks that run their block scans alone.  The device work is in kd_count /
+// kd_locate / kd_match / kd_lcp / kd_parse.hip.  Every query comes twice, for host buffers and for device buffers: the two differ
+// in staging and in the copy out, and in nothing else.
+//
+// All of them judge the arguments before the context's state and the state before the arrays, then run their body through
+// query_call in phase 3, as bce_hip_rank1: the planes are read, so what an allocation may give back is what an enumeration beside
+// them would.  Nothing a stage keeps is written: staging, scratch and result words are the queries' own (common.h: qb).
+#include "common.h"
+#include "parse_step.h"
+
+using namespace bce;
+
+// The body of a query: no exception leaves, the context's device is current, `phase` holds while it runs, and whatever the body
+// has queued is complete -- and has left no error behind -- when BCE_HIP_OK comes back.
+template <class F>
+static int query_call(bce_hip_ctx *c, int phase, F &&body) {
+  return bce_guarded(c, [&]() -> int {
+    BCE_HIP_TRY(c, hipSetDevice(c->device));
+    PhaseScope scope(c, phase);
+    BCE_TRY(body());
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    BCE_HIP_TRY(c, hipGetLastError());
+    return BCE_HIP_OK;
+  });
+}
+
+// `bytes` of the caller's host memory into a grow-only buffer of the context (never an empty allocation); queued
+static int stage(bce_hip_ctx *c, DevBuf &b, const void *host, size_t bytes) {
+  BCE_TRY(ensure(c, b, bytes ? bytes : 1));
+  if (bytes) BCE_HIP_TRY(c, hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, c->stream));
+  return BCE_HIP_OK;
+}
+static int stage_patterns(bce_hip_ctx *c, DevBuf &pat, DevBuf &off, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat) {
+  BCE_TRY(stage(c, pat, patterns, (size_t)offsets[npat]));
+  return stage(c, off, offsets, ((size_t)npat + 1) * 8);
+}
+static int copy_out(bce_hip_ctx *c, void *host, const DevBuf &b, size_t bytes) {
+  if (bytes) BCE_HIP_TRY(c, hipMemcpyAsync(host, b.p, bytes, hipMemcpyDeviceToHost, c->stream));
+  return BCE_HIP_OK;
+}
+
+// a list of npat >= 1 patterns in host memory: offsets that do not decrease, and bytes where they name some
+static int pattern_list_args(bce_hip_ctx *c, const char *what, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat) {
+  if (!offsets) return BCE_HIP_E_ARG;
+  for (uint32_t p = 0; p < npat; ++p)
+    if (offsets[p + 1] < offsets[p]) { snprintf(c->err, sizeof c->err, "%s: pattern offsets decrease at %u", what, p); return BCE_HIP_E_ARG; }
+  return offsets[npat] && !patterns ? BCE_HIP_E_ARG : BCE_HIP_OK;
+}
+static int length_bound(bce_hip_ctx *c, const char *what, uint32_t max_len) {
+  if (max_len >= 1 && max_len <= BCE_HIP_MATCH_MAX_LEN) return BCE_HIP_OK;
+  snprintf(c->err, sizeof c->err, "%s: a length bound of %u, outside 1 .. %u", what, max_len, BCE_HIP_MATCH_MAX_LEN);
+  return BCE_HIP_E_ARG;
+}
+
+// ---- what a query needs of the context ---------------------------------------------------------------------------------------------
+static int planes_state(bce_hip_ctx *c, const char *what) {
+  if (c->stage >= 3) return BCE_HIP_OK;
+  snprintf(c->err, sizeof c->err, "%s: the context holds no planes (stage %d; bce_hip_build_planes first)", what, c->stage);
+  return BCE_HIP_E_STATE;
+}
+// The planes and K1's suffix array.  ctx_trim keeps sa[sa_res] in phase 3, for the depth-first tail, and nothing after K1 writes
+// that array until the next load or decode (K3's tail, the encoder, the estimate, the scan, the queries and the sort hooks only read
+// it or never name it), so it stands for as long as k1_valid does.  A text of one byte has no array: its only rotation starts at 0.
+static int sa_state(bce_hip_ctx *c, const uint32_t **sa, const char *what) {
+  BCE_TRY(planes_state(c, what));
+  *sa = nullptr;
+  if (c->k1_valid && c->sa[c->sa_res].p && c->sa[c->sa_res].cap >= (size_t)c->n * 4) { *sa = c->sa[c->sa_res].as<uint32_t>(); return BCE_HIP_OK; }
+  if (c->n == 1 && c->text_loaded) return BCE_HIP_OK;
+  snprintf(c->err, sizeof c->err, c->text_loaded ? "%s: the suffix array of this input is gone" : "%s: there is no suffix array behind an injected BWT", what);
+  return BCE_HIP_E_STATE;
+}
+// ... and the text itself
+static int text_state(bce_hip_ctx *c, const uint32_t **sa, const char *what) {
+  BCE_TRY(sa_state(c, sa, what));
+  if (c->text_loaded && c->text.p && c->text.cap >= (size_t)c->n) return BCE_HIP_OK;
+  snprintf(c->err, sizeof c->err, "%s: there is no suffix array behind an injected BWT", what);
+  return BCE_HIP_E_STATE;
+}
+
+extern "C" {
+
+// ---- test hooks: the block scans of the index queries alone (kd_lcp.hip, kd_match.hip) ----------------------------
+// Phase 0, as the sort hooks: nothing of the context is given back to make room, and only the features' own rep_* / mat_* buffers
+// are written.  The LCP words are copied into rep_lcp first: the reductions load them sixteen bytes at a time from there.
+int bce_hip_lcp_reduce_device(bce_hip_ctx *c, const void *d_lcp, uint32_t n, const void *d_sa, const uint32_t *ks, uint32_t nk,
+                              bce_hip_kgram *out, uint32_t repeat3[3]) {
+  if (!c || !d_lcp || !d_sa || n == 0 || n > 0x7FFFFFFFu || nk > BCE_HIP_KGRAMS_MAX || (nk && (!ks || !out))) return BCE_HIP_E_ARG;
+  return query_call(c, 0, [&]() -> int {
+    DevBuf &lcp = c->qbuf[qb::rep_lcp];
+    const size_t words = (size_t)n * 4;
+    BCE_TRY(ensure(c, lcp, words));
+    BCE_HIP_TRY(c, hipMemcpyAsync(lcp.p, d_lcp, words, hipMemcpyDeviceToDevice, c->stream));
+    const uint32_t *sa = static_cast<const uint32_t *>(d_sa);
+    if (nk) BCE_TRY(kd_kgrams(c, sa, lcp.as<uint32_t>(), n, ks, nk, out));
+    if (repeat3) BCE_TRY(kd_longest_repeat(c, sa, lcp.as<uint32_t>(), n, repeat3));
+    return BCE_HIP_OK;
+  });
+}
+
+int bce_hip_coverage_of_lengths_device(bce_hip_ctx *c, const void *d_len, uint64_t q, uint32_t min_len, uint64_t *covered) {
+  if (!c || !covered || q > 0x7FFFFFFFull || min_len < 1 || min_len > BCE_HIP_MATCH_MAX_LEN || (q && !d_len)) return BCE_HIP_E_ARG;
+  return query_call(c, 0, [&] { return kd_coverage(c, static_cast<const uint32_t *>(d_len), (uint32_t)q, min_len, covered); });
+}
+
+// ---- pattern counts from the planes (kd_count.hip) ---------------------------------------------------------
+int bce_hip_count(bce_hip_ctx *c, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint64_t *counts) {
+  if (!c) return BCE_HIP_E_ARG;
+  if (npat == 0) return BCE_HIP_OK;
+  BCE_TRY(planes_state(c, "count"));
+  if (!counts) return BCE_HIP_E_ARG;
+  BCE_TRY(pattern_list_args(c, "count", patterns, offsets, npat));
+  return query_call(c, 3, [&]() -> int {
+    DevBuf &pat = c->qbuf[qb::cnt_pat], &off = c->qbuf[qb::cnt_off], &out = c->qbuf[qb::cnt_out];
+    BCE_TRY(ensure(c, out, (size_t)npat * 8));
+    BCE_TRY(stage_patterns(c, pat, off, patterns, offsets, npat));
+    BCE_TRY(kd_count(c, pat.as<uint8_t>(), off.as<uint64_t>(), npat, out.as<uint64_t>()));
+    return copy_out(c, counts, out, (size_t)npat * 8);
+  });
+}
+
+int bce_hip_count_device(bce_hip_ctx *c, const void *d_patterns, const void *d_offsets, uint32_t npat, void *d_counts) {
+  if (!c) return BCE_HIP_E_ARG;
+  if (npat == 0) return BCE_HIP_OK;
+  BCE_TRY(planes_state(c, "count"));
+  if (!d_patterns || !d_offsets || !d_counts) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&] {
+    return kd_count(c, static_cast<const uint8_t *>(d_patterns), static_cast<const uint64_t *>(d_offsets), npat, static_cast<uint64_t *>(d_counts));
+  });
+}
+
+// ---- pattern positions from the planes and K1's suffix array (kd_locate.hip) -----------------------------------------------
+// The overflow protocol, once for both entry points.  d_*: device arrays; h_hits / h_pos: where a call with host buffers wants the
+// offsets and positions (then d_pos is staged in loc_pos once the total is known).  hit offsets and *total are out before the
+// first reason to refuse; the positions are touched only when all of them fit.
+static int locate_run(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, bool linear, uint64_t *d_hits,
+                      uint64_t *h_hits, uint32_t *d_pos, uint32_t *h_pos, bool sizing, uint64_t cap, uint64_t *total) {
+  uint64_t rows = 0, hits = 0;
+  const int rc = kd_locate_size(c, sa, d_pat, d_off, npat, linear, d_hits, &rows, &hits);
+  if (rc != BCE_HIP_OK && rc != BCE_HIP_E_OVERFLOW) return rc;
+  if (h_hits) {
+    BCE_HIP_TRY(c, hipMemcpyAsync(h_hits, d_hits, ((size_t)npat + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  *total = hits;
+  if (rc != BCE_HIP_OK || sizing) return rc;
+  if (hits > cap) { snprintf(c->err, sizeof c->err, "locate: %llu hits, room for %llu", (unsigned long long)hits, (unsigned long long)cap); return BCE_HIP_E_OVERFLOW; }
+  if (hits == 0) return BCE_HIP_OK;
+  if (h_pos) {
+    BCE_TRY(ensure(c, c->qbuf[qb::loc_pos], (size_t)hits * 4));
+    d_pos = c->qbuf[qb::loc_pos].as<uint32_t>();
+  }
+  BCE_TRY(kd_locate_fill(c, sa, d_off, npat, linear, rows, hits, d_pos));
+  return h_pos ? copy_out(c, h_pos, c->qbuf[qb::loc_pos], (size_t)hits * 4) : BCE_HIP_OK;
+}
+
+int bce_hip_locate(bce_hip_ctx *c, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t flags, uint64_t *hit_offsets,
+                   uint32_t *positions, uint64_t cap, uint64_t *total) {
+  if (!c || !total || (flags & ~BCE_HIP_LOCATE_LINEAR)) return BCE_HIP_E_ARG;
+  *total = 0;
+  if (npat == 0) { if (hit_offsets) hit_offsets[0] = 0; return BCE_HIP_OK; }
+  const uint32_t *sa = nullptr;
+  BCE_TRY(sa_state(c, &sa, "locate"));
+  if (!hit_offsets || (!positions && cap)) return BCE_HIP_E_ARG;
+  BCE_TRY(pattern_list_args(c, "locate", patterns, offsets, npat));
+  return query_call(c, 3, [&]() -> int {
+    DevBuf &pat = c->qbuf[qb::loc_pat], &off = c->qbuf[qb::loc_off], &hits = c->qbuf[qb::loc_hits];
+    BCE_TRY(ensure(c, hits, ((size_t)npat + 1) * 8));
+    BCE_TRY(stage_patterns(c, pat, off, patterns, offsets, npat));
+    return locate_run(c, sa, pat.as<uint8_t>(), off.as<uint64_t>(), npat, flags & BCE_HIP_LOCATE_LINEAR, hits.as<uint64_t>(), hit_offsets, nullptr,
+                      positions, !positions, cap, total);
+  });
+}
+
+int bce_hip_locate_device(bce_hip_ctx *c, const void *d_patterns, const void *d_offsets, uint32_t npat, uint32_t flags, void *d_hit_offsets,
+                          void *d_positions, uint64_t cap, uint64_t *total) {
+  if (!c || !total || (flags & ~BCE_HIP_LOCATE_LINEAR)) return BCE_HIP_E_ARG;
+  *total = 0;
+  if (npat == 0) {
+    if (!d_hit_offsets) return BCE_HIP_OK;
+    return query_call(c, 0, [&]() -> int { BCE_HIP_TRY(c, hipMemsetAsync(d_hit_offsets, 0, 8, c->stream)); return BCE_HIP_OK; });
+  }
+  const uint32_t *sa = nullptr;
+  BCE_TRY(sa_state(c, &sa, "locate"));
+  if (!d_patterns || !d_offsets || !d_hit_offsets || (!d_positions && cap)) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&] {
+    return locate_run(c, sa, static_cast<const uint8_t *>(d_patterns), static_cast<const uint64_t *>(d_offsets), npat, flags & BCE_HIP_LOCATE_LINEAR,
+                      static_cast<uint64_t *>(d_hit_offsets), nullptr, static_cast<uint32_t *>(d_positions), nullptr, !d_positions, cap, total);
+  });
+}
+
+// ---- the longest matches of a second buffer in the text (kd_match.hip) -----------------------------------------------------------
+// Cyclic lengths alone need the planes only, so they work behind an injected BWT; positions, and everything in linear mode, read
+// sa[sa_res] by sa_state's rule -- read: nothing here writes that array, the planes or any stage's scratch.
+static int match_args(bce_hip_ctx *c, uint64_t q, uint32_t max_len, uint32_t flags) {
+  if (!c || (flags & ~BCE_HIP_MATCH_LINEAR)) return BCE_HIP_E_ARG;
+  BCE_TRY(length_bound(c, "match", max_len));
+  if (q > 0x7FFFFFFFull) { snprintf(c->err, sizeof c->err, "match: a query of 2^31 bytes or more"); return BCE_HIP_E_ARG; }
+  return BCE_HIP_OK;
+}
+static int match_state(bce_hip_ctx *c, bool need_sa, const uint32_t **sa) {
+  *sa = nullptr;
+  return need_sa ? sa_state(c, sa, "match") : planes_state(c, "match");
+}
+
+int bce_hip_match(bce_hip_ctx *c, const uint8_t *query, uint64_t q, uint32_t max_len, uint32_t flags, uint32_t *len_out, uint32_t *pos_out) {
+  BCE_TRY(match_args(c, q, max_len, flags));
+  if (q == 0) return BCE_HIP_OK;
+  const uint32_t *sa = nullptr;
+  BCE_TRY(match_state(c, (flags & BCE_HIP_MATCH_LINEAR) || pos_out, &sa));
+  if (!query || !len_out) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&]() -> int {
+    DevBuf &qry = c->qbuf[qb::mat_qry], &len = c->qbuf[qb::mat_len], &pos = c->qbuf[qb::mat_pos];
+    const size_t words = (size_t)q * 4;
+    BCE_TRY(ensure(c, len, words));
+    if (pos_out) BCE_TRY(ensure(c, pos, words));
+    BCE_TRY(stage(c, qry, query, (size_t)q));
+    BCE_TRY(kd_match(c, sa, qry.as<uint8_t>(), (uint32_t)q, max_len, flags & BCE_HIP_MATCH_LINEAR, len.as<uint32_t>(),
+                     pos_out ? pos.as<uint32_t>() : nullptr));
+    BCE_TRY(copy_out(c, len_out, len, words));
+    return pos_out ? copy_out(c, pos_out, pos, words) : BCE_HIP_OK;
+  });
+}
+
+int bce_hip_match_device(bce_hip_ctx *c, const void *d_query, uint64_t q, uint32_t max_len, uint32_t flags, void *d_len, void *d_pos) {
+  BCE_TRY(match_args(c, q, max_len, flags));
+  if (q == 0) return BCE_HIP_OK;
+  const uint32_t *sa = nullptr;
+  BCE_TRY(match_state(c, (flags & BCE_HIP_MATCH_LINEAR) || d_pos, &sa));
+  if (!d_query || !d_len) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&] {
+    return kd_match(c, sa, static_cast<const uint8_t *>(d_query), (uint32_t)q, max_len, flags & BCE_HIP_MATCH_LINEAR, static_cast<uint32_t *>(d_len),
+                    static_cast<uint32_t *>(d_pos));
+  });
+}
+
+// The search with max_len = min_len (the windows of min_len bytes that end inside a longer match cover it: DESIGN.md 4.10), then
+// the reduction; of the answer only the result word reaches the host.
+static int coverage_run(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_query, uint32_t q, uint32_t min_len, bool linear, uint64_t *covered) {
+  DevBuf &len = c->qbuf[qb::mat_len];
+  BCE_TRY(ensure(c, len, (size_t)q * 4));
+  BCE_TRY(kd_match(c, sa, d_query, q, min_len, linear, len.as<uint32_t>(), nullptr));
+  return kd_coverage(c, len.as<uint32_t>(), q, min_len, covered);
+}
+// what both coverage entry points judge: *covered = 0 and *sa once the arguments and the state have passed
+static int coverage_args(bce_hip_ctx *c, uint64_t q, uint32_t min_len, uint32_t flags, uint64_t *covered, const uint32_t **sa) {
+  if (!covered) return BCE_HIP_E_ARG;
+  BCE_TRY(match_args(c, q, min_len, flags));
+  *covered = 0;
+  return q ? match_state(c, flags & BCE_HIP_MATCH_LINEAR, sa) : BCE_HIP_OK;
+}
+
+int bce_hip_coverage(bce_hip_ctx *c, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t flags, uint64_t *covered) {
+  const uint32_t *sa = nullptr;
+  BCE_TRY(coverage_args(c, q, min_len, flags, covered, &sa));
+  if (q == 0) return BCE_HIP_OK;
+  if (!query) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&]() -> int {
+    BCE_TRY(stage(c, c->qbuf[qb::mat_qry], query, (size_t)q));
+    return coverage_run(c, sa, c->qbuf[qb::mat_qry].as<uint8_t>(), (uint32_t)q, min_len, flags & BCE_HIP_MATCH_LINEAR, covered);
+  });
+}
+
+int bce_hip_coverage_device(bce_hip_ctx *c, const void *d_query, uint64_t q, uint32_t min_len, uint32_t flags, uint64_t *covered) {
+  const uint32_t *sa = nullptr;
+  BCE_TRY(coverage_args(c, q, min_len, flags, covered, &sa));
+  if (q == 0) return BCE_HIP_OK;
+  if (!d_query) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&] { return coverage_run(c, sa, static_cast<const uint8_t *>(d_query), (uint32_t)q, min_len, flags & BCE_HIP_MATCH_LINEAR, covered); });
+}
+
+// ---- what the text holds by itself: the LCP array of the sorted rotations and its reductions (kd_lcp.hip) ---------------------------
+// The locate's rule PLUS the text (text_state): both sa[sa_res] and `text` are read, neither is written.  Nothing is kept from one
+// call to the next: every call runs its own LCP pass, so there is nothing that a load, bce_hip_set_bwt or a decode could leave stale.
+static int lcp_args(bce_hip_ctx *c, const char *what, uint32_t max_len, const uint32_t **sa) {
+  if (!c) return BCE_HIP_E_ARG;
+  BCE_TRY(length_bound(c, what, max_len));
+  return text_state(c, sa, what);
+}
+// the array of the context's own, for the calls that do not bring device memory for it
+static int lcp_own(bce_hip_ctx *c, const uint32_t *sa, uint32_t max_len) {
+  DevBuf &lcp = c->qbuf[qb::rep_lcp];
+  BCE_TRY(ensure(c, lcp, (size_t)c->n * 4));
+  return kd_lcp(c, sa, max_len, lcp.as<uint32_t>());
+}
+
+int bce_hip_lcp(bce_hip_ctx *c, uint32_t max_len, uint32_t *lcp_out) {
+  const uint32_t *sa = nullptr;
+  BCE_TRY(lcp_args(c, "lcp", max_len, &sa));
+  if (!lcp_out) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&]() -> int {
+    BCE_TRY(lcp_own(c, sa, max_len));
+    return copy_out(c, lcp_out, c->qbuf[qb::rep_lcp], (size_t)c->n * 4);
+  });
+}
+
+int bce_hip_lcp_device(bce_hip_ctx *c, uint32_t max_len, void *d_lcp) {
+  const uint32_t *sa = nullptr;
+  BCE_TRY(lcp_args(c, "lcp", max_len, &sa));
+  if (!d_lcp) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&] { return kd_lcp(c, sa, max_len, static_cast<uint32_t *>(d_lcp)); });
+}
+
+int bce_hip_kgrams(bce_hip_ctx *c, const uint32_t *ks, uint32_t nk, bce_hip_kgram *out) {
+  if (!c) return BCE_HIP_E_ARG;
+  if (nk > BCE_HIP_KGRAMS_MAX) { snprintf(c->err, sizeof c->err, "kgrams: %u values of k, more than %u", nk, BCE_HIP_KGRAMS_MAX); return BCE_HIP_E_ARG; }
+  if (nk == 0) return BCE_HIP_OK;
+  if (!ks) return BCE_HIP_E_ARG;
+  uint32_t bound = 1;                                                 // (k = 0 needs no array at all; the pass is bounded by 1 then)
+  for (uint32_t i = 0; i < nk; ++i) {
+    if (ks[i] > BCE_HIP_MATCH_MAX_LEN) { snprintf(c->err, sizeof c->err, "kgrams: k = %u, outside 0 .. %u", ks[i], BCE_HIP_MATCH_MAX_LEN); return BCE_HIP_E_ARG; }
+    if (ks[i] > bound) bound = ks[i];
+  }
+  const uint32_t *sa = nullptr;
+  BCE_TRY(text_state(c, &sa, "kgrams"));
+  if (!out) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&]() -> int {
+    BCE_TRY(lcp_own(c, sa, bound));
+    return kd_kgrams(c, sa, c->qbuf[qb::rep_lcp].as<uint32_t>(), c->n, ks, nk, out);
+  });
+}
+
+int bce_hip_longest_repeat(bce_hip_ctx *c, uint32_t max_len, uint32_t *len, uint32_t *pos_a, uint32_t *pos_b) {
+  const uint32_t *sa = nullptr;
+  BCE_TRY(lcp_args(c, "longest repeat", max_len, &sa));
+  if (!len || !pos_a || !pos_b) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&]() -> int {
+    uint32_t res[3];
+    BCE_TRY(lcp_own(c, sa, max_len));
+    BCE_TRY(kd_longest_repeat(c, sa, c->qbuf[qb::rep_lcp].as<uint32_t>(), c->n, res));
+    *len = res[0]; *pos_a = res[1]; *pos_b = res[2];
+    return BCE_HIP_OK;
+  });
+}
+
+// ---- a second buffer as a delta against the text: parse and patch (kd_parse.hip) ----------------------------------------------------
+// The parse: the match's rule with positions (sa_state).  The query of a call with a host buffer and the statistics are staged in
+// the match's mat_qry / mat_len / mat_pos; every other temporary is a par_* buffer of the feature's own.  The patch reads the text
+// alone.
+static int parse_args(bce_hip_ctx *c, uint64_t q, uint32_t min_len, uint32_t max_len, const void *ops, uint64_t ops_cap, const void *lits,
+                      uint64_t lits_cap, bce_hip_parse_info *info) {
+  if (!c || !info) return BCE_HIP_E_ARG;
+  if (min_len < 1 || min_len > max_len || max_len > BCE_HIP_MATCH_MAX_LEN) {
+    snprintf(c->err, sizeof c->err, "parse: bounds %u .. %u, outside 1 <= min_len <= max_len <= %u", min_len, max_len, BCE_HIP_MATCH_MAX_LEN);
+    return BCE_HIP_E_ARG;
+  }
+  if (q > 0x7FFFFFFFull) { snprintf(c->err, sizeof c->err, "parse: a query of 2^31 bytes or more"); return BCE_HIP_E_ARG; }
+  if ((!ops && ops_cap) || (!lits && lits_cap)) return BCE_HIP_E_ARG;
+  if (q == 0) *info = bce_hip_parse_info{0, 0, 0, 0};
+  return BCE_HIP_OK;
+}
+// the linear statistics of a query in device memory, with positions, into mat_len / mat_pos; then the parse from them
+static int parse_run(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_query, uint32_t q, uint32_t min_len, uint32_t max_len, uint32_t *d_ops,
+                     uint64_t ops_cap, uint8_t *d_lits, uint64_t lits_cap, bce_hip_parse_info *info) {
+  DevBuf &len = c->qbuf[qb::mat_len], &pos = c->qbuf[qb::mat_pos];
+  BCE_TRY(ensure(c, len, (size_t)q * 4));
+  BCE_TRY(ensure(c, pos, (size_t)q * 4));
+  BCE_TRY(kd_match(c, sa, d_query, q, max_len, true, len.as<uint32_t>(), pos.as<uint32_t>()));
+  return kd_parse(c, len.as<uint32_t>(), pos.as<uint32_t>(), d_query, q, min_len, !d_ops && !d_lits, d_ops, ops_cap, d_lits, lits_cap, info);
+}
+
+int bce_hip_parse(bce_hip_ctx *c, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t max_len, bce_hip_op *ops, uint64_t ops_cap,
+                  uint8_t *lits, uint64_t lits_cap, bce_hip_parse_info *info) {
+  BCE_TRY(parse_args(c, q, min_len, max_len, ops, ops_cap, lits, lits_cap, info));
+  if (q == 0) return BCE_HIP_OK;
+  const uint32_t *sa = nullptr;
+  BCE_TRY(sa_state(c, &sa, "parse"));
+  if (!query) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&]() -> int {
+    DevBuf &qry = c->qbuf[qb::mat_qry], &d_ops = c->qbuf[qb::par_ops], &d_lits = c->qbuf[qb::par_lits];
+    BCE_TRY(stage(c, qry, query, (size_t)q));
+    // Unlike the device entry, sized first: the staging of the two outputs is as large as they are, and an overflow touches neither
+    BCE_TRY(parse_run(c, sa, qry.as<uint8_t>(), (uint32_t)q, min_len, max_len, nullptr, 0, nullptr, 0, info));
+    if (!ops && !lits) return BCE_HIP_OK;
+    BCE_TRY(ensure(c, d_ops, (size_t)info->nops * 8));
+    BCE_TRY(ensure(c, d_lits, info->nlits ? (size_t)info->nlits : 1));
+    BCE_TRY(kd_parse(c, c->qbuf[qb::mat_len].as<uint32_t>(), c->qbuf[qb::mat_pos].as<uint32_t>(), qry.as<uint8_t>(), (uint32_t)q, min_len, false,
+                     d_ops.as<uint32_t>(), ops_cap, d_lits.as<uint8_t>(), lits_cap, info));
+    BCE_TRY(copy_out(c, ops, d_ops, (size_t)info->nops * 8));
+    return copy_out(c, lits, d_lits, (size_t)info->nlits);
+  });
+}
+
+int bce_hip_parse_device(bce_hip_ctx *c, const void *d_query, uint64_t q, uint32_t min_len, uint32_t max_len, void *d_ops, uint64_t ops_cap,
+                         void *d_lits, uint64_t lits_cap, bce_hip_parse_info *info) {
+  BCE_TRY(parse_args(c, q, min_len, max_len, d_ops, ops_cap, d_lits, lits_cap, info));
+  if (q == 0) return BCE_HIP_OK;
+  const uint32_t *sa = nullptr;
+  BCE_TRY(sa_state(c, &sa, "parse"));
+  if (!d_query) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&] {
+    return parse_run(c, sa, static_cast<const uint8_t *>(d_query), (uint32_t)q, min_len, max_len, static_cast<uint32_t *>(d_ops), ops_cap,
+                     static_cast<uint8_t *>(d_lits), lits_cap, info);
+  });
+}
+
+int bce_hip_parse_of_lengths_device(bce_hip_ctx *c, const void *d_len, const void *d_pos, const void *d_query, uint64_t q, uint32_t min_len,
+                                    void *d_ops, uint64_t ops_cap, void *d_lits, uint64_t lits_cap, bce_hip_parse_info *info) {
+  BCE_TRY(parse_args(c, q, min_len, BCE_HIP_MATCH_MAX_LEN, d_ops, ops_cap, d_lits, lits_cap, info));
+  if (q == 0) return BCE_HIP_OK;
+  if (!d_len || !d_query) return BCE_HIP_E_ARG;
+  return query_call(c, 0, [&] {
+    return kd_parse(c, static_cast<const uint32_t *>(d_len), static_cast<const uint32_t *>(d_pos), static_cast<const uint8_t *>(d_query), (uint32_t)q,
+                    min_len, !d_ops && !d_lits, static_cast<uint32_t *>(d_ops), ops_cap, static_cast<uint8_t *>(d_lits), lits_cap, info);
+  });
+}
+
+// Arguments, then the state (a loaded text), then the list without ops: nothing to launch -- the empty result, and no literal byte
+// may be left over.  *empty: the call is answered.
+static int patch_args(bce_hip_ctx *c, const void *ops, uint64_t nops, const void *lits, uint64_t nlits, const void *out, uint64_t cap,
+                      uint64_t *out_len, bool *empty) {
+  if (!c || !out_len) return BCE_HIP_E_ARG;
+  if (nops > 0x7FFFFFFFull) { snprintf(c->err, sizeof c->err, "patch: 2^31 ops or more, a result of 2^31 bytes or more"); return BCE_HIP_E_ARG; }
+  if ((nops && !ops) || (nlits && !lits) || (cap && !out)) return BCE_HIP_E_ARG;
+  if (!(c->text_loaded && c->stage >= 1 && c->text.p && c->text.cap >= (size_t)c->n)) {
+    snprintf(c->err, sizeof c->err, "patch: no loaded input in this context");
+    return BCE_HIP_E_STATE;
+  }
+  *empty = nops == 0;
+  if (!*empty) return BCE_HIP_OK;
+  if (const char *why = bce::patch_list_bad(0, 0, 0, nlits)) { snprintf(c->err, sizeof c->err, "%s", why); return BCE_HIP_E_ARG; }
+  *out_len = 0;
+  return BCE_HIP_OK;
+}
+
+int bce_hip_patch(bce_hip_ctx *c, const bce_hip_op *ops, uint64_t nops, const uint8_t *lits, uint64_t nlits, uint8_t *out, uint64_t cap,
+                  uint64_t *out_len) {
+  bool empty = false;
+  BCE_TRY(patch_args(c, ops, nops, lits, nlits, out, cap, out_len, &empty));
+  if (empty) return BCE_HIP_OK;
+  return query_call(c, 3, [&]() -> int {
+    DevBuf &d_ops = c->qbuf[qb::par_ops], &d_lits = c->qbuf[qb::par_lits], &d_out = c->qbuf[qb::par_out];
+    BCE_TRY(stage(c, d_ops, ops, (size_t)nops * 8));
+    BCE_TRY(stage(c, d_lits, lits, (size_t)nlits));
+    // Unlike the device entry, validated and sized first: the staging of the result is as large as the result
+    uint64_t total = 0;
+    BCE_TRY(kd_patch(c, d_ops.as<uint32_t>(), (uint32_t)nops, d_lits.as<uint8_t>(), nlits, true, nullptr, 0, &total));
+    *out_len = total;
+    if (!out) return BCE_HIP_OK;
+    if (total > cap) { snprintf(c->err, sizeof c->err, "patch: %llu bytes, room for %llu", (unsigned long long)total, (unsigned long long)cap); return BCE_HIP_E_OVERFLOW; }
+    BCE_TRY(ensure(c, d_out, (size_t)total));
+    BCE_TRY(kd_patch(c, d_ops.as<uint32_t>(), (uint32_t)nops, d_lits.as<uint8_t>(), nlits, false, d_out.as<uint8_t>(), total, &total));
+    return copy_out(c, out, d_out, (size_t)total);
+  });
+}
+
+int bce_hip_patch_device(bce_hip_ctx *c, const void *d_ops, uint64_t nops, const void *d_lits, uint64_t nlits, void *d_out, uint64_t cap,
+                         uint64_t *out_len) {
+  bool empty = false;
+  BCE_TRY(patch_args(c, d_ops, nops, d_lits, nlits, d_out, cap, out_len, &empty));
+  if (empty) return BCE_HIP_OK;
+  return query_call(c, 3, [&] {
+    return kd_patch(c, static_cast<const uint32_t *>(d_ops), (uint32_t)nops, static_cast<const uint8_t *>(d_lits), nlits, !d_out,
+                    static_cast<uint8_t *>(d_out), cap, out_len);
+  });
+}
+
+}  // extern "C"

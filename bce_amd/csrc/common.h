@@ -130,6 +130,32 @@ inline void slot_free_host(FlushSlot &s, uint32_t *unmaps = nullptr) {
 
 struct RunEntry { uint64_t start; uint32_t count; uint32_t round; };  // symbols of (round, plane): [start, start+count)
 
+// The buffers of the index queries (bce_hip_ctx::qbuf[qb::name], kd_count / _locate / _match / _lcp / _parse.hip and api_index.hip):
+// one array, so that bce_hip_destroy releases them in one loop and a name added here needs nothing else.
+namespace qb {
+enum Id {
+  cnt_res,                                       // kd_count.hip: its flag word (a buffer of its own, as cmp_res)
+  cnt_pat, cnt_off, cnt_out,                     // bce_hip_count: the patterns, their offsets and the counts of a call with host buffers, staged (grow-only)
+  loc_res,                                       // kd_locate.hip: its flag word and scan total (a buffer of its own, as cnt_res)
+  loc_lo, loc_cnt, loc_drop, loc_start, loc_lin, loc_bsum,   // per pattern: the interval's first row, its rows, those across the text's end; the two CSR offset arrays; the scan's block sums
+  loc_key0, loc_key1, loc_val0, loc_val1,        // (position, pattern) of every row: both halves of the sorts' ping-pong
+  loc_pat, loc_off, loc_hits, loc_pos,           // bce_hip_locate: the arrays of a call with host buffers, staged (all grow-only)
+  mat_res,                                       // kd_match.hip: the coverage's result word (a buffer of its own, as loc_res)
+  mat_bsum,                                      // the coverage scan's block maxima and block counts
+  mat_qry, mat_len, mat_pos,                     // bce_hip_match / _coverage: the query of a call with a host buffer, the lengths and the positions, staged (all grow-only)
+  rep_res,                                       // kd_lcp.hip: its result words, up to 64 k-gram records or the longest repeat's three (a buffer of its own, as mat_res)
+  rep_bsum,                                      // the class and repeat reductions' per-block parts and maxima
+  rep_lcp,                                       // the LCP array of a call that does not bring device memory for it: n words (grow-only, never kept as a cache)
+  par_res,                                       // kd_parse.hip: the result words of the parse and of the patch (a buffer of its own, as mat_res)
+  par_exit, par_entry, par_flag,                 // the parse: every position's exit from its block (+ 1), the blocks' entries, the flag byte per position
+  par_bsum, par_bcnt,                            // the blocks' sums (parse: heads and literals packed; patch: lengths, literal lengths) and their counts / flag bits
+  par_hpre,                                      // per op head: the literal bytes up to it
+  par_off, par_loff,                             // the patch: every op's offset in the output and in the literal bytes
+  par_ops, par_lits, par_out,                    // bce_hip_parse / _patch with host buffers: the ops, the literal bytes and the result, staged (all grow-only)
+  count
+};
+}  // namespace qb
+
 }  // namespace bce
 
 struct bce_hip_ctx {
@@ -210,24 +236,7 @@ struct bce_hip_ctx {
   bce::DevBuf crc_tab;                           // kd_crc32.hip: the step tables of a launch of crc_tab_grid workgroups, its constants, its result word
   uint32_t crc_tab_grid = 0;                     // 0: no step tables uploaded
   bce::DevBuf cmp_res;                           // kd_compare.hip: its result word (a buffer of its own, as kd_crc32.hip's: no stage's scratch is touched)
-  bce::DevBuf cnt_res;                           // kd_count.hip: its flag word (a buffer of its own, as cmp_res)
-  bce::DevBuf cnt_pat, cnt_off, cnt_out;         // bce_hip_count: the patterns, their offsets and the counts of a call with host buffers, staged (grow-only)
-  bce::DevBuf loc_res;                           // kd_locate.hip: its flag word and scan total (a buffer of its own, as cnt_res)
-  bce::DevBuf loc_lo, loc_cnt, loc_drop, loc_start, loc_lin, loc_bsum;   // per pattern: the interval's first row, its rows, those across the text's end; the two CSR offset arrays; the scan's block sums
-  bce::DevBuf loc_key[2], loc_val[2];            // (position, pattern) of every row: both halves of the sorts' ping-pong
-  bce::DevBuf loc_pat, loc_off, loc_hits, loc_pos;   // bce_hip_locate: the arrays of a call with host buffers, staged (all grow-only)
-  bce::DevBuf mat_res;                           // kd_match.hip: the coverage's result word (a buffer of its own, as loc_res)
-  bce::DevBuf mat_bsum;                          // the coverage scan's block maxima and block counts
-  bce::DevBuf mat_qry, mat_len, mat_pos;         // bce_hip_match / _coverage: the query of a call with a host buffer, the lengths and the positions, staged (all grow-only)
-  bce::DevBuf rep_res;                           // kd_lcp.hip: its result words, up to 64 k-gram records or the longest repeat's three (a buffer of its own, as mat_res)
-  bce::DevBuf rep_bsum;                          // the class and repeat reductions' per-block parts and maxima
-  bce::DevBuf rep_lcp;                           // the LCP array of a call that does not bring device memory for it: n words (grow-only, never kept as a cache)
-  bce::DevBuf par_res;                           // kd_parse.hip: the result words of the parse and of the patch (a buffer of its own, as mat_res)
-  bce::DevBuf par_exit, par_entry, par_flag;     // the parse: every position's exit from its block (+ 1), the blocks' entries, the flag byte per position
-  bce::DevBuf par_bsum, par_bcnt;                // the blocks' sums (parse: heads and literals packed; patch: lengths, literal lengths) and their counts / flag bits
-  bce::DevBuf par_hpre;                          // per op head: the literal bytes up to it
-  bce::DevBuf par_off, par_loff;                 // the patch: every op's offset in the output and in the literal bytes
-  bce::DevBuf par_ops, par_lits, par_out;        // bce_hip_parse / _patch with host buffers: the ops, the literal bytes and the result, staged (all grow-only)
+  bce::DevBuf qbuf[bce::qb::count];              // the index queries' buffers, one per bce::qb name (above): each its own grow-only allocation
   bce::DevBuf hook[3];                           // test hooks bce_hip_sort_pairs_device / _wide_device: the second halves of the sorts' ping-pong
   bool crc_const_ready = false;                  // its launch-independent constants are uploaded
   bool text_loaded = false;                      // `text` holds the n bytes of the last bce_hip_load_* (bce_hip_input_crc32)

@@ -53,8 +53,8 @@ __global__ __launch_bounds__(CNT_T) void count_kernel(const Granule *__restrict_
 // kernel is through (the flag word's way back is the wait, as kd_compare's result word).  Offsets that decrease: BCE_HIP_E_ARG.
 int kd_count(bce_hip_ctx *c, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, uint64_t *d_out) {
   if (npat == 0) return BCE_HIP_OK;
-  BCE_TRY(ensure(c, c->cnt_res, 8));
-  uint32_t *d_bad = c->cnt_res.as<uint32_t>();
+  BCE_TRY(ensure(c, c->qbuf[qb::cnt_res], 8));
+  uint32_t *d_bad = c->qbuf[qb::cnt_res].as<uint32_t>();
   BCE_HIP_TRY(c, hipMemsetAsync(d_bad, 0, 8, c->stream));
   Zeros8 z;
   memcpy(z.v, c->zeros, sizeof z.v);

@@ -8,12 +8,12 @@
 //   lcp      one lane per row: two suffix-array words, then rot_lcp on the text.  Plain stores, no LDS, no atomics.
 //   classes  for one k: the maximal runs of rows [s, e) with lcp[r] >= k inside are the distinct cyclic k-grams, e - s = N(w).
 //            A running maximum of "r where lcp[r] < k, or r = 0" gives every row its class start; the last row of a class (the
-//            text's last row, or lcp[r + 1] < k) adds the class to every figure.  Block-wise in the manner of locate_scan_* /
-//            cover_*: maxima of 2048-element blocks, one workgroup that passes the carry from block to block, the blocks again
+//            text's last row, or lcp[r + 1] < k) adds the class to every figure.  Block-wise: maxima of 2048-element blocks,
+//            one workgroup that passes the carry from block to block (scan_util.h's carried pass), the blocks again
 //            with their carry, one workgroup that adds the blocks' figures into the record.  No atomics: every sum is a uint64_t
 //            sum of the same terms, every maximum has one winner.  A class may span any number of blocks.
 //   longest  block maxima of (lcp[r], ~r), then one workgroup, which also fetches sa[r - 1] and sa[r].
-// Everything written is the feature's own (c->rep_*) or the caller's output.  sa[sa_res] and the text are only read.
+// Everything written is the feature's own (qb::rep_* of c->qbuf) or the caller's output.  sa[sa_res] and the text are only read.
 #include "common.h"
 #include "bce_cost.h"
 #include "lcp_step.h"
@@ -38,45 +38,11 @@ __global__ __launch_bounds__(REP_T) void lcp_kernel(const uint8_t *__restrict__ 
   lcp[r] = r ? rot_lcp(text, n, sa[r - 1u], sa[r], max_len) : 0u;
 }
 
-// ---- block primitives ---------------------------------------------------------------------------------------------------------------
-// Exclusive max scan over the REP_T lanes (0 for lane 0); *total = the maximum of all.
-__device__ __forceinline__ uint32_t rep_excl_scan_max(uint32_t v, uint32_t *total) {
-  __shared__ uint32_t inc[REP_T];
-  inc[threadIdx.x] = block_incl_scan_max<REP_T>(v, total);
-  __syncthreads();
-  const uint32_t ex = threadIdx.x ? inc[threadIdx.x - 1] : 0u;
-  __syncthreads();
-  return ex;
-}
-
-// the maximum of v over the workgroup, in every lane
-__device__ __forceinline__ uint64_t rep_reduce_max64(uint64_t v) {
-  __shared__ uint64_t ws[REP_T / 64];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint64_t t = __shfl_xor(v, o);
-    v = v > t ? v : t;
-  }
-  if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = v;
-  __syncthreads();
-  uint64_t m = 0;
-#pragma unroll
-  for (int i = 0; i < REP_T / 64; ++i) m = m > ws[i] ? m : ws[i];
-  __syncthreads();
-  return m;
-}
-
-__device__ __forceinline__ uint64_t rep_reduce_sum64(uint64_t v) {
-  uint64_t tot;
-  (void)block_excl_scan_sum64<REP_T>(v, &tot);
-  return tot;
-}
-
 // ---- the classes of one k -----------------------------------------------------------------------------------------------------------
 // Lane t of a workgroup owns the elements base + t * REP_ITEMS + i, i < REP_ITEMS.
 __device__ __forceinline__ uint32_t class_index(uint32_t base, int i) { return base + threadIdx.x * REP_ITEMS + (uint32_t)i; }
 // w[i] = lcp[first + i], i < REP_ITEMS, as two 16-byte loads where all eight rows exist (first is a multiple of REP_ITEMS and the
-// array a device allocation of its own, c->rep_lcp: 32-byte aligned words); rows at or beyond n read as 0xFFFFFFFF.
+// array a device allocation of its own, c->qbuf[qb::rep_lcp]: 32-byte aligned words); rows at or beyond n read as 0xFFFFFFFF.
 __device__ __forceinline__ void load_rows(const uint32_t *__restrict__ lcp, uint32_t first, uint32_t n, uint32_t (&w)[REP_ITEMS]) {
   if (n - first >= (uint32_t)REP_ITEMS && first < n) {
     const uint4 a = *reinterpret_cast<const uint4 *>(lcp + first), b = *reinterpret_cast<const uint4 *>(lcp + first + 4);
@@ -102,15 +68,7 @@ __global__ __launch_bounds__(REP_T) void class_max_kernel(const uint32_t *__rest
 
 // one workgroup: bmax[0, nb) -> for every block the maximum of the blocks in front of it, in place
 __global__ __launch_bounds__(REP_T) void class_top_kernel(uint32_t *__restrict__ bmax, uint32_t nb) {
-  uint32_t carry = 0;
-  for (uint32_t at = 0; at < nb; at += REP_T) {
-    const uint32_t b = at + threadIdx.x;
-    const uint32_t v = b < nb ? bmax[b] : 0u;
-    uint32_t tot;
-    const uint32_t ex = rep_excl_scan_max(v, &tot);
-    if (b < nb) bmax[b] = carry > ex ? carry : ex;
-    carry = carry > tot ? carry : tot;
-  }
+  block_carried_scan_max<REP_T, false>(bmax, nb);
 }
 
 __global__ __launch_bounds__(REP_T) void class_fill_kernel(const uint32_t *__restrict__ lcp, uint32_t n, uint32_t k,
@@ -125,7 +83,7 @@ __global__ __launch_bounds__(REP_T) void class_fill_kernel(const uint32_t *__res
 #pragma unroll
   for (int i = 0; i < REP_ITEMS; ++i) { v[i] = class_elem(w[i], class_index(base, i), k); m = m > v[i] ? m : v[i]; }
   uint32_t tot;
-  const uint32_t ex = rep_excl_scan_max(m, &tot), front = bmax[blockIdx.x];   // (its barriers also publish tab)
+  const uint32_t ex = block_excl_scan_max<REP_T>(m, &tot), front = bmax[blockIdx.x];   // (its barriers also publish tab)
   uint32_t start = ex > front ? ex : front, distinct = 0, once = 0;
   uint64_t nlogn = 0, top = 0;
 #pragma unroll
@@ -144,8 +102,8 @@ __global__ __launch_bounds__(REP_T) void class_fill_kernel(const uint32_t *__res
   }
   distinct = block_reduce_sum<REP_T>(distinct);
   once = block_reduce_sum<REP_T>(once);
-  nlogn = rep_reduce_sum64(nlogn);
-  top = rep_reduce_max64(top);
+  nlogn = block_reduce_sum64<REP_T>(nlogn);
+  top = block_reduce_max64<REP_T>(top);
   if (threadIdx.x == 0) part[blockIdx.x] = ClassPart{distinct, once, nlogn, top};
 }
 
@@ -158,10 +116,10 @@ __global__ __launch_bounds__(REP_T) void class_sum_kernel(const ClassPart *__res
     distinct += p.distinct; once += p.once; nlogn += p.nlogn;
     top = top > p.top ? top : p.top;
   }
-  distinct = rep_reduce_sum64(distinct);
-  once = rep_reduce_sum64(once);
-  nlogn = rep_reduce_sum64(nlogn);
-  top = rep_reduce_max64(top);
+  distinct = block_reduce_sum64<REP_T>(distinct);
+  once = block_reduce_sum64<REP_T>(once);
+  nlogn = block_reduce_sum64<REP_T>(nlogn);
+  top = block_reduce_max64<REP_T>(top);
   if (threadIdx.x == 0) {
     const uint32_t start = ~(uint32_t)top;
     bce_hip_kgram g;
@@ -184,7 +142,7 @@ __global__ __launch_bounds__(REP_T) void repeat_max_kernel(const uint32_t *__res
     const uint64_t key = r < n ? ((uint64_t)w[i] << 32) | (uint32_t)~r : 0u;
     m = m > key ? m : key;
   }
-  m = rep_reduce_max64(m);
+  m = block_reduce_max64<REP_T>(m);
   if (threadIdx.x == 0) bkey[blockIdx.x] = m;
 }
 
@@ -194,7 +152,7 @@ __global__ __launch_bounds__(REP_T) void repeat_top_kernel(const uint64_t *__res
                                                            uint32_t *__restrict__ out) {
   uint64_t m = 0;
   for (uint32_t b = threadIdx.x; b < nb; b += REP_T) m = m > bkey[b] ? m : bkey[b];
-  m = rep_reduce_max64(m);
+  m = block_reduce_max64<REP_T>(m);
   if (threadIdx.x == 0) {
     const uint32_t r = ~(uint32_t)m;
     out[0] = (uint32_t)(m >> 32);
@@ -220,11 +178,11 @@ int kd_lcp(bce_hip_ctx *c, const uint32_t *sa, uint32_t max_len, uint32_t *d_lcp
 // queued on the context's stream; the records' way back is the wait.
 int kd_kgrams(bce_hip_ctx *c, const uint32_t *sa, const uint32_t *d_lcp, uint32_t n, const uint32_t *ks, uint32_t nk, bce_hip_kgram *out) {
   const uint32_t nb = rep_blocks(n);
-  BCE_TRY(ensure(c, c->rep_res, 64 * sizeof(bce_hip_kgram)));
-  BCE_TRY(ensure(c, c->rep_bsum, (size_t)nb * (sizeof(ClassPart) + 4)));   // the blocks' parts, then their maxima
-  ClassPart *part = c->rep_bsum.as<ClassPart>();
+  BCE_TRY(ensure(c, c->qbuf[qb::rep_res], 64 * sizeof(bce_hip_kgram)));
+  BCE_TRY(ensure(c, c->qbuf[qb::rep_bsum], (size_t)nb * (sizeof(ClassPart) + 4)));   // the blocks' parts, then their maxima
+  ClassPart *part = c->qbuf[qb::rep_bsum].as<ClassPart>();
   uint32_t *bmax = reinterpret_cast<uint32_t *>(part + nb);
-  bce_hip_kgram *d_out = c->rep_res.as<bce_hip_kgram>();
+  bce_hip_kgram *d_out = c->qbuf[qb::rep_res].as<bce_hip_kgram>();
   for (uint32_t i = 0; i < nk; ++i) {
     hipLaunchKernelGGL(class_max_kernel, dim3(nb), dim3(REP_T), 0, c->stream, d_lcp, n, ks[i], bmax);
     hipLaunchKernelGGL(class_top_kernel, dim3(1), dim3(REP_T), 0, c->stream, bmax, nb);
@@ -240,10 +198,10 @@ int kd_kgrams(bce_hip_ctx *c, const uint32_t *sa, const uint32_t *d_lcp, uint32_
 // res[0] = the largest d_lcp[r], r < n, res[1], res[2] = sa[r - 1], sa[r] of the lowest such r (0xFFFFFFFF twice where the largest is 0).
 int kd_longest_repeat(bce_hip_ctx *c, const uint32_t *sa, const uint32_t *d_lcp, uint32_t n, uint32_t res[3]) {
   const uint32_t nb = rep_blocks(n);
-  BCE_TRY(ensure(c, c->rep_res, 64 * sizeof(bce_hip_kgram)));
-  BCE_TRY(ensure(c, c->rep_bsum, (size_t)nb * 8));
-  uint64_t *bkey = c->rep_bsum.as<uint64_t>();
-  uint32_t *d_out = c->rep_res.as<uint32_t>();
+  BCE_TRY(ensure(c, c->qbuf[qb::rep_res], 64 * sizeof(bce_hip_kgram)));
+  BCE_TRY(ensure(c, c->qbuf[qb::rep_bsum], (size_t)nb * 8));
+  uint64_t *bkey = c->qbuf[qb::rep_bsum].as<uint64_t>();
+  uint32_t *d_out = c->qbuf[qb::rep_res].as<uint32_t>();
   hipLaunchKernelGGL(repeat_max_kernel, dim3(nb), dim3(REP_T), 0, c->stream, d_lcp, n, bkey);
   hipLaunchKernelGGL(repeat_top_kernel, dim3(1), dim3(REP_T), 0, c->stream, bkey, nb, sa, d_out);
   BCE_HIP_TRY(c, hipGetLastError());

@@ -7,7 +7,7 @@
 //   range    one lane per pattern, the search of count_kernel (fm_range: both granules of a level issued together, the next
 //            byte loaded off the chain); stores lo and hi - lo.
 //   scan     exclusive u64 scan of the per-pattern row counts: three launches (sums of 2048-element blocks, one workgroup over
-//            those sums, the blocks again).  Its last word is the batch's row total, read back through a word of the locate's own.
+//            those sums -- scan_util.h's carried pass, as in kd_match / kd_lcp / kd_parse.hip -- the blocks again).  Its last word is the batch's row total, read back through a word of the locate's own.
 //   gather   one lane per row: its pattern by binary search in the starts (fm_row_pattern), position sa[lo_p + k] -- the rows of
 //            one interval are neighbouring words.  Stores (position, pattern id); or, asked to, only counts per pattern the rows
 //            whose match runs across the end of the text (fm_linear_hit): at most m - 1 per pattern, so the atomics are few.
@@ -15,7 +15,7 @@
 //            them pattern p's rows stand where they stood, ascending.
 //   compact  linear mode: the rows that run across the end have the largest positions of their pattern, so the kept ones are
 //            the first of its sorted segment: one lane per kept row copies it to its place.
-// Everything written is the locate's own (c->loc_*) or the caller's two outputs; the sort's histograms are c->rs_hist on the
+// Everything written is the locate's own (qb::loc_* of c->qbuf) or the caller's two outputs; the sort's histograms are c->rs_hist on the
 // context's stream, as the sort hooks use them.  Row indices and totals are u64; a batch of more than 2^31 - 1 rows is sized
 // but not gathered (the sort's length is a u32, positions are below 2^31 anyway).
 #include "common.h"
@@ -65,24 +65,15 @@ __global__ __launch_bounds__(LOC_T) void locate_scan_sums_kernel(const uint32_t 
   uint64_t s = 0;
 #pragma unroll
   for (int q = 0; q < LOC_ITEMS; ++q) s += scan_elem(cnt, drop, base + q, npat);
-  uint64_t tot;
-  (void)block_excl_scan_sum64<LOC_T>(s, &tot);
+  const uint64_t tot = block_reduce_sum64<LOC_T>(s);
   if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 
 // one workgroup: bsum[0, nb) -> its exclusive scan, in place; the grand total -> *total and start[npat]
 __global__ __launch_bounds__(LOC_T) void locate_scan_top_kernel(uint64_t *__restrict__ bsum, uint32_t nb, uint64_t *__restrict__ start,
                                                                 uint32_t npat, uint64_t *__restrict__ total) {
-  uint64_t carry = 0;
-  for (uint32_t at = 0; at < nb; at += LOC_T) {
-    const uint32_t i = at + threadIdx.x;
-    const uint64_t v = i < nb ? bsum[i] : 0ull;
-    uint64_t tot;
-    const uint64_t ex = block_excl_scan_sum64<LOC_T>(v, &tot);
-    if (i < nb) bsum[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) { start[npat] = carry; *total = carry; }
+  const uint64_t sum = block_carried_scan_sum64<LOC_T>(bsum, nb);
+  if (threadIdx.x == 0) { start[npat] = sum; *total = sum; }
 }
 
 __global__ __launch_bounds__(LOC_T) void locate_scan_fill_kernel(const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ drop,
@@ -135,9 +126,9 @@ uint32_t stride_grid(uint64_t items) {
 // start[0, npat] = exclusive scan of cnt[i] - drop[i] (drop may be null); *total = its last word
 int locate_scan(bce_hip_ctx *c, const uint32_t *cnt, const uint32_t *drop, uint32_t npat, uint64_t *start, uint64_t *total) {
   const uint32_t nb = (uint32_t)(((uint64_t)npat + LOC_BLOCK - 1) / LOC_BLOCK);
-  BCE_TRY(ensure(c, c->loc_bsum, (size_t)nb * 8));
-  uint64_t *bsum = c->loc_bsum.as<uint64_t>();
-  uint64_t *d_total = c->loc_res.as<uint64_t>() + 1;
+  BCE_TRY(ensure(c, c->qbuf[qb::loc_bsum], (size_t)nb * 8));
+  uint64_t *bsum = c->qbuf[qb::loc_bsum].as<uint64_t>();
+  uint64_t *d_total = c->qbuf[qb::loc_res].as<uint64_t>() + 1;
   hipLaunchKernelGGL(locate_scan_sums_kernel, dim3(nb), dim3(LOC_T), 0, c->stream, cnt, drop, npat, bsum);
   hipLaunchKernelGGL(locate_scan_top_kernel, dim3(1), dim3(LOC_T), 0, c->stream, bsum, nb, start, npat, d_total);
   hipLaunchKernelGGL(locate_scan_fill_kernel, dim3(nb), dim3(LOC_T), 0, c->stream, cnt, drop, npat, bsum, start);
@@ -153,17 +144,17 @@ int locate_scan(bce_hip_ctx *c, const uint32_t *cnt, const uint32_t *drop, uint3
 // d_pat[d_off[p], d_off[p + 1]), p < npat, in the text of the context's planes and suffix array (sa: K1's, or null for a text of one
 // byte), *total their last word -- exact in both modes -- and *rows the batch's cyclic rows.  All arrays: device memory of the
 // context's device.  Queued on the context's stream; complete on return.  Offsets that decrease: BCE_HIP_E_ARG; more than
-// 2^31 - 1 rows: BCE_HIP_E_OVERFLOW, with d_hits and *total written.  Leaves what kd_locate_fill needs in c->loc_*.
+// 2^31 - 1 rows: BCE_HIP_E_OVERFLOW, with d_hits and *total written.  Leaves what kd_locate_fill needs in the loc_* buffers.
 int kd_locate_size(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, bool linear,
                    uint64_t *d_hits, uint64_t *rows, uint64_t *total) {
   const size_t words = (size_t)npat * 4, starts = ((size_t)npat + 1) * 8;
-  BCE_TRY(ensure(c, c->loc_res, 16));                                // [0] the flag word, [1] a scan's total
-  BCE_TRY(ensure(c, c->loc_lo, words));
-  BCE_TRY(ensure(c, c->loc_cnt, words));
-  BCE_TRY(ensure(c, c->loc_start, starts));
-  uint32_t *d_bad = c->loc_res.as<uint32_t>();
-  uint32_t *lo = c->loc_lo.as<uint32_t>(), *cnt = c->loc_cnt.as<uint32_t>();
-  uint64_t *cyc = c->loc_start.as<uint64_t>();
+  BCE_TRY(ensure(c, c->qbuf[qb::loc_res], 16));                                // [0] the flag word, [1] a scan's total
+  BCE_TRY(ensure(c, c->qbuf[qb::loc_lo], words));
+  BCE_TRY(ensure(c, c->qbuf[qb::loc_cnt], words));
+  BCE_TRY(ensure(c, c->qbuf[qb::loc_start], starts));
+  uint32_t *d_bad = c->qbuf[qb::loc_res].as<uint32_t>();
+  uint32_t *lo = c->qbuf[qb::loc_lo].as<uint32_t>(), *cnt = c->qbuf[qb::loc_cnt].as<uint32_t>();
+  uint64_t *cyc = c->qbuf[qb::loc_start].as<uint64_t>();
   BCE_HIP_TRY(c, hipMemsetAsync(d_bad, 0, 16, c->stream));
   Zeros8 z;
   memcpy(z.v, c->zeros, sizeof z.v);
@@ -178,17 +169,17 @@ int kd_locate_size(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, con
   const uint64_t *hits = cyc;
   *total = *rows;
   if (linear) {                                                      // the exact linear offsets, before anything is gathered
-    BCE_TRY(ensure(c, c->loc_drop, words));
-    BCE_TRY(ensure(c, c->loc_lin, starts));
-    uint32_t *drop = c->loc_drop.as<uint32_t>();
+    BCE_TRY(ensure(c, c->qbuf[qb::loc_drop], words));
+    BCE_TRY(ensure(c, c->qbuf[qb::loc_lin], starts));
+    uint32_t *drop = c->qbuf[qb::loc_drop].as<uint32_t>();
     BCE_HIP_TRY(c, hipMemsetAsync(drop, 0, words, c->stream));
     if (*rows) {
       hipLaunchKernelGGL(locate_gather_kernel, dim3(stride_grid(*rows)), dim3(LOC_T), 0, c->stream, sa, c->n, d_off, lo, cyc, npat, *rows,
                          (uint32_t *)nullptr, (uint32_t *)nullptr, drop);
       BCE_HIP_TRY(c, hipGetLastError());
     }
-    hits = c->loc_lin.as<uint64_t>();
-    BCE_TRY(locate_scan(c, cnt, drop, npat, c->loc_lin.as<uint64_t>(), total));
+    hits = c->qbuf[qb::loc_lin].as<uint64_t>();
+    BCE_TRY(locate_scan(c, cnt, drop, npat, c->qbuf[qb::loc_lin].as<uint64_t>(), total));
   }
   BCE_HIP_TRY(c, hipMemcpyAsync(d_hits, hits, starts, hipMemcpyDeviceToDevice, c->stream));
   BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -206,11 +197,11 @@ int kd_locate_fill(bce_hip_ctx *c, const uint32_t *sa, const uint64_t *d_off, ui
   if (total == 0) return BCE_HIP_OK;
   const uint32_t nrows = (uint32_t)rows;
   const size_t rbytes = (size_t)nrows * 4;
-  for (DevBuf *b : {&c->loc_key[0], &c->loc_key[1], &c->loc_val[0], &c->loc_val[1]}) BCE_TRY(ensure(c, *b, rbytes));
-  uint32_t *key[2] = {c->loc_key[0].as<uint32_t>(), c->loc_key[1].as<uint32_t>()};
-  uint32_t *val[2] = {c->loc_val[0].as<uint32_t>(), c->loc_val[1].as<uint32_t>()};
-  const uint64_t *cyc = c->loc_start.as<uint64_t>();
-  hipLaunchKernelGGL(locate_gather_kernel, dim3(stride_grid(rows)), dim3(LOC_T), 0, c->stream, sa, c->n, d_off, c->loc_lo.as<uint32_t>(), cyc,
+  for (DevBuf *b : {&c->qbuf[qb::loc_key0], &c->qbuf[qb::loc_key1], &c->qbuf[qb::loc_val0], &c->qbuf[qb::loc_val1]}) BCE_TRY(ensure(c, *b, rbytes));
+  uint32_t *key[2] = {c->qbuf[qb::loc_key0].as<uint32_t>(), c->qbuf[qb::loc_key1].as<uint32_t>()};
+  uint32_t *val[2] = {c->qbuf[qb::loc_val0].as<uint32_t>(), c->qbuf[qb::loc_val1].as<uint32_t>()};
+  const uint64_t *cyc = c->qbuf[qb::loc_start].as<uint64_t>();
+  hipLaunchKernelGGL(locate_gather_kernel, dim3(stride_grid(rows)), dim3(LOC_T), 0, c->stream, sa, c->n, d_off, c->qbuf[qb::loc_lo].as<uint32_t>(), cyc,
                      npat, rows, key[0], val[0], (uint32_t *)nullptr);
   BCE_HIP_TRY(c, hipGetLastError());
   int res = 0;
@@ -223,7 +214,7 @@ int kd_locate_fill(bce_hip_ctx *c, const uint32_t *sa, const uint64_t *d_off, ui
     sorted = v2[r2];
   }
   if (linear) {
-    hipLaunchKernelGGL(locate_compact_kernel, dim3(stride_grid(total)), dim3(LOC_T), 0, c->stream, sorted, cyc, c->loc_lin.as<uint64_t>(), npat,
+    hipLaunchKernelGGL(locate_compact_kernel, dim3(stride_grid(total)), dim3(LOC_T), 0, c->stream, sorted, cyc, c->qbuf[qb::loc_lin].as<uint64_t>(), npat,
                        total, d_pos);
     BCE_HIP_TRY(c, hipGetLastError());
   } else {

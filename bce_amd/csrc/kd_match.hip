@@ -11,11 +11,11 @@
 //             Stores len[i] and, asked to, pos[i] = sa[row] (0xFFFFFFFF where len[i] == 0): plain stores, no LDS, no atomics.
 //   coverage  the bytes of the query that lie in a match of min_len bytes or more: j is covered when some i >= j has
 //             len[i] >= min_len and i - len[i] + 1 <= j.  A reverse running minimum of s'[i] = i - len[i] + 1 (+inf where the
-//             match is too short) over i >= j, then the j with minimum <= j are counted.  Block-wise, in the style of
-//             locate_scan_*: maxima of 2048-element blocks (the minimum of s' is the maximum of ~s', and 0 stands for +inf: s' is
-//             below 2^31), one workgroup over those maxima from the last block to the first, the blocks again with their carry,
+//             match is too short) over i >= j, then the j with minimum <= j are counted.  Block-wise: maxima of 2048-element
+//             blocks (the minimum of s' is the maximum of ~s', and 0 stands for +inf: s' is below 2^31), one workgroup over
+//             those maxima from the last block to the first (scan_util.h's carried pass), the blocks again with their carry,
 //             one workgroup that adds the blocks' counts into the result word.  No atomics: the count is the same sum every time.
-// Everything written is the match's own (c->mat_*) or the caller's two outputs.  The planes and sa[sa_res] are only read.
+// Everything written is the match's own (qb::mat_* of c->qbuf) or the caller's two outputs.  The planes and sa[sa_res] are only read.
 #include "common.h"
 #include "fm_step.h"
 #include "scan_util.h"
@@ -64,16 +64,6 @@ __device__ __forceinline__ uint32_t cover_elem(const uint32_t *len, uint32_t e, 
 // element to its first, so that a forward scan over the lanes is a running maximum over the elements behind.
 __device__ __forceinline__ uint32_t cover_index(uint32_t base, int k) { return base + (MAT_BLOCK - 1u) - (threadIdx.x * MAT_ITEMS + (uint32_t)k); }
 
-// Exclusive max scan over the MAT_T lanes (0 for lane 0); *total = the maximum of all.
-__device__ __forceinline__ uint32_t block_excl_scan_max(uint32_t v, uint32_t *total) {
-  __shared__ uint32_t inc[MAT_T];
-  inc[threadIdx.x] = block_incl_scan_max<MAT_T>(v, total);
-  __syncthreads();
-  const uint32_t ex = threadIdx.x ? inc[threadIdx.x - 1] : 0u;
-  __syncthreads();
-  return ex;
-}
-
 __global__ __launch_bounds__(MAT_T) void cover_max_kernel(const uint32_t *__restrict__ len, uint32_t q, uint32_t min_len,
                                                           uint32_t *__restrict__ bmax) {
   const uint32_t base = blockIdx.x * MAT_BLOCK;
@@ -86,15 +76,7 @@ __global__ __launch_bounds__(MAT_T) void cover_max_kernel(const uint32_t *__rest
 
 // one workgroup: bmax[0, nb) -> for every block the maximum of the blocks behind it, in place
 __global__ __launch_bounds__(MAT_T) void cover_top_kernel(uint32_t *__restrict__ bmax, uint32_t nb) {
-  uint32_t carry = 0;
-  for (uint32_t at = 0; at < nb; at += MAT_T) {
-    const uint32_t r = at + threadIdx.x;                              // blocks from the last to the first
-    const uint32_t v = r < nb ? bmax[nb - 1u - r] : 0u;
-    uint32_t tot;
-    const uint32_t ex = block_excl_scan_max(v, &tot);
-    if (r < nb) bmax[nb - 1u - r] = carry > ex ? carry : ex;
-    carry = carry > tot ? carry : tot;
-  }
+  block_carried_scan_max<MAT_T, true>(bmax, nb);                      // blocks from the last to the first
 }
 
 __global__ __launch_bounds__(MAT_T) void cover_fill_kernel(const uint32_t *__restrict__ len, uint32_t q, uint32_t min_len,
@@ -104,7 +86,7 @@ __global__ __launch_bounds__(MAT_T) void cover_fill_kernel(const uint32_t *__res
 #pragma unroll
   for (int k = 0; k < MAT_ITEMS; ++k) { v[k] = cover_elem(len, cover_index(base, k), q, min_len); m = m > v[k] ? m : v[k]; }
   uint32_t tot;
-  const uint32_t ex = block_excl_scan_max(m, &tot), behind = bmax[blockIdx.x];
+  const uint32_t ex = block_excl_scan_max<MAT_T>(m, &tot), behind = bmax[blockIdx.x];
   uint32_t run = ex > behind ? ex : behind, covered = 0;
 #pragma unroll
   for (int k = 0; k < MAT_ITEMS; ++k) {
@@ -120,9 +102,8 @@ __global__ __launch_bounds__(MAT_T) void cover_fill_kernel(const uint32_t *__res
 __global__ __launch_bounds__(MAT_T) void cover_sum_kernel(const uint32_t *__restrict__ bcnt, uint32_t nb, uint64_t *__restrict__ total) {
   uint64_t s = 0;
   for (uint32_t b = threadIdx.x; b < nb; b += MAT_T) s += bcnt[b];
-  uint64_t tot;
-  (void)block_excl_scan_sum64<MAT_T>(s, &tot);
-  if (threadIdx.x == 0) *total = tot;
+  s = block_reduce_sum64<MAT_T>(s);
+  if (threadIdx.x == 0) *total = s;
 }
 
 }  // namespace
@@ -153,10 +134,10 @@ int kd_coverage(bce_hip_ctx *c, const uint32_t *d_len, uint32_t q, uint32_t min_
   *covered = 0;
   if (q == 0) return BCE_HIP_OK;
   const uint32_t nb = (uint32_t)(((uint64_t)q + MAT_BLOCK - 1) / MAT_BLOCK);
-  BCE_TRY(ensure(c, c->mat_res, 8));
-  BCE_TRY(ensure(c, c->mat_bsum, (size_t)nb * 8));                    // the blocks' maxima, then their counts
-  uint32_t *bmax = c->mat_bsum.as<uint32_t>(), *bcnt = bmax + nb;
-  uint64_t *d_total = c->mat_res.as<uint64_t>();
+  BCE_TRY(ensure(c, c->qbuf[qb::mat_res], 8));
+  BCE_TRY(ensure(c, c->qbuf[qb::mat_bsum], (size_t)nb * 8));                    // the blocks' maxima, then their counts
+  uint32_t *bmax = c->qbuf[qb::mat_bsum].as<uint32_t>(), *bcnt = bmax + nb;
+  uint64_t *d_total = c->qbuf[qb::mat_res].as<uint64_t>();
   hipLaunchKernelGGL(cover_max_kernel, dim3(nb), dim3(MAT_T), 0, c->stream, d_len, q, min_len, bmax);
   hipLaunchKernelGGL(cover_top_kernel, dim3(1), dim3(MAT_T), 0, c->stream, bmax, nb);
   hipLaunchKernelGGL(cover_fill_kernel, dim3(nb), dim3(MAT_T), 0, c->stream, d_len, q, min_len, bmax, bcnt);

@@ -12,16 +12,16 @@
 //   mark    one workgroup per block: one lane walks the block's hops in LDS from the entry to the base (at most 2048 steps, the
 //           blocks side by side) and sets a flag byte per node; the block's 2048 flag bytes leave as one row, zeros where no node is.
 //   count   per block: the op heads and the literal nodes, packed into one u64 (heads in the high word: both stay below 2^31), and
-//           the copy ends.  top: one workgroup scans the blocks' sums, 256 at a time.  emit: the blocks again, every head writes
-//           its op at its scanned place and every literal node its byte.  A literal run may span any number of blocks, so its
-//           length is not walked: every head leaves the literal count up to itself, and `runs` takes the difference of two
-//           neighbouring heads.
+//           the copy ends.  top: one workgroup scans the blocks' sums, 256 at a time (scan_util.h's carried pass).  emit: the
+//           blocks again, every head writes its op at its scanned place and every literal node its byte.  A literal run may span
+//           any number of blocks, so its length is not walked: every head leaves the literal count up to itself, and `runs` takes
+//           the difference of two neighbouring heads.
 // The patch.  check: per op the rules of parse_step.h, per block the sums of the lengths and of the literal lengths.  top: their
 // scan, the flag bits together.  The host reads three words and refuses before anything is copied.  fill: every op's offset in
 // the output and in the literal bytes.  copy: one lane per 16 bytes of OUTPUT (aligned as the output's address is), a workgroup
 // per 16 KB: it finds the first and last op of its tile by binary search, each lane its own op between them; sixteen bytes that
 // lie in one op move as one load of any alignment and one aligned store, the rest byte by byte.
-// No atomics: every sum is taken in a fixed order.  Everything written is the feature's own (c->par_*) or the caller's outputs;
+// No atomics: every sum is taken in a fixed order.  Everything written is the feature's own (qb::par_* of c->qbuf) or the caller's outputs;
 // the text, the lengths and the positions are only read.
 #include "common.h"
 #include "parse_step.h"
@@ -139,8 +139,7 @@ __global__ __launch_bounds__(PAR_T) void parse_count_kernel(const uint8_t *__res
   load_flags(flag, blockIdx.x * PAR_BLOCK, rows_bytes, f);
   uint32_t cop;
   const uint64_t s = count_flags(f, &cop);
-  uint64_t tot;
-  (void)block_excl_scan_sum64<PAR_T>(s, &tot);
+  const uint64_t tot = block_reduce_sum64<PAR_T>(s);
   cop = block_reduce_sum<PAR_T>(cop);
   if (threadIdx.x == 0) { bsum[blockIdx.x] = tot; bcop[blockIdx.x] = cop; }
 }
@@ -148,19 +147,11 @@ __global__ __launch_bounds__(PAR_T) void parse_count_kernel(const uint8_t *__res
 // one workgroup: bsum[0, nb) -> its exclusive scan, in place; res[0] = heads << 32 | literal nodes of the query, res[1] = its copies
 __global__ __launch_bounds__(PAR_T) void parse_top_kernel(uint64_t *__restrict__ bsum, const uint32_t *__restrict__ bcop, uint32_t nb,
                                                           uint64_t *__restrict__ res) {
-  uint64_t carry = 0, cop = 0;
-  for (uint32_t at = 0; at < nb; at += PAR_T) {
-    const uint32_t i = at + threadIdx.x;
-    const uint64_t v = i < nb ? bsum[i] : 0ull;
-    cop += i < nb ? bcop[i] : 0u;
-    uint64_t tot;
-    const uint64_t ex = block_excl_scan_sum64<PAR_T>(v, &tot);
-    if (i < nb) bsum[i] = carry + ex;
-    carry += tot;
-  }
-  uint64_t copies;
-  (void)block_excl_scan_sum64<PAR_T>(cop, &copies);
-  if (threadIdx.x == 0) { res[0] = carry; res[1] = copies; }
+  const uint64_t sum = block_carried_scan_sum64<PAR_T>(bsum, nb);
+  uint64_t cop = 0;
+  for (uint32_t i = threadIdx.x; i < nb; i += PAR_T) cop += bcop[i];
+  cop = block_reduce_sum64<PAR_T>(cop);
+  if (threadIdx.x == 0) { res[0] = sum; res[1] = cop; }
 }
 
 // ops: nops pairs of words (len, src); a literal head leaves its length to parse_runs_kernel and its literal count in hpre
@@ -220,9 +211,7 @@ __global__ __launch_bounds__(PAR_T) void patch_check_kernel(const uint32_t *__re
     sl += olen[j];
     st += patch_lit_len(olen[j], osrc[j]);
   }
-  uint64_t tl, tt;
-  (void)block_excl_scan_sum64<PAR_T>(sl, &tl);
-  (void)block_excl_scan_sum64<PAR_T>(st, &tt);
+  const uint64_t tl = block_reduce_sum64<PAR_T>(sl), tt = block_reduce_sum64<PAR_T>(st);
   bad = block_reduce_sum<PAR_T>(bad);                                 // (at most 2048 in either half)
   if (threadIdx.x == 0) {
     blen[blockIdx.x] = tl;
@@ -234,19 +223,12 @@ __global__ __launch_bounds__(PAR_T) void patch_check_kernel(const uint32_t *__re
 // one workgroup: both sums -> their exclusive scans, in place; res[0] = the output's bytes, res[1] = the literal bytes, res[2] = the flag bits
 __global__ __launch_bounds__(PAR_T) void patch_top_kernel(uint64_t *__restrict__ blen, uint64_t *__restrict__ blit, const uint32_t *__restrict__ bbad,
                                                           uint32_t nb, uint64_t *__restrict__ res) {
-  uint64_t cl = 0, ct = 0;
+  const uint64_t cl = block_carried_scan_sum64<PAR_T>(blen, nb), ct = block_carried_scan_sum64<PAR_T>(blit, nb);
   uint32_t zero = 0, range = 0;
-  for (uint32_t at = 0; at < nb; at += PAR_T) {
-    const uint32_t i = at + threadIdx.x;
-    const uint64_t vl = i < nb ? blen[i] : 0ull, vt = i < nb ? blit[i] : 0ull;
-    const uint32_t b = i < nb ? bbad[i] : 0u;
+  for (uint32_t i = threadIdx.x; i < nb; i += PAR_T) {
+    const uint32_t b = bbad[i];
     zero |= b & PATCH_BAD_ZERO;
     range |= b & PATCH_BAD_RANGE;
-    uint64_t tl, tt;
-    const uint64_t el = block_excl_scan_sum64<PAR_T>(vl, &tl), et = block_excl_scan_sum64<PAR_T>(vt, &tt);
-    if (i < nb) { blen[i] = cl + el; blit[i] = ct + et; }
-    cl += tl;
-    ct += tt;
   }
   zero = block_reduce_max<PAR_T>(zero);
   range = block_reduce_max<PAR_T>(range);
@@ -334,15 +316,15 @@ int kd_parse(bce_hip_ctx *c, const uint32_t *d_len, const uint32_t *d_pos, const
              uint32_t *d_ops, uint64_t ops_cap, uint8_t *d_lits, uint64_t lits_cap, bce_hip_parse_info *info) {
   const uint32_t nb = (uint32_t)(((uint64_t)q + PAR_BLOCK - 1) / PAR_BLOCK);
   const uint64_t rows_bytes = (uint64_t)nb * PAR_BLOCK;
-  BCE_TRY(ensure(c, c->par_res, 32));
-  BCE_TRY(ensure(c, c->par_exit, (size_t)q * 4));
-  BCE_TRY(ensure(c, c->par_entry, (size_t)nb * 4));
-  BCE_TRY(ensure(c, c->par_flag, (size_t)rows_bytes));
-  BCE_TRY(ensure(c, c->par_bsum, (size_t)nb * 8));
-  BCE_TRY(ensure(c, c->par_bcnt, (size_t)nb * 4));
-  uint32_t *exit1 = c->par_exit.as<uint32_t>(), *entry = c->par_entry.as<uint32_t>(), *bcop = c->par_bcnt.as<uint32_t>();
-  uint8_t *flag = c->par_flag.as<uint8_t>();
-  uint64_t *bsum = c->par_bsum.as<uint64_t>(), *d_res = c->par_res.as<uint64_t>();
+  BCE_TRY(ensure(c, c->qbuf[qb::par_res], 32));
+  BCE_TRY(ensure(c, c->qbuf[qb::par_exit], (size_t)q * 4));
+  BCE_TRY(ensure(c, c->qbuf[qb::par_entry], (size_t)nb * 4));
+  BCE_TRY(ensure(c, c->qbuf[qb::par_flag], (size_t)rows_bytes));
+  BCE_TRY(ensure(c, c->qbuf[qb::par_bsum], (size_t)nb * 8));
+  BCE_TRY(ensure(c, c->qbuf[qb::par_bcnt], (size_t)nb * 4));
+  uint32_t *exit1 = c->qbuf[qb::par_exit].as<uint32_t>(), *entry = c->qbuf[qb::par_entry].as<uint32_t>(), *bcop = c->qbuf[qb::par_bcnt].as<uint32_t>();
+  uint8_t *flag = c->qbuf[qb::par_flag].as<uint8_t>();
+  uint64_t *bsum = c->qbuf[qb::par_bsum].as<uint64_t>(), *d_res = c->qbuf[qb::par_res].as<uint64_t>();
   BCE_HIP_TRY(c, hipMemsetAsync(entry, 0xFF, (size_t)nb * 4, c->stream));
   hipLaunchKernelGGL(parse_exit_kernel, dim3(nb), dim3(PAR_T), 0, c->stream, d_len, q, min_len, exit1);
   hipLaunchKernelGGL(parse_walk_kernel, dim3(1), dim3(64), 0, c->stream, exit1, q, entry);
@@ -358,8 +340,8 @@ int kd_parse(bce_hip_ctx *c, const uint32_t *d_len, const uint32_t *d_pos, const
     return BCE_HIP_E_OVERFLOW;
   }
   const uint32_t nops = (uint32_t)info->nops;                         // >= 1: the last position is a head
-  BCE_TRY(ensure(c, c->par_hpre, (size_t)nops * 4));
-  uint32_t *hpre = c->par_hpre.as<uint32_t>();
+  BCE_TRY(ensure(c, c->qbuf[qb::par_hpre], (size_t)nops * 4));
+  uint32_t *hpre = c->qbuf[qb::par_hpre].as<uint32_t>();
   hipLaunchKernelGGL(parse_emit_kernel, dim3(nb), dim3(PAR_T), 0, c->stream, flag, rows_bytes, bsum, d_len, d_pos, d_query, d_ops, d_lits, hpre);
   hipLaunchKernelGGL(parse_runs_kernel, dim3((nops + PAR_T - 1) / PAR_T), dim3(PAR_T), 0, c->stream, d_ops, hpre, nops);
   BCE_HIP_TRY(c, hipGetLastError());
@@ -375,11 +357,11 @@ int kd_parse(bce_hip_ctx *c, const uint32_t *d_len, const uint32_t *d_pos, const
 int kd_patch(bce_hip_ctx *c, const uint32_t *d_ops, uint32_t nops, const uint8_t *d_lits, uint64_t nlits, bool sizing, uint8_t *d_out,
              uint64_t cap, uint64_t *out_len) {
   const uint32_t nb = (nops + PAR_BLOCK - 1) / PAR_BLOCK;
-  BCE_TRY(ensure(c, c->par_res, 32));
-  BCE_TRY(ensure(c, c->par_bsum, (size_t)nb * 16));
-  BCE_TRY(ensure(c, c->par_bcnt, (size_t)nb * 4));
-  uint64_t *blen = c->par_bsum.as<uint64_t>(), *blit = blen + nb, *d_res = c->par_res.as<uint64_t>();
-  uint32_t *bbad = c->par_bcnt.as<uint32_t>();
+  BCE_TRY(ensure(c, c->qbuf[qb::par_res], 32));
+  BCE_TRY(ensure(c, c->qbuf[qb::par_bsum], (size_t)nb * 16));
+  BCE_TRY(ensure(c, c->qbuf[qb::par_bcnt], (size_t)nb * 4));
+  uint64_t *blen = c->qbuf[qb::par_bsum].as<uint64_t>(), *blit = blen + nb, *d_res = c->qbuf[qb::par_res].as<uint64_t>();
+  uint32_t *bbad = c->qbuf[qb::par_bcnt].as<uint32_t>();
   hipLaunchKernelGGL(patch_check_kernel, dim3(nb), dim3(PAR_T), 0, c->stream, d_ops, nops, c->n, blen, blit, bbad);
   hipLaunchKernelGGL(patch_top_kernel, dim3(1), dim3(PAR_T), 0, c->stream, blen, blit, bbad, nb, d_res);
   BCE_HIP_TRY(c, hipGetLastError());
@@ -393,9 +375,9 @@ int kd_patch(bce_hip_ctx *c, const uint32_t *d_ops, uint32_t nops, const uint8_t
     snprintf(c->err, sizeof c->err, "patch: %llu bytes, room for %llu", (unsigned long long)res[0], (unsigned long long)cap);
     return BCE_HIP_E_OVERFLOW;
   }
-  BCE_TRY(ensure(c, c->par_off, ((size_t)nops + 1) * 4));
-  BCE_TRY(ensure(c, c->par_loff, (size_t)nops * 4));
-  uint32_t *off = c->par_off.as<uint32_t>(), *loff = c->par_loff.as<uint32_t>();
+  BCE_TRY(ensure(c, c->qbuf[qb::par_off], ((size_t)nops + 1) * 4));
+  BCE_TRY(ensure(c, c->qbuf[qb::par_loff], (size_t)nops * 4));
+  uint32_t *off = c->qbuf[qb::par_off].as<uint32_t>(), *loff = c->qbuf[qb::par_loff].as<uint32_t>();
   const uint32_t total = (uint32_t)res[0], lead = (uint32_t)(reinterpret_cast<uintptr_t>(d_out) & (PAT_CHUNK - 1u));
   const uint32_t tiles = (uint32_t)(((uint64_t)lead + total + PAT_TILE - 1) / PAT_TILE);
   hipLaunchKernelGGL(patch_fill_kernel, dim3(nb), dim3(PAR_T), 0, c->stream, d_ops, nops, blen, blit, off, loff);

@@ -482,181 +482,222 @@ static void write_delta_header(uint8_t *p, const DeltaHeader &h) {
   memcpy(p, "BCED", 4); memcpy(p + 4, &ver, 4); memcpy(p + 8, &h.n, 8); memcpy(p + 16, &h.base_crc, 4); memcpy(p + 20, &h.q, 8);
   memcpy(p + 28, &h.crc, 4); memcpy(p + 32, &h.min_len, 4); memcpy(p + 36, &h.max_len, 4); memcpy(p + 40, &h.nops, 8); memcpy(p + 48, &h.nlits, 8);
 }
-enum GrepMode { kGrepCount, kGrepLocate, kGrepCoverage, kGrepKgrams, kGrepDelta, kGrepApply };
-static int count_pattern(const char *pattern, const char *path, bool in_archive, GrepMode mode, const char *query_path = nullptr, uint32_t min_len = 0,
-                         const char *out_path = nullptr) {
-  const bool locate = mode == kGrepLocate, kgrams = mode == kGrepKgrams, delta = mode == kGrepDelta, apply = mode == kGrepApply;
-  const bool coverage = mode == kGrepCoverage || delta || apply;      // (a second file is read)
-  const size_t m = strlen(pattern);
-  const uint8_t *pat = reinterpret_cast<const uint8_t *>(pattern);
-  HostFile file;
-  HostFile query;
+// ---- the front of all twelve index commands ----
+// The indexed file (or archive) and the command's second file are read beside the runtime's start-up and judged in this order: the
+// file or archive, the second file, the device; an archive's blocks are then decoded into one text.  Owns the context: an error
+// path destroys it, index_done() leaves it to fast_exit.
+enum SecondFile { kNoSecond, kSecondQuery, kSecondDelta };
+struct IndexInput {
+  HostFile file, second;                                              // second: the query of -gm / -gr, the delta of -ga
+  DeltaHeader dh{};                                                   // of the delta
+  std::vector<uint8_t> decoded;
+  bce_hip_ctx *ctx = nullptr;
+  const uint8_t *text = nullptr;
+  size_t n = 0;
+  ~IndexInput() { if (ctx) bce_hip_destroy(ctx); }
+};
+// 0, or the command's exit code with its line printed.  have_api: the library has the entry points the command calls.
+static int index_open(IndexInput &in, const char *path, bool in_archive, const char *second_path, SecondFile second, bool have_api) {
+  HostFile &file = in.file, &query = in.second;
   std::thread reader(read_whole_file, path, &file, in_archive ? (size_t)0 : kMaxInput);   // beside the runtime's start-up
   std::thread query_reader;
-  if (coverage) query_reader = std::thread(read_whole_file, query_path, &query, kMaxInput);
-  bce_hip_ctx *ctx = nullptr;
-  const int rc0 = bce_hip_create(&ctx, 0);
+  if (second != kNoSecond) query_reader = std::thread(read_whole_file, second_path, &query, kMaxInput);
+  const int rc0 = bce_hip_create(&in.ctx, 0);
   reader.join();
-  if (coverage) query_reader.join();
-  struct Destroy { bce_hip_ctx *&c; ~Destroy() { if (c) bce_hip_destroy(c); } } destroy{ctx};
+  if (second != kNoSecond) query_reader.join();
   if (in_archive && file.status == -1) { printf("Archive not found.\n"); return -1; }
   if (in_archive && (file.status != 0 || file.size() == 0)) { printf("Could not read Archive.\n"); return -2; }
   if (!in_archive && (file.status != 0 || file.size() == 0 || file.size() >= kMaxInput)) { printf("Error loading file\n"); return -1; }
-  if (apply && query.status == -1) { printf("Archive not found.\n"); return -1; }
-  DeltaHeader dh{};
-  if (apply && (query.status != 0 || !read_delta_header(query.data(), query.size(), dh))) { printf("Could not read Archive.\n"); return -2; }
-  if (coverage && !apply && (query.status != 0 || query.size() == 0 || query.size() >= kMaxInput)) { printf("Error loading file\n"); return -1; }
-  if (rc0 != 0 || !bce_hip_count || (delta && (!bce_hip_parse || !bce_hip_input_crc32)) || (apply && (!bce_hip_patch || !bce_hip_input_crc32)) || (locate && !bce_hip_locate) || (coverage && !bce_hip_coverage) || (kgrams && (!bce_hip_kgrams || !bce_hip_longest_repeat))) { printf("No usable HIP device: %s\n", bce_hip_strerror(rc0 ? rc0 : BCE_HIP_E_DEVICE)); return -3; }
-  const uint8_t *text = file.data();
-  size_t n = file.size();
-  std::vector<uint8_t> decoded;
-  if (in_archive) {
-    std::vector<std::pair<size_t, size_t>> blocks;
-    if (!archive_blocks(file, blocks)) { printf("Could not read Archive.\n"); return -2; }
-    const bool checked = container_version(file) == 2;
-    std::vector<size_t> at(blocks.size() + 1, 0);
-    for (size_t b = 0; b < blocks.size(); ++b) {                    // sizes from the blocks' own headers, which a container's table must name (as -d)
-      size_t hn = 0;
-      const int hr = bce_hip_decompress(file.data() + blocks[b].first, blocks[b].second, nullptr, 0, &hn);
-      if (hr != 0 && blocks.size() == 1 && !is_container(file)) { printf("Decompression failed: %s\n", bce_hip_strerror(hr)); return -4; }
-      if (hr != 0 || hn < 1 || hn >= kMaxInput || (is_container(file) && (uint64_t)hn != table_raw(file, b))) { printf("Could not read Archive.\n"); return -2; }
-      at[b + 1] = at[b] + hn;
-      if (at[b + 1] >= kMaxInput) { printf("The archive holds 2^31 bytes or more: one index covers one text below that\n"); return -2; }
-    }
-    if (checked && !bce_hip_decompress_device_crc32) { printf("No usable HIP device: %s\n", bce_hip_strerror(BCE_HIP_E_DEVICE)); return -3; }
-    decoded.resize(at.back());
-    for (size_t b = 0; b < blocks.size(); ++b) {
-      const uint8_t *ap = file.data() + blocks[b].first;
-      const size_t want = at[b + 1] - at[b];
-      size_t got = 0;
-      uint32_t crc = 0;
-      int rc = checked ? bce_hip_decompress_device_crc32(ctx, ap, blocks[b].second, decoded.data() + at[b], want, &got, &crc)
-                       : bce_hip_decompress_device(ctx, ap, blocks[b].second, decoded.data() + at[b], want, &got);
-      if (rc == 0 && got != want) rc = BCE_HIP_E_INTERNAL;
-      if (rc != 0) {
-        if (bce_hip_last_error(ctx)[0]) printf("%s\n", bce_hip_last_error(ctx));
-        printf("Decompression failed: %s\n", bce_hip_strerror(rc));
-        return -4;
-      }
-      if (checked && crc != table_crc(file, b)) { print_mismatch(b, table_crc(file, b), crc); return -4; }
-    }
-    text = decoded.data();
-    n = decoded.size();
+  if (second == kSecondDelta && query.status == -1) { printf("Archive not found.\n"); return -1; }
+  if (second == kSecondDelta && (query.status != 0 || !read_delta_header(query.data(), query.size(), in.dh))) { printf("Could not read Archive.\n"); return -2; }
+  if (second == kSecondQuery && (query.status != 0 || query.size() == 0 || query.size() >= kMaxInput)) { printf("Error loading file\n"); return -1; }
+  if (rc0 != 0 || !bce_hip_count || !have_api) { printf("No usable HIP device: %s\n", bce_hip_strerror(rc0 ? rc0 : BCE_HIP_E_DEVICE)); return -3; }
+  in.text = file.data();
+  in.n = file.size();
+  if (!in_archive) return 0;
+  std::vector<std::pair<size_t, size_t>> blocks;
+  if (!archive_blocks(file, blocks)) { printf("Could not read Archive.\n"); return -2; }
+  const bool checked = container_version(file) == 2;
+  std::vector<size_t> at(blocks.size() + 1, 0);
+  for (size_t b = 0; b < blocks.size(); ++b) {                      // sizes from the blocks' own headers, which a container's table must name (as -d)
+    size_t hn = 0;
+    const int hr = bce_hip_decompress(file.data() + blocks[b].first, blocks[b].second, nullptr, 0, &hn);
+    if (hr != 0 && blocks.size() == 1 && !is_container(file)) { printf("Decompression failed: %s\n", bce_hip_strerror(hr)); return -4; }
+    if (hr != 0 || hn < 1 || hn >= kMaxInput || (is_container(file) && (uint64_t)hn != table_raw(file, b))) { printf("Could not read Archive.\n"); return -2; }
+    at[b + 1] = at[b] + hn;
+    if (at[b + 1] >= kMaxInput) { printf("The archive holds 2^31 bytes or more: one index covers one text below that\n"); return -2; }
   }
-  if (delta) {
-    const uint32_t max_len = min_len > kDeltaMaxLen ? min_len : kDeltaMaxLen;
-    bce_hip_parse_info info{};
-    DeltaHeader h{};
-    int rc = bce_hip_load_host(ctx, text, (uint32_t)n);
-    if (rc == 0) rc = bce_hip_bwt(ctx, nullptr);
-    if (rc == 0) rc = bce_hip_build_planes(ctx, nullptr);
-    if (rc == 0) rc = bce_hip_input_crc32(ctx, &h.base_crc);
-    if (rc == 0) rc = bce_hip_parse(ctx, query.data(), query.size(), min_len, max_len, nullptr, 0, nullptr, 0, &info);   // how much
-    std::vector<uint8_t> blob;
-    if (rc == 0) {
-      blob.resize(kDeltaHeader + info.nops * 8 + info.nlits);
-      rc = bce_hip_parse(ctx, query.data(), query.size(), min_len, max_len, reinterpret_cast<bce_hip_op *>(blob.data() + kDeltaHeader), info.nops,
-                         blob.data() + kDeltaHeader + info.nops * 8, info.nlits, &info);
-    }
-    if (rc != 0) { printf("Parse failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); return -4; }
-    h.n = n; h.q = query.size(); h.crc = bce_hip_crc32(0, query.data(), query.size()); h.min_len = min_len; h.max_len = max_len;
-    h.nops = info.nops; h.nlits = info.nlits;
-    write_delta_header(blob.data(), h);
-    if (!write_file(out_path, blob.data(), blob.size())) { printf("Could not write Archive.\n"); return -5; }
-    printf("%llu copies of %llu bytes, %llu literal bytes in %llu runs: %zu bytes of delta\n", (unsigned long long)info.ncopies,
-           (unsigned long long)info.copied, (unsigned long long)info.nlits, (unsigned long long)(info.nops - info.ncopies), blob.size());
-    ctx = nullptr;                                                    // (left to fast_exit, like -d)
-    fast_exit(0);
-    return 0;
-  }
-  if (apply) {
-    const bce_hip_op *ops = reinterpret_cast<const bce_hip_op *>(query.data() + kDeltaHeader);   // (56 bytes behind an allocation's start: aligned)
-    const uint8_t *lits = query.data() + kDeltaHeader + dh.nops * 8;
-    if (n != dh.n) { printf("The delta was made against %llu bytes, not %zu\n", (unsigned long long)dh.n, n); return kExitDiffers; }
+  if (checked && !bce_hip_decompress_device_crc32) { printf("No usable HIP device: %s\n", bce_hip_strerror(BCE_HIP_E_DEVICE)); return -3; }
+  in.decoded.resize(at.back());
+  for (size_t b = 0; b < blocks.size(); ++b) {
+    const uint8_t *ap = file.data() + blocks[b].first;
+    const size_t want = at[b + 1] - at[b];
+    size_t got = 0;
     uint32_t crc = 0;
-    int rc = bce_hip_load_host(ctx, text, (uint32_t)n);
-    if (rc == 0) rc = bce_hip_input_crc32(ctx, &crc);
-    if (rc != 0) { printf("Patch failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); return -4; }
-    if (crc != dh.base_crc) { printf("Checksum mismatch in the base: delta %08X, file %08X\n", dh.base_crc, crc); return kExitDiffers; }
-    uint64_t total = 0;
-    rc = bce_hip_patch(ctx, ops, dh.nops, lits, dh.nlits, nullptr, 0, &total);          // judged on the GPU, and how much
-    if (rc == BCE_HIP_E_ARG || (rc == 0 && total != dh.q)) { printf("Could not read Archive.\n"); return -2; }
-    std::vector<uint8_t> out((size_t)total);
-    if (rc == 0 && total) rc = bce_hip_patch(ctx, ops, dh.nops, lits, dh.nlits, out.data(), total, &total);
-    if (rc != 0) { printf("Patch failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); return -4; }
-    crc = bce_hip_crc32(0, out.data(), out.size());
-    if (crc != dh.crc) { printf("Checksum mismatch in the result: delta %08X, rebuilt %08X\n", dh.crc, crc); return kExitDiffers; }
-    if (!write_file(out_path, out.data(), out.size())) { printf("Could not write file.\n"); return -5; }
-    printf("Rebuilt %zu B from %zu B and a delta of %zu B\n", out.size(), n, query.size());
-    ctx = nullptr;                                                    // (left to fast_exit, like -d)
-    fast_exit(0);
-    return 0;
-  }
-  if (coverage) {
-    uint64_t covered = 0;
-    int rc = bce_hip_load_host(ctx, text, (uint32_t)n);
-    if (rc == 0) rc = bce_hip_bwt(ctx, nullptr);
-    if (rc == 0) rc = bce_hip_build_planes(ctx, nullptr);
-    if (rc == 0) rc = bce_hip_coverage(ctx, query.data(), query.size(), min_len, BCE_HIP_MATCH_LINEAR, &covered);
-    if (rc != 0) { printf("Match failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); return -4; }
-    printf("%llu of %zu bytes (%.1f %%) of %s lie in strings of %u bytes or more that occur in %s\n", (unsigned long long)covered, query.size(),
-           100.0 * (double)covered / (double)query.size(), query_path, min_len, path);
-    ctx = nullptr;                                                    // (left to fast_exit, like -d)
-    fast_exit(0);
-    return 0;
-  }
-  if (kgrams) {
-    const uint32_t K = min_len;                                       // (k = 0 .. K, and K + 1 for H_K)
-    uint32_t ks[kMaxKgramOrder + 2];
-    bce_hip_kgram rec[kMaxKgramOrder + 2];
-    for (uint32_t k = 0; k < K + 2; ++k) ks[k] = k;
-    uint32_t len = 0, pos_a = 0, pos_b = 0;
-    int rc = bce_hip_load_host(ctx, text, (uint32_t)n);
-    if (rc == 0) rc = bce_hip_bwt(ctx, nullptr);
-    if (rc == 0) rc = bce_hip_build_planes(ctx, nullptr);
-    if (rc == 0) rc = bce_hip_kgrams(ctx, ks, K + 2, rec);
-    if (rc == 0) rc = bce_hip_longest_repeat(ctx, BCE_HIP_MATCH_MAX_LEN, &len, &pos_a, &pos_b);
-    if (rc != 0) { printf("K-grams failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); return -4; }
-    printf("k-grams of the circular text: k distinct once most H_k\n");
-    for (uint32_t k = 0; k <= K; ++k) {
-      const uint64_t a = rec[k].nlogn_q24, b = rec[k + 1].nlogn_q24;
-      const double h = (double)(a > b ? a - b : 0) / ((double)n * 16777216.0);
-      printf("%u %llu %llu %u %.6f\n", k, (unsigned long long)rec[k].distinct, (unsigned long long)rec[k].once, rec[k].max_count, h);
+    int rc = checked ? bce_hip_decompress_device_crc32(in.ctx, ap, blocks[b].second, in.decoded.data() + at[b], want, &got, &crc)
+                     : bce_hip_decompress_device(in.ctx, ap, blocks[b].second, in.decoded.data() + at[b], want, &got);
+    if (rc == 0 && got != want) rc = BCE_HIP_E_INTERNAL;
+    if (rc != 0) {
+      if (bce_hip_last_error(in.ctx)[0]) printf("%s\n", bce_hip_last_error(in.ctx));
+      printf("Decompression failed: %s\n", bce_hip_strerror(rc));
+      return -4;
     }
-    if (len == 0) printf("longest repeat: none\n");
-    else if (len >= BCE_HIP_MATCH_MAX_LEN) printf("longest repeat: %u or more bytes at %u and %u\n", len, pos_a, pos_b);
-    else printf("longest repeat: %u bytes at %u and %u\n", len, pos_a, pos_b);
-    printf("%zu bytes\n", n);
-    ctx = nullptr;                                                    // (left to fast_exit, like -d)
-    fast_exit(0);
-    return 0;
+    if (checked && crc != table_crc(file, b)) { print_mismatch(b, table_crc(file, b), crc); return -4; }
   }
+  in.text = in.decoded.data();
+  in.n = in.decoded.size();
+  return 0;
+}
+// the text into the context and indexed: K1, K2
+static int index_text(const IndexInput &in) {
+  int rc = bce_hip_load_host(in.ctx, in.text, (uint32_t)in.n);
+  if (rc == 0) rc = bce_hip_bwt(in.ctx, nullptr);
+  if (rc == 0) rc = bce_hip_build_planes(in.ctx, nullptr);
+  return rc;
+}
+static int index_failed(const IndexInput &in, const char *what, int rc) {
+  printf("%s failed: %s (%s)\n", what, bce_hip_strerror(rc), bce_hip_last_error(in.ctx));
+  return -4;
+}
+static int index_done(IndexInput &in) {
+  in.ctx = nullptr;                                                   // (left to fast_exit, like -d)
+  fast_exit(0);
+  return 0;
+}
+
+// -g / -gd
+static int count_command(const char *pattern, const char *path, bool in_archive) {
+  IndexInput in;
+  if (const int ec = index_open(in, path, in_archive, nullptr, kNoSecond, true)) return ec;
+  const size_t m = strlen(pattern);
+  const uint8_t *pat = reinterpret_cast<const uint8_t *>(pattern);
+  uint64_t count = 0;
+  if (m <= in.n) {                                                  // (a longer pattern occurs nowhere in the text, only around it)
+    const uint64_t offsets[2] = {0, m};
+    int rc = index_text(in);
+    if (rc == 0) rc = bce_hip_count(in.ctx, pat, offsets, 1, &count);
+    if (rc != 0) return index_failed(in, "Count", rc);
+    count -= seam_matches(in.text, in.n, pat, m);
+  }
+  printf("%llu occurrences\n", (unsigned long long)count);
+  return index_done(in);
+}
+
+// -gl / -gld
+static int locate_command(const char *pattern, const char *path, bool in_archive) {
+  IndexInput in;
+  if (const int ec = index_open(in, path, in_archive, nullptr, kNoSecond, bce_hip_locate != nullptr)) return ec;
+  const size_t m = strlen(pattern);
+  const uint8_t *pat = reinterpret_cast<const uint8_t *>(pattern);
   uint64_t count = 0;
   std::vector<uint32_t> where;
-  if (m <= n) {                                                     // (a longer pattern occurs nowhere in the text, only around it)
+  if (m <= in.n) {                                                  // (as -g)
     const uint64_t offsets[2] = {0, m};
-    int rc = bce_hip_load_host(ctx, text, (uint32_t)n);
-    if (rc == 0) rc = bce_hip_bwt(ctx, nullptr);
-    if (rc == 0) rc = bce_hip_build_planes(ctx, nullptr);
-    if (locate) {
-      uint64_t hits[2] = {0, 0};
-      if (rc == 0) rc = bce_hip_locate(ctx, pat, offsets, 1, BCE_HIP_LOCATE_LINEAR, hits, nullptr, 0, &count);   // how many
-      if (rc == 0 && count) {
-        where.resize(count);
-        rc = bce_hip_locate(ctx, pat, offsets, 1, BCE_HIP_LOCATE_LINEAR, hits, where.data(), count, &count);
-      }
-      if (rc != 0) { printf("Locate failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); return -4; }
-    } else {
-      if (rc == 0) rc = bce_hip_count(ctx, pat, offsets, 1, &count);
-      if (rc != 0) { printf("Count failed: %s (%s)\n", bce_hip_strerror(rc), bce_hip_last_error(ctx)); return -4; }
-      count -= seam_matches(text, n, pat, m);
+    uint64_t hits[2] = {0, 0};
+    int rc = index_text(in);
+    if (rc == 0) rc = bce_hip_locate(in.ctx, pat, offsets, 1, BCE_HIP_LOCATE_LINEAR, hits, nullptr, 0, &count);   // how many
+    if (rc == 0 && count) {
+      where.resize(count);
+      rc = bce_hip_locate(in.ctx, pat, offsets, 1, BCE_HIP_LOCATE_LINEAR, hits, where.data(), count, &count);
     }
+    if (rc != 0) return index_failed(in, "Locate", rc);
   }
   for (uint32_t at : where) printf("%u\n", at);
   printf("%llu occurrences\n", (unsigned long long)count);
-  ctx = nullptr;                                                    // (left to fast_exit, like -d)
-  fast_exit(0);
-  return 0;
+  return index_done(in);
+}
+
+// -gm / -gmd
+static int coverage_command(uint32_t min_len, const char *path, bool in_archive, const char *query_path) {
+  IndexInput in;
+  if (const int ec = index_open(in, path, in_archive, query_path, kSecondQuery, bce_hip_coverage != nullptr)) return ec;
+  const HostFile &query = in.second;
+  uint64_t covered = 0;
+  int rc = index_text(in);
+  if (rc == 0) rc = bce_hip_coverage(in.ctx, query.data(), query.size(), min_len, BCE_HIP_MATCH_LINEAR, &covered);
+  if (rc != 0) return index_failed(in, "Match", rc);
+  printf("%llu of %zu bytes (%.1f %%) of %s lie in strings of %u bytes or more that occur in %s\n", (unsigned long long)covered, query.size(),
+         100.0 * (double)covered / (double)query.size(), query_path, min_len, path);
+  return index_done(in);
+}
+
+// -gk / -gkd: k = 0 .. K, and K + 1 for H_K
+static int kgrams_command(uint32_t K, const char *path, bool in_archive) {
+  IndexInput in;
+  if (const int ec = index_open(in, path, in_archive, nullptr, kNoSecond, bce_hip_kgrams && bce_hip_longest_repeat)) return ec;
+  uint32_t ks[kMaxKgramOrder + 2];
+  bce_hip_kgram rec[kMaxKgramOrder + 2];
+  for (uint32_t k = 0; k < K + 2; ++k) ks[k] = k;
+  uint32_t len = 0, pos_a = 0, pos_b = 0;
+  int rc = index_text(in);
+  if (rc == 0) rc = bce_hip_kgrams(in.ctx, ks, K + 2, rec);
+  if (rc == 0) rc = bce_hip_longest_repeat(in.ctx, BCE_HIP_MATCH_MAX_LEN, &len, &pos_a, &pos_b);
+  if (rc != 0) return index_failed(in, "K-grams", rc);
+  printf("k-grams of the circular text: k distinct once most H_k\n");
+  for (uint32_t k = 0; k <= K; ++k) {
+    const uint64_t a = rec[k].nlogn_q24, b = rec[k + 1].nlogn_q24;
+    const double h = (double)(a > b ? a - b : 0) / ((double)in.n * 16777216.0);
+    printf("%u %llu %llu %u %.6f\n", k, (unsigned long long)rec[k].distinct, (unsigned long long)rec[k].once, rec[k].max_count, h);
+  }
+  if (len == 0) printf("longest repeat: none\n");
+  else if (len >= BCE_HIP_MATCH_MAX_LEN) printf("longest repeat: %u or more bytes at %u and %u\n", len, pos_a, pos_b);
+  else printf("longest repeat: %u bytes at %u and %u\n", len, pos_a, pos_b);
+  printf("%zu bytes\n", in.n);
+  return index_done(in);
+}
+
+// -gr / -grd
+static int delta_command(uint32_t min_len, const char *path, bool in_archive, const char *query_path, const char *out_path) {
+  IndexInput in;
+  if (const int ec = index_open(in, path, in_archive, query_path, kSecondQuery, bce_hip_parse && bce_hip_input_crc32 && bce_hip_coverage)) return ec;
+  const HostFile &query = in.second;
+  const uint32_t max_len = min_len > kDeltaMaxLen ? min_len : kDeltaMaxLen;
+  bce_hip_parse_info info{};
+  DeltaHeader h{};
+  int rc = index_text(in);
+  if (rc == 0) rc = bce_hip_input_crc32(in.ctx, &h.base_crc);
+  if (rc == 0) rc = bce_hip_parse(in.ctx, query.data(), query.size(), min_len, max_len, nullptr, 0, nullptr, 0, &info);   // how much
+  std::vector<uint8_t> blob;
+  if (rc == 0) {
+    blob.resize(kDeltaHeader + info.nops * 8 + info.nlits);
+    rc = bce_hip_parse(in.ctx, query.data(), query.size(), min_len, max_len, reinterpret_cast<bce_hip_op *>(blob.data() + kDeltaHeader), info.nops,
+                       blob.data() + kDeltaHeader + info.nops * 8, info.nlits, &info);
+  }
+  if (rc != 0) return index_failed(in, "Parse", rc);
+  h.n = in.n; h.q = query.size(); h.crc = bce_hip_crc32(0, query.data(), query.size()); h.min_len = min_len; h.max_len = max_len;
+  h.nops = info.nops; h.nlits = info.nlits;
+  write_delta_header(blob.data(), h);
+  if (!write_file(out_path, blob.data(), blob.size())) { printf("Could not write Archive.\n"); return -5; }
+  printf("%llu copies of %llu bytes, %llu literal bytes in %llu runs: %zu bytes of delta\n", (unsigned long long)info.ncopies,
+         (unsigned long long)info.copied, (unsigned long long)info.nlits, (unsigned long long)(info.nops - info.ncopies), blob.size());
+  return index_done(in);
+}
+
+// -ga / -gad: the base is loaded, not indexed
+static int apply_command(const char *path, bool in_archive, const char *delta_path, const char *out_path) {
+  IndexInput in;
+  if (const int ec = index_open(in, path, in_archive, delta_path, kSecondDelta, bce_hip_patch && bce_hip_input_crc32 && bce_hip_coverage)) return ec;
+  const HostFile &delta = in.second;
+  const DeltaHeader &dh = in.dh;
+  const bce_hip_op *ops = reinterpret_cast<const bce_hip_op *>(delta.data() + kDeltaHeader);   // (56 bytes behind an allocation's start: aligned)
+  const uint8_t *lits = delta.data() + kDeltaHeader + dh.nops * 8;
+  if (in.n != dh.n) { printf("The delta was made against %llu bytes, not %zu\n", (unsigned long long)dh.n, in.n); return kExitDiffers; }
+  uint32_t crc = 0;
+  int rc = bce_hip_load_host(in.ctx, in.text, (uint32_t)in.n);
+  if (rc == 0) rc = bce_hip_input_crc32(in.ctx, &crc);
+  if (rc != 0) return index_failed(in, "Patch", rc);
+  if (crc != dh.base_crc) { printf("Checksum mismatch in the base: delta %08X, file %08X\n", dh.base_crc, crc); return kExitDiffers; }
+  uint64_t total = 0;
+  rc = bce_hip_patch(in.ctx, ops, dh.nops, lits, dh.nlits, nullptr, 0, &total);          // judged on the GPU, and how much
+  if (rc == BCE_HIP_E_ARG || (rc == 0 && total != dh.q)) { printf("Could not read Archive.\n"); return -2; }
+  std::vector<uint8_t> out((size_t)total);
+  if (rc == 0 && total) rc = bce_hip_patch(in.ctx, ops, dh.nops, lits, dh.nlits, out.data(), total, &total);
+  if (rc != 0) return index_failed(in, "Patch", rc);
+  crc = bce_hip_crc32(0, out.data(), out.size());
+  if (crc != dh.crc) { printf("Checksum mismatch in the result: delta %08X, rebuilt %08X\n", dh.crc, crc); return kExitDiffers; }
+  if (!write_file(out_path, out.data(), out.size())) { printf("Could not write file.\n"); return -5; }
+  printf("Rebuilt %zu B from %zu B and a delta of %zu B\n", out.size(), in.n, delta.size());
+  return index_done(in);
 }
 
 // MINLEN of -gm / -gmd: decimal digits only, 1 .. 4096 (BCE_HIP_MATCH_MAX_LEN); anything else: 0
@@ -1011,17 +1052,17 @@ int main(int argc, char **argv) {
   } else if ((argc == 3 || argc == 4) && argv[1][0] == '-' && argv[1][1] == 'e' && argv[1][2] == 0) {
     return estimate_file(argv[2], argc == 4 ? argv[3] : nullptr);
   } else if (argc == 4 && argv[2][0] != 0 && (strcmp(argv[1], "-g") == 0 || strcmp(argv[1], "-gd") == 0)) {
-    return count_pattern(argv[2], argv[3], argv[1][2] == 'd', kGrepCount);
+    return count_command(argv[2], argv[3], argv[1][2] == 'd');
   } else if (argc == 4 && argv[2][0] != 0 && (strcmp(argv[1], "-gl") == 0 || strcmp(argv[1], "-gld") == 0)) {
-    return count_pattern(argv[2], argv[3], argv[1][3] == 'd', kGrepLocate);
+    return locate_command(argv[2], argv[3], argv[1][3] == 'd');
   } else if (argc == 5 && (strcmp(argv[1], "-gm") == 0 || strcmp(argv[1], "-gmd") == 0) && parse_min_len(argv[2]) != 0) {
-    return count_pattern("", argv[3], argv[1][3] == 'd', kGrepCoverage, argv[4], parse_min_len(argv[2]));
+    return coverage_command(parse_min_len(argv[2]), argv[3], argv[1][3] == 'd', argv[4]);
   } else if (argc == 6 && (strcmp(argv[1], "-gr") == 0 || strcmp(argv[1], "-grd") == 0) && parse_min_len(argv[2]) != 0) {
-    return count_pattern("", argv[3], argv[1][3] == 'd', kGrepDelta, argv[4], parse_min_len(argv[2]), argv[5]);
+    return delta_command(parse_min_len(argv[2]), argv[3], argv[1][3] == 'd', argv[4], argv[5]);
   } else if (argc == 5 && (strcmp(argv[1], "-ga") == 0 || strcmp(argv[1], "-gad") == 0)) {
-    return count_pattern("", argv[2], argv[1][3] == 'd', kGrepApply, argv[3], 0, argv[4]);
+    return apply_command(argv[2], argv[1][3] == 'd', argv[3], argv[4]);
   } else if (argc == 4 && (strcmp(argv[1], "-gk") == 0 || strcmp(argv[1], "-gkd") == 0) && parse_order(argv[2]) >= 0) {
-    return count_pattern("", argv[3], argv[1][3] == 'd', kGrepKgrams, nullptr, (uint32_t)parse_order(argv[2]));
+    return kgrams_command((uint32_t)parse_order(argv[2]), argv[3], argv[1][3] == 'd');
   } else if (argc == 4 && argv[1][0] == '-' && argv[1][1] == 's') {
     // Scan (bce.cpp:1384-1402): enumeration on the GPU, ScanCoder optimisation on the host, 288-byte config out
     auto start = std::chrono::high_resolution_clock::now();
