@@ -575,6 +575,23 @@ def _as_ops(ops):
     return a.view(OP_DTYPE).reshape(-1)
 
 
+def _archive_into(c, out=None):
+    """The archive of context `c`'s last encode: into `out` where that is a large enough uint8 array, else a new bytearray."""
+    lib, h = c.lib, c.h
+    n = C.c_size_t()
+    c.check(lib.bce_hip_archive_size(h, C.byref(n)), "bce_hip_archive_size")
+    if out is not None and isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable and out.size >= n.value:
+        c.check(lib.bce_hip_archive_copy(h, out.ctypes.data, out.size), "bce_hip_archive_copy")
+        return memoryview(out.reshape(-1))[:n.value]
+    # the library lays the archive out straight into this buffer (one copy of the coded streams, none in Python):
+    # a bytearray compares, hashes, slices and writes like bytes
+    out = bytearray(n.value)
+    view = (C.c_uint8 * n.value).from_buffer(out)
+    c.check(lib.bce_hip_archive_copy(h, C.addressof(view), n.value), "bce_hip_archive_copy")
+    del view
+    return out
+
+
 class BCE:
     """The reference's BCE<AdaptiveCoder<31>, ...> (bce.cpp:1111-1374), encode side."""
 
@@ -592,32 +609,32 @@ class BCE:
             return f.read()
 
     def _apply(self, rf):
-        lib, h = rf._c.lib, rf._c.h
+        self._apply_ctx(rf._c)
+
+    def _apply_ctx(self, c):
+        lib, h = c.lib, c.h
         cfg = None
         if self.config is not None:
             cfg = _as_u8(self.config)
-        rf._c.check(lib.bce_hip_set_config(h, cfg.ctypes.data if cfg is not None else None), "bce_hip_set_config")
-        rf._c.check(lib.bce_hip_set_symbol_capacity(h, self.symbol_capacity), "bce_hip_set_symbol_capacity")
+        c.check(lib.bce_hip_set_config(h, cfg.ctypes.data if cfg is not None else None), "bce_hip_set_config")
+        c.check(lib.bce_hip_set_symbol_capacity(h, self.symbol_capacity), "bce_hip_set_symbol_capacity")
 
     def encode(self, rf: RankFile, out=None):
         """-> the archive (a bytearray).  With `out` (a writable C-contiguous uint8 numpy array that is large enough) the
         library lays the archive out there -- the C ABI's own shape: the caller's buffer, e.g. pinned memory a collective
         sends from -- and a memoryview of its first len(archive) bytes comes back; too small an `out` is ignored."""
         self._apply(rf)
-        lib, h = rf._c.lib, rf._c.h
-        rf._c.check(lib.bce_hip_encode(h), "bce_hip_encode")
+        rf._c.check(rf._c.lib.bce_hip_encode(rf._c.h), "bce_hip_encode")
+        return _archive_into(rf._c, out)
+
+    def compress_loaded(self, c, load, out=None):
+        """The one-shot entry points (bce_hip_compress / bce_hip_compress_device: `load(ctx handle, length pointer)` calls one of
+        them): the library runs the stages in the order it likes best -- the enumeration's early rounds before K1 has finished.
+        -> the archive, as encode()."""
+        self._apply_ctx(c)
         n = C.c_size_t()
-        rf._c.check(lib.bce_hip_archive_size(h, C.byref(n)), "bce_hip_archive_size")
-        if out is not None and isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous and out.flags.writeable and out.size >= n.value:
-            rf._c.check(lib.bce_hip_archive_copy(h, out.ctypes.data, out.size), "bce_hip_archive_copy")
-            return memoryview(out.reshape(-1))[:n.value]
-        # the library lays the archive out straight into this buffer (one copy of the coded streams, none in Python):
-        # a bytearray compares, hashes, slices and writes like bytes
-        out = bytearray(n.value)
-        view = (C.c_uint8 * n.value).from_buffer(out)
-        rf._c.check(lib.bce_hip_archive_copy(h, C.addressof(view), n.value), "bce_hip_archive_copy")
-        del view
-        return out
+        load(c.h, C.byref(n))
+        return _archive_into(c, out)
 
     # --- BCE::code one round at a time (parity tests) ---
     def code_begin(self, rf: RankFile):
@@ -697,12 +714,16 @@ def stats_of(ctx) -> dict:
 
 def compress(data, config=None, device=0, ctx=None) -> bytes:
     """`bce -c` on an in-memory buffer (bce.cpp:1403-1427 minus file I/O) -> archive bytes."""
-    rf = RankFile(data, device=device, ctx=ctx)
+    a = _as_u8(data)
+    if len(a) == 0:
+        raise BceError(-1, "RankFile", "empty input")
+    c = ctx or _Ctx(device)
     try:
-        return BCE(config).encode(rf)
+        return BCE(config).compress_loaded(
+            c, lambda h, ln: c.check(c.lib.bce_hip_compress(h, a.ctypes.data, len(a), None, 0, ln), "bce_hip_compress"))
     finally:
         if ctx is None:
-            rf.close()
+            c.close()
 
 
 def count(data, patterns, device=0, ctx=None):
@@ -843,14 +864,15 @@ def longest_repeat(data, max_len=MATCH_MAX_LEN, device=0, ctx=None):
             rf.close()
 
 
-def compress_device(device_ptr, n, config=None, device=0, ctx=None, out=None):
-    """Same with the input already resident in HBM.  Returns (archive bytes, stats dict); `out`: see BCE.encode."""
+def compress_device(device_ptr, n, config=None, device=0, ctx=None, out=None, symbol_capacity=0):
+    """Same with the input already resident in HBM.  Returns (archive bytes, stats dict); `out`: see BCE.encode;
+    `symbol_capacity`: records between two model flushes (0: the library's choice)."""
     own = ctx is None
     c = ctx or _Ctx(device)
     try:
-        rf = RankFile(n=n, device_ptr=device_ptr, ctx=c)
-        arch = BCE(config).encode(rf, out=out)
-        return arch, stats(rf)
+        arch = BCE(config, symbol_capacity).compress_loaded(
+            c, lambda h, ln: c.check(c.lib.bce_hip_compress_device(h, int(device_ptr), int(n), None, 0, ln), "bce_hip_compress_device"), out=out)
+        return arch, stats_of(c)
     finally:
         if own:
             c.close()

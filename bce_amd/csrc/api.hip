@@ -131,7 +131,9 @@ size_t ctx_trim(bce_hip_ctx *c) {
       if (c->dec_part == 3) give.push_back(&c->dfs);
     }
   }
-  if (c->phase >= 1 && c->phase <= 3)                  // (an encoder's phase: the decoder's lists are idle)
+  // (phase 6, the early rounds of a one-shot compression: K1's second half is still to come and reads every array of the sort,
+  //  the planes are built a second time, the enumeration is under way -- nothing of the encoder's can go)
+  if ((c->phase >= 1 && c->phase <= 3) || c->phase == 6)   // (an encoder's phase: the decoder's lists are idle)
     for (auto &par : c->dlist) for (DevBuf &b : par) give.push_back(&b);
   size_t freed = 0;
   bool synced = false;
@@ -420,7 +422,10 @@ struct Enumeration {
   struct Batch { Kernels how; uint32_t rounds; uint64_t nodes; bool growing; };   // rounds == 0: flush first; nodes, growing: what bounds the grid
   // What a step leaves for the loop to do: the next batch (after a flush as well); round c->round again, the node lists or the
   // symbol buffer having grown; the next batch behind a split round; nothing.  All but the last mean "look again" and say why.
-  enum class Next { kRounds, kSameRound, kSplitDone, kFinished };
+  // kPaused: round `round_limit` is next (or the depth-first tail would be) and the caller wants the rounds to stop there;
+  // what was buffered is flushed, and run() carries on from the same state once the limit is lifted.
+  enum class Next { kRounds, kSameRound, kSplitDone, kFinished, kPaused };
+  static constexpr uint32_t kNoLimit = 0xFFFFFFFFu;
   static constexpr uint32_t kEarlyMax = 4;         // early small flushes: 1M, 2M, 4M, 8M records (0..5 measured: +3 % on text, neutral on random data)
   bce_hip_ctx *c;
   const std::function<int(uint64_t)> sink;
@@ -435,6 +440,10 @@ struct Enumeration {
   int dfs_try = 0;
   const uint32_t dfs_enter[2];
   FlushPredictor predict;
+  // Rounds below this one run, then run() returns with `paused` set (compress_early: the rounds that do not need K1's
+  // finished order).  The depth-first tail reads K1's suffix array, so where it would start the rounds pause as well.
+  uint32_t round_limit = kNoLimit;
+  bool paused = false;
 
   Enumeration(bce_hip_ctx *ctx, std::function<int(uint64_t)> to)
       : c(ctx), sink(std::move(to)), env(ctx), n(ctx->n), dfs_enter{env.dfs_enter, 2048u} {
@@ -456,19 +465,33 @@ struct Enumeration {
   }
 
   int run() {
-    for (Next next = Next::kRounds; next != Next::kFinished;) {
+    paused = false;
+    for (Next next = Next::kRounds; next != Next::kFinished && next != Next::kPaused;) {
       BCE_TRY(gate_regain(c));                     // (lent to another context behind the last model flush)
       next = Next::kRounds;
-      BCE_TRY(depth_first(&next));
-      if (next != Next::kFinished) BCE_TRY(batch(&next));
+      BCE_TRY(pause(&next));
+      if (next == Next::kRounds) BCE_TRY(depth_first(&next));
+      if (next == Next::kRounds) BCE_TRY(batch(&next));
     }
     return BCE_HIP_OK;
+  }
+  // The round limit is reached, or the depth-first tail is due while a limit stands: hand the coders what is buffered (like the
+  // early small flushes) and stop.  Every batch ends with its state taken in -- a full symbol buffer flushed, lists grown, a
+  // split round complete -- so nothing is pending here but buffered symbols.
+  int pause(Next *next) {
+    if (round_limit == kNoLimit || !(c->round >= round_limit || tail_due())) return BCE_HIP_OK;
+    paused = true;
+    *next = Next::kPaused;
+    return flush();
+  }
+  bool tail_due() const {
+    const bool tail = have_ctl && decaying && !ctl.need_flush && !finished() && dfs_try < 2 && ctl.next_nodes && ctl.next_nodes <= dfs_enter[dfs_try];
+    return tail && (ctl.nodes_total >= 8ull * (n - 1) / 8 || c->round >= 1024u || c->dbg_tail_round);
   }
   // Few live nodes and almost everything visited: finish depth-first (k3_dfs.hip).  The walkers' symbols come after everything
   // emitted so far, so flush that first.
   int depth_first(Next *next) {
-    const bool tail = have_ctl && decaying && !ctl.need_flush && !finished() && dfs_try < 2 && ctl.next_nodes && ctl.next_nodes <= dfs_enter[dfs_try];
-    if (!tail || !(ctl.nodes_total >= 8ull * (n - 1) / 8 || c->round >= 1024u || c->dbg_tail_round)) return BCE_HIP_OK;
+    if (!tail_due()) return BCE_HIP_OK;
     BCE_TRY(flush());
     BCE_TRY(gate_regain(c));
     bool dfs_done = false;
@@ -481,8 +504,14 @@ struct Enumeration {
     *next = Next::kFinished;
     return flush();
   }
-  // The kernels of the next batch and how many rounds of them to queue.
+  // The kernels of the next batch and how many rounds of them to queue: no round at or past the limit (pause() has seen that
+  // c->round is below it; a batch of no rounds means "flush first").
   Batch plan() {
+    Batch b = plan_unbounded();
+    if (round_limit != kNoLimit && b.rounds > round_limit - c->round) b.rounds = round_limit - c->round;
+    return b;
+  }
+  Batch plan_unbounded() {
     if ((!c->dbg_no_tail || cur_nodes == 0) && cur_nodes <= K3_TAIL_ENTER)       // (no node at all, e.g. one byte repeated: only this kernel says "done" then)
       // narrow phase: the persistent single-workgroup kernel loops over rounds on the device
       // (while the depth-first tail may still take over, come back after 1024 rounds: an input that is one long run
@@ -1029,13 +1058,10 @@ int bce_hip_model_flush(bce_hip_ctx *c, const uint32_t *key_words, const uint32_
 }
 
 // ---- BCE::encode ------------------------------------------------------------------------------------
-static int encode_body(bce_hip_ctx *c);
-int bce_hip_encode(bce_hip_ctx *c) { return gate_on_error(c, bce_guarded(c, [&] { return encode_body(c); })); }
-static int encode_body(bce_hip_ctx *c) {
-  BCE_TRY(check_stage(c, 3));
-  PhaseScope phase(c, 3);
+// The enumeration of -c between its two ends: encode_start readies the model, the node lists and the coders from the planes'
+// zero counts (and takes the device gate), encode_end waits for the coders and lays the streams out.
+static int encode_start(bce_hip_ctx *c) {
   c->gate_wait_s = 0; c->gate_held_s = 0; c->gate_lent = false;
-  const double t_enc0 = now_s();
   gate_acquire(c);
   BCE_HIP_TRY(c, hipSetDevice(c->device));
   const uint32_t n = c->n;
@@ -1046,9 +1072,9 @@ static int encode_body(bce_hip_ctx *c) {
   for (int i = 0; i < 8; ++i) C[i] = c->zeros[(i + 7) & 7];   // bce.cpp:1128
   c->coder->begin(c->config, C, n);
   c->stats.symbols = 0; c->stats.flushes = 0; c->stats.t_model = 0; c->stats.t_model_kernels = 0; c->stats.t_coder = 0;
-
-  Enumeration e(c, [&](uint64_t nsym) { return flush_symbols(c, nsym); });
-  BCE_TRY(e.run());
+  return BCE_HIP_OK;
+}
+static int encode_end(bce_hip_ctx *c, const EnumCtl &ctl, double t_enc0) {
   gate_release(c);                               // the GPU phase is over (the last flush and its copy are queued): next context
   c->gate_lent = false;
   static const bool gate_timing = getenv("BCE_HIP_GATE_TIMING") != nullptr;
@@ -1061,9 +1087,9 @@ static int encode_body(bce_hip_ctx *c) {
   }
   if (c->coder->failed()) { snprintf(c->err, sizeof c->err, "host allocation failed in a range-coder thread"); return BCE_HIP_E_NOMEM; }
   c->stats.t_coder_busy = c->coder->busy_seconds();
-  c->stats.rounds = e.ctl.done_round;
-  c->stats.nodes = e.ctl.nodes_total;
-  c->coder->finish(c->config, n, c->offset);     // the archive is laid out by bce_hip_archive_copy, straight into the caller's buffer
+  c->stats.rounds = ctl.done_round;
+  c->stats.nodes = ctl.nodes_total;
+  c->coder->finish(c->config, c->n, c->offset);  // the archive is laid out by bce_hip_archive_copy, straight into the caller's buffer
   c->enum_active = false;
   c->stage = 4;
   c->stats.t_enum = c->stats.k3_ms * 1e-3;      // GPU time of the enumeration; K4, copies and coding overlap it and each other
@@ -1072,6 +1098,107 @@ static int encode_body(bce_hip_ctx *c) {
             (void *)c, c->gate_wait_s * 1e3, c->gate_held_s * 1e3, (t_gpu_done - t_enc0) * 1e3, c->stats.k3_ms, c->stats.t_model * 1e3,
             (unsigned long long)c->stats.flushes, (now_s() - t_gpu_done) * 1e3);
   return BCE_HIP_OK;
+}
+
+static int encode_body(bce_hip_ctx *c);
+int bce_hip_encode(bce_hip_ctx *c) { return gate_on_error(c, bce_guarded(c, [&] { return encode_body(c); })); }
+static int encode_body(bce_hip_ctx *c) {
+  BCE_TRY(check_stage(c, 3));
+  PhaseScope phase(c, 3);
+  const double t_enc0 = now_s();
+  BCE_TRY(encode_start(c));
+  Enumeration e(c, [&](uint64_t nsym) { return flush_symbols(c, nsym); });
+  BCE_TRY(e.run());
+  return encode_end(c, e.ctl, t_enc0);
+}
+
+// ---- the one-shot compression with the enumeration started on the first sort's order ----------------------------------------
+// K1's first sort orders the rotations by their first h bytes.  The rounds r < 8 h of the enumeration ask for ranks only at
+// boundaries between rows that differ within their first h bytes, and any order sorted that
+// deep has the same rows on either side of such a boundary: same ranks, same zeros per plane, same children, same symbol
+// records.  So those rounds run on the planes of a BWT gathered right behind the first sort, and the coder threads have work
+// while the rest of K1 runs: ranks, active list, segmented and deferred rounds, the final gather, the planes again.
+// All on c->stream, one after the other.  BCE_HIP_EARLY_ENUM=0: the stages in their old order; BCE_HIP_EARLY_CAP=<rounds>
+// lowers the number of early rounds (tests), never raises it.
+static bool early_enum_applies(const bce_hip_ctx *c) {
+  const char *e = getenv("BCE_HIP_EARLY_ENUM");
+  return !(e && e[0] == '0' && !e[1]) && k1_two_halves(c);
+}
+static uint32_t early_round_limit(uint32_t h) {
+  uint32_t limit = 8u * h;                         // rounds 0 .. 8 h - 1
+  if (const char *e = getenv("BCE_HIP_EARLY_CAP")) { const unsigned long v = strtoul(e, nullptr, 10); if (v < limit) limit = (uint32_t)v; }
+  return limit;
+}
+static int compress_early_body(bce_hip_ctx *c) {
+  BCE_TRY(check_stage(c, 1));
+  BCE_HIP_TRY(c, hipSetDevice(c->device));
+  c->stage = 1; c->enum_active = false;           // (what an earlier compression of this input left is void from here on)
+  uint32_t h = 0;
+  double t0 = now_s();
+  PhaseScope phase(c, 1);
+  {
+    RoctxRange range("bce K1 first sort + provisional BWT");
+    BCE_TRY(k1_first_sort(c, &h));
+    BCE_TRY(k1_provisional_bwt(c));
+  }
+  double t_bwt = now_s() - t0;
+  t0 = now_s();
+  phase.set(2);
+  {
+    RoctxRange range("bce K2 planes + rank directory (provisional)");
+    BCE_TRY(k2_build_planes(c));
+  }
+  double t_planes = now_s() - t0;
+  uint32_t zeros0[8];
+  memcpy(zeros0, c->zeros, sizeof zeros0);
+
+  phase.set(6);                                    // K1's arrays, the planes and the enumeration's buffers are all in use
+  const double t_enc0 = now_s();
+  BCE_TRY(encode_start(c));
+  Enumeration e(c, [&](uint64_t nsym) { return flush_symbols(c, nsym); });
+  e.round_limit = early_round_limit(h);
+  BCE_TRY(e.run());
+  if (!e.paused) { gate_release(c); c->gate_lent = false; }   // (it ended inside the early rounds: the rest needs no gate)
+  const uint32_t paused_at = c->round;
+  const uint64_t early_syms = c->stats.symbols;
+  const double t_early = now_s() - t_enc0;
+
+  t0 = now_s();
+  {
+    RoctxRange range("bce K1 second half + BWT");
+    BCE_TRY(k1_finish(c));
+    BCE_TRY(k1_final_bwt(c, c->k1_first_final));
+  }
+  t_bwt += now_s() - t0;
+  if (!c->k1_first_final) {
+    // the first sort left ties, so the BWT has changed inside them: the planes again, into the same buffers (the rounds to
+    // come are queued behind them)
+    t0 = now_s();
+    RoctxRange range("bce K2 planes + rank directory");
+    BCE_TRY(k2_build_planes(c));
+    t_planes += now_s() - t0;
+    if (memcmp(zeros0, c->zeros, sizeof zeros0) != 0) {
+      snprintf(c->err, sizeof c->err, "early rounds: the planes of the provisional and of the final BWT differ in their zero counts");
+      return BCE_HIP_E_INTERNAL;
+    }
+  }
+  c->stats.t_bwt = t_bwt;
+  c->stats.t_planes = t_planes;
+  if (getenv("BCE_HIP_EARLY_TRACE"))
+    fprintf(stderr, "early: h %u limit %u %s at round %u (%s) symbols %llu rounds %.2f ms k1_finish+planes %.2f ms first_sort_final %d\n", h, e.round_limit,
+            e.paused ? "paused" : "finished", paused_at, !e.paused ? "end" : (paused_at >= e.round_limit ? "limit" : "tail due"),
+            (unsigned long long)early_syms, t_early * 1e3, (now_s() - t_enc0 - t_early) * 1e3, (int)c->k1_first_final);
+  phase.set(3);
+  if (e.paused) {
+    e.round_limit = Enumeration::kNoLimit;
+    BCE_TRY(e.run());
+  }
+  return encode_end(c, e.ctl, t_enc0);
+}
+static int compress_early(bce_hip_ctx *c) {
+  const int rc = gate_on_error(c, bce_guarded(c, [&] { return compress_early_body(c); }));
+  if (rc != BCE_HIP_OK && c) { c->stage = c->text_loaded ? 1 : 0; c->enum_active = false; c->k1_valid = false; }   // nothing half-done stays usable
+  return rc;
 }
 
 // `bce -s`: BCE<ScanCoder<31>, unbwt::noop>::encode + save_config (bce.cpp:1384-1402, 726-834).  The enumeration
@@ -1203,9 +1330,13 @@ int bce_hip_archive_copy(bce_hip_ctx *c, uint8_t *out, size_t cap) {
 
 static int compress_loaded(bce_hip_ctx *c, uint8_t *out, size_t cap, size_t *out_len) {
   const double t0 = now_s();
-  BCE_TRY(bce_hip_bwt(c, nullptr));
-  BCE_TRY(bce_hip_build_planes(c, nullptr));
-  BCE_TRY(bce_hip_encode(c));
+  if (c && c->stage >= 1 && early_enum_applies(c)) {
+    BCE_TRY(compress_early(c));
+  } else {
+    BCE_TRY(bce_hip_bwt(c, nullptr));
+    BCE_TRY(bce_hip_build_planes(c, nullptr));
+    BCE_TRY(bce_hip_encode(c));
+  }
   c->stats.t_total = now_s() - t0 + c->stats.t_load;
   if (getenv("BCE_CLI_TIMING"))
     fprintf(stderr, "lib: load %.3f bwt %.3f planes %.3f encode %.3f s (K3 %.1f ms, coder busiest %.3f s, waited for coders %.3f s); device allocations %u calls %.1f MB %.3f s, pinned %u calls %.1f MB %.3f s\n",

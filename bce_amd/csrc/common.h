@@ -181,7 +181,9 @@ struct bce_hip_ctx {
   uint32_t n = 0;
   int stage = 0;  // 0 empty, 1 loaded, 2 bwt, 3 planes, 4 encoded
   int phase = 0;  // what is running: 1 K1, 2 K2, 3 the enumeration / model (-c, -s), 4 a decode, 5 the inverse BWT of the libdivsufsort
-                  // seam (bce_hip_inverse_bwt); 0 nothing.  Every entry point that sets it sets it back to 0.  ctx_trim() gives back the
+                  // seam (bce_hip_inverse_bwt), 6 the early rounds of the enumeration with K1 unfinished, K1's second half and the
+                  // second plane build of a one-shot compression (K1's, K2's and K3's buffers are all live);
+                  // 0 nothing.  Every entry point that sets it sets it back to 0.  ctx_trim() gives back the
                   // buffers the running phase does not use when the device runs out of memory (the context keeps every stage's
                   // buffers for its next input; at n ~ 2^31 they do not all fit together)
   uint32_t offset = 0;
@@ -191,6 +193,11 @@ struct bce_hip_ctx {
   bool k1_unique = false;                        // K1 ended with all rotations distinct
   bool k1_valid = false;                         // sa[sa_res] / rank hold this input's suffix order (K1 ran; no injected BWT)
   int sa_res = 0;
+  // K1 in two halves (k1_first_sort / k1_finish): which of sa[] / key[] / khi[] holds the first sort's result, the bytes of a
+  // rotation it has ordered, and whether that order was the final one already
+  int k1_res = 0;
+  uint32_t k1_h = 0;
+  bool k1_first_final = false;
   // debug knobs (bce_hip_debug_set): 0 = default
   uint32_t dbg_dfs_budget = 0, dbg_no_dfs = 0, dbg_no_tail = 0, dbg_no_skip = 0, dbg_no_small = 0, dbg_step_small = 0, dbg_no_fused = 0, dbg_no_local = 0, dbg_capp_div = 0, dbg_local_from = 0, dbg_local_budget = 0, dbg_tail_round = 0;
   uint32_t dbg_dec_budget = 0;                   // knob 13: the decoder's query budget (0 = 2^30)
@@ -407,6 +414,7 @@ inline int bce_guarded(bce_hip_ctx *c, F &&body) {
 struct PhaseScope {
   PhaseScope(bce_hip_ctx *c, int phase) : c_(c) { c_->phase = phase; }
   ~PhaseScope() { c_->phase = 0; }
+  void set(int phase) { c_->phase = phase; }     // an entry point that runs several phases in turn
   PhaseScope(const PhaseScope &) = delete;
   PhaseScope &operator=(const PhaseScope &) = delete;
  private:
@@ -439,6 +447,14 @@ inline uint32_t ceil_log2(uint32_t v) { uint32_t b = 0; while ((1ull << b) < v) 
 
 // ---- stage implementations (one .hip file each) ----
 int k1_bwt(bce_hip_ctx *c);                         // k1_bwt.hip
+// K1 in two halves, where k1_two_halves() says the wide first sort applies: k1_first_sort orders the rotations by their first
+// *h_symbols bytes, k1_provisional_bwt queues the BWT of that order into c->bwt, k1_finish is the rest of the sort and
+// k1_final_bwt the BWT of the finished order (have_bwt: c->bwt holds it already) and offset_.  k1_bwt is all of it in one call.
+bool k1_two_halves(const bce_hip_ctx *c);
+int k1_first_sort(bce_hip_ctx *c, uint32_t *h_symbols);
+int k1_provisional_bwt(bce_hip_ctx *c);
+int k1_finish(bce_hip_ctx *c);
+int k1_final_bwt(bce_hip_ctx *c, bool have_bwt);
 int k1_divbwt(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n, uint32_t *pidx);   // the libdivsufsort seam
 int kd_inverse_bw_transform(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n, uint32_t idx);   // kd_decode.hip
 // kd_decode.hip, test hooks: the decoder's planes() and inverse_bwt() stages on arrays of the caller's in device memory

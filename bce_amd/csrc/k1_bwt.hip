@@ -18,6 +18,9 @@
 //     pass.  Groups larger than 2048 are DEFERRED to one wide radix sort on (group number, rank[p + h]).  New ranks are
 //     applied by a second kernel: a gather of another workgroup must never see a rank of this round (mixing old and new
 //     ranks inside one comparison can order two suffixes wrongly).
+// The sort comes in two halves (k1_first_sort: the first sort alone; k1_finish: ranks and every later round) so that the one-shot
+// compression can gather a provisional BWT between them and start the enumeration on it (api.hip compress_early);
+// k1_bwt runs both and the final gather.
 // The sorter of rounds 1-2 stays as k1_sort_rotations_v1 behind BCE_K1_V1=1 for A/B runs only: a 4-byte first key (4 radix
 // passes), then full rounds in which the sequence SA[j]-h (j ascending) is already ordered by rank[p+h], so a STABLE sort
 // of it by rank[p] alone orders by (rank[p], rank[p+h]) (the Manber-Myers induction as a stable LSD radix sort).
@@ -797,8 +800,45 @@ __global__ __launch_bounds__(K1_T) void k1_defer_flags_kernel(const uint32_t *__
   }
 }
 
-static int k1_sort_rotations(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool sentinel) {
-  if (getenv("BCE_K1_V1")) return k1_sort_rotations_v1(c, T, n, sentinel);
+// Elements from which the two rank scatters are done as sorts (K1_PART_MIN; BCE_K1_PART_MIN overrides it, read once).
+static uint32_t k1_part_min() {
+  static const uint32_t part_min = getenv("BCE_K1_PART_MIN") ? (uint32_t)strtoul(getenv("BCE_K1_PART_MIN"), nullptr, 10) : K1_PART_MIN;
+  return part_min;
+}
+
+// The sorter's arrays and its trace, as both halves of the sort see them (everything is the context's: k1_first_sort_wide sizes it).
+struct K1View {
+  bce_hip_ctx *c;
+  uint32_t n, g;
+  K1Plan pl;
+  uint32_t *blockmax, *scalars;  // scalars: [0] groups, [1] offset, [2] active elements, [3] deferred elements, [4..5] deferred list;
+                                 // histogram; code table; a second per-block array
+  uint32_t *rank, *k2, *nrk;
+  uint8_t *flag;
+  uint32_t *lo[2], *hi[2], *val[2];
+  bool trace;
+  double t_prev;
+  explicit K1View(bce_hip_ctx *ctx, uint32_t n_) : c(ctx), n(n_), g(grid_for(n_)), pl(k1_plan(n_)) {
+    blockmax = c->blk.as<uint32_t>();
+    scalars = blockmax + K1_MAXB;
+    rank = c->rank.as<uint32_t>(); k2 = c->k2.as<uint32_t>(); nrk = c->nrk.as<uint32_t>();
+    flag = c->kflag.as<uint8_t>();
+    for (int i = 0; i < 2; ++i) { lo[i] = c->key[i].as<uint32_t>(); hi[i] = c->khi[i].as<uint32_t>(); val[i] = c->sa[i].as<uint32_t>(); }
+    trace = getenv("BCE_K1_TRACE") != nullptr;
+    t_prev = now_s();
+  }
+  void lap(const char *what, uint64_t h, uint32_t m, uint32_t nd) {
+    if (!trace) return;
+    (void)hipStreamSynchronize(c->stream);
+    const double t = now_s();
+    fprintf(stderr, "k1 %p: %-10s h %llu active %u deferred %u (+%.2f ms)\n", (void *)c, what, (unsigned long long)h, m, nd, (t - t_prev) * 1e3);
+    t_prev = t;
+  }
+};
+
+// First half of the sort: the rotations ordered by their first c->k1_h symbols (one byte each), ties by position, in
+// sa[c->k1_res]; the sorted keys beside them.  Nothing of the rank array yet.
+static int k1_first_sort_wide(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool sentinel) {
   const size_t b4 = (size_t)n * 4;
   for (int i = 0; i < 2; ++i) { BCE_TRY(ensure(c, c->sa[i], b4)); BCE_TRY(ensure(c, c->key[i], b4)); BCE_TRY(ensure(c, c->khi[i], b4)); }
   BCE_TRY(ensure(c, c->rank, b4));
@@ -806,23 +846,10 @@ static int k1_sort_rotations(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool 
   BCE_TRY(ensure(c, c->nrk, b4));
   BCE_TRY(ensure(c, c->kflag, (size_t)n + 16));
   for (int i = 0; i < 2; ++i) { BCE_TRY(ensure(c, c->act[i], b4)); BCE_TRY(ensure(c, c->actv[i], b4)); }
-  const K1Plan pl = k1_plan(n);
   BCE_TRY(ensure(c, c->blk, (size_t)(K1_MAXB + K1_SC_CODE + 128 + K1_MAXB) * 4));
-  uint32_t *blockmax = c->blk.as<uint32_t>();
-  uint32_t *scalars = blockmax + K1_MAXB;  // [0] groups, [1] offset, [2] active elements, [3] deferred elements, [4..5] deferred list;
-                                           // histogram; code table; a second per-block array
-  uint32_t *rank = c->rank.as<uint32_t>(), *k2 = c->k2.as<uint32_t>(), *nrk = c->nrk.as<uint32_t>();
-  uint8_t *flag = c->kflag.as<uint8_t>();
-  const uint32_t g = grid_for(n);
-  const bool trace = getenv("BCE_K1_TRACE") != nullptr;
-  double t_prev = now_s();
-  auto lap = [&](const char *what, uint64_t h, uint32_t m, uint32_t nd) {
-    if (!trace) return;
-    (void)hipStreamSynchronize(c->stream);
-    const double t = now_s();
-    fprintf(stderr, "k1 %p: %-10s h %llu active %u deferred %u (+%.2f ms)\n", (void *)c, what, (unsigned long long)h, m, nd, (t - t_prev) * 1e3);
-    t_prev = t;
-  };
+  K1View v(c, n);
+  uint32_t *const scalars = v.scalars;
+  const uint32_t g = v.g;
 
   // ---- alphabet: the symbols that occur, in byte order, ceil(log2) bits each ----
   const uint32_t nbytes = sentinel ? n - 1u : n;
@@ -840,7 +867,7 @@ static int k1_sort_rotations(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool 
   // (diagnostic: a narrower first key -- more of the order is left to the segmented and active rounds; measured at 10^8 B,
   //  text / natural corpus / binary corpus: 64 bits 16.9 / 33.3 / 28.2 ms, 54: 17.8 / 36.1 / 29.1, 48: 18.7 / 35.9 / 28.9,
   //  40: 19.5 / 38.1 / 30.7, 32: 23.3 / 41.9 / 32.7 -- every pass of the wide sort earns more than it costs)
-  if (const char *e = getenv("BCE_K1_KEYBITS")) { const uint32_t v = (uint32_t)strtoul(e, nullptr, 10); if (v >= bits && v / bits < nsym) nsym = v / bits; }
+  if (const char *e = getenv("BCE_K1_KEYBITS")) { const uint32_t kb = (uint32_t)strtoul(e, nullptr, 10); if (kb >= bits && kb / bits < nsym) nsym = kb / bits; }
   const uint32_t keybits = nsym * bits;
   {
     if (!c->h_small) BCE_TRY(pin_alloc(c, &c->h_small, 4096));
@@ -849,22 +876,38 @@ static int k1_sort_rotations(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool 
   }
 
   // ---- first sort: 64-bit keys of nsym symbols ----
-  uint32_t *lo[2] = {c->key[0].as<uint32_t>(), c->key[1].as<uint32_t>()};
-  uint32_t *hi[2] = {c->khi[0].as<uint32_t>(), c->khi[1].as<uint32_t>()};
-  uint32_t *val[2] = {c->sa[0].as<uint32_t>(), c->sa[1].as<uint32_t>()};
   {
     const uint32_t per = K1_T * K1I_E;
     hipLaunchKernelGGL(k1_init64_kernel, dim3((uint32_t)(((uint64_t)n + per - 1) / per)), dim3(K1_T), 0, c->stream, T, n, nbytes,
-                       reinterpret_cast<const uint16_t *>(scalars + K1_SC_CODE), bits, nsym, lo[0], hi[0], val[0]);
+                       reinterpret_cast<const uint16_t *>(scalars + K1_SC_CODE), bits, nsym, v.lo[0], v.hi[0], v.val[0]);
   }
   int res = 0;
-  BCE_TRY(radix_sort_wide(c, lo, hi, val, n, keybits, &res, 9));     // (9-bit digits: a 10-bit pass costs 1.0 ms at 10^8, a 9-bit one 0.57)
-  lap("first sort", nsym, n, 0);
+  BCE_TRY(radix_sort_wide(c, v.lo, v.hi, v.val, n, keybits, &res, 9));     // (9-bit digits: a 10-bit pass costs 1.0 ms at 10^8, a 9-bit one 0.57)
+  v.lap("first sort", nsym, n, 0);
+  BCE_HIP_TRY(c, hipGetLastError());
+  c->k1_res = res;
+  c->k1_h = nsym;
+  return BCE_HIP_OK;
+}
+
+// Second half: ranks from the sorted keys, then the segmented rounds until nothing is active.  It reorders sa[c->k1_res] inside
+// the groups the first half left tied, in place.  c->k1_first_final: the first half had already settled every rotation.
+static int k1_finish_wide(bce_hip_ctx *c, uint32_t n) {
+  K1View v(c, n);
+  const K1Plan pl = v.pl;
+  uint32_t *const blockmax = v.blockmax, *const scalars = v.scalars, *const rank = v.rank, *const k2 = v.k2, *const nrk = v.nrk;
+  uint8_t *const flag = v.flag;
+  uint32_t **const lo = v.lo, **const hi = v.hi, **const val = v.val;
+  const uint32_t g = v.g;
+  (void)g;
+  const int res = c->k1_res;
+  const uint32_t nsym = c->k1_h;
+  auto lap = [&](const char *what, uint64_t h, uint32_t m, uint32_t nd) { v.lap(what, h, m, nd); };
   // ranks: group heads from the sorted keys, one scatter; the first active list
   BCE_HIP_TRY(c, hipMemsetAsync(scalars, 0, 16, c->stream));
   hipLaunchKernelGGL(k1_heads_kernel, dim3(pl.nb), dim3(K1_T), 0, c->stream, hi[res], lo[res], n, pl.per_block, nrk, blockmax, scalars);
   const uint32_t rbits = ceil_log2(n);
-  static const uint32_t part_min = getenv("BCE_K1_PART_MIN") ? (uint32_t)strtoul(getenv("BCE_K1_PART_MIN"), nullptr, 10) : K1_PART_MIN;
+  const uint32_t part_min = k1_part_min();
   const bool sorted_apply = n >= part_min;
   if (sorted_apply) hipLaunchKernelGGL(k1_headidx_kernel, dim3(pl.nb), dim3(K1_T), 0, c->stream, nrk, blockmax, n, pl.per_block, k2);
   else hipLaunchKernelGGL(k1_apply_kernel, dim3(pl.nb), dim3(K1_T), 0, c->stream, nrk, blockmax, n, pl.per_block, val[res], rank);
@@ -888,6 +931,7 @@ static int k1_sort_rotations(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool 
   }
   BCE_TRY(read_back(c, &m, scalars + 2, 4));
   lap("first ranks", nsym, m, 0);
+  c->k1_first_final = m == 0 || nsym >= n;       // (no round follows: the order stays as the first sort left it)
 
   // ---- segmented rounds ----
   uint64_t h = nsym;
@@ -965,26 +1009,56 @@ static int k1_sort_rotations(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool 
   return BCE_HIP_OK;
 }
 
-int k1_bwt(bce_hip_ctx *c) {
-  const uint32_t n = c->n;
-  uint8_t *T = c->text.as<uint8_t>();
-  BCE_TRY(ensure(c, c->bwt, n));
-  uint8_t *bwt = c->bwt.as<uint8_t>();
+static int k1_sort_rotations(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool sentinel) {
+  if (getenv("BCE_K1_V1")) return k1_sort_rotations_v1(c, T, n, sentinel);
+  BCE_TRY(k1_first_sort_wide(c, T, n, sentinel));
+  return k1_finish_wide(c, n);
+}
+
+// ---- K1 in two halves (api.hip: the one-shot compression starts the enumeration between them) ----------------------------
+// Where the first sort is the wide one and the rank scatters are the direct ones: not behind BCE_K1_V1, not for one byte, not
+// from K1_PART_MIN elements up.
+bool k1_two_halves(const bce_hip_ctx *c) {
+  return c->n >= 2 && c->n < k1_part_min() && !getenv("BCE_K1_V1");
+}
+
+static int k1_begin(bce_hip_ctx *c) {
+  BCE_TRY(ensure(c, c->bwt, c->n));
   c->stats.sort_rounds = 0;
   c->k1_unique = false;
   c->k1_valid = false;
-  if (n == 1) {
-    BCE_HIP_TRY(c, hipMemcpyAsync(bwt, T, 1, hipMemcpyDeviceToDevice, c->stream));
-    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->offset = 0;
-    return BCE_HIP_OK;
-  }
-  BCE_TRY(k1_sort_rotations(c, T, n, false));
+  c->k1_first_final = false;
+  return BCE_HIP_OK;
+}
+
+int k1_first_sort(bce_hip_ctx *c, uint32_t *h_symbols) {
+  BCE_TRY(k1_begin(c));
+  BCE_TRY(k1_first_sort_wide(c, c->text.as<uint8_t>(), c->n, false));
+  if (h_symbols) *h_symbols = c->k1_h;
+  return BCE_HIP_OK;
+}
+
+// The BWT of the first sort's order (queued): it differs from the final one only inside groups of rows that share their
+// first k1_h bytes.
+int k1_provisional_bwt(bce_hip_ctx *c) {
+  const uint32_t n = c->n;
+  hipLaunchKernelGGL(k1_bwt_kernel, dim3(grid_for(n)), dim3(K1_T), 0, c->stream, c->text.as<uint8_t>(), c->sa[c->k1_res].as<uint32_t>(), n,
+                     c->bwt.as<uint8_t>());
+  BCE_HIP_TRY(c, hipGetLastError());
+  return BCE_HIP_OK;
+}
+
+int k1_finish(bce_hip_ctx *c) { return k1_finish_wide(c, c->n); }
+
+// The BWT of the finished order and offset_.  have_bwt: c->bwt already holds it (the provisional one, the first sort having
+// settled everything).
+int k1_final_bwt(bce_hip_ctx *c, bool have_bwt) {
+  const uint32_t n = c->n;
   const uint32_t g = grid_for(n);
   uint32_t *scalars = c->blk.as<uint32_t>() + K1_MAXB;   // [0] groups, [1] offset
   const uint32_t *sa = c->sa[c->sa_res].as<uint32_t>();
   BCE_HIP_TRY(c, hipMemsetAsync(scalars + 1, 0xFF, 4, c->stream));
-  hipLaunchKernelGGL(k1_bwt_kernel, dim3(g), dim3(K1_T), 0, c->stream, T, sa, n, bwt);
+  if (!have_bwt) hipLaunchKernelGGL(k1_bwt_kernel, dim3(g), dim3(K1_T), 0, c->stream, c->text.as<uint8_t>(), sa, n, c->bwt.as<uint8_t>());
   hipLaunchKernelGGL(k1_offset_kernel, dim3(g), dim3(K1_T), 0, c->stream, c->rank.as<uint32_t>(), n, scalars + 1);
   uint32_t off = 0;
   BCE_TRY(read_back(c, &off, scalars + 1, 4));
@@ -993,6 +1067,20 @@ int k1_bwt(bce_hip_ctx *c) {
   c->offset = off;
   c->k1_valid = true;
   return BCE_HIP_OK;
+}
+
+int k1_bwt(bce_hip_ctx *c) {
+  const uint32_t n = c->n;
+  uint8_t *T = c->text.as<uint8_t>();
+  BCE_TRY(k1_begin(c));
+  if (n == 1) {
+    BCE_HIP_TRY(c, hipMemcpyAsync(c->bwt.p, T, 1, hipMemcpyDeviceToDevice, c->stream));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->offset = 0;
+    return BCE_HIP_OK;
+  }
+  BCE_TRY(k1_sort_rotations(c, T, n, false));
+  return k1_final_bwt(c, false);
 }
 
 // ---- the libdivsufsort seam (include/divsufsort_hip.h; bce.cpp:901) -------------------------------------------------------
