@@ -123,6 +123,7 @@ SYMBOLS = [
     ("bce_hip_planes_from_ranks_device", C.c_int, [C.c_void_p, _vp, C.c_uint32, _vp, _vp, _vp]),
     ("bce_hip_unbwt_device", C.c_int, [C.c_void_p, _vp, C.c_uint32, C.c_uint32, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("bce_hip_lcp_reduce_device", C.c_int, [C.c_void_p, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp]),
+    ("bce_hip_top_classes_of_lcp_device", C.c_int, [C.c_void_p, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, _vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _vp]),
     ("bce_hip_coverage_of_lengths_device", C.c_int, [C.c_void_p, _vp, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
     ("bce_hip_count", C.c_int, [C.c_void_p, _u8p, _vp, C.c_uint32, _vp]),
     ("bce_hip_count_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, _vp]),
@@ -137,6 +138,8 @@ SYMBOLS = [
     ("bce_hip_lcp_device", C.c_int, [C.c_void_p, C.c_uint32, _vp]),
     ("bce_hip_kgrams", C.c_int, [C.c_void_p, _vp, C.c_uint32, _vp]),
     ("bce_hip_longest_repeat", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("bce_hip_top_kgrams", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _vp]),
+    ("bce_hip_top_kgrams_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _vp]),
     ("bce_hip_parse", C.c_int, [C.c_void_p, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _u8p, C.c_uint64, C.POINTER(ParseInfo)]),
     ("bce_hip_parse_device", C.c_int, [C.c_void_p, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(ParseInfo)]),
     ("bce_hip_patch", C.c_int, [C.c_void_p, _vp, C.c_uint64, _u8p, C.c_uint64, _u8p, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -185,6 +188,8 @@ LOCATE_LINEAR = 1                               # BCE_HIP_LOCATE_LINEAR
 MATCH_LINEAR = 1                                # BCE_HIP_MATCH_LINEAR
 MATCH_MAX_LEN = 4096                            # BCE_HIP_MATCH_MAX_LEN: a work bound per end position, not a format limit
 KGRAMS_MAX = 64                                 # BCE_HIP_KGRAMS_MAX: values of k in one bce_hip_kgrams call
+TOP_MAX = 1 << 20                               # BCE_HIP_TOP_MAX: the longest list of one bce_hip_top_kgrams call
+TOP_DTYPE = np.dtype([("count", "<u4"), ("row", "<u4"), ("pos", "<u4")])   # bce_hip_top_kgram as a numpy record
 E_OVERFLOW = -5                                 # BCE_HIP_E_OVERFLOW
 OP_LITERAL = 0xFFFFFFFF                         # BCE_HIP_OP_LITERAL: bce_hip_op::src of a literal run
 PARSE_MAX_LEN = 256                             # the default length bound of a parse: the search costs up to q * max_len lane steps
@@ -236,6 +241,31 @@ class KGram(C.Structure):
 
     def __repr__(self):
         return "KGram(%s)" % ", ".join("%s=%d" % kv for kv in self.as_dict().items())
+
+
+class TopKGram(C.Structure):
+    """bce_hip_top_kgram: one entry of the list of the most frequent k-grams (RankFile.top_kgrams)."""
+    _fields_ = [("count", C.c_uint32), ("row", C.c_uint32), ("pos", C.c_uint32)]
+
+
+class TopKGrams(list):
+    """What RankFile.top_kgrams returns: a list of (count, pos, row, bytes), most frequent first and equal counts in the order of
+    their bytes, with `distinct` (the number of distinct k-grams) and `size_hist` (32 ints: the k-grams whose count N has
+    floor(log2 N) = b) beside it."""
+
+    def __init__(self, entries, distinct, size_hist):
+        super().__init__(entries)
+        self.distinct = int(distinct)
+        self.size_hist = [int(v) for v in size_hist]
+
+
+def _top_limit(k, limit):
+    k, limit = int(k), int(limit)
+    if k < 0 or k > 0xFFFFFFFF:
+        raise ValueError("k is 0 .. %d" % MATCH_MAX_LEN)
+    if limit < 0 or limit > 0xFFFFFFFF:
+        raise ValueError("limit is 1 .. %d" % TOP_MAX)
+    return k, limit
 
 
 def entropy_from_sums(n, s_k, s_k1) -> float:
@@ -516,6 +546,32 @@ class RankFile:
         ln, a, b = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         self._c.check(self._c.lib.bce_hip_longest_repeat(self._c.h, int(max_len), C.byref(ln), C.byref(a), C.byref(b)), "bce_hip_longest_repeat")
         return ln.value, a.value, b.value
+
+    def top_kgrams(self, k, limit, with_bytes=True):
+        """The `limit` (1 .. 2^20) most frequent cyclic k-grams of the text (bce_hip_top_kgrams: selected, sorted and gathered on the
+        GPU) -> a TopKGrams list of (count, pos, row, bytes): by count descending and, among equal counts, in the order of the
+        bytes; pos is where one occurrence starts, row the first row of the k-gram among the sorted rotations, bytes the k-gram
+        (None with with_bytes=False).  `.distinct` and `.size_hist` come with it.  k: 0 .. 4096; k > n wraps around the text."""
+        k, limit = _top_limit(k, limit)
+        sound = 1 <= limit <= TOP_MAX and k <= MATCH_MAX_LEN             # (otherwise the library refuses: no room is made)
+        out = np.zeros(limit if sound else 1, dtype=TOP_DTYPE)
+        raw = np.zeros(max(1, limit * k) if sound else 1, dtype=np.uint8) if with_bytes else None
+        found, distinct, hist = C.c_uint32(0), C.c_uint64(0), (C.c_uint64 * 32)()
+        self._c.check(self._c.lib.bce_hip_top_kgrams(self._c.h, k, limit, out.ctypes.data, raw.ctypes.data if with_bytes else None,
+                                                     limit * k if with_bytes else 0, C.byref(found), C.byref(distinct), C.addressof(hist)), "bce_hip_top_kgrams")
+        ents = [(int(e["count"]), int(e["pos"]), int(e["row"]), raw[i * k:(i + 1) * k].tobytes() if with_bytes else None) for i, e in enumerate(out[:found.value])]
+        return TopKGrams(ents, distinct.value, hist)
+
+    def top_kgrams_device(self, k, limit, out_ptr, bytes_ptr=None, bytes_cap=0):
+        """bce_hip_top_kgrams_device: the same into device memory (int pointers: room for `limit` entries of three uint32 -- count,
+        row, pos -- and, unless bytes_ptr is None, for bytes_cap >= limit * k bytes) -> (found, distinct, size_hist).  Stream rule:
+        as count_device."""
+        k, limit = _top_limit(k, limit)
+        found, distinct, hist = C.c_uint32(0), C.c_uint64(0), (C.c_uint64 * 32)()
+        self._c.check(self._c.lib.bce_hip_top_kgrams_device(self._c.h, k, limit, None if out_ptr is None else int(out_ptr),
+                                                            None if bytes_ptr is None else int(bytes_ptr), int(bytes_cap), C.byref(found), C.byref(distinct),
+                                                            C.addressof(hist)), "bce_hip_top_kgrams_device")
+        return found.value, distinct.value, [int(v) for v in hist]
 
     def parse(self, query, min_len, max_len=PARSE_MAX_LEN):
         """`query` (a bytes-like, a second buffer) written as copies out of the text plus the bytes that are new (bce_hip_parse: the
@@ -839,6 +895,16 @@ def kgrams(data, ks, device=0, ctx=None):
     rf = RankFile(data, device=device, ctx=ctx)
     try:
         return rf.kgrams(ks)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def top_kgrams(data, k, limit, with_bytes=True, device=0, ctx=None):
+    """The `limit` most frequent cyclic k-grams of `data` (RankFile.top_kgrams): indexed, selected and sorted on the GPU."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.top_kgrams(k, limit, with_bytes=with_bytes)
     finally:
         if ctx is None:
             rf.close()
@@ -1204,6 +1270,17 @@ def lcp_reduce_device(ptr_lcp, n, ptr_sa, ks, ctx, repeat=True):
     ctx.check(ctx.lib.bce_hip_lcp_reduce_device(ctx.h, _ptr(ptr_lcp), int(n), _ptr(ptr_sa), karr.ctypes.data if len(karr) else None, len(karr),
                                                 C.addressof(out), C.addressof(rep) if repeat else None), "bce_hip_lcp_reduce_device")
     return [out[i] for i in range(len(karr))], (tuple(rep) if repeat else None)
+
+
+def top_classes_of_lcp_device(ptr_lcp, n, ptr_sa, k, limit, ctx):
+    """Test hook (bce_hip_top_classes_of_lcp_device): the selection of top_kgrams() on `n` uint32 words at device pointer `ptr_lcp`
+    read as an LCP array, with the `n` words at `ptr_sa` as the suffix array -> (a numpy record array (count, row, pos) of the
+    entries found, distinct, size_hist)."""
+    out = np.zeros(max(1, int(limit)), dtype=TOP_DTYPE)
+    found, distinct, hist = C.c_uint32(0), C.c_uint64(0), (C.c_uint64 * 32)()
+    ctx.check(ctx.lib.bce_hip_top_classes_of_lcp_device(ctx.h, _ptr(ptr_lcp), int(n), _ptr(ptr_sa), int(k), int(limit), out.ctypes.data, C.byref(found),
+                                                        C.byref(distinct), C.addressof(hist)), "bce_hip_top_classes_of_lcp_device")
+    return out[:found.value], distinct.value, [int(v) for v in hist]
 
 
 def coverage_of_lengths_device(ptr_len, q, min_len, ctx) -> int:

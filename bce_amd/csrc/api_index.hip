@@ -1,5 +1,5 @@
 // api_index.hip -- C ABI of the index queries (include/bce_hip.h): counts, positions, longest matches and coverage, the LCP array and
-// its reductions, parse and patch; and the two test hooks that run their block scans alone.  The device work is in kd_count /
+// its reductions, the list of the most frequent k-grams, parse and patch; and the three test hooks that run their block scans alone.  The device work is in kd_count /
 // kd_locate / kd_match / kd_lcp / kd_parse.hip.  Every query comes twice, for host buffers and for device buffers: the two differ
 // in staging and in the copy out, and in nothing else.
 //
@@ -96,6 +96,28 @@ int bce_hip_lcp_reduce_device(bce_hip_ctx *c, const void *d_lcp, uint32_t n, con
     if (repeat3) BCE_TRY(kd_longest_repeat(c, sa, lcp.as<uint32_t>(), n, repeat3));
     return BCE_HIP_OK;
   });
+}
+
+// the selection of bce_hip_top_kgrams alone: the entries are staged in top_out, as a call with host buffers stages them
+int bce_hip_top_classes_of_lcp_device(bce_hip_ctx *c, const void *d_lcp, uint32_t n, const void *d_sa, uint32_t k, uint32_t limit,
+                                      bce_hip_top_kgram *out, uint32_t *found, uint64_t *distinct, uint64_t size_hist[32]) {
+  if (!c || !d_lcp || !d_sa || !out || !found || n == 0 || n > 0x7FFFFFFFu || k > BCE_HIP_MATCH_MAX_LEN || limit < 1 || limit > BCE_HIP_TOP_MAX) return BCE_HIP_E_ARG;
+  uint32_t got = 0;
+  uint64_t classes = 0, hist[32];
+  BCE_TRY(query_call(c, 0, [&]() -> int {
+    DevBuf &lcp = c->qbuf[qb::rep_lcp], &ent = c->qbuf[qb::top_out];
+    const size_t words = (size_t)n * 4;
+    BCE_TRY(ensure(c, lcp, words));
+    BCE_TRY(ensure(c, ent, (size_t)(limit < n ? limit : n) * sizeof(bce_hip_top_kgram)));
+    BCE_HIP_TRY(c, hipMemcpyAsync(lcp.p, d_lcp, words, hipMemcpyDeviceToDevice, c->stream));
+    BCE_TRY(kd_top_kgrams(c, static_cast<const uint32_t *>(d_sa), lcp.as<uint32_t>(), n, nullptr, k, limit, ent.as<bce_hip_top_kgram>(), nullptr, &got,
+                          &classes, hist));
+    return copy_out(c, out, ent, (size_t)got * sizeof(bce_hip_top_kgram));
+  }));
+  *found = got;
+  if (distinct) *distinct = classes;
+  if (size_hist) memcpy(size_hist, hist, sizeof hist);
+  return BCE_HIP_OK;
 }
 
 int bce_hip_coverage_of_lengths_device(bce_hip_ctx *c, const void *d_len, uint64_t q, uint32_t min_len, uint64_t *covered) {
@@ -331,6 +353,64 @@ int bce_hip_longest_repeat(bce_hip_ctx *c, uint32_t max_len, uint32_t *len, uint
     *len = res[0]; *pos_a = res[1]; *pos_b = res[2];
     return BCE_HIP_OK;
   });
+}
+
+// ---- the most frequent k-grams of the text, as a list (kd_lcp.hip: kd_top_kgrams; top_step.h) --------------------------------------
+// bce_hip_kgrams' rule and order of refusals.  found, distinct and size_hist are written once everything queued has completed.
+static int top_args(bce_hip_ctx *c, uint32_t k, uint32_t limit, const void *bytes, uint64_t bytes_cap, const uint32_t *found, const uint32_t **sa) {
+  if (!c) return BCE_HIP_E_ARG;
+  if (k > BCE_HIP_MATCH_MAX_LEN) { snprintf(c->err, sizeof c->err, "top k-grams: k = %u, outside 0 .. %u", k, BCE_HIP_MATCH_MAX_LEN); return BCE_HIP_E_ARG; }
+  if (limit < 1 || limit > BCE_HIP_TOP_MAX) { snprintf(c->err, sizeof c->err, "top k-grams: a limit of %u, outside 1 .. %u", limit, BCE_HIP_TOP_MAX); return BCE_HIP_E_ARG; }
+  if (!found) { snprintf(c->err, sizeof c->err, "top k-grams: no place for the number of entries"); return BCE_HIP_E_ARG; }
+  if (bytes && bytes_cap < (uint64_t)limit * k) {
+    snprintf(c->err, sizeof c->err, "top k-grams: room for %llu bytes, %u entries of %u bytes need %llu", (unsigned long long)bytes_cap, limit, k,
+             (unsigned long long)((uint64_t)limit * k));
+    return BCE_HIP_E_ARG;
+  }
+  return text_state(c, sa, "top k-grams");
+}
+
+int bce_hip_top_kgrams(bce_hip_ctx *c, uint32_t k, uint32_t limit, bce_hip_top_kgram *out, uint8_t *bytes, uint64_t bytes_cap, uint32_t *found,
+                       uint64_t *distinct, uint64_t size_hist[32]) {
+  const uint32_t *sa = nullptr;
+  BCE_TRY(top_args(c, k, limit, bytes, bytes_cap, found, &sa));
+  if (!out) return BCE_HIP_E_ARG;
+  uint32_t got = 0;
+  uint64_t classes = 0, hist[32];
+  BCE_TRY(query_call(c, 3, [&]() -> int {
+    DevBuf &ent = c->qbuf[qb::top_out], &gram = c->qbuf[qb::top_bytes];
+    const bool with_bytes = bytes && k;
+    const uint32_t room = limit < c->n ? limit : c->n;                 // (there are at most n classes)
+    BCE_TRY(lcp_own(c, sa, k ? k : 1u));
+    BCE_TRY(ensure(c, ent, (size_t)room * sizeof(bce_hip_top_kgram)));
+    if (with_bytes) BCE_TRY(ensure(c, gram, (size_t)room * k));
+    BCE_TRY(kd_top_kgrams(c, sa, c->qbuf[qb::rep_lcp].as<uint32_t>(), c->n, c->text.as<uint8_t>(), k, limit, ent.as<bce_hip_top_kgram>(),
+                          with_bytes ? gram.as<uint8_t>() : nullptr, &got, &classes, hist));
+    BCE_TRY(copy_out(c, out, ent, (size_t)got * sizeof(bce_hip_top_kgram)));
+    return with_bytes ? copy_out(c, bytes, gram, (size_t)got * k) : BCE_HIP_OK;
+  }));
+  *found = got;
+  if (distinct) *distinct = classes;
+  if (size_hist) memcpy(size_hist, hist, sizeof hist);
+  return BCE_HIP_OK;
+}
+
+int bce_hip_top_kgrams_device(bce_hip_ctx *c, uint32_t k, uint32_t limit, void *d_out, void *d_bytes, uint64_t bytes_cap, uint32_t *found,
+                              uint64_t *distinct, uint64_t size_hist[32]) {
+  const uint32_t *sa = nullptr;
+  BCE_TRY(top_args(c, k, limit, d_bytes, bytes_cap, found, &sa));
+  if (!d_out) return BCE_HIP_E_ARG;
+  uint32_t got = 0;
+  uint64_t classes = 0, hist[32];
+  BCE_TRY(query_call(c, 3, [&]() -> int {
+    BCE_TRY(lcp_own(c, sa, k ? k : 1u));
+    return kd_top_kgrams(c, sa, c->qbuf[qb::rep_lcp].as<uint32_t>(), c->n, c->text.as<uint8_t>(), k, limit, static_cast<bce_hip_top_kgram *>(d_out),
+                         static_cast<uint8_t *>(d_bytes), &got, &classes, hist);
+  }));
+  *found = got;
+  if (distinct) *distinct = classes;
+  if (size_hist) memcpy(size_hist, hist, sizeof hist);
+  return BCE_HIP_OK;
 }
 
 // ---- a second buffer as a delta against the text: parse and patch (kd_parse.hip) ----------------------------------------------------

@@ -146,6 +146,10 @@ enum Id {
   rep_res,                                       // kd_lcp.hip: its result words, up to 64 k-gram records or the longest repeat's three (a buffer of its own, as mat_res)
   rep_bsum,                                      // the class and repeat reductions' per-block parts and maxima
   rep_lcp,                                       // the LCP array of a call that does not bring device memory for it: n words (grow-only, never kept as a cache)
+  top_res,                                       // kd_lcp.hip, the most frequent k-grams: the 32 counters of the size histogram (a buffer of its own, as rep_res)
+  top_bsum,                                      // per block: its candidates (then their offsets), its class-start carry, its 32 counters
+  top_key0, top_key1, top_val0, top_val1,        // (key_max - size, first row) of every candidate: both halves of the sort's ping-pong, sized by the histogram's count
+  top_out, top_bytes,                            // bce_hip_top_kgrams with host buffers, and the hook: the entries and the k-grams' bytes, staged (all grow-only)
   par_res,                                       // kd_parse.hip: the result words of the parse and of the patch (a buffer of its own, as mat_res)
   par_exit, par_entry, par_flag,                 // the parse: every position's exit from its block (+ 1), the blocks' entries, the flag byte per position
   par_bsum, par_bcnt,                            // the blocks' sums (parse: heads and literals packed; patch: lengths, literal lengths) and their counts / flag bits
@@ -480,6 +484,9 @@ int kd_coverage(bce_hip_ctx *c, const uint32_t *d_len, uint32_t q, uint32_t min_
 int kd_lcp(bce_hip_ctx *c, const uint32_t *sa, uint32_t max_len, uint32_t *d_lcp);
 int kd_kgrams(bce_hip_ctx *c, const uint32_t *sa, const uint32_t *d_lcp, uint32_t n, const uint32_t *ks, uint32_t nk, bce_hip_kgram *out);
 int kd_longest_repeat(bce_hip_ctx *c, const uint32_t *sa, const uint32_t *d_lcp, uint32_t n, uint32_t res[3]);
+// the first min(limit, distinct) classes of k by size descending, first row ascending, into device memory; complete on return
+int kd_top_kgrams(bce_hip_ctx *c, const uint32_t *sa, const uint32_t *d_lcp, uint32_t n, const uint8_t *text, uint32_t k, uint32_t limit,
+                  bce_hip_top_kgram *d_out, uint8_t *d_bytes, uint32_t *found, uint64_t *distinct, uint64_t size_hist[32]);
 // kd_parse.hip: the query as copies out of the text plus literal bytes, from its lengths and positions; and back.  Both wait.
 int kd_parse(bce_hip_ctx *c, const uint32_t *d_len, const uint32_t *d_pos, const uint8_t *d_query, uint32_t q, uint32_t min_len, bool sizing,
              uint32_t *d_ops, uint64_t ops_cap, uint8_t *d_lits, uint64_t lits_cap, bce_hip_parse_info *info);

@@ -10,6 +10,7 @@
 //   bce -gr MINLEN file query_file out.bcd, -grd ... archive ...   (extension) writes query_file as a delta against the first: copies out of it plus the new bytes
 //   bce -ga file in.bcd out_file, -gad archive in.bcd out_file     (extension) rebuilds a file from the first and a delta, both sides checked by CRC-32
 //   bce -gk K file, -gkd K archive          (extension) the k-grams of the circular text for k = 0..K: how many, how many occur once, the most frequent, H_k; the longest repeat
+//   bce -gf K N file, -gfd K N archive      (extension) the N most frequent K-grams of the circular text: count, one position and the bytes of each
 // Banner, usage text, summary line, argument detection and exit codes follow the reference
 // (banner :1377-1379, -c :1403-1427, -d :1428-1472, usage :1473-1483).  -d uses the GPU-assisted decoder (kd_decode.hip), -ds the host decoder (decoder.cpp);
 // -s runs the enumeration on the GPU in scan mode and the ScanCoder optimisation on the host (scan_coder.cpp).
@@ -36,6 +37,7 @@
 #include <vector>
 
 #include "../../include/bce_hip.h"
+#include "top_step.h"
 
 // "Coded: %u.%02u %%\r" as BCE::code prints it (bce.cpp:1354-1358); cleared at the end like :1372
 static void progress(uint64_t done, uint64_t total, void *user) {
@@ -136,6 +138,8 @@ extern "C" int bce_hip_locate(bce_hip_ctx *ctx, const uint8_t *patterns, const u
 extern "C" int bce_hip_coverage(bce_hip_ctx *ctx, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t flags, uint64_t *covered) __attribute__((weak));
 extern "C" int bce_hip_kgrams(bce_hip_ctx *ctx, const uint32_t *ks, uint32_t nk, bce_hip_kgram *out) __attribute__((weak));
 extern "C" int bce_hip_longest_repeat(bce_hip_ctx *ctx, uint32_t max_len, uint32_t *len, uint32_t *pos_a, uint32_t *pos_b) __attribute__((weak));
+extern "C" int bce_hip_top_kgrams(bce_hip_ctx *ctx, uint32_t k, uint32_t limit, bce_hip_top_kgram *out, uint8_t *bytes, uint64_t bytes_cap,
+                                  uint32_t *found, uint64_t *distinct, uint64_t size_hist[32]) __attribute__((weak));
 extern "C" int bce_hip_parse(bce_hip_ctx *ctx, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t max_len, bce_hip_op *ops, uint64_t ops_cap,
                              uint8_t *lits, uint64_t lits_cap, bce_hip_parse_info *info) __attribute__((weak));
 extern "C" int bce_hip_patch(bce_hip_ctx *ctx, const bce_hip_op *ops, uint64_t nops, const uint8_t *lits, uint64_t nlits, uint8_t *out, uint64_t cap,
@@ -457,6 +461,10 @@ static uint64_t seam_matches(const uint8_t *t, size_t n, const uint8_t *pat, siz
   return found;
 }
 constexpr uint32_t kMaxKgramOrder = 32;                            // -gk / -gkd: the largest K
+// `-gf K N file` / `-gfd K N archive` (most frequent): the file or archive is read, judged, decoded and indexed in the same way.  A head
+// line, then the first N classes of bce_hip_top_kgrams for K, most frequent first and among equal counts in the order of the bytes:
+// count, the position of one occurrence, the K bytes (top_step.h: top_escape); then the distinct K-grams and the text's size.
+constexpr uint32_t kMaxTopLen = 256, kMaxTopCount = 65536;          // -gf / -gfd: the largest K and N
 // `-gr MINLEN file query_file out.bcd` / `-grd` (delta): the file or archive is read, judged, decoded and indexed in the same way,
 // query_file judged as -gm's; the query is parsed on the GPU (bce_hip_parse at the bounds MINLEN and max(256, MINLEN)) and written
 // as a delta file.  `-ga file in.bcd out_file` / `-gad` (apply): in.bcd is read and judged as -d judges an archive, before the
@@ -482,7 +490,7 @@ static void write_delta_header(uint8_t *p, const DeltaHeader &h) {
   memcpy(p, "BCED", 4); memcpy(p + 4, &ver, 4); memcpy(p + 8, &h.n, 8); memcpy(p + 16, &h.base_crc, 4); memcpy(p + 20, &h.q, 8);
   memcpy(p + 28, &h.crc, 4); memcpy(p + 32, &h.min_len, 4); memcpy(p + 36, &h.max_len, 4); memcpy(p + 40, &h.nops, 8); memcpy(p + 48, &h.nlits, 8);
 }
-// ---- the front of all twelve index commands ----
+// ---- the front of all fourteen index commands ----
 // The indexed file (or archive) and the command's second file are read beside the runtime's start-up and judged in this order: the
 // file or archive, the second file, the device; an archive's blocks are then decoded into one text.  Owns the context: an error
 // path destroys it, index_done() leaves it to fast_exit.
@@ -646,6 +654,29 @@ static int kgrams_command(uint32_t K, const char *path, bool in_archive) {
   return index_done(in);
 }
 
+// -gf / -gfd
+static int top_command(uint32_t K, uint32_t N, const char *path, bool in_archive) {
+  IndexInput in;
+  if (const int ec = index_open(in, path, in_archive, nullptr, kNoSecond, bce_hip_top_kgrams != nullptr)) return ec;
+  std::vector<bce_hip_top_kgram> ent(N);                              // (at most 65536 entries of 256 bytes: 16 MB)
+  std::vector<uint8_t> gram((size_t)N * K);
+  uint32_t found = 0;
+  uint64_t distinct = 0;
+  int rc = index_text(in);
+  if (rc == 0) rc = bce_hip_top_kgrams(in.ctx, K, N, ent.data(), gram.data(), gram.size(), &found, &distinct, nullptr);
+  if (rc != 0) return index_failed(in, "Top k-grams", rc);
+  printf("most frequent %u-grams of the circular text: count position bytes\n", K);
+  std::string line;
+  for (uint32_t e = 0; e < found; ++e) {
+    line.clear();
+    char esc[5];
+    for (uint32_t j = 0; j < K; ++j) { bce::top_escape(gram[(size_t)e * K + j], esc); line += esc; }
+    printf("%u %u %s\n", ent[e].count, ent[e].pos, line.c_str());
+  }
+  printf("%llu distinct, %zu bytes\n", (unsigned long long)distinct, in.n);
+  return index_done(in);
+}
+
 // -gr / -grd
 static int delta_command(uint32_t min_len, const char *path, bool in_archive, const char *query_path, const char *out_path) {
   IndexInput in;
@@ -724,6 +755,18 @@ static int parse_order(const char *s) {
   return (int)v;
 }
 
+// K of -gf / -gfd (1 .. 256) and its N (1 .. 65536): decimal digits only; anything else: 0
+static uint32_t parse_count(const char *s, uint32_t most) {
+  uint32_t v = 0;
+  if (!*s) return 0;
+  for (; *s; ++s) {
+    if (*s < '0' || *s > '9') return 0;
+    v = v * 10 + (uint32_t)(*s - '0');
+    if (v > most) return 0;
+  }
+  return v;
+}
+
 static int usage() {
   printf("Usage:\n");
   printf("  bce -c archive.bce file [config.bcc]\n");
@@ -784,6 +827,12 @@ static int usage() {
   printf("\n");
   printf("  bce -gad archive.bce in.bcd out_file\n");
   printf("   The same from what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU (extension)\n");
+  printf("\n");
+  printf("  bce -gf K N file\n");
+  printf("   Prints the N (1..65536) most frequent K-grams (K = 1..256) of the circular text of \"file\", most frequent first and equal counts in the order of their bytes: count, the position of one occurrence and the bytes (\\xHH for all but printable ASCII), then the number of distinct K-grams; selected and sorted on the GPU from the LCP array of the sorted rotations (extension)\n");
+  printf("\n");
+  printf("  bce -gfd K N archive.bce\n");
+  printf("   The same list for what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
   return 0;
 }
 
@@ -1063,6 +1112,9 @@ int main(int argc, char **argv) {
     return apply_command(argv[2], argv[1][3] == 'd', argv[3], argv[4]);
   } else if (argc == 4 && (strcmp(argv[1], "-gk") == 0 || strcmp(argv[1], "-gkd") == 0) && parse_order(argv[2]) >= 0) {
     return kgrams_command((uint32_t)parse_order(argv[2]), argv[3], argv[1][3] == 'd');
+  } else if (argc == 5 && (strcmp(argv[1], "-gf") == 0 || strcmp(argv[1], "-gfd") == 0) && parse_count(argv[2], kMaxTopLen) != 0 &&
+             parse_count(argv[3], kMaxTopCount) != 0) {
+    return top_command(parse_count(argv[2], kMaxTopLen), parse_count(argv[3], kMaxTopCount), argv[4], argv[1][3] == 'd');
   } else if (argc == 4 && argv[1][0] == '-' && argv[1][1] == 's') {
     // Scan (bce.cpp:1384-1402): enumeration on the GPU, ScanCoder optimisation on the host, 288-byte config out
     auto start = std::chrono::high_resolution_clock::now();

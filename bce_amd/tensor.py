@@ -311,6 +311,35 @@ def entropy_profile_in_archive(blob, K, device="cuda:0"):
     return entropy_profile_tensor(decompress_container_tensor(blob, device=device), K)
 
 
+def top_kgrams_tensor(t, k, limit, with_bytes=True, ctx=None):
+    """The `limit` most frequent cyclic k-grams of the 1-D uint8 CUDA tensor `t` (api.RankFile.top_kgrams with everything left on
+    the device: bce_hip_top_kgrams_device) -> (entries, grams, distinct, size_hist): entries an int32 tensor (found, 3) of (count,
+    row, pos) on t's device, by count descending and equal counts in the order of the bytes; grams a uint8 tensor (found, k) of the
+    k-grams (None with with_bytes=False); distinct and size_hist as api.TopKGrams has them.  Only those 33 numbers and `found`
+    reach the host.  Synchronises t's current stream first; `ctx` (an api._Ctx of t's device) is reused if given."""
+    k, limit = api._top_limit(k, limit)
+    sound = 1 <= limit <= api.TOP_MAX and k <= api.MATCH_MAX_LEN          # (otherwise the library refuses: no room is made)
+
+    def use(rf):
+        ent = torch.zeros((limit if sound else 1, 3), dtype=torch.int32, device=t.device)
+        grams = torch.zeros((limit if sound else 1, max(k, 1) if sound else 1), dtype=torch.uint8, device=t.device) if with_bytes else None
+        torch.cuda.current_stream(t.device).synchronize()            # (the zero fills are done before the library's stream writes)
+        found, distinct, hist = rf.top_kgrams_device(k, limit, ent.data_ptr(), grams.data_ptr() if with_bytes else None, limit * k if with_bytes else 0)
+        if with_bytes:
+            grams = grams.reshape(-1)[:found * k].reshape(found, k)
+        return ent[:found], grams, distinct, hist
+    return _indexed(t, "top_kgrams_tensor", ctx, use)
+
+
+def top_kgrams_in_archive(blob, k, limit, with_bytes=True, device="cuda:0"):
+    """top_kgrams_tensor on what an archive holds, decoded as count_in_archive decodes it: into ONE tensor on the device, so the
+    k-grams across block boundaries count.  A container of 2^31 bytes or more: ValueError, before anything is decoded."""
+    total = sum(t[0] for t in _blocks_of(blob))
+    if total > _MAX_BLOCK:
+        raise ValueError("the archive holds %d bytes: one index covers one text of less than 2^31" % total)
+    return top_kgrams_tensor(decompress_container_tensor(blob, device=device), k, limit, with_bytes=with_bytes)
+
+
 def decompress_tensor(archive, device="cuda:0", out=None, ctx=None):
     """The GPU-assisted decoder with the text left on the device (bce_hip_decompress_to_device) -> a 1-D uint8 tensor there.
 

@@ -411,6 +411,36 @@ int bce_hip_kgrams(bce_hip_ctx *ctx, const uint32_t *ks, uint32_t nk, bce_hip_kg
  * bce_hip_lcp; all three outputs are required. */
 int bce_hip_longest_repeat(bce_hip_ctx *ctx, uint32_t max_len, uint32_t *len, uint32_t *pos_a, uint32_t *pos_b);
 
+/* ---- extension: the MOST FREQUENT k-grams of the input, as a list (kd_lcp.hip, top_step.h) ---------------------------------------
+ * For one k in 0 .. BCE_HIP_MATCH_MAX_LEN, the classes of bce_hip_kgrams (circular text: k = 0 gives one class of n rows, k > n wraps
+ * around, n == 1 gives the one class {1, 0, 0} for every k) ordered by size descending and, among equal sizes, by first row
+ * ascending.  Rows are sorted rotations, so the tie order is the lexicographic order of the k-grams as byte strings: the order,
+ * every count and every row are a function of the text alone.  The first min(limit, distinct) classes are returned:
+ *   out[e].count  N(w);    out[e].row  the class's first row s;    out[e].pos  sa[s], the start of ONE occurrence (which of the tied
+ *                 rotations of a periodic text it names is not specified; 0 for n == 1);
+ *   bytes[e * k .. e * k + k)  T[(pos + j) mod n], the k-gram itself.  bytes may be NULL: the bytes are not wanted.  With bytes
+ *                 non-NULL, bytes_cap must be at least limit * k: there is no sizing call.  out has room for limit entries.
+ *   *found        the entries written;    *distinct (may be NULL)  the classes, bce_hip_kgram.distinct;
+ *   size_hist[b]  (may be NULL) the classes with floor(log2 N) = b: the coarse frequency spectrum the selection computes anyway.
+ * Selected on the device: the sizes are binned, the host picks the largest bin t with at least min(limit, distinct) classes at or
+ * above it, those classes -- their number is known exactly, the buffers are sized by it and not by n -- are compacted in row order,
+ * sorted stably on the size bits that can differ, and the first entries gathered with their bytes.  When every class lies in one
+ * bin (all k-grams distinct, say) every class is a candidate.  Own LCP pass bounded by max(k, 1); nothing is cached; only buffers
+ * of the feature's own are written and no compression state changes.
+ * A null ctx, k > BCE_HIP_MATCH_MAX_LEN, a limit outside 1 .. BCE_HIP_TOP_MAX, a null found, bytes with bytes_cap < limit * k:
+ * BCE_HIP_E_ARG (bce_hip_last_error has the words) before any device call; then the state, as bce_hip_kgrams; then a null out:
+ * BCE_HIP_E_ARG.  A refused call leaves its outputs untouched. */
+#define BCE_HIP_TOP_MAX (1u << 20)
+typedef struct bce_hip_top_kgram {
+  uint32_t count, row, pos;
+} bce_hip_top_kgram;
+int bce_hip_top_kgrams(bce_hip_ctx *ctx, uint32_t k, uint32_t limit, bce_hip_top_kgram *out, uint8_t *bytes, uint64_t bytes_cap,
+                       uint32_t *found, uint64_t *distinct, uint64_t size_hist[32]);
+/* The same into device memory of the context's device (d_out 4-byte aligned); found, distinct and size_hist stay host pointers.
+ * Stream rule: as bce_hip_count_device. */
+int bce_hip_top_kgrams_device(bce_hip_ctx *ctx, uint32_t k, uint32_t limit, void *d_out, void *d_bytes, uint64_t bytes_cap,
+                              uint32_t *found, uint64_t *distinct, uint64_t size_hist[32]);
+
 /* ---- extension: a second buffer as a DELTA against the input: parse and patch (kd_parse.hip, parse_step.h) ----------------------
  * T: the n bytes the context indexed.  Q: a query of q bytes, 0 <= q < 2^31.  1 <= min_len <= max_len <= BCE_HIP_MATCH_MAX_LEN.
  * len[i], pos[i]: the LINEAR matching statistics of Q at bound max_len, exactly what bce_hip_match_device gives with
@@ -534,6 +564,13 @@ int bce_hip_unbwt_device(bce_hip_ctx *ctx, const void *d_bwt, uint32_t n, uint32
  * before any device call. */
 int bce_hip_lcp_reduce_device(bce_hip_ctx *ctx, const void *d_lcp, uint32_t n, const void *d_sa, const uint32_t *ks, uint32_t nk,
                               bce_hip_kgram *out, uint32_t repeat3[3]);
+/* Test hook: the selection of bce_hip_top_kgrams (kd_top_kgrams) on the n words at d_lcp read as an LCP array (d_lcp[0] must be 0)
+ * with the n words at d_sa as the suffix array, copied and aligned as above.  No bytes are gathered.  out: a HOST array with room
+ * for limit entries (pos = d_sa[row]); found, distinct (may be NULL) and size_hist (may be NULL) as in the real call.  Writes only
+ * rep_lcp and the feature's top_* buffers.  A null ctx, d_lcp, d_sa, out or found, n == 0, n >= 2^31, k above
+ * BCE_HIP_MATCH_MAX_LEN, a limit outside 1 .. BCE_HIP_TOP_MAX: BCE_HIP_E_ARG before any device call. */
+int bce_hip_top_classes_of_lcp_device(bce_hip_ctx *ctx, const void *d_lcp, uint32_t n, const void *d_sa, uint32_t k, uint32_t limit,
+                                      bce_hip_top_kgram *out, uint32_t *found, uint64_t *distinct, uint64_t size_hist[32]);
 /* Test hook: kd_coverage, the reduction of bce_hip_coverage, on q lengths of the caller's (u32, 4-byte aligned) with
  * d_len[i] <= i + 1 (a match does not start in front of the query): *covered = the j < q for which some i >= j has
  * d_len[i] >= min_len and i - d_len[i] + 1 <= j.  Writes only mat_res and mat_bsum.  q == 0: *covered = 0, d_len ignored.  A null
