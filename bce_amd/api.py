@@ -145,6 +145,12 @@ SYMBOLS = [
     ("bce_hip_patch", C.c_int, [C.c_void_p, _vp, C.c_uint64, _u8p, C.c_uint64, _u8p, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("bce_hip_patch_device", C.c_int, [C.c_void_p, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("bce_hip_parse_of_lengths_device", C.c_int, [C.c_void_p, _vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(ParseInfo)]),
+    ("bce_hip_lpf", C.c_int, [C.c_void_p, C.c_uint32, _vp, _vp]),
+    ("bce_hip_lpf_device", C.c_int, [C.c_void_p, C.c_uint32, _vp, _vp]),
+    ("bce_hip_self_parse", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _u8p, C.c_uint64, C.POINTER(ParseInfo)]),
+    ("bce_hip_self_parse_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(ParseInfo)]),
+    ("bce_hip_nsv_device", C.c_int, [C.c_void_p, _vp, C.c_uint32, _vp, _vp]),
+    ("bce_hip_self_parse_of_lpf_device", C.c_int, [C.c_void_p, _vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(ParseInfo)]),
     ("bce_hip_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     ("bce_hip_synth_text", None, [C.c_uint64, _u8p, C.c_size_t]),
     ("bce_hip_synth_rand", None, [C.c_uint64, _u8p, C.c_size_t]),
@@ -598,6 +604,43 @@ class RankFile:
                                                        _ptr(lits_ptr), int(lits_cap), C.byref(info)), "bce_hip_parse_device")
         return info.as_dict()
 
+    def lpf(self, max_len=PARSE_MAX_LEN, sources=True):
+        """The longest previous factors of the LINEAR text (bce_hip_lpf: all nearest smaller values over the suffix array, then two
+        compares per row, on the GPU) -> (lpf, src), numpy uint32 arrays of n words: lpf[i] = the most bytes, at most
+        min(max_len, n - i), that text[i:] shares with text[j:] for some j < i (overlap allowed), src[i] = one such j, OP_LITERAL
+        (0xFFFFFFFF) where lpf[i] == 0.  sources=False: src is None.  Needs the suffix array and the text, as lcp()."""
+        out = np.zeros(self._n, dtype=np.uint32)
+        src = np.zeros(self._n, dtype=np.uint32) if sources else None
+        self._c.check(self._c.lib.bce_hip_lpf(self._c.h, int(max_len), out.ctypes.data, src.ctypes.data if sources else None), "bce_hip_lpf")
+        return out, src
+
+    def lpf_device(self, max_len=PARSE_MAX_LEN, lpf_ptr=None, src_ptr=None):
+        """bce_hip_lpf_device: the same into n uint32 words each of device memory (int pointers; src_ptr may be None).  Stream
+        rule: as count_device."""
+        self._c.check(self._c.lib.bce_hip_lpf_device(self._c.h, int(max_len), _ptr(lpf_ptr), _ptr(src_ptr)), "bce_hip_lpf_device")
+
+    def self_parse(self, min_len, max_len=PARSE_MAX_LEN):
+        """The text written as copies of its OWN earlier bytes plus the bytes that are new (bce_hip_self_parse: from position 0 a
+        copy of lpf[s] bytes from src[s] wherever lpf[s] >= min_len, else a literal byte; the greedy LZ77 factorisation, on the
+        GPU) -> (ops, lits, info) as parse() gives them, in text order.  Every copy's src lies in front of its destination, so the
+        list decodes from left to right without the text; patch(ops, lits) gives the text back as well.  With min_len 1,
+        info["ncopies"] + info["nlits"] is z, the number of LZ77 phrases."""
+        info = ParseInfo()
+        self._c.check(self._c.lib.bce_hip_self_parse(self._c.h, int(min_len), int(max_len), None, 0, None, 0, C.byref(info)), "bce_hip_self_parse")
+        ops, lits = np.zeros(info.nops, dtype=OP_DTYPE), np.zeros(info.nlits, dtype=np.uint8)
+        self._c.check(self._c.lib.bce_hip_self_parse(self._c.h, int(min_len), int(max_len), ops.ctypes.data, len(ops),
+                                                     lits.ctypes.data if len(lits) else None, len(lits), C.byref(info)), "bce_hip_self_parse")
+        return ops, lits, info.as_dict()
+
+    def self_parse_device(self, min_len, max_len=PARSE_MAX_LEN, ops_ptr=None, ops_cap=0, lits_ptr=None, lits_cap=0):
+        """bce_hip_self_parse_device: the same into `ops_cap` ops (8 bytes each, 4-byte aligned) at ops_ptr and `lits_cap` bytes at
+        lits_ptr (int pointers; both None with caps 0: a sizing call) -> the info dict.  More ops or literal bytes than room:
+        BceError with status E_OVERFLOW, nothing written.  Stream rule: as count_device."""
+        info = ParseInfo()
+        self._c.check(self._c.lib.bce_hip_self_parse_device(self._c.h, int(min_len), int(max_len), _ptr(ops_ptr), int(ops_cap), _ptr(lits_ptr),
+                                                            int(lits_cap), C.byref(info)), "bce_hip_self_parse_device")
+        return info.as_dict()
+
     def patch(self, ops, lits):
         """The bytes that `ops` (a record array as parse() gives, or an (nops, 2) uint32 array of (len, src)) and `lits` describe
         over the text (bce_hip_patch: validated and copied on the GPU) -> a numpy uint8 array.  Any well-formed list is taken; one
@@ -878,6 +921,41 @@ def apply_delta(base, blob, device=0, ctx=None) -> bytes:
     finally:
         if ctx is None:
             rf.close()
+
+
+def lpf(data, max_len=PARSE_MAX_LEN, sources=True, device=0, ctx=None):
+    """The longest previous factors of `data` -> (lpf, src) as RankFile.lpf: K1 and K2 index the data on the GPU."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.lpf(max_len, sources=sources)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def self_parse(data, min_len, max_len=PARSE_MAX_LEN, device=0, ctx=None):
+    """`data` as copies of its own earlier bytes plus literal bytes -> (ops, lits, info) as RankFile.self_parse."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.self_parse(min_len, max_len)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def nsv_device(ptr_vals, n, ptr_psv, ptr_nsv, ctx):
+    """Test hook (bce_hip_nsv_device): all nearest smaller values of `n` uint32 words at a device pointer, strictly smaller, into
+    two arrays of n words (0xFFFFFFFF: none) -> the status."""
+    return ctx.lib.bce_hip_nsv_device(ctx.h, _ptr(ptr_vals), int(n), _ptr(ptr_psv), _ptr(ptr_nsv))
+
+
+def self_parse_of_lpf_device(ptr_lpf, ptr_src, ptr_text, n, min_len, ctx, ptr_ops=None, ops_cap=0, ptr_lits=None, lits_cap=0):
+    """Test hook (bce_hip_self_parse_of_lpf_device): the self-parse's chain alone on `n` uint32 lengths (lpf[i] <= n - i), sources
+    (ptr_src may be None: src = 0) and text bytes at device pointers -> (status, info dict); both outputs None with caps 0 sizes."""
+    info = ParseInfo()
+    rc = ctx.lib.bce_hip_self_parse_of_lpf_device(ctx.h, _ptr(ptr_lpf), _ptr(ptr_src), _ptr(ptr_text), int(n), int(min_len), _ptr(ptr_ops), int(ops_cap),
+                                                  _ptr(ptr_lits), int(lits_cap), C.byref(info))
+    return rc, info.as_dict()
 
 
 def parse_of_lengths_device(ptr_len, ptr_pos, ptr_query, q, min_len, ctx, ptr_ops=None, ops_cap=0, ptr_lits=None, lits_cap=0):

@@ -1,6 +1,6 @@
 // api_index.hip -- C ABI of the index queries (include/bce_hip.h): counts, positions, longest matches and coverage, the LCP array and
-// its reductions, the list of the most frequent k-grams, parse and patch; and the three test hooks that run their block scans alone.  The device work is in kd_count /
-// kd_locate / kd_match / kd_lcp / kd_parse.hip.  Every query comes twice, for host buffers and for device buffers: the two differ
+// its reductions, the list of the most frequent k-grams, parse and patch, the longest previous factors and the self-parse; and the test hooks that run their block scans alone.  The device work is in kd_count /
+// kd_locate / kd_match / kd_lcp / kd_parse / kd_self.hip.  Every query comes twice, for host buffers and for device buffers: the two differ
 // in staging and in the copy out, and in nothing else.
 //
 // All of them judge the arguments before the context's state and the state before the arrays, then run their body through
@@ -532,6 +532,94 @@ int bce_hip_patch_device(bce_hip_ctx *c, const void *d_ops, uint64_t nops, const
   return query_call(c, 3, [&] {
     return kd_patch(c, static_cast<const uint32_t *>(d_ops), (uint32_t)nops, static_cast<const uint8_t *>(d_lits), nlits, !d_out,
                     static_cast<uint8_t *>(d_out), cap, out_len);
+  });
+}
+
+// ---- what the text repeats of itself: longest previous factors and the self-parse (kd_self.hip) -----------------------------------
+// The LCP array's rule (text_state): sa[sa_res] and `text` are read, neither is written; every temporary is a slf_* buffer of the
+// feature's own, or kd_parse's par_*.  Nothing is kept from one call to the next.
+int bce_hip_lpf(bce_hip_ctx *c, uint32_t max_len, uint32_t *lpf_out, uint32_t *src_out) {
+  const uint32_t *sa = nullptr;
+  BCE_TRY(lcp_args(c, "lpf", max_len, &sa));
+  if (!lpf_out) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&]() -> int {
+    DevBuf &lpf = c->qbuf[qb::slf_lpf], &src = c->qbuf[qb::slf_src];
+    const size_t words = (size_t)c->n * 4;
+    BCE_TRY(ensure(c, lpf, words));
+    if (src_out) BCE_TRY(ensure(c, src, words));
+    BCE_TRY(kd_lpf(c, sa, max_len, false, lpf.as<uint32_t>(), src_out ? src.as<uint32_t>() : nullptr));
+    BCE_TRY(copy_out(c, lpf_out, lpf, words));
+    return src_out ? copy_out(c, src_out, src, words) : BCE_HIP_OK;
+  });
+}
+
+int bce_hip_lpf_device(bce_hip_ctx *c, uint32_t max_len, void *d_lpf, void *d_src) {
+  const uint32_t *sa = nullptr;
+  BCE_TRY(lcp_args(c, "lpf", max_len, &sa));
+  if (!d_lpf) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&] { return kd_lpf(c, sa, max_len, false, static_cast<uint32_t *>(d_lpf), static_cast<uint32_t *>(d_src)); });
+}
+
+static int self_args(bce_hip_ctx *c, uint32_t min_len, uint32_t max_len, const void *ops, uint64_t ops_cap, const void *lits, uint64_t lits_cap,
+                     bce_hip_parse_info *info, const uint32_t **sa) {
+  if (!c || !info) return BCE_HIP_E_ARG;
+  if (min_len < 1 || min_len > max_len || max_len > BCE_HIP_MATCH_MAX_LEN) {
+    snprintf(c->err, sizeof c->err, "self-parse: bounds %u .. %u, outside 1 <= min_len <= max_len <= %u", min_len, max_len, BCE_HIP_MATCH_MAX_LEN);
+    return BCE_HIP_E_ARG;
+  }
+  if ((!ops && ops_cap) || (!lits && lits_cap)) return BCE_HIP_E_ARG;
+  return text_state(c, sa, "self-parse");
+}
+// lpf, src and the text at their mirrors (slf_rlen / slf_rsrc / slf_rtext), ready for the chain
+static int self_mirrors(bce_hip_ctx *c, const uint32_t *sa, uint32_t max_len) {
+  BCE_TRY(kd_self_mirror(c, nullptr, nullptr, c->text.as<uint8_t>(), c->n));
+  BCE_TRY(ensure(c, c->qbuf[qb::slf_rsrc], (size_t)c->n * 4));
+  return kd_lpf(c, sa, max_len, true, c->qbuf[qb::slf_rlen].as<uint32_t>(), c->qbuf[qb::slf_rsrc].as<uint32_t>());
+}
+
+int bce_hip_self_parse(bce_hip_ctx *c, uint32_t min_len, uint32_t max_len, bce_hip_op *ops, uint64_t ops_cap, uint8_t *lits, uint64_t lits_cap,
+                       bce_hip_parse_info *info) {
+  const uint32_t *sa = nullptr;
+  BCE_TRY(self_args(c, min_len, max_len, ops, ops_cap, lits, lits_cap, info, &sa));
+  return query_call(c, 3, [&]() -> int {
+    DevBuf &d_ops = c->qbuf[qb::slf_ops], &d_lits = c->qbuf[qb::slf_lits];
+    BCE_TRY(self_mirrors(c, sa, max_len));
+    // as bce_hip_parse: sized first, the staging of the two outputs is as large as they are, and an overflow touches neither
+    BCE_TRY(kd_self_parse(c, c->n, min_len, true, true, nullptr, 0, nullptr, 0, info));
+    if (!ops && !lits) return BCE_HIP_OK;
+    BCE_TRY(ensure(c, d_ops, (size_t)info->nops * 8));
+    BCE_TRY(ensure(c, d_lits, info->nlits ? (size_t)info->nlits : 1));
+    BCE_TRY(kd_self_parse(c, c->n, min_len, true, false, d_ops.as<uint32_t>(), ops_cap, d_lits.as<uint8_t>(), lits_cap, info));
+    BCE_TRY(copy_out(c, ops, d_ops, (size_t)info->nops * 8));
+    return copy_out(c, lits, d_lits, (size_t)info->nlits);
+  });
+}
+
+int bce_hip_self_parse_device(bce_hip_ctx *c, uint32_t min_len, uint32_t max_len, void *d_ops, uint64_t ops_cap, void *d_lits, uint64_t lits_cap,
+                              bce_hip_parse_info *info) {
+  const uint32_t *sa = nullptr;
+  BCE_TRY(self_args(c, min_len, max_len, d_ops, ops_cap, d_lits, lits_cap, info, &sa));
+  return query_call(c, 3, [&]() -> int {
+    BCE_TRY(self_mirrors(c, sa, max_len));
+    return kd_self_parse(c, c->n, min_len, true, !d_ops && !d_lits, static_cast<uint32_t *>(d_ops), ops_cap, static_cast<uint8_t *>(d_lits), lits_cap, info);
+  });
+}
+
+// test hooks: phase 0, as the scans' hooks above
+int bce_hip_nsv_device(bce_hip_ctx *c, const void *d_vals, uint32_t n, void *d_psv, void *d_nsv) {
+  if (!c || !d_vals || !d_psv || !d_nsv || n == 0 || n > 0x7FFFFFFFu) return BCE_HIP_E_ARG;
+  return query_call(c, 0, [&] { return kd_nsv(c, static_cast<const uint32_t *>(d_vals), n, static_cast<uint32_t *>(d_psv), static_cast<uint32_t *>(d_nsv)); });
+}
+
+int bce_hip_self_parse_of_lpf_device(bce_hip_ctx *c, const void *d_lpf, const void *d_src, const void *d_text, uint64_t n, uint32_t min_len,
+                                     void *d_ops, uint64_t ops_cap, void *d_lits, uint64_t lits_cap, bce_hip_parse_info *info) {
+  BCE_TRY(parse_args(c, n, min_len, BCE_HIP_MATCH_MAX_LEN, d_ops, ops_cap, d_lits, lits_cap, info));
+  if (n == 0) return BCE_HIP_OK;
+  if (!d_lpf || !d_text) return BCE_HIP_E_ARG;
+  return query_call(c, 0, [&]() -> int {
+    BCE_TRY(kd_self_mirror(c, static_cast<const uint32_t *>(d_lpf), static_cast<const uint32_t *>(d_src), static_cast<const uint8_t *>(d_text), (uint32_t)n));
+    return kd_self_parse(c, (uint32_t)n, min_len, d_src != nullptr, !d_ops && !d_lits, static_cast<uint32_t *>(d_ops), ops_cap,
+                         static_cast<uint8_t *>(d_lits), lits_cap, info);
   });
 }
 

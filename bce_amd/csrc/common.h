@@ -130,7 +130,7 @@ inline void slot_free_host(FlushSlot &s, uint32_t *unmaps = nullptr) {
 
 struct RunEntry { uint64_t start; uint32_t count; uint32_t round; };  // symbols of (round, plane): [start, start+count)
 
-// The buffers of the index queries (bce_hip_ctx::qbuf[qb::name], kd_count / _locate / _match / _lcp / _parse.hip and api_index.hip):
+// The buffers of the index queries (bce_hip_ctx::qbuf[qb::name], kd_count / _locate / _match / _lcp / _parse / _self.hip and api_index.hip):
 // one array, so that bce_hip_destroy releases them in one loop and a name added here needs nothing else.
 namespace qb {
 enum Id {
@@ -156,6 +156,9 @@ enum Id {
   par_hpre,                                      // per op head: the literal bytes up to it
   par_off, par_loff,                             // the patch: every op's offset in the output and in the literal bytes
   par_ops, par_lits, par_out,                    // bce_hip_parse / _patch with host buffers: the ops, the literal bytes and the result, staged (all grow-only)
+  slf_tree, slf_top,                             // kd_self.hip: the blocks' min-trees (2048 words a block) and the tree over the blocks' minima
+  slf_rlen, slf_rsrc, slf_rtext,                 // the self-parse: lpf, src and the text written at n - 1 - i, what kd_parse's chain runs on
+  slf_lpf, slf_src, slf_ops, slf_lits,           // bce_hip_lpf / _self_parse with host buffers: the arrays, the ops and the literal bytes, staged (all grow-only)
   count
 };
 }  // namespace qb
@@ -492,6 +495,14 @@ int kd_parse(bce_hip_ctx *c, const uint32_t *d_len, const uint32_t *d_pos, const
              uint32_t *d_ops, uint64_t ops_cap, uint8_t *d_lits, uint64_t lits_cap, bce_hip_parse_info *info);
 int kd_patch(bce_hip_ctx *c, const uint32_t *d_ops, uint32_t nops, const uint8_t *d_lits, uint64_t nlits, bool sizing, uint8_t *d_out,
              uint64_t cap, uint64_t *out_len);
+// kd_self.hip: all nearest smaller values of n words; the longest previous factor of every text position (at n - 1 - i: mirror);
+// the mirrors of lengths, sources and text in slf_rlen / slf_rsrc / slf_rtext; kd_parse's chain over those, turned round.  The
+// first three are queued and the caller waits; the last is complete on return.
+int kd_nsv(bce_hip_ctx *c, const uint32_t *d_vals, uint32_t n, uint32_t *d_psv, uint32_t *d_nsv);
+int kd_lpf(bce_hip_ctx *c, const uint32_t *sa, uint32_t max_len, bool mirror, uint32_t *d_lpf, uint32_t *d_src);
+int kd_self_mirror(bce_hip_ctx *c, const uint32_t *d_lpf, const uint32_t *d_src, const uint8_t *d_text, uint32_t n);
+int kd_self_parse(bce_hip_ctx *c, uint32_t n, uint32_t min_len, bool with_src, bool sizing, uint32_t *d_ops, uint64_t ops_cap, uint8_t *d_lits,
+                  uint64_t lits_cap, bce_hip_parse_info *info);
 int k2_build_planes(bce_hip_ctx *c);                // k2_planes.hip
 int k2_get_plane_bits(bce_hip_ctx *c, int plane, uint8_t *out);
 int k2_rank1(bce_hip_ctx *c, int plane, const uint32_t *idx, uint32_t count, uint32_t *out);

@@ -11,6 +11,7 @@
 //   bce -ga file in.bcd out_file, -gad archive in.bcd out_file     (extension) rebuilds a file from the first and a delta, both sides checked by CRC-32
 //   bce -gk K file, -gkd K archive          (extension) the k-grams of the circular text for k = 0..K: how many, how many occur once, the most frequent, H_k; the longest repeat
 //   bce -gf K N file, -gfd K N archive      (extension) the N most frequent K-grams of the circular text: count, one position and the bytes of each
+//   bce -gz MINLEN file, -gzd MINLEN archive   (extension) the text as copies of its own earlier bytes: the greedy LZ77 factorisation, counted on the GPU
 // Banner, usage text, summary line, argument detection and exit codes follow the reference
 // (banner :1377-1379, -c :1403-1427, -d :1428-1472, usage :1473-1483).  -d uses the GPU-assisted decoder (kd_decode.hip), -ds the host decoder (decoder.cpp);
 // -s runs the enumeration on the GPU in scan mode and the ScanCoder optimisation on the host (scan_coder.cpp).
@@ -144,6 +145,8 @@ extern "C" int bce_hip_parse(bce_hip_ctx *ctx, const uint8_t *query, uint64_t q,
                              uint8_t *lits, uint64_t lits_cap, bce_hip_parse_info *info) __attribute__((weak));
 extern "C" int bce_hip_patch(bce_hip_ctx *ctx, const bce_hip_op *ops, uint64_t nops, const uint8_t *lits, uint64_t nlits, uint8_t *out, uint64_t cap,
                              uint64_t *out_len) __attribute__((weak));
+extern "C" int bce_hip_self_parse(bce_hip_ctx *ctx, uint32_t min_len, uint32_t max_len, bce_hip_op *ops, uint64_t ops_cap, uint8_t *lits,
+                                  uint64_t lits_cap, bce_hip_parse_info *info) __attribute__((weak));
 
 // `bce -cN`: N contiguous blocks over the GPUs of the node.  With more blocks than GPUs every device gets up to four
 // gated contexts (bce_hip_set_gated), one host thread each: their GPU phases take turns while the coder threads of the
@@ -490,7 +493,7 @@ static void write_delta_header(uint8_t *p, const DeltaHeader &h) {
   memcpy(p, "BCED", 4); memcpy(p + 4, &ver, 4); memcpy(p + 8, &h.n, 8); memcpy(p + 16, &h.base_crc, 4); memcpy(p + 20, &h.q, 8);
   memcpy(p + 28, &h.crc, 4); memcpy(p + 32, &h.min_len, 4); memcpy(p + 36, &h.max_len, 4); memcpy(p + 40, &h.nops, 8); memcpy(p + 48, &h.nlits, 8);
 }
-// ---- the front of all fourteen index commands ----
+// ---- the front of all sixteen index commands ----
 // The indexed file (or archive) and the command's second file are read beside the runtime's start-up and judged in this order: the
 // file or archive, the second file, the device; an archive's blocks are then decoded into one text.  Owns the context: an error
 // path destroys it, index_done() leaves it to fast_exit.
@@ -626,6 +629,22 @@ static int coverage_command(uint32_t min_len, const char *path, bool in_archive,
   if (rc != 0) return index_failed(in, "Match", rc);
   printf("%llu of %zu bytes (%.1f %%) of %s lie in strings of %u bytes or more that occur in %s\n", (unsigned long long)covered, query.size(),
          100.0 * (double)covered / (double)query.size(), query_path, min_len, path);
+  return index_done(in);
+}
+
+// -gz / -gzd: the file or archive is read, judged, decoded and indexed as for the others; the text is parsed against itself on the GPU
+// (bce_hip_self_parse at the bounds MINLEN and max(256, MINLEN), a sizing call: only the four counts come back) and one line printed.
+static int self_command(uint32_t min_len, const char *path, bool in_archive) {
+  IndexInput in;
+  if (const int ec = index_open(in, path, in_archive, nullptr, kNoSecond, bce_hip_self_parse != nullptr)) return ec;
+  const uint32_t max_len = min_len > kDeltaMaxLen ? min_len : kDeltaMaxLen;
+  bce_hip_parse_info info{};
+  int rc = index_text(in);
+  if (rc == 0) rc = bce_hip_self_parse(in.ctx, min_len, max_len, nullptr, 0, nullptr, 0, &info);
+  if (rc != 0) return index_failed(in, "Self-parse", rc);
+  printf("%llu copies of %llu bytes, %llu literal bytes in %llu runs: %llu phrases at bounds %u .. %u; %llu of %zu bytes repeat earlier text\n",
+         (unsigned long long)info.ncopies, (unsigned long long)info.copied, (unsigned long long)info.nlits, (unsigned long long)(info.nops - info.ncopies),
+         (unsigned long long)(info.ncopies + info.nlits), min_len, max_len, (unsigned long long)info.copied, in.n);
   return index_done(in);
 }
 
@@ -797,6 +816,12 @@ static int usage() {
   printf("\n");
   printf("  bce -gd PATTERN archive.bce\n");
   printf("   The same count in what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
+  printf("\n");
+  printf("  bce -gz MINLEN file\n");
+  printf("   Prints how \"file\" parses into copies of MINLEN (1..4096) bytes or more of its OWN earlier bytes plus the bytes that are new: copies, literal bytes and runs, the phrase count (with MINLEN 1 the LZ77 measure z) and how many bytes repeat earlier text; longest previous factors and the chain are computed on the GPU (extension)\n");
+  printf("\n");
+  printf("  bce -gzd MINLEN archive.bce\n");
+  printf("   The same line for what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
   printf("\n");
   printf("  bce -gl PATTERN file\n");
   printf("   Prints where the bytes of PATTERN occur in \"file\": the byte offsets, one per line, ascending, then the count; they come from the index and the suffix array on the GPU (extension)\n");
@@ -1106,6 +1131,8 @@ int main(int argc, char **argv) {
     return locate_command(argv[2], argv[3], argv[1][3] == 'd');
   } else if (argc == 5 && (strcmp(argv[1], "-gm") == 0 || strcmp(argv[1], "-gmd") == 0) && parse_min_len(argv[2]) != 0) {
     return coverage_command(parse_min_len(argv[2]), argv[3], argv[1][3] == 'd', argv[4]);
+  } else if (argc == 4 && (strcmp(argv[1], "-gz") == 0 || strcmp(argv[1], "-gzd") == 0) && parse_min_len(argv[2]) != 0) {
+    return self_command(parse_min_len(argv[2]), argv[3], argv[1][3] == 'd');
   } else if (argc == 6 && (strcmp(argv[1], "-gr") == 0 || strcmp(argv[1], "-grd") == 0) && parse_min_len(argv[2]) != 0) {
     return delta_command(parse_min_len(argv[2]), argv[3], argv[1][3] == 'd', argv[4], argv[5]);
   } else if (argc == 5 && (strcmp(argv[1], "-ga") == 0 || strcmp(argv[1], "-gad") == 0)) {

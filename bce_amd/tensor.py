@@ -292,6 +292,42 @@ def lcp_tensor(t, max_len, ctx=None):
     return _indexed(t, "lcp_tensor", ctx, use)
 
 
+def lpf_tensor(t, max_len=api.PARSE_MAX_LEN, ctx=None):
+    """The longest previous factors of the linear text in the 1-D uint8 CUDA tensor `t` (api.RankFile.lpf, everything left where it
+    is: bce_hip_lpf_device) -> (lpf, src), int32 tensors of n words on t's device; src == -1 (0xFFFFFFFF) where lpf == 0.  Nothing
+    reaches the host.  Synchronises t's current stream first; `ctx` (an api._Ctx of t's device) is reused if given."""
+    def use(rf):
+        out = torch.zeros(t.numel(), dtype=torch.int32, device=t.device)
+        src = torch.zeros(t.numel(), dtype=torch.int32, device=t.device)
+        torch.cuda.current_stream(t.device).synchronize()            # (the zero fills are done before the library's stream writes)
+        rf.lpf_device(max_len, out.data_ptr(), src.data_ptr())
+        return out, src
+    return _indexed(t, "lpf_tensor", ctx, use)
+
+
+def self_parse_tensor(t, min_len, max_len=api.PARSE_MAX_LEN, ctx=None):
+    """The 1-D uint8 CUDA tensor `t` as copies of its own earlier bytes plus literal bytes (api.RankFile.self_parse with the outputs
+    where they stay: bce_hip_self_parse_device, a sizing call and the full call) -> (ops, lits, info) as parse_tensor gives them.
+    Nothing but info reaches the host."""
+    def use(rf):
+        info = rf.self_parse_device(min_len, max_len)
+        ops = torch.zeros((info["nops"], 2), dtype=torch.int32, device=t.device)
+        lits = torch.zeros(info["nlits"], dtype=torch.uint8, device=t.device)
+        torch.cuda.synchronize(t.device)
+        info = rf.self_parse_device(min_len, max_len, ops.data_ptr(), info["nops"], lits.data_ptr() if info["nlits"] else None, info["nlits"])
+        return ops, lits, info
+    return _indexed(t, "self_parse_tensor", ctx, use)
+
+
+def self_parse_in_archive(blob, min_len, max_len=api.PARSE_MAX_LEN, device="cuda:0"):
+    """self_parse_tensor on what an archive holds, decoded as count_in_archive decodes it: into ONE tensor on the device, so a
+    copy may reach back across block boundaries.  A container of 2^31 bytes or more: ValueError, before anything is decoded."""
+    total = sum(t[0] for t in _blocks_of(blob))
+    if total > _MAX_BLOCK:
+        raise ValueError("the archive holds %d bytes: one index covers one text of less than 2^31" % total)
+    return self_parse_tensor(decompress_container_tensor(blob, device=device), min_len, max_len)
+
+
 def kgrams_tensor(t, ks, ctx=None):
     """api.RankFile.kgrams of the 1-D uint8 CUDA tensor `t`, indexed and reduced where it lies; 32 bytes per k reach the host."""
     return _indexed(t, "kgrams_tensor", ctx, lambda rf: rf.kgrams(ks))

@@ -370,9 +370,10 @@ int bce_hip_coverage_device(bce_hip_ctx *ctx, const void *d_query, uint64_t q, u
 
 /* ---- extension: what the input holds by ITSELF: LCP array, k-gram classes, longest repeat (kd_lcp.hip, lcp_step.h) -------------
  * Everything here is about the CIRCULAR text, as bce_hip_count's cyclic mode and the coder see it: rotation a of the n bytes T is
- * T[(a + j) mod n], j = 0, 1, ...  A linear variant is out of scope: the longest repeat of the linear text is not a maximum over
- * adjacent rows (a middle row that starts near the text's end truncates the pairs with both of its neighbours), so it is no cheap
- * by-product of this array.
+ * T[(a + j) mod n], j = 0, 1, ...  The LINEAR variant is the section "what the input REPEATS of itself" below (bce_hip_lpf): the
+ * longest repeat of the linear text is not a maximum over adjacent rows (a middle row that starts near the text's end truncates
+ * the pairs with both of its neighbours), so it is no by-product of this array; its neighbours are the nearest rows that start
+ * earlier in the text, and it is the largest lpf[i].
  *   lcp[0] = 0, and for 1 <= r < n lcp[r] = the largest l <= max_len with T[(sa[r-1] + j) mod n] == T[(sa[r] + j) mod n] for all
  *   j < l, sa = the sorted rotations (what bce_hip_locate reads).  There is NO cap at n: two equal rotations of a periodic text
  *   give max_len.  So the capped array is a function of the text alone -- rows tied to max_len bytes all carry max_len among
@@ -499,6 +500,49 @@ int bce_hip_patch_device(bce_hip_ctx *ctx, const void *d_ops, uint64_t nops, con
 int bce_hip_parse_of_lengths_device(bce_hip_ctx *ctx, const void *d_len, const void *d_pos, const void *d_query, uint64_t q,
                                     uint32_t min_len, void *d_ops, uint64_t ops_cap, void *d_lits, uint64_t lits_cap,
                                     bce_hip_parse_info *info);
+
+/* ---- extension: what the input REPEATS of itself: longest previous factors and the LZ77 factorisation (kd_self.hip, lpf_step.h) ----
+ * T: the n bytes the context indexed, taken as LINEAR.  1 <= min_len <= max_len <= BCE_HIP_MATCH_MAX_LEN.
+ *   lpf[i]  the largest l <= min(max_len, n - i) such that some j < i has T[j .. j + l) == T[i .. i + l); the source may overlap the
+ *           destination; lpf[0] = 0.  max_len is a work bound per position, as for bce_hip_lcp.
+ *   src[i]  one such j, 0xFFFFFFFF where lpf[i] == 0.  Which j it names is not specified (as pos[i] of the match); everything else
+ *           is a function of the text alone.
+ * With sa the sorted rotations and sa[r] = i, the candidates are the nearest row above r and the nearest row below r whose sa
+ * value is smaller than i (all nearest smaller values over sa, an implicit min-tree: O(log n) loads per row and side, 4 n bytes of
+ * the feature's own); lpf[i] is the longer of the two common prefixes at the bound min(max_len, n - i), with which no compare wraps.
+ * The self-parse is the chain
+ *     s = 0;  while s < n:  lpf[s] >= min_len ?  a copy of lpf[s] bytes from T[src[s] ..], s += lpf[s]  :  the literal byte T[s], s += 1
+ * and comes out as bce_hip_parse gives a parse: ops in ascending text order, neighbouring literal bytes merged into maximal runs
+ * with src == BCE_HIP_OP_LITERAL, plus the literal bytes; info as there, nlits + copied == n.  Every copy has src < its
+ * destination, so the list decodes from left to right WITHOUT T (a copy may overlap its own output: byte by byte); bce_hip_patch
+ * over T gives T back as well.  For min_len == 1 no parse of T into earlier-occurring substrings of at most max_len bytes and
+ * single literal bytes has fewer phrases (ncopies + nlits): the greedy LZ77 factorisation, z = ncopies + nlits.
+ * State: as bce_hip_lcp (the suffix array AND the loaded text, else BCE_HIP_E_STATE in bce_hip_locate's words).  n == 1: lpf = [0],
+ * one literal op, no array is read.  No call here changes the compression state or writes a stage's buffers; nothing is cached.
+ * Sizing call, BCE_HIP_E_OVERFLOW and info exactly as bce_hip_parse.  A null ctx (or info), bounds outside 1 <= (min_len <=)
+ * max_len <= BCE_HIP_MATCH_MAX_LEN, a null output with a cap above 0: BCE_HIP_E_ARG before any device call; then the state; then a
+ * null lpf_out: BCE_HIP_E_ARG.  src_out may be NULL: the sources are not wanted.  A refused call leaves its outputs untouched. */
+int bce_hip_lpf(bce_hip_ctx *ctx, uint32_t max_len, uint32_t *lpf_out, uint32_t *src_out);
+/* The same into n words each of device memory of the context's device, 4-byte aligned (d_src may be NULL).  Stream rule: as
+ * bce_hip_count_device. */
+int bce_hip_lpf_device(bce_hip_ctx *ctx, uint32_t max_len, void *d_lpf, void *d_src);
+int bce_hip_self_parse(bce_hip_ctx *ctx, uint32_t min_len, uint32_t max_len, bce_hip_op *ops, uint64_t ops_cap, uint8_t *lits,
+                       uint64_t lits_cap, bce_hip_parse_info *info);
+/* The same with the ops (4-byte aligned) and the literal bytes in device memory; info stays a host pointer. */
+int bce_hip_self_parse_device(bce_hip_ctx *ctx, uint32_t min_len, uint32_t max_len, void *d_ops, uint64_t ops_cap, void *d_lits,
+                              uint64_t lits_cap, bce_hip_parse_info *info);
+/* Test hooks (tests/test_gpu_nsv.py, tests/test_gpu_self_scans.py), valid in any state of the context, with the launches and launch
+ * geometry of the real calls (which run the same functions); they write only the feature's slf_* buffers (the second also
+ * kd_parse's par_*) and their outputs.
+ * nsv: d_psv[r] / d_nsv[r] = the nearest row above / below r with d_vals[row] < d_vals[r], STRICTLY (equal values are never
+ * smaller), 0xFFFFFFFF where there is none; any n words, 1 <= n < 2^31.  A null pointer, n == 0 or n >= 2^31: BCE_HIP_E_ARG.
+ * self_parse_of_lpf: the chain alone on n lengths, sources (d_src may be NULL: every copy's src is 0) and text bytes of the
+ * caller's.  It requires only d_lpf[i] <= n - i, so a jump can cross any number of blocks.  Arguments as
+ * bce_hip_parse_of_lengths_device. */
+int bce_hip_nsv_device(bce_hip_ctx *ctx, const void *d_vals, uint32_t n, void *d_psv, void *d_nsv);
+int bce_hip_self_parse_of_lpf_device(bce_hip_ctx *ctx, const void *d_lpf, const void *d_src, const void *d_text, uint64_t n,
+                                     uint32_t min_len, void *d_ops, uint64_t ops_cap, void *d_lits, uint64_t lits_cap,
+                                     bce_hip_parse_info *info);
 
 /* ---- test hooks: the device primitives every stage rests on, alone (tests/test_gpu_sort.py, tests/test_gpu_compare.py) ----
  * Stream rule of bce_hip_crc32_device for all three: the work runs on the context's stream and is complete on return; the caller's
