@@ -329,7 +329,7 @@ int flush_symbols(bce_hip_ctx *c, uint64_t nsym) {
     for (int p = 0; p < 8; ++p) {
       slot.batch.runs[p].clear();
       slot.batch.runs[p].reserve(c->run_log[p].size());
-      for (const RunEntry &e : c->run_log[p]) slot.batch.runs[p].push_back(SymRun{e.start, e.count, e.round});
+      for (const RunEntry &e : c->run_log[p]) { slot.batch.runs[p].push_back(SymRun{e.start, e.count, e.round}); c->plane_syms[p] += e.count; }
     }
     slot.once = std::make_shared<std::once_flag>();
     {
@@ -1071,6 +1071,7 @@ static int encode_start(bce_hip_ctx *c) {
   uint32_t C[8];
   for (int i = 0; i < 8; ++i) C[i] = c->zeros[(i + 7) & 7];   // bce.cpp:1128
   c->coder->begin(c->config, C, n);
+  memset(c->plane_syms, 0, sizeof c->plane_syms);
   c->stats.symbols = 0; c->stats.flushes = 0; c->stats.t_model = 0; c->stats.t_model_kernels = 0; c->stats.t_coder = 0;
   return BCE_HIP_OK;
 }
@@ -1116,7 +1117,8 @@ static int encode_body(bce_hip_ctx *c) {
 // K1's first sort orders the rotations by their first h bytes.  The rounds r < 8 h of the enumeration ask for ranks only at
 // boundaries between rows that differ within their first h bytes, and any order sorted that
 // deep has the same rows on either side of such a boundary: same ranks, same zeros per plane, same children, same symbol
-// records.  So those rounds run on the planes of a BWT gathered right behind the first sort, and the coder threads have work
+// records.  So those rounds run on the planes of a BWT made right behind the first sort (read off the sorted keys where they carry
+// the preceding byte, gathered otherwise: k1_provisional_bwt), and the coder threads have work
 // while the rest of K1 runs: ranks, active list, segmented and deferred rounds, the final gather, the planes again.
 // All on c->stream, one after the other.  BCE_HIP_EARLY_ENUM=0: the stages in their old order; BCE_HIP_EARLY_CAP=<rounds>
 // lowers the number of early rounds (tests), never raises it.
@@ -1129,6 +1131,14 @@ static uint32_t early_round_limit(uint32_t h) {
   if (const char *e = getenv("BCE_HIP_EARLY_CAP")) { const unsigned long v = strtoul(e, nullptr, 10); if (v < limit) limit = (uint32_t)v; }
   return limit;
 }
+// The depth asked of the first sort, in symbols per alphabet width in bits (0: all the key holds).  Behind the first sort stand
+// the coders, not the rest of K1: a pass less is time the busiest coder starts earlier, as long as the rounds below 8 h still
+// feed it until the final planes exist.  Measured at 10^8 B (DESIGN 4.13 has the sweep): 5-bit text runs 3 ms a step faster at
+// h = 8 .. 11 with the byte carried, and from h = 8 down its coder begins to wait, so 9 (five 9-bit passes, the byte rides);
+// on bytes h = 7 loses on the natural corpus, whose coder waits already at 8, so bytes keep 8.  Widths nobody measured keep the
+// full key.  Inputs below kEarlyDepthMinN keep it too: their passes are bound by their launches and a shallower sort buys nothing.
+constexpr uint32_t kEarlyDepthMinN = 1u << 22;
+static const uint8_t kEarlyDepth[9] = {0, 0, 0, 0, 0, 9, 0, 0, 0};
 static int compress_early_body(bce_hip_ctx *c) {
   BCE_TRY(check_stage(c, 1));
   BCE_HIP_TRY(c, hipSetDevice(c->device));
@@ -1138,7 +1148,7 @@ static int compress_early_body(bce_hip_ctx *c) {
   PhaseScope phase(c, 1);
   {
     RoctxRange range("bce K1 first sort + provisional BWT");
-    BCE_TRY(k1_first_sort(c, &h));
+    BCE_TRY(k1_first_sort(c, &h, c->n >= kEarlyDepthMinN ? kEarlyDepth : nullptr));
     BCE_TRY(k1_provisional_bwt(c));
   }
   double t_bwt = now_s() - t0;
@@ -1162,6 +1172,8 @@ static int compress_early_body(bce_hip_ctx *c) {
   const uint32_t paused_at = c->round;
   const uint64_t early_syms = c->stats.symbols;
   const double t_early = now_s() - t_enc0;
+  uint64_t early_plane[8];
+  memcpy(early_plane, c->plane_syms, sizeof early_plane);
 
   t0 = now_s();
   {
@@ -1184,16 +1196,26 @@ static int compress_early_body(bce_hip_ctx *c) {
   }
   c->stats.t_bwt = t_bwt;
   c->stats.t_planes = t_planes;
-  if (getenv("BCE_HIP_EARLY_TRACE"))
-    fprintf(stderr, "early: h %u limit %u %s at round %u (%s) symbols %llu rounds %.2f ms k1_finish+planes %.2f ms first_sort_final %d\n", h, e.round_limit,
-            e.paused ? "paused" : "finished", paused_at, !e.paused ? "end" : (paused_at >= e.round_limit ? "limit" : "tail due"),
-            (unsigned long long)early_syms, t_early * 1e3, (now_s() - t_enc0 - t_early) * 1e3, (int)c->k1_first_final);
+  const double t_second = now_s() - t_enc0 - t_early;
+  const uint32_t early_limit = e.round_limit;
+  const bool early_paused = e.paused;
   phase.set(3);
   if (e.paused) {
     e.round_limit = Enumeration::kNoLimit;
     BCE_TRY(e.run());
   }
-  return encode_end(c, e.ctl, t_enc0);
+  BCE_TRY(encode_end(c, e.ctl, t_enc0));
+  if (getenv("BCE_HIP_EARLY_TRACE")) {
+    // the busiest plane: the records its coder had from the early rounds, and how long it stood without a batch after its first
+    int bp = 0;
+    for (int p = 1; p < 8; ++p) if (c->plane_syms[p] > c->plane_syms[bp]) bp = p;
+    fprintf(stderr, "early: h %u limit %u %s at round %u (%s) symbols %llu rounds %.2f ms k1_finish+planes %.2f ms depth asked %u got %u carry %d "
+            "plane %d early records %llu of %llu idle %.2f ms first_sort_final %d\n", h, early_limit,
+            early_paused ? "paused" : "finished", paused_at, !early_paused ? "end" : (paused_at >= early_limit ? "limit" : "tail due"),
+            (unsigned long long)early_syms, t_early * 1e3, t_second * 1e3, c->k1_h_asked, h, (int)c->k1_carry, bp, (unsigned long long)early_plane[bp],
+            (unsigned long long)c->plane_syms[bp], c->coder->idle_seconds(bp) * 1e3, (int)c->k1_first_final);
+  }
+  return BCE_HIP_OK;
 }
 static int compress_early(bce_hip_ctx *c) {
   const int rc = gate_on_error(c, bce_guarded(c, [&] { return compress_early_body(c); }));
@@ -1523,7 +1545,7 @@ int bce_hip_sort_wide_device(bce_hip_ctx *c, void *d_lo, void *d_hi, void *d_val
     uint32_t *hi[2] = {static_cast<uint32_t *>(d_hi), c->hook[1].as<uint32_t>()};
     uint32_t *val[2] = {static_cast<uint32_t *>(d_val), c->hook[2].as<uint32_t>()};
     int res = 0;
-    BCE_TRY(radix_sort_wide(c, lo, hi, val, n, bits, &res, max_digit_bits));
+    BCE_TRY(radix_sort_wide(c, lo, hi, val, n, 0, bits, &res, max_digit_bits));
     if (res) {
       BCE_HIP_TRY(c, hipMemcpyAsync(d_lo, lo[1], bytes, hipMemcpyDeviceToDevice, c->stream));
       BCE_HIP_TRY(c, hipMemcpyAsync(d_hi, hi[1], bytes, hipMemcpyDeviceToDevice, c->stream));

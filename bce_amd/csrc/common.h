@@ -201,10 +201,14 @@ struct bce_hip_ctx {
   bool k1_valid = false;                         // sa[sa_res] / rank hold this input's suffix order (K1 ran; no injected BWT)
   int sa_res = 0;
   // K1 in two halves (k1_first_sort / k1_finish): which of sa[] / key[] / khi[] holds the first sort's result, the bytes of a
-  // rotation it has ordered, and whether that order was the final one already
+  // rotation it has ordered, and whether that order was the final one already.  k1_carry: the sorted keys hold each rotation's
+  // preceding byte in their low 8 bits (the provisional BWT is read off them; k1_finish masks it out)
   int k1_res = 0;
   uint32_t k1_h = 0;
   bool k1_first_final = false;
+  bool k1_carry = false;
+  uint32_t k1_h_asked = 0;                       // the depth the caller's table asked for (k1_h: what it got, after the overrides)
+  uint64_t plane_syms[8] = {0};                  // symbol records handed to each plane's coder since encode_start
   // debug knobs (bce_hip_debug_set): 0 = default
   uint32_t dbg_dfs_budget = 0, dbg_no_dfs = 0, dbg_no_tail = 0, dbg_no_skip = 0, dbg_no_small = 0, dbg_step_small = 0, dbg_no_fused = 0, dbg_no_local = 0, dbg_capp_div = 0, dbg_local_from = 0, dbg_local_budget = 0, dbg_tail_round = 0;
   uint32_t dbg_dec_budget = 0;                   // knob 13: the decoder's query budget (0 = 2^30)
@@ -457,8 +461,11 @@ int k1_bwt(bce_hip_ctx *c);                         // k1_bwt.hip
 // K1 in two halves, where k1_two_halves() says the wide first sort applies: k1_first_sort orders the rotations by their first
 // *h_symbols bytes, k1_provisional_bwt queues the BWT of that order into c->bwt, k1_finish is the rest of the sort and
 // k1_final_bwt the BWT of the finished order (have_bwt: c->bwt holds it already) and offset_.  k1_bwt is all of it in one call.
+// want_by_bits (or null): the depth the caller wants from the first sort, in symbols, indexed by the alphabet's width in bits
+// (0: as many symbols as the key holds, what k1_bwt takes); the key carries the preceding byte where it has room for it
+// (c->k1_carry).  BCE_K1_KEYBITS overrides the depth, BCE_HIP_CARRY_BYTE=0 the carry.
 bool k1_two_halves(const bce_hip_ctx *c);
-int k1_first_sort(bce_hip_ctx *c, uint32_t *h_symbols);
+int k1_first_sort(bce_hip_ctx *c, uint32_t *h_symbols, const uint8_t *want_by_bits);
 int k1_provisional_bwt(bce_hip_ctx *c);
 int k1_finish(bce_hip_ctx *c);
 int k1_final_bwt(bce_hip_ctx *c, bool have_bwt);
@@ -541,7 +548,7 @@ int radix_sort_pairs(bce_hip_ctx *c, uint32_t *key[2], uint32_t *val[2], uint32_
 int radix_sort_pairs_on(bce_hip_ctx *c, hipStream_t stream, DevBuf &hist, uint32_t *key[2], uint32_t *val[2], uint32_t n,
                         uint32_t first_bit, uint32_t bits, int *res, uint32_t max_digit_bits = 8);
 // the same with 64-bit keys in two u32 arrays (hi:lo) on key bits [0, bits), bits <= 64 (K1's first sort)
-int radix_sort_wide(bce_hip_ctx *c, uint32_t *lo[2], uint32_t *hi[2], uint32_t *val[2], uint32_t n, uint32_t bits, int *res,
+int radix_sort_wide(bce_hip_ctx *c, uint32_t *lo[2], uint32_t *hi[2], uint32_t *val[2], uint32_t n, uint32_t first_bit, uint32_t bits, int *res,
                     uint32_t max_digit_bits = 10);
 bool k4_in_flight(bce_hip_ctx *c);                  // a model flush may still be running beside the main stream
 

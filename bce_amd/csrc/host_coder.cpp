@@ -54,7 +54,7 @@ void HostCoder::begin(const uint8_t config[9][32], const uint32_t C[8], uint32_t
   drain();
   failed_.store(false);
   for (int i = 0; i < 8; ++i) {
-    w_[i].busy = 0; w_[i].nsym = 0;
+    w_[i].busy = 0; w_[i].nsym = 0; w_[i].idle = 0; w_[i].started = false;
     plane[i] = RangeCoder();
     plane[i].preamble(config[i]);
     plane[i].uniform(C[i], n + 1);
@@ -186,19 +186,26 @@ void HostCoder::run(int p) {
   Worker &w = w_[p];
   for (;;) {
     CoderBatch *b = nullptr;
+    double wait_s = 0;
     {
       std::unique_lock<std::mutex> lk(w.mu);
+      const bool dry = w.q.empty();
+      const auto tw = std::chrono::steady_clock::now();
       w.cv.wait(lk, [&] { return w.stop || !w.q.empty(); });
       if (w.q.empty()) return;          // stop requested and nothing left
       b = w.q.front();
       w.q.pop_front();
+      wait_s = dry ? std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count() : 0.0;
     }
     const auto t0 = std::chrono::steady_clock::now();
     // No exception leaves this thread (it would end in std::terminate, across the C ABI): a failed allocation of the
     // output vector marks the coder as failed; the batch still counts as done so that wait / drain never hang, and
     // the encode entry point reports BCE_HIP_E_NOMEM (failed()).
     try {
-      if (b->wait_ready) b->wait_ready();
+      if (b->wait_ready) {
+        b->wait_ready();                // (the batch's copy: time without records to code, like an empty queue)
+        wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      }
       if (!failed_.load(std::memory_order_relaxed) && ((plane_mask >> p) & 1u)) {
         consume(p, b->runs[p].data(), b->runs[p].size(), b->out);
         for (const SymRun &r : b->runs[p]) w.nsym += r.count;
@@ -210,6 +217,8 @@ void HostCoder::run(int p) {
     {
       std::lock_guard<std::mutex> g(done_mu_);
       w.busy += dt;
+      if (w.started) w.idle += wait_s;
+      w.started = true;
       b->pending.fetch_sub(1);
       ++completed_;
     }
@@ -241,6 +250,11 @@ double HostCoder::busy_seconds() {
   double m = 0;
   for (int p = 0; p < 8; ++p) m = w_[p].busy > m ? w_[p].busy : m;
   return m;
+}
+
+double HostCoder::idle_seconds(int p) {
+  std::lock_guard<std::mutex> g(done_mu_);
+  return w_[p].idle;
 }
 
 // BCE::encode :1134-1150: flush the plane coders and code the header (n, offset, stream sizes).  The archive itself

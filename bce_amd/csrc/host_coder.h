@@ -90,6 +90,7 @@ struct HostCoder {
   void assemble(uint16_t *dst) const;
   void finish(const uint8_t config[9][32], uint32_t n, uint32_t offset, std::vector<uint16_t> &archive);   // all in one (tests)
   double busy_seconds();             // max over planes of the time spent coding since begin()
+  double idle_seconds(int p);        // plane p's coder: time without records to code (queue empty, or a batch's copy not done) behind its first batch since begin()
   bool failed() const { return failed_.load(); }   // a coder thread ran out of memory since begin()
 
  private:
@@ -98,7 +99,8 @@ struct HostCoder {
     std::mutex mu;
     std::condition_variable cv;
     std::deque<CoderBatch *> q;
-    double busy = 0;
+    double busy = 0, idle = 0;
+    bool started = false;            // it has had a batch since begin()
     uint64_t nsym = 0;
     bool stop = false;
   };

@@ -19,8 +19,10 @@
 //     applied by a second kernel: a gather of another workgroup must never see a rank of this round (mixing old and new
 //     ranks inside one comparison can order two suffixes wrongly).
 // The sort comes in two halves (k1_first_sort: the first sort alone; k1_finish: ranks and every later round) so that the one-shot
-// compression can gather a provisional BWT between them and start the enumeration on it (api.hip compress_early);
-// k1_bwt runs both and the final gather.
+// compression can make a provisional BWT between them and start the enumeration on it (api.hip compress_early): it
+// asks the first sort for the depth that suits the step and, where the key has 8 bits to spare, lets each rotation's preceding
+// byte ride in the key's low bits, so that the provisional BWT is read off the sorted keys.  k1_bwt runs both halves at the full
+// depth, without the byte, and the final gather.
 // The sorter of rounds 1-2 stays as k1_sort_rotations_v1 behind BCE_K1_V1=1 for A/B runs only: a 4-byte first key (4 radix
 // passes), then full rounds in which the sequence SA[j]-h (j ascending) is already ordered by rank[p+h], so a STABLE sort
 // of it by rank[p] alone orders by (rank[p], rank[p+h]) (the Manber-Myers induction as a stable LSD radix sort).
@@ -111,9 +113,10 @@ __global__ __launch_bounds__(K1_T) void k1_gather_next_kernel(const uint32_t *__
   }
 }
 
-// nrk[j] = j where a new group starts, else 0; per-block max and the global group count
+// nrk[j] = j where a new group starts, else 0; per-block max and the global group count.  k2_mask: the bits of k2 that are key
+// (a carried byte below them is not)
 __global__ __launch_bounds__(K1_T) void k1_heads_kernel(const uint32_t *__restrict__ k1,
-                                                        const uint32_t *__restrict__ k2, uint32_t n,
+                                                        const uint32_t *__restrict__ k2, uint32_t k2_mask, uint32_t n,
                                                         uint32_t per_block, uint32_t *__restrict__ nrk,
                                                         uint32_t *__restrict__ blockmax, uint32_t *__restrict__ groups) {
   const uint64_t beg = (uint64_t)blockIdx.x * per_block;
@@ -124,7 +127,7 @@ __global__ __launch_bounds__(K1_T) void k1_heads_kernel(const uint32_t *__restri
     bool head = (j == 0);
     if (!head) {
       head = k1[j] != k1[j - 1];
-      if (!head && k2) head = k2[j] != k2[j - 1];
+      if (!head && k2) head = ((k2[j] ^ k2[j - 1]) & k2_mask) != 0u;
     }
     nrk[j] = head ? (uint32_t)j : 0u;
     if (head) { mx = (uint32_t)j; ++cnt; }
@@ -212,6 +215,21 @@ __global__ __launch_bounds__(K1_T) void k1_bwt_kernel(const uint8_t *__restrict_
   for (uint64_t j = (uint64_t)blockIdx.x * K1_T + threadIdx.x; j < n; j += (uint64_t)gridDim.x * K1_T) {
     const uint32_t q = sa[j];
     bwt[j] = T[q ? q - 1 : n - 1];
+  }
+}
+
+// The same from sorted keys that carry the preceding byte in their low 8 bits: four keys in, four bytes out.
+__global__ __launch_bounds__(K1_T) void k1_bwt_carried_kernel(const uint32_t *__restrict__ lo, uint32_t n, uint8_t *__restrict__ bwt) {
+  const uint32_t quads = n >> 2;
+  const uint4 *lo4 = reinterpret_cast<const uint4 *>(lo);
+  uint32_t *bwt4 = reinterpret_cast<uint32_t *>(bwt);
+  for (uint64_t i = (uint64_t)blockIdx.x * K1_T + threadIdx.x; i < quads; i += (uint64_t)gridDim.x * K1_T) {
+    const uint4 k = lo4[i];
+    bwt4[i] = (k.x & 0xFFu) | (k.y & 0xFFu) << 8 | (k.z & 0xFFu) << 16 | (k.w & 0xFFu) << 24;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3u)) {
+    const uint32_t j = (quads << 2) + threadIdx.x;
+    bwt[j] = (uint8_t)lo[j];
   }
 }
 
@@ -374,7 +392,7 @@ static int k1_sort_rotations_v1(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bo
   uint32_t groups = 0;
   auto rerank = [&](const uint32_t *k1s, const uint32_t *k2s, const uint32_t *sa) -> int {
     BCE_HIP_TRY(c, hipMemsetAsync(scalars, 0, 4, c->stream));
-    hipLaunchKernelGGL(k1_heads_kernel, dim3(pl.nb), dim3(K1_T), 0, c->stream, k1s, k2s, n, pl.per_block, nrk,
+    hipLaunchKernelGGL(k1_heads_kernel, dim3(pl.nb), dim3(K1_T), 0, c->stream, k1s, k2s, 0xFFFFFFFFu, n, pl.per_block, nrk,
                        blockmax, scalars);
     hipLaunchKernelGGL(k1_apply_kernel, dim3(pl.nb), dim3(K1_T), 0, c->stream, nrk, blockmax, n, pl.per_block, sa,
                        rank);
@@ -479,9 +497,10 @@ __global__ __launch_bounds__(K1_T) void k1_bytehist_kernel(const uint8_t *__rest
 
 // key[p] = the first nsym symbols of rotation p, `bits` bits each, first symbol most significant; val[p] = p.
 // m = number of rotations (n bytes of T, plus the sentinel when m = n + 1: symbol 0, every byte's code is then >= 1).
+// carry (never with the sentinel, nsym * bits <= 56): the key moves up by 8 bits and T[p - 1], the rotation's BWT byte, rides below.
 constexpr int K1I_E = 8;
 __global__ __launch_bounds__(K1_T) void k1_init64_kernel(const uint8_t *__restrict__ T, uint32_t m, uint32_t nbytes,
-                                                         const uint16_t *__restrict__ code, uint32_t bits, uint32_t nsym,
+                                                         const uint16_t *__restrict__ code, uint32_t bits, uint32_t nsym, uint32_t carry,
                                                          uint32_t *__restrict__ lo, uint32_t *__restrict__ hi, uint32_t *__restrict__ val) {
   __shared__ uint16_t sym[K1_T * K1I_E + 16];
   __shared__ uint16_t lut[256];
@@ -501,6 +520,7 @@ __global__ __launch_bounds__(K1_T) void k1_init64_kernel(const uint8_t *__restri
     if (p < m) {
       uint64_t k = 0;
       for (uint32_t b = 0; b < nsym; ++b) k = (k << bits) | sym[o + b];
+      if (carry) k = (k << 8) | T[p ? p - 1 : (uint64_t)nbytes - 1];
       lo[p] = (uint32_t)k;
       hi[p] = (uint32_t)(k >> 32);
       val[p] = (uint32_t)p;
@@ -838,7 +858,7 @@ struct K1View {
 
 // First half of the sort: the rotations ordered by their first c->k1_h symbols (one byte each), ties by position, in
 // sa[c->k1_res]; the sorted keys beside them.  Nothing of the rank array yet.
-static int k1_first_sort_wide(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool sentinel) {
+static int k1_first_sort_wide(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool sentinel, const uint8_t *want_by_bits = nullptr, bool may_carry = false) {
   const size_t b4 = (size_t)n * 4;
   for (int i = 0; i < 2; ++i) { BCE_TRY(ensure(c, c->sa[i], b4)); BCE_TRY(ensure(c, c->key[i], b4)); BCE_TRY(ensure(c, c->khi[i], b4)); }
   BCE_TRY(ensure(c, c->rank, b4));
@@ -866,9 +886,17 @@ static int k1_first_sort_wide(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool
   if (nsym > 16u) nsym = 16u;
   // (diagnostic: a narrower first key -- more of the order is left to the segmented and active rounds; measured at 10^8 B,
   //  text / natural corpus / binary corpus: 64 bits 16.9 / 33.3 / 28.2 ms, 54: 17.8 / 36.1 / 29.1, 48: 18.7 / 35.9 / 28.9,
-  //  40: 19.5 / 38.1 / 30.7, 32: 23.3 / 41.9 / 32.7 -- every pass of the wide sort earns more than it costs)
-  if (const char *e = getenv("BCE_K1_KEYBITS")) { const uint32_t kb = (uint32_t)strtoul(e, nullptr, 10); if (kb >= bits && kb / bits < nsym) nsym = kb / bits; }
+  //  40: 19.5 / 38.1 / 30.7, 32: 23.3 / 41.9 / 32.7 -- every pass of the wide sort earns more than it costs in K1's
+  //  total.  The one-shot route, where only the first sort stands before the coders, may ask for less: want_h)
+  const uint32_t most = nsym;
+  const uint32_t want_h = want_by_bits && bits <= 8u ? want_by_bits[bits] : 0u;
+  if (want_h && want_h < nsym) nsym = want_h;
+  c->k1_h_asked = nsym;
+  if (const char *e = getenv("BCE_K1_KEYBITS")) { const uint32_t kb = (uint32_t)strtoul(e, nullptr, 10); if (kb >= bits) nsym = kb / bits < most ? kb / bits : most; }
   const uint32_t keybits = nsym * bits;
+  const char *ce = getenv("BCE_HIP_CARRY_BYTE");
+  const bool carry = may_carry && !sentinel && keybits + 8u <= 64u && !(ce && ce[0] == '0' && !ce[1]);
+  const uint32_t first_bit = carry ? 8u : 0u;
   {
     if (!c->h_small) BCE_TRY(pin_alloc(c, &c->h_small, 4096));
     memcpy(c->h_small, code, sizeof code);
@@ -879,14 +907,15 @@ static int k1_first_sort_wide(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool
   {
     const uint32_t per = K1_T * K1I_E;
     hipLaunchKernelGGL(k1_init64_kernel, dim3((uint32_t)(((uint64_t)n + per - 1) / per)), dim3(K1_T), 0, c->stream, T, n, nbytes,
-                       reinterpret_cast<const uint16_t *>(scalars + K1_SC_CODE), bits, nsym, v.lo[0], v.hi[0], v.val[0]);
+                       reinterpret_cast<const uint16_t *>(scalars + K1_SC_CODE), bits, nsym, carry ? 1u : 0u, v.lo[0], v.hi[0], v.val[0]);
   }
   int res = 0;
-  BCE_TRY(radix_sort_wide(c, v.lo, v.hi, v.val, n, keybits, &res, 9));     // (9-bit digits: a 10-bit pass costs 1.0 ms at 10^8, a 9-bit one 0.57)
+  BCE_TRY(radix_sort_wide(c, v.lo, v.hi, v.val, n, first_bit, keybits, &res, 9));     // (9-bit digits: a 10-bit pass costs 1.0 ms at 10^8, a 9-bit one 0.57)
   v.lap("first sort", nsym, n, 0);
   BCE_HIP_TRY(c, hipGetLastError());
   c->k1_res = res;
   c->k1_h = nsym;
+  c->k1_carry = carry;
   return BCE_HIP_OK;
 }
 
@@ -905,7 +934,8 @@ static int k1_finish_wide(bce_hip_ctx *c, uint32_t n) {
   auto lap = [&](const char *what, uint64_t h, uint32_t m, uint32_t nd) { v.lap(what, h, m, nd); };
   // ranks: group heads from the sorted keys, one scatter; the first active list
   BCE_HIP_TRY(c, hipMemsetAsync(scalars, 0, 16, c->stream));
-  hipLaunchKernelGGL(k1_heads_kernel, dim3(pl.nb), dim3(K1_T), 0, c->stream, hi[res], lo[res], n, pl.per_block, nrk, blockmax, scalars);
+  hipLaunchKernelGGL(k1_heads_kernel, dim3(pl.nb), dim3(K1_T), 0, c->stream, hi[res], lo[res], c->k1_carry ? 0xFFFFFF00u : 0xFFFFFFFFu, n, pl.per_block,
+                     nrk, blockmax, scalars);
   const uint32_t rbits = ceil_log2(n);
   const uint32_t part_min = k1_part_min();
   const bool sorted_apply = n >= part_min;
@@ -969,7 +999,7 @@ static int k1_finish_wide(bce_hip_ctx *c, uint32_t n) {
       hipLaunchKernelGGL(k1_big_gather_kernel, dim3(ga), dim3(K1_T), 0, c->stream, idx, gid, (const uint32_t *)actv[0], rank, n, nd, (uint32_t)h, rbits,
                          bl[0], bh[0], bv[0]);
       int rb = 0;
-      BCE_TRY(radix_sort_wide(c, bl, bh, bv, nd, rbits + gbits, &rb, 9));
+      BCE_TRY(radix_sort_wide(c, bl, bh, bv, nd, 0, rbits + gbits, &rb, 9));
       const K1Plan dp = k1_plan(nd);
       uint32_t *snrk = bv[rb ^ 1];                 // (the other value buffer is free after the sort)
       hipLaunchKernelGGL(k1_big_heads_kernel, dim3(dp.nb), dim3(K1_T), 0, c->stream, slots, bl[rb], bh[rb], bv[rb], nd, dp.per_block, sa, snrk, blockmax);
@@ -1031,18 +1061,21 @@ static int k1_begin(bce_hip_ctx *c) {
   return BCE_HIP_OK;
 }
 
-int k1_first_sort(bce_hip_ctx *c, uint32_t *h_symbols) {
+int k1_first_sort(bce_hip_ctx *c, uint32_t *h_symbols, const uint8_t *want_by_bits) {
   BCE_TRY(k1_begin(c));
-  BCE_TRY(k1_first_sort_wide(c, c->text.as<uint8_t>(), c->n, false));
+  BCE_TRY(k1_first_sort_wide(c, c->text.as<uint8_t>(), c->n, false, want_by_bits, /*may_carry=*/true));
   if (h_symbols) *h_symbols = c->k1_h;
   return BCE_HIP_OK;
 }
 
 // The BWT of the first sort's order (queued): it differs from the final one only inside groups of rows that share their
-// first k1_h bytes.
+// first k1_h bytes.  Where the keys carried the byte it is read off them, in order; a gather from the text otherwise.
 int k1_provisional_bwt(bce_hip_ctx *c) {
   const uint32_t n = c->n;
-  hipLaunchKernelGGL(k1_bwt_kernel, dim3(grid_for(n)), dim3(K1_T), 0, c->stream, c->text.as<uint8_t>(), c->sa[c->k1_res].as<uint32_t>(), n,
+  if (c->k1_carry)
+    hipLaunchKernelGGL(k1_bwt_carried_kernel, dim3(grid_for((n >> 2) + 1u)), dim3(K1_T), 0, c->stream, (const uint32_t *)c->key[c->k1_res].as<uint32_t>(), n,
+                       c->bwt.as<uint8_t>());
+  else hipLaunchKernelGGL(k1_bwt_kernel, dim3(grid_for(n)), dim3(K1_T), 0, c->stream, c->text.as<uint8_t>(), c->sa[c->k1_res].as<uint32_t>(), n,
                      c->bwt.as<uint8_t>());
   BCE_HIP_TRY(c, hipGetLastError());
   return BCE_HIP_OK;

@@ -408,12 +408,13 @@ __global__ __launch_bounds__(RS_THREADS) void rw_scatter_kernel(const uint32_t *
   }
 }
 
-// Stable LSD sort of (64-bit key = hi:lo, u32 value) triples on key bits [0, bits), bits <= 64.  Result in lo[res] / hi[res] / val[res].
-int radix_sort_wide(bce_hip_ctx *c, uint32_t *lo[2], uint32_t *hi[2], uint32_t *val[2], uint32_t n, uint32_t bits, int *res,
-                    uint32_t max_digit_bits) {
+// Stable LSD sort of (64-bit key = hi:lo, u32 value) triples on key bits [first_bit, first_bit + bits), first_bit + bits <= 64: the
+// bits below first_bit travel with the key and take no part in the order.  Result in lo[res] / hi[res] / val[res].
+int radix_sort_wide(bce_hip_ctx *c, uint32_t *lo[2], uint32_t *hi[2], uint32_t *val[2], uint32_t n, uint32_t first_bit, uint32_t bits,
+                    int *res, uint32_t max_digit_bits) {
   *res = 0;
   if (n <= 1 || bits == 0) return BCE_HIP_OK;
-  if (bits > 64) return BCE_HIP_E_ARG;
+  if ((uint64_t)first_bit + bits > 64) return BCE_HIP_E_ARG;
   if (max_digit_bits < 1 || max_digit_bits > (uint32_t)RS_MAXBITS) max_digit_bits = 8;
   const RsPlan pl = rw_plan(n);
   BCE_TRY(ensure(c, c->rs_hist, ((size_t)RS_MAXBINS * pl.nb + RS_MAXBINS) * sizeof(uint32_t)));
@@ -427,11 +428,11 @@ int radix_sort_wide(bce_hip_ctx *c, uint32_t *lo[2], uint32_t *hi[2], uint32_t *
     const int nbits = (int)((left + pleft - 1) / pleft);
     const uint32_t nbins = 1u << nbits;
     hipLaunchKernelGGL(rw_hist_kernel, dim3(pl.nb), dim3(RS_THREADS), 0, c->stream, lo[cur], hi[cur], n, pl.per_block, pl.nb,
-                       (int)done, nbits, hist);
+                       (int)(first_bit + done), nbits, hist);
     hipLaunchKernelGGL(rs_scan_kernel, dim3(nbins), dim3(RS_THREADS), 0, c->stream, hist, pl.nb, rowtotal);
 #define RW_SCATTER(NB)                                                                                                      \
   hipLaunchKernelGGL(rw_scatter_kernel<NB>, dim3(pl.nb), dim3(RS_THREADS), 0, c->stream, lo[cur], hi[cur], val[cur], lo[cur ^ 1], \
-                     hi[cur ^ 1], val[cur ^ 1], n, pl.per_block, pl.nb, (int)done, nbits, hist, rowtotal)
+                     hi[cur ^ 1], val[cur ^ 1], n, pl.per_block, pl.nb, (int)(first_bit + done), nbits, hist, rowtotal)
     switch (nbits) {
       case 10: RW_SCATTER(10); break;
       case 9: RW_SCATTER(9); break;
