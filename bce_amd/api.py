@@ -151,6 +151,10 @@ SYMBOLS = [
     ("bce_hip_self_parse_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(ParseInfo)]),
     ("bce_hip_nsv_device", C.c_int, [C.c_void_p, _vp, C.c_uint32, _vp, _vp]),
     ("bce_hip_self_parse_of_lpf_device", C.c_int, [C.c_void_p, _vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(ParseInfo)]),
+    ("bce_hip_suffix_array", C.c_int, [C.c_void_p, _u8p, C.c_uint32, _vp, _vp]),
+    ("bce_hip_suffix_array_device", C.c_int, [C.c_void_p, _vp, C.c_uint32, _vp, _vp]),
+    ("bce_hip_sufcheck", C.c_int, [C.c_void_p, _u8p, _vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    ("bce_hip_sufcheck_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("bce_hip_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     ("bce_hip_synth_text", None, [C.c_uint64, _u8p, C.c_size_t]),
     ("bce_hip_synth_rand", None, [C.c_uint64, _u8p, C.c_size_t]),
@@ -941,6 +945,66 @@ def self_parse(data, min_len, max_len=PARSE_MAX_LEN, device=0, ctx=None):
     finally:
         if ctx is None:
             rf.close()
+
+
+SUFCHECK_REASONS = (None, "range", "missing", "order")   # BCE_HIP_SUFCHECK_*: what bce_hip_sufcheck found, by its reason word
+
+
+def _sufcheck_verdict(reason, bad):
+    return None if reason == 0 else (SUFCHECK_REASONS[reason], int(bad))
+
+
+def suffix_array(data, inverse=False, device=0, ctx=None):
+    """The suffix array of `data` (bytes-like, 0 < n < 2^31 - 1), sorted on the GPU (bce_hip_suffix_array: K1 on data + a unique
+    sentinel) -> a numpy int32 array of n rows, or (sa, isa) with inverse=True, isa[sa[r]] == r.  The context's compression state
+    is dropped, as by the libdivsufsort seam's divbwt."""
+    a = _as_u8(data)
+    own = ctx is None
+    c = ctx or _Ctx(device)
+    try:
+        sa = np.empty(len(a), dtype=np.int32)
+        isa = np.empty(len(a), dtype=np.int32) if inverse else None
+        c.check(c.lib.bce_hip_suffix_array(c.h, a.ctypes.data if len(a) else None, len(a), sa.ctypes.data, isa.ctypes.data if inverse else None),
+                "bce_hip_suffix_array")
+        return (sa, isa) if inverse else sa
+    finally:
+        if own:
+            c.close()
+
+
+def sufcheck(data, sa, device=0, ctx=None):
+    """Is `sa` (n 32-bit words, any values) the suffix array of `data` (n bytes)?  Checked on the GPU in linear time
+    (bce_hip_sufcheck) -> None for a sound array, else (reason, index): ("range", the first row with an entry outside [0, n)),
+    ("missing", the first text position no row names) or ("order", the first row that stands below a larger suffix).  Valid in any
+    state of `ctx`; nothing of a compression under way is touched."""
+    a = _as_u8(data)
+    s = np.ascontiguousarray(sa)
+    if s.dtype.itemsize != 4 or s.dtype.kind not in "iu" or s.ndim != 1 or len(s) != len(a):
+        raise ValueError("sa must hold one 32-bit integer per byte of data")
+    own = ctx is None
+    c = ctx or _Ctx(device)
+    try:
+        bad, reason = C.c_uint64(0), C.c_uint32(0)
+        c.check(c.lib.bce_hip_sufcheck(c.h, a.ctypes.data if len(a) else None, s.ctypes.data if len(a) else None, len(a), C.byref(bad), C.byref(reason)),
+                "bce_hip_sufcheck")
+        return _sufcheck_verdict(reason.value, bad.value)
+    finally:
+        if own:
+            c.close()
+
+
+def suffix_array_device(ptr, n, sa_ptr, isa_ptr=None, ctx=None):
+    """bce_hip_suffix_array_device on raw device pointers: the `n` bytes at `ptr` -> n uint32 words at `sa_ptr` and, unless None, at
+    `isa_ptr`.  -> the status (0, or a negative BCE_HIP_E_* that the caller asserts).  Stream rule: as decompress_to_device."""
+    return ctx.lib.bce_hip_suffix_array_device(ctx.h, _ptr(ptr), int(n), _ptr(sa_ptr), _ptr(isa_ptr))
+
+
+def sufcheck_device(ptr, sa_ptr, n, ctx):
+    """bce_hip_sufcheck_device on raw device pointers: `n` bytes at `ptr`, n uint32 words at `sa_ptr` -> (status, verdict), the
+    verdict as sufcheck gives it (None where the status is not 0)."""
+    bad, reason = C.c_uint64(0), C.c_uint32(0)
+    rc = ctx.lib.bce_hip_sufcheck_device(ctx.h, _ptr(ptr), _ptr(sa_ptr), int(n), C.byref(bad), C.byref(reason))
+    return rc, (_sufcheck_verdict(reason.value, bad.value) if rc == 0 else None)
 
 
 def nsv_device(ptr_vals, n, ptr_psv, ptr_nsv, ctx):

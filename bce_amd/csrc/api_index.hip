@@ -605,6 +605,54 @@ int bce_hip_self_parse_device(bce_hip_ctx *c, uint32_t min_len, uint32_t max_len
   });
 }
 
+// ---- the suffix array as a product, and a checker for one (k1_bwt.hip: k1_suffix_array; kd_sufsort.hip) ---------------------------
+// The sort is bce_hip_divbwt's: phase 1, the coder drained, the compression state dropped.  The checker is a hook's equal: phase 0,
+// only its own sfc_* buffers written, valid in any state.
+int bce_hip_suffix_array(bce_hip_ctx *c, const uint8_t *in, uint32_t n, uint32_t *sa_out, uint32_t *isa_out) {
+  if (!c || !in || !sa_out || n == 0 || n >= 0x7FFFFFFFu) return BCE_HIP_E_ARG;
+  return query_call(c, 1, [&]() -> int {
+    c->coder->drain();
+    DevBuf &sa = c->qbuf[qb::sfa_sa], &isa = c->qbuf[qb::sfa_isa];
+    const size_t words = (size_t)n * 4;
+    BCE_TRY(ensure(c, sa, words));
+    if (isa_out) BCE_TRY(ensure(c, isa, words));
+    BCE_TRY(k1_suffix_array(c, in, false, n, sa.as<uint32_t>(), isa_out ? isa.as<uint32_t>() : nullptr));
+    BCE_TRY(copy_out(c, sa_out, sa, words));
+    return isa_out ? copy_out(c, isa_out, isa, words) : BCE_HIP_OK;
+  });
+}
+
+int bce_hip_suffix_array_device(bce_hip_ctx *c, const void *d_in, uint32_t n, void *d_sa, void *d_isa) {
+  if (!c || !d_in || !d_sa || n == 0 || n >= 0x7FFFFFFFu) return BCE_HIP_E_ARG;
+  return query_call(c, 1, [&]() -> int {
+    c->coder->drain();
+    return k1_suffix_array(c, static_cast<const uint8_t *>(d_in), true, n, static_cast<uint32_t *>(d_sa), static_cast<uint32_t *>(d_isa));
+  });
+}
+
+int bce_hip_sufcheck(bce_hip_ctx *c, const uint8_t *in, const uint32_t *sa, uint32_t n, uint64_t *bad, uint32_t *reason) {
+  if (!c || !in || !sa || !bad || !reason || n == 0 || n >= 0x80000000u) return BCE_HIP_E_ARG;
+  uint64_t at = UINT64_MAX;
+  uint32_t why = BCE_HIP_SUFCHECK_OK;
+  BCE_TRY(query_call(c, 0, [&]() -> int {
+    DevBuf &text = c->qbuf[qb::sfc_text], &arr = c->qbuf[qb::sfc_sa];
+    BCE_TRY(stage(c, text, in, (size_t)n));
+    BCE_TRY(stage(c, arr, sa, (size_t)n * 4));
+    return kd_sufcheck(c, text.as<uint8_t>(), arr.as<uint32_t>(), n, &at, &why);
+  }));
+  *bad = at; *reason = why;
+  return BCE_HIP_OK;
+}
+
+int bce_hip_sufcheck_device(bce_hip_ctx *c, const void *d_in, const void *d_sa, uint32_t n, uint64_t *bad, uint32_t *reason) {
+  if (!c || !d_in || !d_sa || !bad || !reason || n == 0 || n >= 0x80000000u) return BCE_HIP_E_ARG;
+  uint64_t at = UINT64_MAX;
+  uint32_t why = BCE_HIP_SUFCHECK_OK;
+  BCE_TRY(query_call(c, 0, [&] { return kd_sufcheck(c, static_cast<const uint8_t *>(d_in), static_cast<const uint32_t *>(d_sa), n, &at, &why); }));
+  *bad = at; *reason = why;
+  return BCE_HIP_OK;
+}
+
 // test hooks: phase 0, as the scans' hooks above
 int bce_hip_nsv_device(bce_hip_ctx *c, const void *d_vals, uint32_t n, void *d_psv, void *d_nsv) {
   if (!c || !d_vals || !d_psv || !d_nsv || n == 0 || n > 0x7FFFFFFFu) return BCE_HIP_E_ARG;

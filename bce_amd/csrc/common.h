@@ -159,6 +159,10 @@ enum Id {
   slf_tree, slf_top,                             // kd_self.hip: the blocks' min-trees (2048 words a block) and the tree over the blocks' minima
   slf_rlen, slf_rsrc, slf_rtext,                 // the self-parse: lpf, src and the text written at n - 1 - i, what kd_parse's chain runs on
   slf_lpf, slf_src, slf_ops, slf_lits,           // bce_hip_lpf / _self_parse with host buffers: the arrays, the ops and the literal bytes, staged (all grow-only)
+  sfc_res,                                       // kd_sufsort.hip: the checker's three result words (a buffer of its own, as par_res)
+  sfc_inv, sfc_bsum,                             // the checker's inverse (n words) and the three stages' block results
+  sfc_text, sfc_sa,                              // bce_hip_sufcheck with host buffers: the text and the array, staged (grow-only)
+  sfa_sa, sfa_isa,                               // bce_hip_suffix_array with host buffers: the array and its inverse, staged (grow-only)
   count
 };
 }  // namespace qb
@@ -470,6 +474,9 @@ int k1_provisional_bwt(bce_hip_ctx *c);
 int k1_finish(bce_hip_ctx *c);
 int k1_final_bwt(bce_hip_ctx *c, bool have_bwt);
 int k1_divbwt(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n, uint32_t *pidx);   // the libdivsufsort seam
+// The suffix array of n bytes (host memory, or device memory of the context's device) and, unless d_isa is null, its inverse,
+// into device memory: k1_divbwt's sort, then kd_sufsort.hip's gather.  Complete on return.
+int k1_suffix_array(bce_hip_ctx *c, const uint8_t *T_src, bool src_on_device, uint32_t n, uint32_t *d_sa, uint32_t *d_isa);
 int kd_inverse_bw_transform(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n, uint32_t idx);   // kd_decode.hip
 // kd_decode.hip, test hooks: the decoder's planes() and inverse_bwt() stages on arrays of the caller's in device memory
 int kd_planes_from_ranks(bce_hip_ctx *c, const uint32_t *d_R, uint32_t n, uint8_t *d_bwt, uint32_t *d_words, uint32_t *d_rankw);
@@ -510,6 +517,10 @@ int kd_lpf(bce_hip_ctx *c, const uint32_t *sa, uint32_t max_len, bool mirror, ui
 int kd_self_mirror(bce_hip_ctx *c, const uint32_t *d_lpf, const uint32_t *d_src, const uint8_t *d_text, uint32_t n);
 int kd_self_parse(bce_hip_ctx *c, uint32_t n, uint32_t min_len, bool with_src, bool sizing, uint32_t *d_ops, uint64_t ops_cap, uint8_t *d_lits,
                   uint64_t lits_cap, bce_hip_parse_info *info);
+// kd_sufsort.hip: rows 1 .. n of K1's order of T$ and the rank array as suffix array and inverse (queued, the caller waits); the
+// verdict on n words as a suffix array of n bytes, both in device memory (complete on return)
+int kd_sa_gather(bce_hip_ctx *c, const uint32_t *sa, const uint32_t *rank, uint32_t n, uint32_t *d_sa, uint32_t *d_isa);
+int kd_sufcheck(bce_hip_ctx *c, const uint8_t *d_text, const uint32_t *d_sa, uint32_t n, uint64_t *bad, uint32_t *reason);
 int k2_build_planes(bce_hip_ctx *c);                // k2_planes.hip
 int k2_get_plane_bits(bce_hip_ctx *c, int plane, uint8_t *out);
 int k2_rank1(bce_hip_ctx *c, int plane, const uint32_t *idx, uint32_t count, uint32_t *out);

@@ -1151,4 +1151,24 @@ int k1_divbwt(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n
   return BCE_HIP_OK;
 }
 
+// The same sort with its order kept: rows 1 .. n of sa[sa_res] are the suffix array of T, and with every group a singleton
+// rank[i] is the row of suffix i (kd_sufsort.hip: kd_sa_gather).  T_src: n bytes of host memory, or of device memory of the
+// context's device, copied into `text` either way.
+int k1_suffix_array(bce_hip_ctx *c, const uint8_t *T_src, bool src_on_device, uint32_t n, uint32_t *d_sa, uint32_t *d_isa) {
+  if (n == 0 || n >= 0x7FFFFFFFu) return BCE_HIP_E_ARG;
+  const uint32_t m = n + 1u;
+  // the context's compression state is gone -- before the first allocation, which may give back its planes and node lists
+  c->stage = 0; c->k1_valid = false; c->enum_active = false; c->text_loaded = false;
+  BCE_TRY(ensure(c, c->text, m));
+  uint8_t *T = c->text.as<uint8_t>();
+  BCE_HIP_TRY(c, hipMemcpyAsync(T, T_src, n, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+  c->stats.sort_rounds = 0;
+  BCE_TRY(k1_sort_rotations(c, T, m, true));
+  if (!c->k1_unique) { snprintf(c->err, sizeof c->err, "suffix array: the sort left rotations of T$ tied"); return BCE_HIP_E_INTERNAL; }
+  BCE_TRY(kd_sa_gather(c, c->sa[c->sa_res].as<uint32_t>(), c->rank.as<uint32_t>(), n, d_sa, d_isa));
+  BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  BCE_HIP_TRY(c, hipGetLastError());
+  return BCE_HIP_OK;
+}
+
 }  // namespace bce

@@ -12,6 +12,8 @@
 //   bce -gk K file, -gkd K archive          (extension) the k-grams of the circular text for k = 0..K: how many, how many occur once, the most frequent, H_k; the longest repeat
 //   bce -gf K N file, -gfd K N archive      (extension) the N most frequent K-grams of the circular text: count, one position and the bytes of each
 //   bce -gz MINLEN file, -gzd MINLEN archive   (extension) the text as copies of its own earlier bytes: the greedy LZ77 factorisation, counted on the GPU
+//   bce -gs file out.sa, -gsd archive out.sa   (extension) the suffix array of the text, sorted on the GPU, as native 32-bit words
+//   bce -gsc file in.sa                        (extension) checks such a file against the text, on the GPU
 // Banner, usage text, summary line, argument detection and exit codes follow the reference
 // (banner :1377-1379, -c :1403-1427, -d :1428-1472, usage :1473-1483).  -d uses the GPU-assisted decoder (kd_decode.hip), -ds the host decoder (decoder.cpp);
 // -s runs the enumeration on the GPU in scan mode and the ScanCoder optimisation on the host (scan_coder.cpp).
@@ -147,6 +149,8 @@ extern "C" int bce_hip_patch(bce_hip_ctx *ctx, const bce_hip_op *ops, uint64_t n
                              uint64_t *out_len) __attribute__((weak));
 extern "C" int bce_hip_self_parse(bce_hip_ctx *ctx, uint32_t min_len, uint32_t max_len, bce_hip_op *ops, uint64_t ops_cap, uint8_t *lits,
                                   uint64_t lits_cap, bce_hip_parse_info *info) __attribute__((weak));
+extern "C" int bce_hip_suffix_array(bce_hip_ctx *ctx, const uint8_t *in, uint32_t n, uint32_t *sa_out, uint32_t *isa_out) __attribute__((weak));
+extern "C" int bce_hip_sufcheck(bce_hip_ctx *ctx, const uint8_t *in, const uint32_t *sa, uint32_t n, uint64_t *bad, uint32_t *reason) __attribute__((weak));
 
 // `bce -cN`: N contiguous blocks over the GPUs of the node.  With more blocks than GPUs every device gets up to four
 // gated contexts (bce_hip_set_gated), one host thread each: their GPU phases take turns while the coder threads of the
@@ -493,13 +497,14 @@ static void write_delta_header(uint8_t *p, const DeltaHeader &h) {
   memcpy(p, "BCED", 4); memcpy(p + 4, &ver, 4); memcpy(p + 8, &h.n, 8); memcpy(p + 16, &h.base_crc, 4); memcpy(p + 20, &h.q, 8);
   memcpy(p + 28, &h.crc, 4); memcpy(p + 32, &h.min_len, 4); memcpy(p + 36, &h.max_len, 4); memcpy(p + 40, &h.nops, 8); memcpy(p + 48, &h.nlits, 8);
 }
-// ---- the front of all sixteen index commands ----
+// ---- the front of all nineteen index commands ----
 // The indexed file (or archive) and the command's second file are read beside the runtime's start-up and judged in this order: the
 // file or archive, the second file, the device; an archive's blocks are then decoded into one text.  Owns the context: an error
 // path destroys it, index_done() leaves it to fast_exit.
-enum SecondFile { kNoSecond, kSecondQuery, kSecondDelta };
+enum SecondFile { kNoSecond, kSecondQuery, kSecondDelta, kSecondArray };
 struct IndexInput {
-  HostFile file, second;                                              // second: the query of -gm / -gr, the delta of -ga
+  HostFile file, second;                                              // second: the query of -gm / -gr, the delta of -ga, the array of -gsc
+  bool one_text = false;                                              // -gsd: a container is refused, its blocks are separate texts
   DeltaHeader dh{};                                                   // of the delta
   std::vector<uint8_t> decoded;
   bce_hip_ctx *ctx = nullptr;
@@ -512,16 +517,22 @@ static int index_open(IndexInput &in, const char *path, bool in_archive, const c
   HostFile &file = in.file, &query = in.second;
   std::thread reader(read_whole_file, path, &file, in_archive ? (size_t)0 : kMaxInput);   // beside the runtime's start-up
   std::thread query_reader;
-  if (second != kNoSecond) query_reader = std::thread(read_whole_file, second_path, &query, kMaxInput);
+  if (second != kNoSecond) query_reader = std::thread(read_whole_file, second_path, &query, second == kSecondArray ? 4 * kMaxInput : kMaxInput);
   const int rc0 = bce_hip_create(&in.ctx, 0);
   reader.join();
   if (second != kNoSecond) query_reader.join();
   if (in_archive && file.status == -1) { printf("Archive not found.\n"); return -1; }
   if (in_archive && (file.status != 0 || file.size() == 0)) { printf("Could not read Archive.\n"); return -2; }
   if (!in_archive && (file.status != 0 || file.size() == 0 || file.size() >= kMaxInput)) { printf("Error loading file\n"); return -1; }
+  if (in_archive && in.one_text && is_container(file)) { printf("A container holds separate texts, each with a suffix array of its own: decode it and sort its blocks one by one\n"); return -2; }
   if (second == kSecondDelta && query.status == -1) { printf("Archive not found.\n"); return -1; }
   if (second == kSecondDelta && (query.status != 0 || !read_delta_header(query.data(), query.size(), in.dh))) { printf("Could not read Archive.\n"); return -2; }
   if (second == kSecondQuery && (query.status != 0 || query.size() == 0 || query.size() >= kMaxInput)) { printf("Error loading file\n"); return -1; }
+  if (second == kSecondArray && (query.status == -1 || query.status == -2)) { printf("Error loading file\n"); return -1; }
+  if (second == kSecondArray && query.size() != 4 * file.size()) {
+    printf("%s holds %zu bytes: the suffix array of the %zu bytes of %s has %zu\n", second_path, query.size(), file.size(), path, 4 * file.size());
+    return -2;
+  }
   if (rc0 != 0 || !bce_hip_count || !have_api) { printf("No usable HIP device: %s\n", bce_hip_strerror(rc0 ? rc0 : BCE_HIP_E_DEVICE)); return -3; }
   in.text = file.data();
   in.n = file.size();
@@ -646,6 +657,41 @@ static int self_command(uint32_t min_len, const char *path, bool in_archive) {
          (unsigned long long)info.ncopies, (unsigned long long)info.copied, (unsigned long long)info.nlits, (unsigned long long)(info.nops - info.ncopies),
          (unsigned long long)(info.ncopies + info.nlits), min_len, max_len, (unsigned long long)info.copied, in.n);
   return index_done(in);
+}
+
+// -gs / -gsd: the file or archive is read, judged and decoded as for the others (a container is refused: its blocks are separate
+// texts); the text is sorted on the GPU (bce_hip_suffix_array) and its n rows written as native 32-bit words, the layout of
+// libdivsufsort's mksary.  A write that fails leaves no file.
+static int sa_command(const char *path, bool in_archive, const char *out_path) {
+  IndexInput in;
+  in.one_text = true;
+  if (const int ec = index_open(in, path, in_archive, nullptr, kNoSecond, bce_hip_suffix_array != nullptr)) return ec;
+  if (in.n >= kMaxInput - 1) { printf("Error loading file\n"); return -1; }   // (the sort adds a sentinel: n < 2^31 - 1)
+  std::vector<uint32_t> sa(in.n);
+  const int rc = bce_hip_suffix_array(in.ctx, in.text, (uint32_t)in.n, sa.data(), nullptr);
+  if (rc != 0) return index_failed(in, "Suffix sort", rc);
+  if (!write_file(out_path, sa.data(), sa.size() * 4)) { remove(out_path); printf("Could not write file.\n"); return -5; }
+  printf("%zu suffixes\n", in.n);
+  return index_done(in);
+}
+
+// -gsc: the file, then the array (4 n bytes), then the device; checked on the GPU (bce_hip_sufcheck).  One line; exit status 0 =
+// sorted, kExitDiffers = not.
+static int sa_check_command(const char *path, const char *sa_path) {
+  IndexInput in;
+  if (const int ec = index_open(in, path, false, sa_path, kSecondArray, bce_hip_sufcheck != nullptr)) return ec;
+  uint64_t bad = 0;
+  uint32_t reason = 0;
+  const int rc = bce_hip_sufcheck(in.ctx, in.text, reinterpret_cast<const uint32_t *>(in.second.data()), (uint32_t)in.n, &bad, &reason);
+  if (rc != 0) return index_failed(in, "Suffix check", rc);
+  const uint32_t *sa = reinterpret_cast<const uint32_t *>(in.second.data());
+  switch (reason) {
+    case BCE_HIP_SUFCHECK_OK: printf("%zu suffixes in order\n", in.n); return index_done(in);
+    case BCE_HIP_SUFCHECK_RANGE: printf("Out of range: row %llu holds %u, the text has %zu bytes\n", (unsigned long long)bad, sa[bad], in.n); break;
+    case BCE_HIP_SUFCHECK_MISSING: printf("Not a permutation: no row holds position %llu\n", (unsigned long long)bad); break;
+    default: printf("Out of order: row %llu (suffix %u) sorts before row %llu (suffix %u)\n", (unsigned long long)bad, sa[bad], (unsigned long long)bad - 1, sa[bad - 1]); break;
+  }
+  return kExitDiffers;
 }
 
 // -gk / -gkd: k = 0 .. K, and K + 1 for H_K
@@ -810,6 +856,15 @@ static int usage() {
   printf("\n");
   printf("  bce -e file [config.bcc]\n");
   printf("   Estimates the size -c would give for \"file\" [using config \"config.bcc\"]: the model's code lengths are summed on the GPU, nothing is coded or written (extension)\n");
+  printf("\n");
+  printf("  bce -gs file out.sa\n");
+  printf("   Writes the suffix array of \"file\" to \"out.sa\": one native 32-bit word per suffix in sorted order (the layout of libdivsufsort's mksary), sorted on the GPU (extension)\n");
+  printf("\n");
+  printf("  bce -gsd archive.bce out.sa\n");
+  printf("   The same array for what \"archive.bce\" holds, decoded on the GPU; a -cN / -CN container is refused, its blocks are separate texts (extension)\n");
+  printf("\n");
+  printf("  bce -gsc file in.sa\n");
+  printf("   Checks on the GPU, in linear time, that \"in.sa\" is the suffix array of \"file\" (extension; exit status 0 = in order, %d = not: the line names the row or the position)\n", kExitDiffers);
   printf("\n");
   printf("  bce -g PATTERN file\n");
   printf("   Counts how often the bytes of PATTERN occur in \"file\", overlapping matches included: the file is indexed on the GPU and the count comes from the index (extension)\n");
@@ -1142,6 +1197,10 @@ int main(int argc, char **argv) {
   } else if (argc == 5 && (strcmp(argv[1], "-gf") == 0 || strcmp(argv[1], "-gfd") == 0) && parse_count(argv[2], kMaxTopLen) != 0 &&
              parse_count(argv[3], kMaxTopCount) != 0) {
     return top_command(parse_count(argv[2], kMaxTopLen), parse_count(argv[3], kMaxTopCount), argv[4], argv[1][3] == 'd');
+  } else if (argc == 4 && (strcmp(argv[1], "-gs") == 0 || strcmp(argv[1], "-gsd") == 0)) {
+    return sa_command(argv[2], argv[1][3] == 'd', argv[3]);
+  } else if (argc == 4 && strcmp(argv[1], "-gsc") == 0) {
+    return sa_check_command(argv[2], argv[3]);
   } else if (argc == 4 && argv[1][0] == '-' && argv[1][1] == 's') {
     // Scan (bce.cpp:1384-1402): enumeration on the GPU, ScanCoder optimisation on the host, 288-byte config out
     auto start = std::chrono::high_resolution_clock::now();

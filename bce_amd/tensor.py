@@ -305,6 +305,54 @@ def lpf_tensor(t, max_len=api.PARSE_MAX_LEN, ctx=None):
     return _indexed(t, "lpf_tensor", ctx, use)
 
 
+def _sorted_text(t, what):
+    _check(t, "t")
+    n = t.numel()
+    if n == 0:
+        raise api.BceError(-1, what, "empty input")
+    if n > _MAX_BLOCK:
+        raise ValueError("one suffix array covers one text of less than 2^31 bytes, not %d" % n)
+    return n
+
+
+def suffix_array_tensor(t, inverse=False, ctx=None):
+    """The suffix array of the linear text in the 1-D uint8 CUDA tensor `t` (bce_hip_suffix_array_device) -> an int32 tensor of n
+    rows on t's device, or (sa, isa) with inverse=True.  The text is sorted where it lies and the arrays are written where they
+    stay; only the status reaches the host.  The context's compression state is dropped.
+    Synchronises t's current stream first; `ctx` (an api._Ctx of t's device) is reused if given."""
+    n = _sorted_text(t, "suffix_array_tensor")
+    sa = torch.zeros(n, dtype=torch.int32, device=t.device)
+    isa = torch.zeros(n, dtype=torch.int32, device=t.device) if inverse else None
+    _ready(t)                                                         # (the zero fills too are done before the library's stream writes)
+    own = ctx is None
+    c = ctx or api._Ctx(t.device.index)
+    try:
+        c.check(api.suffix_array_device(t.data_ptr(), n, sa.data_ptr(), isa.data_ptr() if inverse else None, ctx=c), "bce_hip_suffix_array_device")
+        return (sa, isa) if inverse else sa
+    finally:
+        if own:
+            c.close()
+
+
+def sufcheck_tensor(t, sa, ctx=None):
+    """Is the 1-D int32 CUDA tensor `sa` the suffix array of the 1-D uint8 CUDA tensor `t`?  Checked where both lie
+    (bce_hip_sufcheck_device) -> what api.sufcheck returns: None, or (reason, index).  Twelve bytes reach the host.
+    Synchronises the current stream of t's device first; `ctx` (an api._Ctx of t's device) is reused if given."""
+    n = _sorted_text(t, "sufcheck_tensor")
+    if not isinstance(sa, torch.Tensor) or sa.dtype != torch.int32 or sa.dim() != 1 or sa.device != t.device or not sa.is_contiguous() or sa.numel() != n:
+        raise ValueError("sa must be a contiguous 1-D int32 tensor of t's length on t's device")
+    _ready(t)
+    own = ctx is None
+    c = ctx or api._Ctx(t.device.index)
+    try:
+        rc, verdict = api.sufcheck_device(t.data_ptr(), sa.data_ptr(), n, c)
+        c.check(rc, "bce_hip_sufcheck_device")
+        return verdict
+    finally:
+        if own:
+            c.close()
+
+
 def self_parse_tensor(t, min_len, max_len=api.PARSE_MAX_LEN, ctx=None):
     """The 1-D uint8 CUDA tensor `t` as copies of its own earlier bytes plus literal bytes (api.RankFile.self_parse with the outputs
     where they stay: bce_hip_self_parse_device, a sizing call and the full call) -> (ops, lits, info) as parse_tensor gives them.

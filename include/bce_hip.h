@@ -544,6 +544,46 @@ int bce_hip_self_parse_of_lpf_device(bce_hip_ctx *ctx, const void *d_lpf, const 
                                      uint32_t min_len, void *d_ops, uint64_t ops_cap, void *d_lits, uint64_t lits_cap,
                                      bce_hip_parse_info *info);
 
+/* ---- extension: the SUFFIX ARRAY of a buffer as a product, and a checker for one (k1_bwt.hip, kd_sufsort.hip) --------------------
+ * T: n bytes, 0 < n < 2^31 - 1, taken as LINEAR.  sa[r], r < n, is the start of the r-th smallest suffix of T (a suffix that is a
+ * prefix of another sorts before it: libdivsufsort's divsufsort); isa[i] is the row of suffix i, isa[sa[r]] = r.  The sort is
+ * bce_hip_divbwt's -- K1 on the n + 1 rotations of T$ with a unique smallest sentinel, which orders them as suffixes -- with its
+ * order kept: one pass copies rows 1 .. n out and, where isa_out is not NULL, the rank array the sort maintains as the inverse
+ * (8 n bytes read and written a side).  Nothing is cached: every call sorts.
+ * State: as bce_hip_divbwt, the context's compression state is DROPPED (planes, suffix array and loaded input of an earlier load are
+ * gone: the index queries answer BCE_HIP_E_STATE afterwards, a later load and compression give the archive of a fresh context).
+ * Device memory held: what bce_hip_divbwt holds, plus 4 n bytes per output staged for a call with host buffers.
+ * A null ctx, in or sa_out, n == 0, n >= 2^31 - 1: BCE_HIP_E_ARG before any device call; isa_out may be NULL. */
+int bce_hip_suffix_array(bce_hip_ctx *ctx, const uint8_t *in, uint32_t n, uint32_t *sa_out, uint32_t *isa_out /* may be NULL */);
+/* The same with the bytes and both outputs in device memory of the context's device.  d_in is copied into the context's text
+ * buffer; the outputs are 4-byte aligned, n words each, and may not overlap d_in or each other.  Only the status comes back.
+ * Stream rule: as bce_hip_count_device. */
+int bce_hip_suffix_array_device(bce_hip_ctx *ctx, const void *d_in, uint32_t n, void *d_sa, void *d_isa /* may be NULL */);
+/* Is sa[0, n) -- ANY n words, read as unsigned -- the suffix array of in[0, n), 0 < n < 2^31?  Linear work, on the device, in three
+ * stages; the first stage that finds something decides, so *reason and *bad are a function of the two inputs alone:
+ *   BCE_HIP_SUFCHECK_RANGE    *bad = the smallest row i with sa[i] >= n;
+ *   BCE_HIP_SUFCHECK_MISSING  every entry is in range, and *bad = the smallest text position that no row names (an entry that
+ *                             stands twice leaves one);
+ *   BCE_HIP_SUFCHECK_ORDER    the array is a permutation, and *bad = the smallest row i >= 1 that breaks the rule: with a = sa[i - 1]
+ *                             and b = sa[i], either in[a] < in[b], or in[a] == in[b] and a + 1 == n, or in[a] == in[b], b + 1 < n and
+ *                             suffix a + 1 stands in a row above suffix b + 1's.  A permutation keeps the rule on every row
+ *                             exactly when it is sorted (Burkhardt and Karkkainen's inductive check);
+ *   BCE_HIP_SUFCHECK_OK       none of these: *bad = UINT64_MAX.  n == 1 is sound when sa[0] == 0.
+ * An array that is not sorted is NOT an error: the call returns BCE_HIP_OK and the verdict is in *reason and *bad (host pointers,
+ * both required).  Block reductions without atomics; twelve bytes come back.  Device memory held: 4 n bytes for the inverse the
+ * second stage builds, 12 bytes per 2048 rows, plus the 5 n bytes of a call with host buffers, staged.
+ * State: valid in ANY state of the context, between the stages of a compression included: only buffers of the checker's own are
+ * written and nothing a stage keeps is read, so an encode after a check gives the archive of a fresh context.
+ * A null ctx, in, sa, bad or reason, n == 0, n >= 2^31: BCE_HIP_E_ARG before any device call, the outputs untouched. */
+#define BCE_HIP_SUFCHECK_OK 0u
+#define BCE_HIP_SUFCHECK_RANGE 1u
+#define BCE_HIP_SUFCHECK_MISSING 2u
+#define BCE_HIP_SUFCHECK_ORDER 3u
+int bce_hip_sufcheck(bce_hip_ctx *ctx, const uint8_t *in, const uint32_t *sa, uint32_t n, uint64_t *bad, uint32_t *reason);
+/* The same with the bytes and the array (4-byte aligned) in device memory of the context's device; bad and reason stay host
+ * pointers.  Neither array is written.  Stream rule: as bce_hip_count_device. */
+int bce_hip_sufcheck_device(bce_hip_ctx *ctx, const void *d_in, const void *d_sa, uint32_t n, uint64_t *bad, uint32_t *reason);
+
 /* ---- test hooks: the device primitives every stage rests on, alone (tests/test_gpu_sort.py, tests/test_gpu_compare.py) ----
  * Stream rule of bce_hip_crc32_device for all three: the work runs on the context's stream and is complete on return; the caller's
  * memory (device memory of the context's device) must be ready when the call is made.  Valid in any state of the context, between
