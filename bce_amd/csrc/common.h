@@ -462,7 +462,7 @@ inline uint32_t ceil_log2(uint32_t v) { uint32_t b = 0; while ((1ull << b) < v) 
 
 // ---- stage implementations (one .hip file each) ----
 int k1_bwt(bce_hip_ctx *c);                         // k1_bwt.hip
-// K1 in two halves, where k1_two_halves() says the wide first sort applies: k1_first_sort orders the rotations by their first
+// K1 in two halves, where k1_two_halves() says so (two bytes or more, below K1_PART_MIN elements): k1_first_sort orders the rotations by their first
 // *h_symbols bytes, k1_provisional_bwt queues the BWT of that order into c->bwt, k1_finish is the rest of the sort and
 // k1_final_bwt the BWT of the finished order (have_bwt: c->bwt holds it already) and offset_.  k1_bwt is all of it in one call.
 // want_by_bits (or null): the depth the caller wants from the first sort, in symbols, indexed by the alphabet's width in bits

@@ -8,7 +8,7 @@
 // have equal preceding bytes, so their relative order does not matter.
 //
 // Algorithm (MI355X-first, no sentinel, no recursion): prefix doubling on cyclic ranks; ranks are "index of the group head",
-// so they only ever refine; stop when every group is a singleton or h >= n.  The sorter is k1_sort_rotations ("v2"):
+// so they only ever refine; stop when every group is a singleton or h >= n.  The sorter is k1_sort_rotations:
 //   * first sort on a 64-BIT key of as many symbols as fit (alphabet compacted to ceil(log2 sigma) bits: 12 symbols
 //     of text, 8 of arbitrary bytes) built in text order -- no gather at all; ranks by one scatter.
 //   * every later round works on the ACTIVE list only (elements of non-singleton groups, ascending SA slots, head
@@ -23,9 +23,8 @@
 // asks the first sort for the depth that suits the step and, where the key has 8 bits to spare, lets each rotation's preceding
 // byte ride in the key's low bits, so that the provisional BWT is read off the sorted keys.  k1_bwt runs both halves at the full
 // depth, without the byte, and the final gather.
-// The sorter of rounds 1-2 stays as k1_sort_rotations_v1 behind BCE_K1_V1=1 for A/B runs only: a 4-byte first key (4 radix
-// passes), then full rounds in which the sequence SA[j]-h (j ascending) is already ordered by rank[p+h], so a STABLE sort
-// of it by rank[p] alone orders by (rank[p], rank[p+h]) (the Manber-Myers induction as a stable LSD radix sort).
+// The second half reads top to bottom as the steps of K1View (first_ranks, then per round segmented_round, sort_deferred,
+// apply_ranks, relist); K1Buffers and K1View are the one place that says which of the context's buffers plays which part when.
 #include <stdlib.h>
 
 #include <utility>
@@ -34,10 +33,6 @@
 #include "scan_util.h"
 
 namespace bce {
-
-#ifndef K1_ACT_TENTHS
-#define K1_ACT_TENTHS 6   // switch to the active-set rounds below this many tenths of n (4, 6, 8 measured: 6 is best on repetitive text)
-#endif
 
 constexpr int K1_T = 256;
 
@@ -58,96 +53,70 @@ static K1Plan k1_plan(uint32_t n) {
   return {nb, cpb * chunk};
 }
 
-__global__ __launch_bounds__(K1_T) void k1_init_kernel(const uint8_t *__restrict__ T, uint32_t n,
-                                                       uint32_t *__restrict__ keys, uint32_t *__restrict__ vals) {
-  for (uint64_t i = (uint64_t)blockIdx.x * K1_T + threadIdx.x; i < n; i += (uint64_t)gridDim.x * K1_T) {
-    uint32_t k = 0;
-#pragma unroll
-    for (uint32_t b = 0; b < 4; ++b) {
-      uint64_t q = i + b;
-      if (q >= n) q %= n;
-      k = (k << 8) | T[q];
-    }
-    keys[i] = k;
-    vals[i] = (uint32_t)i;
-  }
+// The words of c->blk behind the per-block array (blockmax / blockcnt, K1_MAXB words): results the host reads back, and
+// three small tables.  k1_word() is the one place that knows where they lie.
+enum K1Word : uint32_t {
+  K1W_GROUPS = 0,                  // (unused; zeroed with the next three)
+  K1W_OFFSET = 1,                  // offset_: k1_final_bwt
+  K1W_ACTIVE = 2,                  // length of the next round's active list
+  K1W_DEFERRED = 3,                // elements of groups too large for LDS in this round
+  K1W_DL_COUNT = 4,                // the deferred list as built: its elements ...
+  K1W_DL_GROUPS = 5,               // ... and its groups (written as a pair, behind K1W_DL_COUNT)
+  K1W_HIST = 16,                   // byte histogram, 256 words
+  K1W_CODE = 16 + 256,             // symbol code table, 256 x u16 (with the sentinel 257 symbols can occur)
+  K1W_BLOCKCNT2 = 16 + 256 + 128,  // a second per-block array, K1_MAXB words (the deferred list's heads per block)
+  K1W_END = 16 + 256 + 128 + K1_MAXB
+};
+static uint32_t *k1_word(bce_hip_ctx *c, K1Word w) { return c->blk.as<uint32_t>() + K1_MAXB + w; }
+
+constexpr uint32_t K1_SLOT = 0x7FFFFFFFu, K1_HEAD = 0x80000000u;   // an active-list element: SA slot | starts a group
+constexpr uint8_t KF_HEAD = 1, KF_KEEP = 2, KF_DEFER = 4;          // a round's verdict on a list element (flag[])
+
+// What the blocks before this one hand on to it, from a per-block array that an earlier kernel filled:
+// the max of blockmax[0 .. blockIdx.x) ...
+__device__ __forceinline__ uint32_t k1_blocks_before_max(const uint32_t *__restrict__ blockmax) {
+  uint32_t c = 0;
+  for (uint32_t b = threadIdx.x; b < blockIdx.x; b += K1_T) { const uint32_t v = blockmax[b]; c = c > v ? c : v; }
+  return block_reduce_max<K1_T>(c);
+}
+// ... and the sum of blockcnt[0 .. blockIdx.x), with the sum of all nb of them in *all
+__device__ __forceinline__ uint32_t k1_blocks_before_sum(const uint32_t *__restrict__ blockcnt, uint32_t nb, uint32_t *all) {
+  uint32_t b = 0, a = 0;
+  for (uint32_t k = threadIdx.x; k < nb; k += K1_T) { const uint32_t v = blockcnt[k]; a += v; if (k < blockIdx.x) b += v; }
+  const uint32_t before = block_reduce_sum<K1_T>(b);
+  *all = block_reduce_sum<K1_T>(a);
+  return before;
 }
 
-// The same for T$ with a unique smallest sentinel (the libdivsufsort seam, k1_divbwt): m = n + 1 rotations, 9-bit symbols
-// (0 = $, byte + 1 otherwise), three of them per key.  Rotations of T$ compare like the suffixes of T$.
-__global__ __launch_bounds__(K1_T) void k1_init_sentinel_kernel(const uint8_t *__restrict__ T, uint32_t m,
-                                                                uint32_t *__restrict__ keys, uint32_t *__restrict__ vals) {
-  for (uint64_t i = (uint64_t)blockIdx.x * K1_T + threadIdx.x; i < m; i += (uint64_t)gridDim.x * K1_T) {
-    uint32_t k = 0;
-#pragma unroll
-    for (uint32_t b = 0; b < 3; ++b) {
-      uint64_t q = i + b;
-      if (q >= m) q -= m;
-      k = (k << 9) | (q == m - 1u ? 0u : (uint32_t)T[q] + 1u);
-    }
-    keys[i] = k;
-    vals[i] = (uint32_t)i;
-  }
-}
-
-// keys[j] = rank[SA[j] - h], vals[j] = SA[j] - h   (indices mod n)
-__global__ __launch_bounds__(K1_T) void k1_gather_prev_kernel(const uint32_t *__restrict__ sa,
-                                                              const uint32_t *__restrict__ rank, uint32_t n,
-                                                              uint32_t h, uint32_t *__restrict__ keys,
-                                                              uint32_t *__restrict__ vals) {
-  for (uint64_t j = (uint64_t)blockIdx.x * K1_T + threadIdx.x; j < n; j += (uint64_t)gridDim.x * K1_T) {
-    const uint32_t q = sa[j];
-    const uint32_t p = q >= h ? q - h : q + (n - h);
-    vals[j] = p;
-    keys[j] = rank[p];
-  }
-}
-
-// k2[j] = rank[SA[j] + h]
-__global__ __launch_bounds__(K1_T) void k1_gather_next_kernel(const uint32_t *__restrict__ sa,
-                                                              const uint32_t *__restrict__ rank, uint32_t n,
-                                                              uint32_t h, uint32_t *__restrict__ k2) {
-  for (uint64_t j = (uint64_t)blockIdx.x * K1_T + threadIdx.x; j < n; j += (uint64_t)gridDim.x * K1_T) {
-    const uint64_t q = (uint64_t)sa[j] + h;
-    k2[j] = rank[q >= n ? q - n : q];
-  }
-}
-
-// nrk[j] = j where a new group starts, else 0; per-block max and the global group count.  k2_mask: the bits of k2 that are key
-// (a carried byte below them is not)
+// nrk[j] = j where a new group starts, else 0; per-block max.  (k1, k2): the sorted key's high and low word; k2_mask: the bits
+// of k2 that are key (a carried byte below them is not)
 __global__ __launch_bounds__(K1_T) void k1_heads_kernel(const uint32_t *__restrict__ k1,
                                                         const uint32_t *__restrict__ k2, uint32_t k2_mask, uint32_t n,
                                                         uint32_t per_block, uint32_t *__restrict__ nrk,
-                                                        uint32_t *__restrict__ blockmax, uint32_t *__restrict__ groups) {
+                                                        uint32_t *__restrict__ blockmax) {
   const uint64_t beg = (uint64_t)blockIdx.x * per_block;
   uint64_t end = beg + per_block;
   if (end > n) end = n;
-  uint32_t mx = 0, cnt = 0;
+  uint32_t mx = 0;
   for (uint64_t j = beg + threadIdx.x; j < end; j += K1_T) {
     bool head = (j == 0);
     if (!head) {
       head = k1[j] != k1[j - 1];
-      if (!head && k2) head = ((k2[j] ^ k2[j - 1]) & k2_mask) != 0u;
+      if (!head) head = ((k2[j] ^ k2[j - 1]) & k2_mask) != 0u;
     }
     nrk[j] = head ? (uint32_t)j : 0u;
-    if (head) { mx = (uint32_t)j; ++cnt; }
+    if (head) mx = (uint32_t)j;
   }
   mx = block_reduce_max<K1_T>(mx);
-  cnt = block_reduce_sum<K1_T>(cnt);
-  if (threadIdx.x == 0) {
-    blockmax[blockIdx.x] = mx;
-    if (cnt) atomicAdd(groups, cnt);
-  }
+  if (threadIdx.x == 0) blockmax[blockIdx.x] = mx;
 }
 
-// rank[SA[j]] = max(nrk[0..j])  (running max == index of the group head)
-__global__ __launch_bounds__(K1_T) void k1_apply_kernel(const uint32_t *__restrict__ nrk,
-                                                        const uint32_t *__restrict__ blockmax, uint32_t n,
-                                                        uint32_t per_block, const uint32_t *__restrict__ sa,
-                                                        uint32_t *__restrict__ rank) {
-  uint32_t c = 0;
-  for (uint32_t b = threadIdx.x; b < blockIdx.x; b += K1_T) { const uint32_t v = blockmax[b]; c = c > v ? c : v; }
-  uint32_t carry = block_reduce_max<K1_T>(c);
+// The running max of nrk over this block's range of [0, n), seeded by the blocks before it: with nrk[j] = "a number that
+// grows with j where a group starts, else 0" that is the number of j's group head.  VIA_IDX: dst[idx[j]] = it, else dst[j] = it.
+template <bool VIA_IDX>
+__device__ __forceinline__ void k1_running_max(const uint32_t *__restrict__ nrk, const uint32_t *__restrict__ blockmax, uint32_t n,
+                                               uint32_t per_block, const uint32_t *__restrict__ idx, uint32_t *__restrict__ dst) {
+  uint32_t carry = k1_blocks_before_max(blockmax);
   const uint64_t beg = (uint64_t)blockIdx.x * per_block;
   uint64_t end = beg + per_block;
   if (end > n) end = n;
@@ -158,9 +127,18 @@ __global__ __launch_bounds__(K1_T) void k1_apply_kernel(const uint32_t *__restri
     uint32_t tot;
     uint32_t inc = block_incl_scan_max<K1_T>(v, &tot);
     inc = inc > carry ? inc : carry;
-    if (valid) rank[sa[j]] = inc;
+    if (valid) dst[VIA_IDX ? idx[j] : j] = inc;
     carry = carry > tot ? carry : tot;
   }
+}
+
+// rank[sa[j]] = max(nrk[0..j]): the rank of a suffix is the number of its group's head.  After the first sort sa is the whole
+// order and the number an index; for the deferred groups sa is their sorted suffixes and the number a slot.
+__global__ __launch_bounds__(K1_T) void k1_apply_kernel(const uint32_t *__restrict__ nrk,
+                                                        const uint32_t *__restrict__ blockmax, uint32_t n,
+                                                        uint32_t per_block, const uint32_t *__restrict__ sa,
+                                                        uint32_t *__restrict__ rank) {
+  k1_running_max<true>(nrk, blockmax, n, per_block, sa, rank);
 }
 
 // ---- rank scatters as sorts (inputs far beyond the caches: 10^9 B) ----
@@ -179,22 +157,7 @@ __global__ __launch_bounds__(K1_T) void k1_apply_kernel(const uint32_t *__restri
 // hv[j] = max(nrk[0..j]) = index of j's group head (what k1_apply_kernel scatters), written in place of order j
 __global__ __launch_bounds__(K1_T) void k1_headidx_kernel(const uint32_t *__restrict__ nrk, const uint32_t *__restrict__ blockmax, uint32_t n,
                                                           uint32_t per_block, uint32_t *__restrict__ hv) {
-  uint32_t c = 0;
-  for (uint32_t b = threadIdx.x; b < blockIdx.x; b += K1_T) { const uint32_t v = blockmax[b]; c = c > v ? c : v; }
-  uint32_t carry = block_reduce_max<K1_T>(c);
-  const uint64_t beg = (uint64_t)blockIdx.x * per_block;
-  uint64_t end = beg + per_block;
-  if (end > n) end = n;
-  for (uint64_t base = beg; base < end; base += K1_T) {
-    const uint64_t j = base + threadIdx.x;
-    const bool valid = j < end;
-    const uint32_t v = valid ? nrk[j] : 0u;
-    uint32_t tot;
-    uint32_t inc = block_incl_scan_max<K1_T>(v, &tot);
-    inc = inc > carry ? inc : carry;
-    if (valid) hv[j] = inc;
-    carry = carry > tot ? carry : tot;
-  }
+  k1_running_max<false>(nrk, blockmax, n, per_block, nullptr, hv);
 }
 // dst[key[i]] = val[i] for the keys below `limit` (pairs grouped by destination range)
 __global__ __launch_bounds__(K1_T) void k1_scatter32_kernel(const uint32_t *__restrict__ key, const uint32_t *__restrict__ val, uint32_t m,
@@ -246,19 +209,15 @@ __global__ __launch_bounds__(K1_T) void k1_offset_kernel(const uint32_t *__restr
   if ((threadIdx.x & 63u) == 0 && best != 0xFFFFFFFFu) atomicMin(out, best);
 }
 
-// ---- active-set rounds -----------------------------------------------------------------------------
-// Once most suffixes sit in singleton groups, only the rest (the ACTIVE list A of SA indices, ascending) is
-// worked on: sort the active suffixes by rank[p+h], then stably by their group (rank[p]), write them back into
-// their SA slots (groups are contiguous in A as in SA), re-rank inside the groups, drop new singletons.
-
-// count (pass 0) / write (pass 1) the elements that stay active.  head(i) = i == 0 || nrk[i] != 0;
-// an element is a singleton iff it is a head and its successor is a head (or it is the last one).
+// The first active list, from the first sort's heads: count (pass 0) / write (pass 1) the elements of non-singleton groups.
+// head(i) = i == 0 || nrk[i] != 0; an element is a singleton iff it is a head and its successor is a head (or it is the last
+// one).  out = the element's slot i | K1_HEAD where it starts a group (the rounds find the groups of the list from these
+// bits), vout = the suffix at the slot: it travels with the list.
 template <int PASS>
-__global__ __launch_bounds__(K1_T) void k1_active_kernel(const uint32_t *__restrict__ nrk,
-                                                         const uint32_t *__restrict__ src, uint32_t m,
+__global__ __launch_bounds__(K1_T) void k1_active_kernel(const uint32_t *__restrict__ nrk, uint32_t m,
                                                          uint32_t per_block, uint32_t nb, uint32_t *__restrict__ blockcnt,
-                                                         uint32_t *__restrict__ out, uint32_t *__restrict__ total, uint32_t mark = 0,
-                                                         const uint32_t *__restrict__ sa_in = nullptr, uint32_t *__restrict__ vout = nullptr) {
+                                                         uint32_t *__restrict__ out, uint32_t *__restrict__ total,
+                                                         const uint32_t *__restrict__ sa_in, uint32_t *__restrict__ vout) {
   const uint64_t beg = (uint64_t)blockIdx.x * per_block;
   uint64_t end = beg + per_block;
   if (end > m) end = m;
@@ -273,88 +232,20 @@ __global__ __launch_bounds__(K1_T) void k1_active_kernel(const uint32_t *__restr
     c = block_reduce_sum<K1_T>(c);
     if (threadIdx.x == 0) blockcnt[blockIdx.x] = c;
   } else {
-    uint32_t b = 0, a = 0;
-    for (uint32_t k = threadIdx.x; k < nb; k += K1_T) { const uint32_t v = blockcnt[k]; a += v; if (k < blockIdx.x) b += v; }
-    uint32_t base = block_reduce_sum<K1_T>(b);
-    const uint32_t all = block_reduce_sum<K1_T>(a);
+    uint32_t all;
+    uint32_t base = k1_blocks_before_sum(blockcnt, nb, &all);
     if (blockIdx.x == 0 && threadIdx.x == 0) *total = all;
     for (uint64_t c0 = beg; c0 < end; c0 += K1_T) {
       const uint64_t i = c0 + threadIdx.x;
       const bool k = i < end && keep(i);
       uint32_t tot;
       const uint32_t ex = block_excl_scan_sum<K1_T>(k ? 1u : 0u, &tot);
-      // mark: bit 31 = this element starts a group (the v2 rounds find the groups of the list from these bits)
       if (k) {
-        out[base + ex] = (src ? src[i] : (uint32_t)i) | ((mark && (i == 0 || nrk[i] != 0)) ? 0x80000000u : 0u);
-        if (vout) vout[base + ex] = sa_in[i];               // (v2: the suffix at the slot travels with the list)
+        out[base + ex] = (uint32_t)i | ((i == 0 || nrk[i] != 0) ? K1_HEAD : 0u);
+        vout[base + ex] = sa_in[i];
       }
       base += tot;
     }
-  }
-}
-
-// keys[i] = rank[SA[A[i]] + h], vals[i] = SA[A[i]]
-__global__ __launch_bounds__(K1_T) void k1_act_gather_kernel(const uint32_t *__restrict__ A, const uint32_t *__restrict__ sa,
-                                                             const uint32_t *__restrict__ rank, uint32_t n, uint32_t m,
-                                                             uint32_t h, uint32_t *__restrict__ keys,
-                                                             uint32_t *__restrict__ vals) {
-  for (uint64_t i = (uint64_t)blockIdx.x * K1_T + threadIdx.x; i < m; i += (uint64_t)gridDim.x * K1_T) {
-    const uint32_t p = sa[A[i]];
-    const uint64_t q = (uint64_t)p + h;
-    vals[i] = p;
-    keys[i] = rank[q >= n ? q - n : q];
-  }
-}
-// keys[i] = rank[vals[i]]  (the group of each active suffix)
-__global__ __launch_bounds__(K1_T) void k1_act_group_kernel(const uint32_t *__restrict__ vals,
-                                                            const uint32_t *__restrict__ rank, uint32_t m,
-                                                            uint32_t *__restrict__ keys) {
-  for (uint64_t i = (uint64_t)blockIdx.x * K1_T + threadIdx.x; i < m; i += (uint64_t)gridDim.x * K1_T)
-    keys[i] = rank[vals[i]];
-}
-// write the sorted suffixes back to their SA slots; nrk[i] = A[i] where a new group starts (else 0);
-// k2 = rank[p+h] is gathered again here (the second sort carried only the group key)
-__global__ __launch_bounds__(K1_T) void k1_act_heads_kernel(const uint32_t *__restrict__ A, const uint32_t *__restrict__ vals,
-                                                            const uint32_t *__restrict__ k1s,
-                                                            const uint32_t *__restrict__ rank, uint32_t n, uint32_t m,
-                                                            uint32_t h, uint32_t per_block, uint32_t *__restrict__ sa,
-                                                            uint32_t *__restrict__ nrk, uint32_t *__restrict__ blockmax) {
-  const uint64_t beg = (uint64_t)blockIdx.x * per_block;
-  uint64_t end = beg + per_block;
-  if (end > m) end = m;
-  uint32_t mx = 0;
-  auto key2 = [&](uint64_t i) -> uint32_t { const uint64_t q = (uint64_t)vals[i] + h; return rank[q >= n ? q - n : q]; };
-  for (uint64_t i = beg + threadIdx.x; i < end; i += K1_T) {
-    const uint32_t slot = A[i];
-    sa[slot] = vals[i];
-    bool head = i == 0 || k1s[i] != k1s[i - 1];
-    if (!head) head = key2(i) != key2(i - 1);
-    nrk[i] = head ? slot : 0u;
-    if (head) mx = slot;
-  }
-  mx = block_reduce_max<K1_T>(mx);
-  if (threadIdx.x == 0) blockmax[blockIdx.x] = mx;
-}
-// rank[vals[i]] = running max of nrk (= SA index of the group head)
-__global__ __launch_bounds__(K1_T) void k1_act_apply_kernel(const uint32_t *__restrict__ nrk,
-                                                            const uint32_t *__restrict__ blockmax, uint32_t m,
-                                                            uint32_t per_block, const uint32_t *__restrict__ vals,
-                                                            uint32_t *__restrict__ rank) {
-  uint32_t c = 0;
-  for (uint32_t b = threadIdx.x; b < blockIdx.x; b += K1_T) { const uint32_t v = blockmax[b]; c = c > v ? c : v; }
-  uint32_t carry = block_reduce_max<K1_T>(c);
-  const uint64_t beg = (uint64_t)blockIdx.x * per_block;
-  uint64_t end = beg + per_block;
-  if (end > m) end = m;
-  for (uint64_t base = beg; base < end; base += K1_T) {
-    const uint64_t i = base + threadIdx.x;
-    const bool valid = i < end;
-    const uint32_t v = valid ? nrk[i] : 0u;
-    uint32_t tot;
-    uint32_t inc = block_incl_scan_max<K1_T>(v, &tot);
-    inc = inc > carry ? inc : carry;
-    if (valid) rank[vals[i]] = inc;
-    carry = carry > tot ? carry : tot;
   }
 }
 
@@ -363,129 +254,7 @@ static uint32_t grid_for(uint32_t n) {
   return (uint32_t)(b < 4096 ? (b ? b : 1) : 4096);
 }
 
-// Sort the n cyclic rotations of T (sentinel = false), or the n = |T| + 1 rotations of T$ (sentinel = true: T holds n - 1
-// bytes).  Leaves the order in c->sa[c->sa_res] and its inverse (the rank of the group head for tied rotations) in c->rank.
-static int k1_sort_rotations_v1(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool sentinel) {
-  const size_t b4 = (size_t)n * 4;
-  for (int i = 0; i < 2; ++i) { BCE_TRY(ensure(c, c->sa[i], b4)); BCE_TRY(ensure(c, c->key[i], b4)); }
-  BCE_TRY(ensure(c, c->rank, b4));
-  BCE_TRY(ensure(c, c->k2, b4));
-  BCE_TRY(ensure(c, c->nrk, b4));
-  for (int i = 0; i < 2; ++i) BCE_TRY(ensure(c, c->act[i], b4));
-  const K1Plan pl = k1_plan(n);
-  BCE_TRY(ensure(c, c->blk, (size_t)(K1_MAXB + 16) * 4));
-  uint32_t *blockmax = c->blk.as<uint32_t>();
-  uint32_t *scalars = blockmax + K1_MAXB;  // [0] groups, [1] offset, [2] active elements
-  uint32_t *rank = c->rank.as<uint32_t>(), *k2 = c->k2.as<uint32_t>(), *nrk = c->nrk.as<uint32_t>();
-  const uint32_t g = grid_for(n);
-
-  uint32_t *key[2] = {c->key[0].as<uint32_t>(), c->key[1].as<uint32_t>()};
-  uint32_t *val[2] = {c->sa[0].as<uint32_t>(), c->sa[1].as<uint32_t>()};
-  int res = 0;
-  if (sentinel) {
-    hipLaunchKernelGGL(k1_init_sentinel_kernel, dim3(g), dim3(K1_T), 0, c->stream, T, n, key[0], val[0]);
-    BCE_TRY(radix_sort_pairs(c, key, val, n, 0, 27, &res, 9));
-  } else {
-    hipLaunchKernelGGL(k1_init_kernel, dim3(g), dim3(K1_T), 0, c->stream, T, n, key[0], val[0]);
-    BCE_TRY(radix_sort_pairs(c, key, val, n, 0, 32, &res));
-  }
-  uint32_t groups = 0;
-  auto rerank = [&](const uint32_t *k1s, const uint32_t *k2s, const uint32_t *sa) -> int {
-    BCE_HIP_TRY(c, hipMemsetAsync(scalars, 0, 4, c->stream));
-    hipLaunchKernelGGL(k1_heads_kernel, dim3(pl.nb), dim3(K1_T), 0, c->stream, k1s, k2s, 0xFFFFFFFFu, n, pl.per_block, nrk,
-                       blockmax, scalars);
-    hipLaunchKernelGGL(k1_apply_kernel, dim3(pl.nb), dim3(K1_T), 0, c->stream, nrk, blockmax, n, pl.per_block, sa,
-                       rank);
-    BCE_TRY(read_back(c, &groups, scalars, 4));
-    return BCE_HIP_OK;
-  };
-  BCE_TRY(rerank(key[res], nullptr, val[res]));
-  const uint32_t bits = ceil_log2(n);
-  const uint32_t dg = 9;   // digit width of the rank sorts (7..9 measured equal)
-  uint64_t h = sentinel ? 3 : 4;
-  uint32_t *act[2] = {c->act[0].as<uint32_t>(), c->act[1].as<uint32_t>()};
-  uint32_t m = n;                 // active elements; the list is implicit (identity) while every element is active
-  bool have_list = false;
-  // active elements after a re-rank: not (head && next is head)
-  auto build_active = [&](const uint32_t *nrk_in, const uint32_t *src, uint32_t cnt, uint32_t *out) -> int {
-    const K1Plan ap = k1_plan(cnt);
-    hipLaunchKernelGGL(k1_active_kernel<0>, dim3(ap.nb), dim3(K1_T), 0, c->stream, nrk_in, src, cnt, ap.per_block, ap.nb,
-                       blockmax, out, scalars + 2);
-    hipLaunchKernelGGL(k1_active_kernel<1>, dim3(ap.nb), dim3(K1_T), 0, c->stream, nrk_in, src, cnt, ap.per_block, ap.nb,
-                       blockmax, out, scalars + 2);
-    BCE_TRY(read_back(c, &m, scalars + 2, 4));
-    return BCE_HIP_OK;
-  };
-  const bool trace = getenv("BCE_K1_TRACE") != nullptr;
-  double t_prev = now_s();
-  if (trace) fprintf(stderr, "k1 %p: start n %u groups %u\n", (void *)c, n, groups);
-  while (groups < n && h < n) {
-    if (trace) { const double t = now_s(); fprintf(stderr, "k1 %p: h %llu groups %u m %u list %d (+%.2f ms)\n", (void *)c, (unsigned long long)h, groups, m, (int)have_list, (t - t_prev) * 1e3); t_prev = t; }
-    if (!have_list && (uint64_t)(n - groups) * 10 < (uint64_t)n * K1_ACT_TENTHS + 10) {
-      // few elements can still be in non-singleton groups (at most 2 per missing group... bound: n - groups < 0.4 n
-      // means at most 0.8 n active): build the explicit list and check its real size
-      BCE_TRY(build_active(nrk, nullptr, n, act[0]));
-      have_list = true;
-      if (m == 0) break;
-    }
-    if (have_list && (uint64_t)m * 10 < (uint64_t)n * K1_ACT_TENTHS) {
-      // ---- active round on m elements ----
-      const uint32_t *A = act[0];
-      uint32_t *ki[2] = {key[0], key[1]};
-      uint32_t *vi[2] = {val[res ^ 1], k2};
-      const uint32_t ga = grid_for(m);
-      hipLaunchKernelGGL(k1_act_gather_kernel, dim3(ga), dim3(K1_T), 0, c->stream, A, val[res], rank, n, m, (uint32_t)h,
-                         ki[0], vi[0]);
-      int r1 = 0;
-      BCE_TRY(radix_sort_pairs(c, ki, vi, m, 0, bits, &r1, dg));
-      // second sort: by group, input = output of the first
-      uint32_t *kj[2] = {ki[r1 ^ 1], ki[r1]};
-      uint32_t *vj[2] = {vi[r1], vi[r1 ^ 1]};
-      hipLaunchKernelGGL(k1_act_group_kernel, dim3(ga), dim3(K1_T), 0, c->stream, vj[0], rank, m, kj[0]);
-      int r2 = 0;
-      BCE_TRY(radix_sort_pairs(c, kj, vj, m, 0, bits, &r2, dg));
-      const K1Plan ap = k1_plan(m);
-      hipLaunchKernelGGL(k1_act_heads_kernel, dim3(ap.nb), dim3(K1_T), 0, c->stream, A, vj[r2], kj[r2], rank, n, m,
-                         (uint32_t)h, ap.per_block, val[res], nrk, blockmax);
-      hipLaunchKernelGGL(k1_act_apply_kernel, dim3(ap.nb), dim3(K1_T), 0, c->stream, nrk, blockmax, m, ap.per_block,
-                         vj[r2], rank);
-      BCE_TRY(build_active(nrk, A, m, act[1]));
-      std::swap(act[0], act[1]);
-      h <<= 1;
-      c->stats.sort_rounds++;
-      if (m == 0) break;
-      continue;
-    }
-    // ---- full round on all n elements ----
-    // input of the sort goes to slot 0 of a local ping-pong so the result index is well defined
-    uint32_t *ki[2] = {key[res ^ 1], key[res]};
-    uint32_t *vi[2] = {val[res ^ 1], val[res]};
-    hipLaunchKernelGGL(k1_gather_prev_kernel, dim3(g), dim3(K1_T), 0, c->stream, val[res], rank, n, (uint32_t)h,
-                       ki[0], vi[0]);
-    int r2 = 0;
-    BCE_TRY(radix_sort_pairs(c, ki, vi, n, 0, bits, &r2, dg));
-    uint32_t *sk = ki[r2], *ssa = vi[r2];
-    hipLaunchKernelGGL(k1_gather_next_kernel, dim3(g), dim3(K1_T), 0, c->stream, ssa, rank, n, (uint32_t)h, k2);
-    BCE_TRY(rerank(sk, k2, ssa));
-    // make (key[res], val[res]) name the sorted arrays again
-    res = (ssa == val[0]) ? 0 : 1;
-    h <<= 1;
-    c->stats.sort_rounds++;
-    have_list = false;
-  }
-  // all rotations distinct <=> rank[] is the inverse of the suffix array (used by the depth-first tail of K3)
-  c->k1_unique = (groups >= n) || (have_list && m == 0);
-  c->sa_res = res;
-  return BCE_HIP_OK;
-}
-
-
-// ---- v2: 64-bit first key + segmented rounds --------------------------------------------------------------------------
-constexpr uint32_t K1_SLOT = 0x7FFFFFFFu, K1_HEAD = 0x80000000u;
-constexpr uint32_t K1_SC_HIST = 16, K1_SC_CODE = 16 + 256;     // words behind the scalars: byte histogram, symbol code table (256 x u16:
-                                                               // with the sentinel 257 symbols can occur)
-constexpr uint8_t KF_HEAD = 1, KF_KEEP = 2, KF_DEFER = 4;
-
+// ---- first sort: a 64-bit key of as many symbols as fit ---------------------------------------------------------------------
 __global__ __launch_bounds__(K1_T) void k1_bytehist_kernel(const uint8_t *__restrict__ T, uint32_t n, uint32_t *__restrict__ hist) {
   __shared__ uint32_t lh[256];
   lh[threadIdx.x] = 0;
@@ -718,7 +487,7 @@ __global__ __launch_bounds__(K1_T) void k1_relist_kernel(const uint32_t *__restr
                                                          const uint8_t *__restrict__ flag, uint32_t m,
                                                          uint32_t per_block, uint32_t nb, uint32_t *__restrict__ blockcnt,
                                                          uint32_t *__restrict__ out, uint32_t *__restrict__ out2, uint32_t *__restrict__ total,
-                                                         uint32_t *__restrict__ blockcnt2 = nullptr, uint32_t *__restrict__ out3 = nullptr) {
+                                                         uint32_t *__restrict__ blockcnt2, uint32_t *__restrict__ out3) {
   const uint64_t beg = (uint64_t)blockIdx.x * per_block;
   uint64_t end = beg + per_block;
   if (end > m) end = m;
@@ -734,18 +503,11 @@ __global__ __launch_bounds__(K1_T) void k1_relist_kernel(const uint32_t *__restr
     if (MODE == 0) hc = block_reduce_sum<K1_T>(hc);
     if (threadIdx.x == 0) { blockcnt[blockIdx.x] = cnt; if (MODE == 0) blockcnt2[blockIdx.x] = hc; }
   } else {
-    uint32_t b = 0, a = 0, b2 = 0, a2 = 0;
-    for (uint32_t k = threadIdx.x; k < nb; k += K1_T) {
-      const uint32_t v = blockcnt[k];
-      a += v; if (k < blockIdx.x) b += v;
-      if (MODE == 0) { const uint32_t v2 = blockcnt2[k]; a2 += v2; if (k < blockIdx.x) b2 += v2; }
-    }
-    uint32_t base = block_reduce_sum<K1_T>(b);
-    const uint32_t all = block_reduce_sum<K1_T>(a);
-    uint32_t hbase = 0;
+    uint32_t all, hbase = 0;
+    uint32_t base = k1_blocks_before_sum(blockcnt, nb, &all);
     if (MODE == 0) {
-      hbase = block_reduce_sum<K1_T>(b2);
-      const uint32_t all2 = block_reduce_sum<K1_T>(a2);
+      uint32_t all2;
+      hbase = k1_blocks_before_sum(blockcnt2, nb, &all2);
       if (blockIdx.x == 0 && threadIdx.x == 0) total[1] = all2;     // deferred groups
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) total[0] = all;
@@ -771,8 +533,7 @@ __global__ __launch_bounds__(K1_T) void k1_relist_kernel(const uint32_t *__restr
 // ---- the global path (round 3): the elements of groups too large for LDS, all such groups in ONE sort ----------------
 // key = (number of the group among the deferred groups) << rbits | rank[p + h], value = p: one stable sort on the bits in
 // use orders every deferred group by its second key where it lies (the list is ascending and holds whole groups, so the
-// sorted sequence lines up with the slots).  Against v1's active round: one random gather and one random scatter per
-// element instead of seven, five wide passes instead of six narrow ones and a gather.
+// sorted sequence lines up with the slots).  One random gather and one random scatter per element, five wide passes.
 __global__ __launch_bounds__(K1_T) void k1_big_gather_kernel(const uint32_t *__restrict__ idx, const uint32_t *__restrict__ gid,
                                                              const uint32_t *__restrict__ V, const uint32_t *__restrict__ rank,
                                                              uint32_t n, uint32_t nd, uint32_t h, uint32_t rbits,
@@ -787,7 +548,7 @@ __global__ __launch_bounds__(K1_T) void k1_big_gather_kernel(const uint32_t *__r
     val[j] = p;
   }
 }
-// the sorted suffixes go back to their slots; nrk[j] = slot where a new group starts (else 0), per-block maxima for k1_act_apply_kernel
+// the sorted suffixes go back to their slots; nrk[j] = slot where a new group starts (else 0), per-block maxima for k1_apply_kernel
 __global__ __launch_bounds__(K1_T) void k1_big_heads_kernel(const uint32_t *__restrict__ slots, const uint32_t *__restrict__ lo,
                                                             const uint32_t *__restrict__ hi, const uint32_t *__restrict__ val,
                                                             uint32_t nd, uint32_t per_block, uint32_t *__restrict__ sa,
@@ -826,39 +587,167 @@ static uint32_t k1_part_min() {
   return part_min;
 }
 
-// The sorter's arrays and its trace, as both halves of the sort see them (everything is the context's: k1_first_sort_wide sizes it).
-struct K1View {
+// The context's buffers as the sort names them (k1_first_sort_wide sizes them all) and the trace: what both halves see.
+// Everything is queued on c->stream, so "free" below means "every kernel that reads it is queued ahead".  DESIGN, K1, has the
+// roles as a table.
+struct K1Buffers {
   bce_hip_ctx *c;
   uint32_t n, g;
-  K1Plan pl;
-  uint32_t *blockmax, *scalars;  // scalars: [0] groups, [1] offset, [2] active elements, [3] deferred elements, [4..5] deferred list;
-                                 // histogram; code table; a second per-block array
-  uint32_t *rank, *k2, *nrk;
-  uint8_t *flag;
-  uint32_t *lo[2], *hi[2], *val[2];
+  uint32_t *blockmax;            // c->blk's first K1_MAXB words: what the first kernel of a pair leaves per block for the second
+  uint32_t *rank;                // c->rank: rank of every rotation = index of its group's head
+  uint32_t *lo[2], *hi[2], *val[2];   // c->key[] / c->khi[] / c->sa[]: the first sort's ping-pong of (low word, high word, rotation), from side 0
+  uint32_t *nrk;                 // c->nrk: "index where a group starts, else 0" over the first sort's order; free once the first list is queued
+  uint32_t *k2;                  // c->k2: the first sorted apply's head indices; free when that sort is queued
+  uint8_t *flag;                 // c->kflag: KF_* of every list element, rewritten by each round
+  uint32_t *act[2], *actv[2];    // c->act[] / c->actv[]: the active list (slot | head bit), the suffix at each slot; [0] this round's, [1] the next one's
   bool trace;
   double t_prev;
-  explicit K1View(bce_hip_ctx *ctx, uint32_t n_) : c(ctx), n(n_), g(grid_for(n_)), pl(k1_plan(n_)) {
+
+  K1Buffers(bce_hip_ctx *ctx, uint32_t n_) : c(ctx), n(n_), g(grid_for(n_)) {
     blockmax = c->blk.as<uint32_t>();
-    scalars = blockmax + K1_MAXB;
     rank = c->rank.as<uint32_t>(); k2 = c->k2.as<uint32_t>(); nrk = c->nrk.as<uint32_t>();
     flag = c->kflag.as<uint8_t>();
-    for (int i = 0; i < 2; ++i) { lo[i] = c->key[i].as<uint32_t>(); hi[i] = c->khi[i].as<uint32_t>(); val[i] = c->sa[i].as<uint32_t>(); }
+    for (int i = 0; i < 2; ++i) {
+      lo[i] = c->key[i].as<uint32_t>(); hi[i] = c->khi[i].as<uint32_t>(); val[i] = c->sa[i].as<uint32_t>();
+      act[i] = c->act[i].as<uint32_t>(); actv[i] = c->actv[i].as<uint32_t>();
+    }
     trace = getenv("BCE_K1_TRACE") != nullptr;
     t_prev = now_s();
   }
-  void lap(const char *what, uint64_t h, uint32_t m, uint32_t nd) {
+  uint32_t *word(K1Word w) const { return k1_word(c, w); }
+  void lap(const char *what, uint64_t h_, uint32_t m_, uint32_t nd_) {
     if (!trace) return;
     (void)hipStreamSynchronize(c->stream);
     const double t = now_s();
-    fprintf(stderr, "k1 %p: %-10s h %llu active %u deferred %u (+%.2f ms)\n", (void *)c, what, (unsigned long long)h, m, nd, (t - t_prev) * 1e3);
+    fprintf(stderr, "k1 %p: %-10s h %llu active %u deferred %u (+%.2f ms)\n", (void *)c, what, (unsigned long long)h_, m_, nd_, (t - t_prev) * 1e3);
     t_prev = t;
   }
 };
 
+// The second half's state, built from what the first half left in the context (k1_res, k1_h, k1_carry), and its steps.
+struct K1View : K1Buffers {
+  K1Plan pl;                     // the per-block passes over all n elements
+  uint32_t rbits, part_min;      // bits of a rank; elements from which a rank scatter is done as a sort
+  int res;                       // (lo[res], hi[res], val[res]) hold the first sort's keys and its order
+  uint32_t *sa;                  // = val[res]: the order; every round reorders it inside its groups, in place
+  uint32_t *nr, *vs;             // = hi[0], hi[1]: a round's new rank and suffix per list position.  Free once the heads are taken from
+                                 // the first sort's keys (hi[res ^ 1]: a key buffer of the first sorted apply, before the first round)
+  // The first sorted apply also takes lo[res ^ 1] (keys), val[res ^ 1] and rank (values: its last pass writes the ranks themselves).
+  // The deferred sort takes lo[] (low words; free once the heads are taken and a provisional BWT is queued), val[res ^ 1] and k2
+  // (high words), nrk and c->dl[3] (values; the one it leaves unused takes the heads of its result) beside the list in c->dl[0 .. 2]:
+  // all free again when the round's apply is queued, which as a sort takes lo[] (keys), k2 and val[res ^ 1] (values) in its turn.
+  uint64_t h;                    // symbols by which the rotations are ordered
+  uint32_t m, nd;                // active elements; of them deferred in this round
+
+  K1View(bce_hip_ctx *ctx, uint32_t n_) : K1Buffers(ctx, n_), pl(k1_plan(n_)), rbits(ceil_log2(n_)), part_min(k1_part_min()), res(ctx->k1_res),
+                                          sa(val[res]), nr(hi[0]), vs(hi[1]), h(ctx->k1_h), m(0), nd(0) {}
+
+  // A scatter dst[key] = value as a sort: cnt (destination, value) pairs sorted on rbits bits in two steps, the digit of a balanced
+  // pass and then the rest.  The first step reads (k_in, v_in) and writes (k_a, v_a); the rest goes between (k_a, v_a) and
+  // (k_b, v_b), where k_b may be k_in again.  *at_b: the result lies in (k_b, v_b), else in (k_a, v_a).
+  int sort_by_dest(uint32_t cnt, uint32_t *k_in, uint32_t *v_in, uint32_t *k_a, uint32_t *v_a, uint32_t *k_b, uint32_t *v_b, int *at_b) {
+    const uint32_t b1 = rbits / ((rbits + 9u) / 10u);
+    uint32_t *pk[2] = {k_in, k_a}, *pv[2] = {v_in, v_a};
+    BCE_TRY(radix_sort_pairs(c, pk, pv, cnt, 0, b1, at_b, 10));             // one pass: the input is left alone
+    uint32_t *qk[2] = {k_a, k_b}, *qv[2] = {v_a, v_b};
+    return radix_sort_pairs(c, qk, qv, cnt, b1, rbits - b1, at_b, 10);
+  }
+
+  // Ranks from the sorted keys (group heads, then one scatter of their indices -- or the sort that stands for it) and the first
+  // active list.
+  int first_ranks() {
+    BCE_HIP_TRY(c, hipMemsetAsync(word(K1W_GROUPS), 0, 16, c->stream));     // the four result words
+    hipLaunchKernelGGL(k1_heads_kernel, dim3(pl.nb), dim3(K1_T), 0, c->stream, hi[res], lo[res], c->k1_carry ? 0xFFFFFF00u : 0xFFFFFFFFu, n, pl.per_block,
+                       nrk, blockmax);
+    const bool sorted_apply = n >= part_min;
+    if (sorted_apply) hipLaunchKernelGGL(k1_headidx_kernel, dim3(pl.nb), dim3(K1_T), 0, c->stream, nrk, blockmax, n, pl.per_block, k2);
+    else hipLaunchKernelGGL(k1_apply_kernel, dim3(pl.nb), dim3(K1_T), 0, c->stream, nrk, blockmax, n, pl.per_block, sa, rank);
+    hipLaunchKernelGGL(k1_active_kernel<0>, dim3(pl.nb), dim3(K1_T), 0, c->stream, nrk, n, pl.per_block, pl.nb, blockmax, act[0], word(K1W_ACTIVE), sa, actv[0]);
+    hipLaunchKernelGGL(k1_active_kernel<1>, dim3(pl.nb), dim3(K1_T), 0, c->stream, nrk, n, pl.per_block, pl.nb, blockmax, act[0], word(K1W_ACTIVE), sa, actv[0]);
+    if (sorted_apply) {
+      // rank = the head indices (k2) sorted by suffix: the first pass reads the suffix array and leaves it alone, the last one
+      // writes the rank array itself
+      int at_b = 0;
+      BCE_TRY(sort_by_dest(n, sa, k2, lo[res ^ 1], rank, hi[res ^ 1], val[res ^ 1], &at_b));
+      if (at_b) BCE_HIP_TRY(c, hipMemcpyAsync(rank, val[res ^ 1], (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));   // (an odd number of passes behind the first: n > 2^30)
+    }
+    BCE_TRY(read_back(c, &m, word(K1W_ACTIVE), 4));
+    lap("first ranks", h, m, 0);
+    return BCE_HIP_OK;
+  }
+
+  // One doubling round on the groups that fit LDS, each sorted where it lies: sa reordered, the new ranks staged in (nr, vs),
+  // flags; the larger groups' elements are flagged and counted (nd).
+  int segmented_round() {
+    const uint32_t nblk = (uint32_t)(((uint64_t)m + SEG_CH - 1) / SEG_CH);
+    BCE_HIP_TRY(c, hipMemsetAsync(word(K1W_DEFERRED), 0, 4, c->stream));
+    hipLaunchKernelGGL(k1_seg_sort_kernel, dim3(nblk), dim3(SEG_T), 0, c->stream, act[0], actv[0], m, sa, rank, n, (uint32_t)h, nr, vs, flag, word(K1W_DEFERRED));
+    return read_back(c, &nd, word(K1W_DEFERRED), 4);
+  }
+
+  // The groups that do not fit LDS: one sort of all their elements by (group, second key), their suffixes back to their slots,
+  // their ranks applied, their flags and vs written like the segmented round's.
+  int sort_deferred() {
+    for (int i = 0; i < 4; ++i) BCE_TRY(ensure(c, c->dl[i], (size_t)nd * 4));
+    uint32_t *idx = c->dl[0].as<uint32_t>(), *slots = c->dl[1].as<uint32_t>(), *gid = c->dl[2].as<uint32_t>();
+    const K1Plan ap = k1_plan(m);
+    hipLaunchKernelGGL((k1_relist_kernel<0, 0>), dim3(ap.nb), dim3(K1_T), 0, c->stream, act[0], vs, flag, m, ap.per_block, ap.nb, blockmax, idx, slots,
+                       word(K1W_DL_COUNT), word(K1W_BLOCKCNT2), gid);
+    hipLaunchKernelGGL((k1_relist_kernel<1, 0>), dim3(ap.nb), dim3(K1_T), 0, c->stream, act[0], vs, flag, m, ap.per_block, ap.nb, blockmax, idx, slots,
+                       word(K1W_DL_COUNT), word(K1W_BLOCKCNT2), gid);
+    uint32_t cnts[2] = {0, 0};                   // K1W_DL_COUNT, K1W_DL_GROUPS
+    BCE_TRY(read_back(c, cnts, word(K1W_DL_COUNT), 8));
+    if (cnts[0] != nd || cnts[1] == 0 || cnts[1] > nd) { snprintf(c->err, sizeof c->err, "k1: deferred list %u / %u groups, expected %u elements", cnts[0], cnts[1], nd); return BCE_HIP_E_INTERNAL; }
+    const uint32_t gbits = ceil_log2(cnts[1]);
+    uint32_t *bl[2] = {lo[0], lo[1]};
+    uint32_t *bh[2] = {val[res ^ 1], k2};
+    uint32_t *bv[2] = {nrk, c->dl[3].as<uint32_t>()};
+    const uint32_t ga = grid_for(nd);
+    hipLaunchKernelGGL(k1_big_gather_kernel, dim3(ga), dim3(K1_T), 0, c->stream, idx, gid, actv[0], rank, n, nd, (uint32_t)h, rbits, bl[0], bh[0], bv[0]);
+    int rb = 0;
+    BCE_TRY(radix_sort_wide(c, bl, bh, bv, nd, 0, rbits + gbits, &rb, 9));
+    const K1Plan dp = k1_plan(nd);
+    uint32_t *snrk = bv[rb ^ 1];
+    hipLaunchKernelGGL(k1_big_heads_kernel, dim3(dp.nb), dim3(K1_T), 0, c->stream, slots, bl[rb], bh[rb], bv[rb], nd, dp.per_block, sa, snrk, blockmax);
+    hipLaunchKernelGGL(k1_apply_kernel, dim3(dp.nb), dim3(K1_T), 0, c->stream, snrk, blockmax, nd, dp.per_block, bv[rb], rank);
+    hipLaunchKernelGGL(k1_defer_flags_kernel, dim3(ga), dim3(K1_T), 0, c->stream, snrk, idx, bv[rb], nd, flag, vs);
+    return BCE_HIP_OK;
+  }
+
+  // rank[vs[i]] = nr[i] for the elements the segmented round sorted: a scatter, or from part_min elements up a sort by suffix
+  // and a store stream in ascending order.
+  int apply_ranks() {
+    if (m >= part_min) {
+      hipLaunchKernelGGL(k1_seg_pairs_kernel, dim3(grid_for(m)), dim3(K1_T), 0, c->stream, vs, flag, KF_DEFER, m, lo[0]);
+      int at_b = 0;
+      BCE_TRY(sort_by_dest(m, lo[0], nr, lo[1], k2, lo[0], val[res ^ 1], &at_b));
+      hipLaunchKernelGGL(k1_scatter32_kernel, dim3(grid_for(m)), dim3(K1_T), 0, c->stream, at_b ? lo[0] : lo[1], at_b ? val[res ^ 1] : k2, m, n, rank);
+    } else {
+      hipLaunchKernelGGL(k1_seg_apply_kernel, dim3(grid_for(m)), dim3(K1_T), 0, c->stream, nr, vs, flag, m, rank);
+    }
+    return BCE_HIP_OK;
+  }
+
+  // The next round's list: the elements that are still in a group of two or more, with their new head bits.
+  int relist() {
+    const K1Plan ap = k1_plan(m);
+    hipLaunchKernelGGL((k1_relist_kernel<0, 1>), dim3(ap.nb), dim3(K1_T), 0, c->stream, act[0], vs, flag, m, ap.per_block, ap.nb, blockmax, act[1], actv[1],
+                       word(K1W_ACTIVE), nullptr, nullptr);
+    hipLaunchKernelGGL((k1_relist_kernel<1, 1>), dim3(ap.nb), dim3(K1_T), 0, c->stream, act[0], vs, flag, m, ap.per_block, ap.nb, blockmax, act[1], actv[1],
+                       word(K1W_ACTIVE), nullptr, nullptr);
+    BCE_TRY(read_back(c, &m, word(K1W_ACTIVE), 4));
+    std::swap(act[0], act[1]);
+    std::swap(actv[0], actv[1]);
+    h <<= 1;
+    c->stats.sort_rounds++;
+    lap("round", h, m, nd);
+    return BCE_HIP_OK;
+  }
+};
+
 // First half of the sort: the rotations ordered by their first c->k1_h symbols (one byte each), ties by position, in
-// sa[c->k1_res]; the sorted keys beside them.  Nothing of the rank array yet.
-static int k1_first_sort_wide(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool sentinel, const uint8_t *want_by_bits = nullptr, bool may_carry = false) {
+// sa[c->k1_res]; the sorted keys beside them.  Nothing of the rank array yet.  want_by_bits (or null) and may_carry: common.h.
+static int k1_first_sort_wide(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool sentinel, const uint8_t *want_by_bits, bool may_carry) {
   const size_t b4 = (size_t)n * 4;
   for (int i = 0; i < 2; ++i) { BCE_TRY(ensure(c, c->sa[i], b4)); BCE_TRY(ensure(c, c->key[i], b4)); BCE_TRY(ensure(c, c->khi[i], b4)); }
   BCE_TRY(ensure(c, c->rank, b4));
@@ -866,17 +755,16 @@ static int k1_first_sort_wide(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool
   BCE_TRY(ensure(c, c->nrk, b4));
   BCE_TRY(ensure(c, c->kflag, (size_t)n + 16));
   for (int i = 0; i < 2; ++i) { BCE_TRY(ensure(c, c->act[i], b4)); BCE_TRY(ensure(c, c->actv[i], b4)); }
-  BCE_TRY(ensure(c, c->blk, (size_t)(K1_MAXB + K1_SC_CODE + 128 + K1_MAXB) * 4));
-  K1View v(c, n);
-  uint32_t *const scalars = v.scalars;
+  BCE_TRY(ensure(c, c->blk, (size_t)(K1_MAXB + K1W_END) * 4));
+  K1Buffers v(c, n);
   const uint32_t g = v.g;
 
   // ---- alphabet: the symbols that occur, in byte order, ceil(log2) bits each ----
   const uint32_t nbytes = sentinel ? n - 1u : n;
-  BCE_HIP_TRY(c, hipMemsetAsync(scalars + K1_SC_HIST, 0, 256 * 4, c->stream));
-  hipLaunchKernelGGL(k1_bytehist_kernel, dim3(g < 1024u ? g : 1024u), dim3(K1_T), 0, c->stream, T, nbytes, scalars + K1_SC_HIST);
+  BCE_HIP_TRY(c, hipMemsetAsync(v.word(K1W_HIST), 0, 256 * 4, c->stream));
+  hipLaunchKernelGGL(k1_bytehist_kernel, dim3(g < 1024u ? g : 1024u), dim3(K1_T), 0, c->stream, T, nbytes, v.word(K1W_HIST));
   uint32_t hist[256];
-  BCE_TRY(read_back(c, hist, scalars + K1_SC_HIST, sizeof hist));
+  BCE_TRY(read_back(c, hist, v.word(K1W_HIST), sizeof hist));
   uint16_t code[256];
   uint32_t sigma = sentinel ? 1u : 0u;
   for (int b = 0; b < 256; ++b) { code[b] = (uint16_t)sigma; if (hist[b]) ++sigma; }    // (absent bytes: any value, never read)
@@ -884,7 +772,7 @@ static int k1_first_sort_wide(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool
   if (bits < 1) bits = 1;
   uint32_t nsym = 64u / bits;
   if (nsym > 16u) nsym = 16u;
-  // (diagnostic: a narrower first key -- more of the order is left to the segmented and active rounds; measured at 10^8 B,
+  // (diagnostic: a narrower first key -- more of the order is left to the segmented rounds; measured at 10^8 B,
   //  text / natural corpus / binary corpus: 64 bits 16.9 / 33.3 / 28.2 ms, 54: 17.8 / 36.1 / 29.1, 48: 18.7 / 35.9 / 28.9,
   //  40: 19.5 / 38.1 / 30.7, 32: 23.3 / 41.9 / 32.7 -- every pass of the wide sort earns more than it costs in K1's
   //  total.  The one-shot route, where only the first sort stands before the coders, may ask for less: want_h)
@@ -900,14 +788,14 @@ static int k1_first_sort_wide(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool
   {
     if (!c->h_small) BCE_TRY(pin_alloc(c, &c->h_small, 4096));
     memcpy(c->h_small, code, sizeof code);
-    BCE_HIP_TRY(c, hipMemcpyAsync(scalars + K1_SC_CODE, c->h_small, sizeof code, hipMemcpyHostToDevice, c->stream));
+    BCE_HIP_TRY(c, hipMemcpyAsync(v.word(K1W_CODE), c->h_small, sizeof code, hipMemcpyHostToDevice, c->stream));
   }
 
   // ---- first sort: 64-bit keys of nsym symbols ----
   {
     const uint32_t per = K1_T * K1I_E;
     hipLaunchKernelGGL(k1_init64_kernel, dim3((uint32_t)(((uint64_t)n + per - 1) / per)), dim3(K1_T), 0, c->stream, T, n, nbytes,
-                       reinterpret_cast<const uint16_t *>(scalars + K1_SC_CODE), bits, nsym, carry ? 1u : 0u, v.lo[0], v.hi[0], v.val[0]);
+                       reinterpret_cast<const uint16_t *>(v.word(K1W_CODE)), bits, nsym, carry ? 1u : 0u, v.lo[0], v.hi[0], v.val[0]);
   }
   int res = 0;
   BCE_TRY(radix_sort_wide(c, v.lo, v.hi, v.val, n, first_bit, keybits, &res, 9));     // (9-bit digits: a 10-bit pass costs 1.0 ms at 10^8, a 9-bit one 0.57)
@@ -923,133 +811,31 @@ static int k1_first_sort_wide(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool
 // the groups the first half left tied, in place.  c->k1_first_final: the first half had already settled every rotation.
 static int k1_finish_wide(bce_hip_ctx *c, uint32_t n) {
   K1View v(c, n);
-  const K1Plan pl = v.pl;
-  uint32_t *const blockmax = v.blockmax, *const scalars = v.scalars, *const rank = v.rank, *const k2 = v.k2, *const nrk = v.nrk;
-  uint8_t *const flag = v.flag;
-  uint32_t **const lo = v.lo, **const hi = v.hi, **const val = v.val;
-  const uint32_t g = v.g;
-  (void)g;
-  const int res = c->k1_res;
-  const uint32_t nsym = c->k1_h;
-  auto lap = [&](const char *what, uint64_t h, uint32_t m, uint32_t nd) { v.lap(what, h, m, nd); };
-  // ranks: group heads from the sorted keys, one scatter; the first active list
-  BCE_HIP_TRY(c, hipMemsetAsync(scalars, 0, 16, c->stream));
-  hipLaunchKernelGGL(k1_heads_kernel, dim3(pl.nb), dim3(K1_T), 0, c->stream, hi[res], lo[res], c->k1_carry ? 0xFFFFFF00u : 0xFFFFFFFFu, n, pl.per_block,
-                     nrk, blockmax, scalars);
-  const uint32_t rbits = ceil_log2(n);
-  const uint32_t part_min = k1_part_min();
-  const bool sorted_apply = n >= part_min;
-  if (sorted_apply) hipLaunchKernelGGL(k1_headidx_kernel, dim3(pl.nb), dim3(K1_T), 0, c->stream, nrk, blockmax, n, pl.per_block, k2);
-  else hipLaunchKernelGGL(k1_apply_kernel, dim3(pl.nb), dim3(K1_T), 0, c->stream, nrk, blockmax, n, pl.per_block, val[res], rank);
-  uint32_t *act[2] = {c->act[0].as<uint32_t>(), c->act[1].as<uint32_t>()};
-  uint32_t *actv[2] = {c->actv[0].as<uint32_t>(), c->actv[1].as<uint32_t>()};
-  uint32_t m = 0;
-  hipLaunchKernelGGL(k1_active_kernel<0>, dim3(pl.nb), dim3(K1_T), 0, c->stream, nrk, (const uint32_t *)nullptr, n, pl.per_block, pl.nb,
-                     blockmax, act[0], scalars + 2, 1u, (const uint32_t *)val[res], actv[0]);
-  hipLaunchKernelGGL(k1_active_kernel<1>, dim3(pl.nb), dim3(K1_T), 0, c->stream, nrk, (const uint32_t *)nullptr, n, pl.per_block, pl.nb,
-                     blockmax, act[0], scalars + 2, 1u, (const uint32_t *)val[res], actv[0]);
-  if (sorted_apply) {
-    // rank = the head indices (k2) sorted by suffix: the first pass reads the suffix array and leaves it alone, the last one
-    // writes the rank array itself
-    const uint32_t b1 = rbits / ((rbits + 9u) / 10u);                       // the digit of a balanced pass
-    uint32_t *pk[2] = {val[res], lo[res ^ 1]}, *pv[2] = {k2, rank};
-    int pr = 0;
-    BCE_TRY(radix_sort_pairs(c, pk, pv, n, 0, b1, &pr, 10));                // one pass: (lo[res^1], rank)
-    uint32_t *qk[2] = {lo[res ^ 1], hi[res ^ 1]}, *qv[2] = {rank, val[res ^ 1]};
-    BCE_TRY(radix_sort_pairs(c, qk, qv, n, b1, rbits - b1, &pr, 10));
-    if (pr) BCE_HIP_TRY(c, hipMemcpyAsync(rank, qv[1], (size_t)n * 4, hipMemcpyDeviceToDevice, c->stream));   // (an odd number of passes behind the first: n > 2^30)
-  }
-  BCE_TRY(read_back(c, &m, scalars + 2, 4));
-  lap("first ranks", nsym, m, 0);
-  c->k1_first_final = m == 0 || nsym >= n;       // (no round follows: the order stays as the first sort left it)
-
-  // ---- segmented rounds ----
-  uint64_t h = nsym;
-  uint32_t *sa = val[res];
-  uint32_t *nr = hi[0], *vs = hi[1];             // (the high key words are free now)
-  while (m > 0 && h < n) {
-    const uint32_t *A = act[0];
-    const uint32_t nblk = (uint32_t)(((uint64_t)m + SEG_CH - 1) / SEG_CH);
-    BCE_HIP_TRY(c, hipMemsetAsync(scalars + 3, 0, 4, c->stream));
-    hipLaunchKernelGGL(k1_seg_sort_kernel, dim3(nblk), dim3(SEG_T), 0, c->stream, A, (const uint32_t *)actv[0], m, sa, rank, n, (uint32_t)h, nr, vs,
-                       flag, scalars + 3);
-    uint32_t nd = 0;
-    BCE_TRY(read_back(c, &nd, scalars + 3, 4));
-    const K1Plan ap = k1_plan(m);
-    if (nd) {
-      // ---- the groups that do not fit LDS: one sort of all their elements by (group, second key) ----
-      BCE_TRY(ensure(c, c->dl[0], (size_t)nd * 4));
-      BCE_TRY(ensure(c, c->dl[1], (size_t)nd * 4));
-      BCE_TRY(ensure(c, c->dl[2], (size_t)nd * 4));
-      BCE_TRY(ensure(c, c->dl[3], (size_t)nd * 4));
-      uint32_t *idx = c->dl[0].as<uint32_t>(), *slots = c->dl[1].as<uint32_t>(), *gid = c->dl[2].as<uint32_t>();
-      uint32_t *blockcnt2 = scalars + K1_SC_CODE + 128;
-      hipLaunchKernelGGL((k1_relist_kernel<0, 0>), dim3(ap.nb), dim3(K1_T), 0, c->stream, A, (const uint32_t *)vs, flag, m, ap.per_block, ap.nb, blockmax, idx, slots,
-                         scalars + 4, blockcnt2, gid);
-      hipLaunchKernelGGL((k1_relist_kernel<1, 0>), dim3(ap.nb), dim3(K1_T), 0, c->stream, A, (const uint32_t *)vs, flag, m, ap.per_block, ap.nb, blockmax, idx, slots,
-                         scalars + 4, blockcnt2, gid);
-      uint32_t cnts[2] = {0, 0};
-      BCE_TRY(read_back(c, cnts, scalars + 4, 8));
-      if (cnts[0] != nd || cnts[1] == 0 || cnts[1] > nd) { snprintf(c->err, sizeof c->err, "k1: deferred list %u / %u groups, expected %u elements", cnts[0], cnts[1], nd); return BCE_HIP_E_INTERNAL; }
-      const uint32_t gbits = ceil_log2(cnts[1]);
-      uint32_t *bl[2] = {lo[0], lo[1]};
-      uint32_t *bh[2] = {val[res ^ 1], k2};
-      uint32_t *bv[2] = {nrk, c->dl[3].as<uint32_t>()};
-      const uint32_t ga = grid_for(nd);
-      hipLaunchKernelGGL(k1_big_gather_kernel, dim3(ga), dim3(K1_T), 0, c->stream, idx, gid, (const uint32_t *)actv[0], rank, n, nd, (uint32_t)h, rbits,
-                         bl[0], bh[0], bv[0]);
-      int rb = 0;
-      BCE_TRY(radix_sort_wide(c, bl, bh, bv, nd, 0, rbits + gbits, &rb, 9));
-      const K1Plan dp = k1_plan(nd);
-      uint32_t *snrk = bv[rb ^ 1];                 // (the other value buffer is free after the sort)
-      hipLaunchKernelGGL(k1_big_heads_kernel, dim3(dp.nb), dim3(K1_T), 0, c->stream, slots, bl[rb], bh[rb], bv[rb], nd, dp.per_block, sa, snrk, blockmax);
-      hipLaunchKernelGGL(k1_act_apply_kernel, dim3(dp.nb), dim3(K1_T), 0, c->stream, snrk, blockmax, nd, dp.per_block, bv[rb], rank);
-      uint32_t *vjr = bv[rb];
-      hipLaunchKernelGGL(k1_defer_flags_kernel, dim3(ga), dim3(K1_T), 0, c->stream, snrk, idx, (const uint32_t *)vjr, nd, flag, vs);
-    }
-    if (m >= part_min) {
-      // (the deferred groups' buffers -- lo[], k2, the other suffix array -- are free again: their kernels are queued ahead)
-      const uint32_t b1 = rbits / ((rbits + 9u) / 10u);
-      uint32_t *pk[2] = {lo[0], lo[1]}, *pv[2] = {nr, k2};
-      hipLaunchKernelGGL(k1_seg_pairs_kernel, dim3(grid_for(m)), dim3(K1_T), 0, c->stream, (const uint32_t *)vs, (const uint8_t *)flag, KF_DEFER, m, pk[0]);
-      int pr = 0;
-      BCE_TRY(radix_sort_pairs(c, pk, pv, m, 0, b1, &pr, 10));               // one pass: (lo[1], k2); nr is left alone
-      uint32_t *qk[2] = {lo[1], lo[0]}, *qv[2] = {k2, val[res ^ 1]};
-      BCE_TRY(radix_sort_pairs(c, qk, qv, m, b1, rbits - b1, &pr, 10));
-      hipLaunchKernelGGL(k1_scatter32_kernel, dim3(grid_for(m)), dim3(K1_T), 0, c->stream, (const uint32_t *)qk[pr], (const uint32_t *)qv[pr], m, n, rank);
-    } else {
-      hipLaunchKernelGGL(k1_seg_apply_kernel, dim3(grid_for(m)), dim3(K1_T), 0, c->stream, nr, vs, flag, m, rank);
-    }
-    hipLaunchKernelGGL((k1_relist_kernel<0, 1>), dim3(ap.nb), dim3(K1_T), 0, c->stream, A, (const uint32_t *)vs, flag, m, ap.per_block, ap.nb, blockmax, act[1],
-                       actv[1], scalars + 2);
-    hipLaunchKernelGGL((k1_relist_kernel<1, 1>), dim3(ap.nb), dim3(K1_T), 0, c->stream, A, (const uint32_t *)vs, flag, m, ap.per_block, ap.nb, blockmax, act[1],
-                       actv[1], scalars + 2);
-    const uint32_t m_old = m;
-    BCE_TRY(read_back(c, &m, scalars + 2, 4));
-    std::swap(act[0], act[1]);
-    std::swap(actv[0], actv[1]);
-    h <<= 1;
-    c->stats.sort_rounds++;
-    lap("round", h, m, nd);
-    (void)m_old;
+  BCE_TRY(v.first_ranks());
+  c->k1_first_final = v.m == 0 || v.h >= n;      // (no round follows: the order stays as the first sort left it)
+  while (v.m > 0 && v.h < n) {
+    BCE_TRY(v.segmented_round());
+    if (v.nd) BCE_TRY(v.sort_deferred());
+    BCE_TRY(v.apply_ranks());
+    BCE_TRY(v.relist());
   }
   BCE_HIP_TRY(c, hipGetLastError());
-  c->k1_unique = m == 0;
-  c->sa_res = res;
+  c->k1_unique = v.m == 0;
+  c->sa_res = v.res;
   return BCE_HIP_OK;
 }
 
+// Sort the n cyclic rotations of T (sentinel = false), or the n = |T| + 1 rotations of T$ (sentinel = true: T holds n - 1
+// bytes).  Leaves the order in c->sa[c->sa_res] and its inverse (the rank of the group head for tied rotations) in c->rank.
 static int k1_sort_rotations(bce_hip_ctx *c, const uint8_t *T, uint32_t n, bool sentinel) {
-  if (getenv("BCE_K1_V1")) return k1_sort_rotations_v1(c, T, n, sentinel);
-  BCE_TRY(k1_first_sort_wide(c, T, n, sentinel));
+  BCE_TRY(k1_first_sort_wide(c, T, n, sentinel, /*want_by_bits=*/nullptr, /*may_carry=*/false));
   return k1_finish_wide(c, n);
 }
 
 // ---- K1 in two halves (api.hip: the one-shot compression starts the enumeration between them) ----------------------------
-// Where the first sort is the wide one and the rank scatters are the direct ones: not behind BCE_K1_V1, not for one byte, not
-// from K1_PART_MIN elements up.
+// Where the rank scatters are the direct ones: not for one byte, not from K1_PART_MIN elements up.
 bool k1_two_halves(const bce_hip_ctx *c) {
-  return c->n >= 2 && c->n < k1_part_min() && !getenv("BCE_K1_V1");
+  return c->n >= 2 && c->n < k1_part_min();
 }
 
 static int k1_begin(bce_hip_ctx *c) {
@@ -1088,13 +874,13 @@ int k1_finish(bce_hip_ctx *c) { return k1_finish_wide(c, c->n); }
 int k1_final_bwt(bce_hip_ctx *c, bool have_bwt) {
   const uint32_t n = c->n;
   const uint32_t g = grid_for(n);
-  uint32_t *scalars = c->blk.as<uint32_t>() + K1_MAXB;   // [0] groups, [1] offset
+  uint32_t *const d_off = k1_word(c, K1W_OFFSET);
   const uint32_t *sa = c->sa[c->sa_res].as<uint32_t>();
-  BCE_HIP_TRY(c, hipMemsetAsync(scalars + 1, 0xFF, 4, c->stream));
+  BCE_HIP_TRY(c, hipMemsetAsync(d_off, 0xFF, 4, c->stream));
   if (!have_bwt) hipLaunchKernelGGL(k1_bwt_kernel, dim3(g), dim3(K1_T), 0, c->stream, c->text.as<uint8_t>(), sa, n, c->bwt.as<uint8_t>());
-  hipLaunchKernelGGL(k1_offset_kernel, dim3(g), dim3(K1_T), 0, c->stream, c->rank.as<uint32_t>(), n, scalars + 1);
+  hipLaunchKernelGGL(k1_offset_kernel, dim3(g), dim3(K1_T), 0, c->stream, c->rank.as<uint32_t>(), n, d_off);
   uint32_t off = 0;
-  BCE_TRY(read_back(c, &off, scalars + 1, 4));
+  BCE_TRY(read_back(c, &off, d_off, 4));
   BCE_HIP_TRY(c, hipGetLastError());
   if (off >= n) { snprintf(c->err, sizeof c->err, "k1: no rank-0 rotation found"); return BCE_HIP_E_INTERNAL; }
   c->offset = off;
@@ -1128,21 +914,28 @@ __global__ __launch_bounds__(K1_T) void k1_divbwt_gather_kernel(const uint8_t *_
   }
 }
 
-int k1_divbwt(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n, uint32_t *pidx_out) {
+// What both entries of the seam begin with: the context's compression state is gone -- before the first allocation, which may
+// give back its planes and node lists --, T (n bytes of host memory, or of device memory of the context's device) is copied
+// into `text`, and the m = n + 1 rotations of T$ are sorted.  with_bwt: c->bwt is sized for them as well.
+static int k1_sort_text_sentinel(bce_hip_ctx *c, const uint8_t *T_src, bool src_on_device, uint32_t n, bool with_bwt) {
   if (n == 0 || n >= 0x7FFFFFFFu) return BCE_HIP_E_ARG;
   const uint32_t m = n + 1u;
-  // the context's compression state is gone -- before the first allocation, which may give back its planes and node lists
   c->stage = 0; c->k1_valid = false; c->enum_active = false; c->text_loaded = false;
   BCE_TRY(ensure(c, c->text, m));
-  BCE_TRY(ensure(c, c->bwt, m));
+  if (with_bwt) BCE_TRY(ensure(c, c->bwt, m));
   uint8_t *T = c->text.as<uint8_t>();
-  BCE_HIP_TRY(c, hipMemcpyAsync(T, T_host, n, hipMemcpyHostToDevice, c->stream));
+  BCE_HIP_TRY(c, hipMemcpyAsync(T, T_src, n, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
   c->stats.sort_rounds = 0;
-  BCE_TRY(k1_sort_rotations(c, T, m, true));
+  return k1_sort_rotations(c, T, m, true);
+}
+
+int k1_divbwt(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n, uint32_t *pidx_out) {
+  BCE_TRY(k1_sort_text_sentinel(c, T_host, /*src_on_device=*/false, n, /*with_bwt=*/true));
+  const uint32_t m = n + 1u;
   uint32_t pidx = 0;
   BCE_TRY(read_back(c, &pidx, c->rank.as<uint32_t>(), 4));   // row of suffix 0
   if (pidx == 0 || pidx > n) { snprintf(c->err, sizeof c->err, "divbwt: primary index %u out of range", pidx); return BCE_HIP_E_INTERNAL; }
-  hipLaunchKernelGGL(k1_divbwt_gather_kernel, dim3(grid_for(m)), dim3(K1_T), 0, c->stream, T, c->sa[c->sa_res].as<uint32_t>(), m,
+  hipLaunchKernelGGL(k1_divbwt_gather_kernel, dim3(grid_for(m)), dim3(K1_T), 0, c->stream, c->text.as<uint8_t>(), c->sa[c->sa_res].as<uint32_t>(), m,
                      pidx, c->bwt.as<uint8_t>());
   BCE_HIP_TRY(c, hipMemcpyAsync(U_host, c->bwt.p, n, hipMemcpyDeviceToHost, c->stream));
   BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1155,15 +948,7 @@ int k1_divbwt(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n
 // rank[i] is the row of suffix i (kd_sufsort.hip: kd_sa_gather).  T_src: n bytes of host memory, or of device memory of the
 // context's device, copied into `text` either way.
 int k1_suffix_array(bce_hip_ctx *c, const uint8_t *T_src, bool src_on_device, uint32_t n, uint32_t *d_sa, uint32_t *d_isa) {
-  if (n == 0 || n >= 0x7FFFFFFFu) return BCE_HIP_E_ARG;
-  const uint32_t m = n + 1u;
-  // the context's compression state is gone -- before the first allocation, which may give back its planes and node lists
-  c->stage = 0; c->k1_valid = false; c->enum_active = false; c->text_loaded = false;
-  BCE_TRY(ensure(c, c->text, m));
-  uint8_t *T = c->text.as<uint8_t>();
-  BCE_HIP_TRY(c, hipMemcpyAsync(T, T_src, n, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-  c->stats.sort_rounds = 0;
-  BCE_TRY(k1_sort_rotations(c, T, m, true));
+  BCE_TRY(k1_sort_text_sentinel(c, T_src, src_on_device, n, /*with_bwt=*/false));
   if (!c->k1_unique) { snprintf(c->err, sizeof c->err, "suffix array: the sort left rotations of T$ tied"); return BCE_HIP_E_INTERNAL; }
   BCE_TRY(kd_sa_gather(c, c->sa[c->sa_res].as<uint32_t>(), c->rank.as<uint32_t>(), n, d_sa, d_isa));
   BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """K1 (rotation sort + BWT) time on the three 10^8-byte workloads, and the archive check against the oracle's hashes.
-    python tools/k1_time.py [--trace]      (--trace: BCE_K1_TRACE=1 for one extra compression per workload: one line per round)
-    BCE_K1_V1=1 python tools/k1_time.py    (the round-2 sorter, for A/B)"""
+    python tools/k1_time.py [--trace]      (--trace: BCE_K1_TRACE=1 for one extra compression per workload: one line per round)"""
 import hashlib
 import json
 import os
