@@ -477,8 +477,8 @@ int k1_divbwt(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n
 // The suffix array of n bytes (host memory, or device memory of the context's device) and, unless d_isa is null, its inverse,
 // into device memory: k1_divbwt's sort, then kd_sufsort.hip's gather.  Complete on return.
 int k1_suffix_array(bce_hip_ctx *c, const uint8_t *T_src, bool src_on_device, uint32_t n, uint32_t *d_sa, uint32_t *d_isa);
-int kd_inverse_bw_transform(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n, uint32_t idx);   // kd_decode.hip
-// kd_decode.hip, test hooks: the decoder's planes() and inverse_bwt() stages on arrays of the caller's in device memory
+int kd_inverse_bw_transform(bce_hip_ctx *c, const uint8_t *T_host, uint8_t *U_host, uint32_t n, uint32_t idx);   // kd_backend.hip
+// kd_backend.hip, test hooks: the decoder's planes() and inverse_bwt() stages on arrays of the caller's in device memory
 int kd_planes_from_ranks(bce_hip_ctx *c, const uint32_t *d_R, uint32_t n, uint8_t *d_bwt, uint32_t *d_words, uint32_t *d_rankw);
 int kd_unbwt(bce_hip_ctx *c, const uint8_t *d_bwt, uint32_t n, uint32_t offset, uint8_t *d_out, uint64_t *cycle, uint32_t *walkers);
 int kd_compare(bce_hip_ctx *c, const uint8_t *a, const uint8_t *b, uint64_t m, uint64_t *first_diff);   // kd_compare.hip: first differing byte of two device buffers

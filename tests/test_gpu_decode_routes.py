@@ -1,4 +1,4 @@
-"""GPU: every route of the GPU-assisted decoder (kd_decode.hip) against the oracle's archives, under list growth and small query
+"""GPU: every route of the GPU-assisted decoder (kd_decode.hip drives; kd_rounds.hip, kd_tail.hip, kd_host_tail.hip) against the oracle's archives, under list growth and small query
 budgets -- the exact input comes back, and every case shows from the decoder's own summary lines that its route and its memory
 mode actually ran.
 

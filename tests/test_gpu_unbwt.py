@@ -1,4 +1,4 @@
-"""GPU: the back end of the GPU decoder (kd_decode.hip) alone, through its two test hooks, compared exactly with the plain
+"""GPU: the back end of the GPU decoder (kd_backend.hip) alone, through its two test hooks, compared exactly with the plain
 reference of tests/unbwt_ref.py.
 
 bce_hip_planes_from_ranks_device: sparse boundary ranks -> plane words and word ranks (fill_chunkmax / fill_chunkscan / fill_kernel)
