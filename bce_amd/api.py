@@ -130,6 +130,10 @@ SYMBOLS = [
     ("bce_hip_input_bytes", C.c_int, [C.c_void_p, C.c_uint64, C.c_size_t, _u8p]),
     ("bce_hip_locate", C.c_int, [C.c_void_p, _u8p, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("bce_hip_locate_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("bce_hip_count_near", C.c_int, [C.c_void_p, _u8p, _vp, C.c_uint32, C.c_uint32, _vp]),
+    ("bce_hip_count_near_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, _vp]),
+    ("bce_hip_locate_near", C.c_int, [C.c_void_p, _u8p, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("bce_hip_locate_near_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("bce_hip_match", C.c_int, [C.c_void_p, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp]),
     ("bce_hip_match_device", C.c_int, [C.c_void_p, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp]),
     ("bce_hip_coverage", C.c_int, [C.c_void_p, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
@@ -195,6 +199,8 @@ def _as_u8(data):
 
 
 LOCATE_LINEAR = 1                               # BCE_HIP_LOCATE_LINEAR
+NEAR_MAX_K = 2                                  # BCE_HIP_NEAR_MAX_K: mismatches allowed at most; a work bound, not a format limit
+NEAR_MAX_LEN = 4096                             # BCE_HIP_NEAR_MAX_LEN: bytes of a pattern searched with mismatches
 MATCH_LINEAR = 1                                # BCE_HIP_MATCH_LINEAR
 MATCH_MAX_LEN = 4096                            # BCE_HIP_MATCH_MAX_LEN: a work bound per end position, not a format limit
 KGRAMS_MAX = 64                                 # BCE_HIP_KGRAMS_MAX: values of k in one bce_hip_kgrams call
@@ -239,6 +245,25 @@ def linear_counts(cyclic, patterns, n, ends):
             out[i] = 0
         elif m > 1:
             out[i] -= seam_count(head[:m - 1], tail[len(tail) - (m - 1):], p)
+    return out
+
+
+def near_linear_counts(cyclic, patterns, n, ends):
+    """Cyclic counts per distance (rows of k + 1: RankFile.count_near) -> the counts a sliding window over the n-byte text gives.
+    ends: as for linear_counts.  A pattern longer than the text is nowhere; otherwise each of the m - 1 windows that start in the
+    text's last m - 1 bytes and run into its first comes off at its own distance, where that is within k."""
+    out = np.array(cyclic, dtype=np.uint64).reshape(len(patterns), -1)
+    k = out.shape[1] - 1
+    longest = max([len(p) for p in patterns if len(p) <= n] + [1])
+    head, tail = ends(longest - 1)
+    for i, p in enumerate(patterns):
+        m = len(p)
+        if m > n:
+            out[i] = 0
+        elif m > 1:
+            seam = np.frombuffer(bytes(tail[len(tail) - (m - 1):]) + bytes(head[:m - 1]), dtype=np.uint8)
+            d = (np.lib.stride_tricks.sliding_window_view(seam, m)[:m - 1] != np.frombuffer(bytes(p), dtype=np.uint8)).sum(axis=1)
+            out[i] -= np.bincount(d[d <= k], minlength=k + 1)[:k + 1].astype(np.uint64)
     return out
 
 
@@ -464,6 +489,81 @@ class RankFile:
         ptr = lambda v: None if v is None else int(v)  # noqa: E731
         self._c.check(self._c.lib.bce_hip_locate_device(self._c.h, ptr(patterns_ptr), ptr(offsets_ptr), int(npat), 0 if cyclic else LOCATE_LINEAR,
                                                         ptr(hit_offsets_ptr), ptr(positions_ptr), int(cap), C.byref(total)), "bce_hip_locate_device")
+        return total.value
+
+    def _near_args(self, patterns, k, cyclic, what):
+        """-> (one, pats, flat, offsets) of a search with mismatches, judged as count() and locate() judge theirs"""
+        if not 0 <= int(k) <= NEAR_MAX_K:
+            raise ValueError("k = %r, outside 0 .. %d" % (k, NEAR_MAX_K))
+        one = _is_one_pattern(patterns)
+        pats = [_as_u8(patterns)] if one else [_as_u8(p) for p in patterns]
+        if not cyclic:
+            if not self._has_text:
+                raise ValueError("a RankFile built from an injected BWT holds no text: only cyclic=True %s are defined" % what)
+            if any(len(p) == 0 for p in pats):
+                raise ValueError("an empty pattern has no linear %s (cyclic=True: every position, at distance 0)" % what)
+        if any(len(p) > NEAR_MAX_LEN for p in pats):
+            raise ValueError("a pattern of more than %d bytes" % NEAR_MAX_LEN)
+        offsets = np.zeros(len(pats) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([len(p) for p in pats], dtype=np.uint64)
+        flat = np.concatenate(pats) if pats and int(offsets[-1]) else np.zeros(1, dtype=np.uint8)
+        return one, pats, flat, offsets
+
+    def count_near(self, patterns, k, cyclic=False):
+        """How often something occurs in the text that differs from a pattern in at most k bytes (Hamming distance, k = 0 ..
+        NEAR_MAX_K), counted on the GPU by backward search that branches (bce_hip_count_near).  `patterns`: one bytes-like -> a
+        numpy uint64 array of k + 1 counts, the hits at distance exactly 0 .. k; a sequence -> shape (npat, k + 1).
+        cyclic=False: what a sliding window over the text finds; zeros for a pattern longer than the text; an empty pattern
+        raises ValueError.  cyclic=True: the hits in the circular text, defined for every length (the empty pattern: n at
+        distance 0; k >= m: every position).  Patterns of more than NEAR_MAX_LEN bytes: ValueError."""
+        one, pats, flat, offsets = self._near_args(patterns, k, cyclic, "counts")
+        out = np.zeros((len(pats), int(k) + 1), dtype=np.uint64)
+        if pats:
+            self._c.check(self._c.lib.bce_hip_count_near(self._c.h, flat.ctypes.data, offsets.ctypes.data, len(pats), int(k), out.ctypes.data),
+                          "bce_hip_count_near")
+            if not cyclic:
+                out = near_linear_counts(out, pats, self._n, self._text_ends)
+        return out[0] if one else out
+
+    def count_near_device(self, patterns_ptr, offsets_ptr, npat, k, counts_ptr):
+        """bce_hip_count_near_device: the cyclic counts per distance of `npat` patterns that lie concatenated in device memory (int
+        pointers: the bytes, npat + 1 uint64 offsets, npat * (k + 1) uint64 counts out).  Stream rule: as count_device."""
+        ptr = lambda v: None if v is None else int(v)  # noqa: E731
+        self._c.check(self._c.lib.bce_hip_count_near_device(self._c.h, ptr(patterns_ptr), ptr(offsets_ptr), int(npat), int(k), ptr(counts_ptr)),
+                      "bce_hip_count_near_device")
+
+    def locate_near(self, patterns, k, cyclic=False, limit=None, max_hits=1 << 26):
+        """Where something occurs that differs from a pattern in at most k bytes: (positions uint32 ascending, dists uint8, the
+        distance of each) for one bytes-like, a list of such pairs for a sequence (bce_hip_locate_near).  cyclic, the empty
+        pattern and an injected BWT: as locate(), with count_near()'s distances.  `max_hits` and `limit`: locate()'s rules -- a
+        sizing call first, ValueError above max_hits before any room is made; limit keeps each pattern's first hits in text
+        order and bounds the result, not the work."""
+        one, pats, flat, offsets = self._near_args(patterns, k, cyclic, "hits")
+        if limit is not None and limit < 0:
+            raise ValueError("limit must not be negative")
+        if not pats:
+            return []
+        lib, flags = self._c.lib, 0 if cyclic else LOCATE_LINEAR
+        hits, total = np.zeros(len(pats) + 1, dtype=np.uint64), C.c_uint64(0)
+        rc = lib.bce_hip_locate_near(self._c.h, flat.ctypes.data, offsets.ctypes.data, len(pats), int(k), flags, hits.ctypes.data, None, None, 0,
+                                     C.byref(total))
+        if rc in (0, E_OVERFLOW) and total.value > max_hits:
+            raise ValueError("%d hits in all, more than max_hits = %d" % (total.value, max_hits))
+        self._c.check(rc, "bce_hip_locate_near")
+        pos, dist = _positions_buffer(total.value), np.empty(max(total.value, 1), dtype=np.uint8)
+        self._c.check(lib.bce_hip_locate_near(self._c.h, flat.ctypes.data, offsets.ctypes.data, len(pats), int(k), flags, hits.ctypes.data,
+                                              pos.ctypes.data, dist.ctypes.data, total.value, C.byref(total)), "bce_hip_locate_near")
+        out = [(pos[int(hits[i]):int(hits[i + 1])][:limit].copy(), dist[int(hits[i]):int(hits[i + 1])][:limit].copy()) for i in range(len(pats))]
+        return out[0] if one else out
+
+    def locate_near_device(self, patterns_ptr, offsets_ptr, npat, k, hit_offsets_ptr, positions_ptr, dists_ptr, cap, cyclic=False) -> int:
+        """bce_hip_locate_near_device: locate_device with mismatches (out, beside the positions: up to `cap` uint8 distances) -> the
+        total.  positions_ptr and dists_ptr None with cap 0 only sizes.  Stream rule: as count_device."""
+        total = C.c_uint64(0)
+        ptr = lambda v: None if v is None else int(v)  # noqa: E731
+        self._c.check(self._c.lib.bce_hip_locate_near_device(self._c.h, ptr(patterns_ptr), ptr(offsets_ptr), int(npat), int(k),
+                                                             0 if cyclic else LOCATE_LINEAR, ptr(hit_offsets_ptr), ptr(positions_ptr), ptr(dists_ptr),
+                                                             int(cap), C.byref(total)), "bce_hip_locate_near_device")
         return total.value
 
     def _match_flags(self, cyclic, what):
@@ -846,6 +946,27 @@ def locate(data, patterns, cyclic=False, limit=None, max_hits=1 << 26, device=0,
     rf = RankFile(data, device=device, ctx=ctx)
     try:
         return rf.locate(patterns, cyclic=cyclic, limit=limit, max_hits=max_hits)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def count_near(data, patterns, k, cyclic=False, device=0, ctx=None):
+    """The hits of `patterns` in `data` within k mismatches, per distance (RankFile.count_near): K1 and K2 index the data on the
+    GPU, the branching backward search asks the index."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.count_near(patterns, k, cyclic=cyclic)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def locate_near(data, patterns, k, cyclic=False, limit=None, max_hits=1 << 26, device=0, ctx=None):
+    """Where `patterns` occur in `data` within k mismatches -> (positions, dists) as RankFile.locate_near."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.locate_near(patterns, k, cyclic=cyclic, limit=limit, max_hits=max_hits)
     finally:
         if ctx is None:
             rf.close()

@@ -1,6 +1,6 @@
-// api_index.hip -- C ABI of the index queries (include/bce_hip.h): counts, positions, longest matches and coverage, the LCP array and
+// api_index.hip -- C ABI of the index queries (include/bce_hip.h): counts, positions, both within k mismatches, longest matches and coverage, the LCP array and
 // its reductions, the list of the most frequent k-grams, parse and patch, the longest previous factors and the self-parse; and the test hooks that run their block scans alone.  The device work is in kd_count /
-// kd_locate / kd_match / kd_lcp / kd_parse / kd_self.hip.  Every query comes twice, for host buffers and for device buffers: the two differ
+// kd_locate / kd_near / kd_match / kd_lcp / kd_parse / kd_self.hip.  Every query comes twice, for host buffers and for device buffers: the two differ
 // in staging and in the copy out, and in nothing else.
 //
 // All of them judge the arguments before the context's state and the state before the arrays, then run their body through
@@ -208,6 +208,108 @@ int bce_hip_locate_device(bce_hip_ctx *c, const void *d_patterns, const void *d_
   return query_call(c, 3, [&] {
     return locate_run(c, sa, static_cast<const uint8_t *>(d_patterns), static_cast<const uint64_t *>(d_offsets), npat, flags & BCE_HIP_LOCATE_LINEAR,
                       static_cast<uint64_t *>(d_hit_offsets), nullptr, static_cast<uint32_t *>(d_positions), nullptr, !d_positions, cap, total);
+  });
+}
+
+// ---- counts and positions within k mismatches (kd_near.hip) ----------------------------------------------------------------------
+// The count's and the locate's rules, checks and protocol; k is judged beside ctx and the flags, the patterns' lengths with the list.
+static int near_lengths(bce_hip_ctx *c, const char *what, const uint64_t *offsets, uint32_t npat) {
+  for (uint32_t p = 0; p < npat; ++p)
+    if (offsets[p + 1] - offsets[p] > BCE_HIP_NEAR_MAX_LEN) {
+      snprintf(c->err, sizeof c->err, "%s: pattern %u has %llu bytes, more than %u", what, p, (unsigned long long)(offsets[p + 1] - offsets[p]), BCE_HIP_NEAR_MAX_LEN);
+      return BCE_HIP_E_ARG;
+    }
+  return BCE_HIP_OK;
+}
+
+int bce_hip_count_near(bce_hip_ctx *c, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t k, uint64_t *counts) {
+  if (!c || k > BCE_HIP_NEAR_MAX_K) return BCE_HIP_E_ARG;
+  if (npat == 0) return BCE_HIP_OK;
+  BCE_TRY(planes_state(c, "count_near"));
+  if (!counts) return BCE_HIP_E_ARG;
+  BCE_TRY(pattern_list_args(c, "count_near", patterns, offsets, npat));
+  BCE_TRY(near_lengths(c, "count_near", offsets, npat));
+  return query_call(c, 3, [&]() -> int {
+    DevBuf &pat = c->qbuf[qb::near_pat], &off = c->qbuf[qb::near_off], &out = c->qbuf[qb::near_out];
+    const size_t bytes = (size_t)npat * (k + 1) * 8;
+    BCE_TRY(ensure(c, out, bytes));
+    BCE_TRY(stage_patterns(c, pat, off, patterns, offsets, npat));
+    BCE_TRY(kd_near_count(c, pat.as<uint8_t>(), off.as<uint64_t>(), npat, k, out.as<uint64_t>()));
+    return copy_out(c, counts, out, bytes);
+  });
+}
+
+int bce_hip_count_near_device(bce_hip_ctx *c, const void *d_patterns, const void *d_offsets, uint32_t npat, uint32_t k, void *d_counts) {
+  if (!c || k > BCE_HIP_NEAR_MAX_K) return BCE_HIP_E_ARG;
+  if (npat == 0) return BCE_HIP_OK;
+  BCE_TRY(planes_state(c, "count_near"));
+  if (!d_patterns || !d_offsets || !d_counts) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&] {
+    return kd_near_count(c, static_cast<const uint8_t *>(d_patterns), static_cast<const uint64_t *>(d_offsets), npat, k, static_cast<uint64_t *>(d_counts));
+  });
+}
+
+// locate_run with the distances beside the positions
+static int locate_near_run(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, uint32_t k, bool linear,
+                           uint64_t *d_hits, uint64_t *h_hits, uint32_t *d_pos, uint8_t *d_dist, uint32_t *h_pos, uint8_t *h_dist, bool sizing,
+                           uint64_t cap, uint64_t *total) {
+  uint64_t rows = 0, hits = 0;
+  const int rc = kd_near_size(c, sa, d_pat, d_off, npat, k, linear, d_hits, &rows, &hits);
+  if (rc != BCE_HIP_OK && rc != BCE_HIP_E_OVERFLOW) return rc;
+  if (h_hits) {
+    BCE_HIP_TRY(c, hipMemcpyAsync(h_hits, d_hits, ((size_t)npat + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  *total = hits;
+  if (rc != BCE_HIP_OK || sizing) return rc;
+  if (hits > cap) { snprintf(c->err, sizeof c->err, "locate_near: %llu hits, room for %llu", (unsigned long long)hits, (unsigned long long)cap); return BCE_HIP_E_OVERFLOW; }
+  if (hits == 0) return BCE_HIP_OK;
+  if (h_pos) {
+    BCE_TRY(ensure(c, c->qbuf[qb::near_pos], (size_t)hits * 4));
+    BCE_TRY(ensure(c, c->qbuf[qb::near_dist], (size_t)hits));
+    d_pos = c->qbuf[qb::near_pos].as<uint32_t>();
+    d_dist = c->qbuf[qb::near_dist].as<uint8_t>();
+  }
+  BCE_TRY(kd_near_fill(c, sa, d_pat, d_off, npat, k, linear, rows, hits, d_pos, d_dist));
+  if (!h_pos) return BCE_HIP_OK;
+  BCE_TRY(copy_out(c, h_pos, c->qbuf[qb::near_pos], (size_t)hits * 4));
+  return copy_out(c, h_dist, c->qbuf[qb::near_dist], (size_t)hits);
+}
+
+int bce_hip_locate_near(bce_hip_ctx *c, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t k, uint32_t flags,
+                        uint64_t *hit_offsets, uint32_t *positions, uint8_t *dists, uint64_t cap, uint64_t *total) {
+  if (!c || !total || (flags & ~BCE_HIP_LOCATE_LINEAR) || k > BCE_HIP_NEAR_MAX_K || npat > (1u << 30)) return BCE_HIP_E_ARG;
+  *total = 0;
+  if (npat == 0) { if (hit_offsets) hit_offsets[0] = 0; return BCE_HIP_OK; }
+  const uint32_t *sa = nullptr;
+  BCE_TRY(sa_state(c, &sa, "locate_near"));
+  if (!hit_offsets || (!positions && cap) || !positions != !dists) return BCE_HIP_E_ARG;
+  BCE_TRY(pattern_list_args(c, "locate_near", patterns, offsets, npat));
+  BCE_TRY(near_lengths(c, "locate_near", offsets, npat));
+  return query_call(c, 3, [&]() -> int {
+    DevBuf &pat = c->qbuf[qb::near_pat], &off = c->qbuf[qb::near_off], &hits = c->qbuf[qb::near_hits];
+    BCE_TRY(ensure(c, hits, ((size_t)npat + 1) * 8));
+    BCE_TRY(stage_patterns(c, pat, off, patterns, offsets, npat));
+    return locate_near_run(c, sa, pat.as<uint8_t>(), off.as<uint64_t>(), npat, k, flags & BCE_HIP_LOCATE_LINEAR, hits.as<uint64_t>(), hit_offsets,
+                           nullptr, nullptr, positions, dists, !positions, cap, total);
+  });
+}
+
+int bce_hip_locate_near_device(bce_hip_ctx *c, const void *d_patterns, const void *d_offsets, uint32_t npat, uint32_t k, uint32_t flags,
+                               void *d_hit_offsets, void *d_positions, void *d_dists, uint64_t cap, uint64_t *total) {
+  if (!c || !total || (flags & ~BCE_HIP_LOCATE_LINEAR) || k > BCE_HIP_NEAR_MAX_K || npat > (1u << 30)) return BCE_HIP_E_ARG;
+  *total = 0;
+  if (npat == 0) {
+    if (!d_hit_offsets) return BCE_HIP_OK;
+    return query_call(c, 0, [&]() -> int { BCE_HIP_TRY(c, hipMemsetAsync(d_hit_offsets, 0, 8, c->stream)); return BCE_HIP_OK; });
+  }
+  const uint32_t *sa = nullptr;
+  BCE_TRY(sa_state(c, &sa, "locate_near"));
+  if (!d_patterns || !d_offsets || !d_hit_offsets || (!d_positions && cap) || !d_positions != !d_dists) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&] {
+    return locate_near_run(c, sa, static_cast<const uint8_t *>(d_patterns), static_cast<const uint64_t *>(d_offsets), npat, k,
+                           flags & BCE_HIP_LOCATE_LINEAR, static_cast<uint64_t *>(d_hit_offsets), nullptr, static_cast<uint32_t *>(d_positions),
+                           static_cast<uint8_t *>(d_dists), nullptr, nullptr, !d_positions, cap, total);
   });
 }
 

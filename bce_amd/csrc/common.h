@@ -140,6 +140,9 @@ enum Id {
   loc_lo, loc_cnt, loc_drop, loc_start, loc_lin, loc_bsum,   // per pattern: the interval's first row, its rows, those across the text's end; the two CSR offset arrays; the scan's block sums
   loc_key0, loc_key1, loc_val0, loc_val1,        // (position, pattern) of every row: both halves of the sorts' ping-pong
   loc_pat, loc_off, loc_hits, loc_pos,           // bce_hip_locate: the arrays of a call with host buffers, staged (all grow-only)
+  near_res,                                      // kd_near.hip: its flag word (a buffer of its own, as loc_res); its scratch is the locate's loc_cnt .. loc_val1
+  near_pat, near_off, near_out,                  // bce_hip_count_near / _locate_near: the patterns, their offsets and the counts of a call with host buffers, staged (grow-only)
+  near_hits, near_pos, near_dist,                // bce_hip_locate_near with host buffers: the CSR offsets, positions and distances, staged (grow-only)
   mat_res,                                       // kd_match.hip: the coverage's result word (a buffer of its own, as loc_res)
   mat_bsum,                                      // the coverage scan's block maxima and block counts
   mat_qry, mat_len, mat_pos,                     // bce_hip_match / _coverage: the query of a call with a host buffer, the lengths and the positions, staged (all grow-only)
@@ -491,6 +494,14 @@ int kd_locate_size(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, con
                    uint64_t *d_hits, uint64_t *rows, uint64_t *total);
 int kd_locate_fill(bce_hip_ctx *c, const uint32_t *sa, const uint64_t *d_off, uint32_t npat, bool linear, uint64_t rows, uint64_t total,
                    uint32_t *d_pos);
+int locate_scan(bce_hip_ctx *c, const uint32_t *cnt, const uint32_t *drop, uint32_t npat, uint64_t *start, uint64_t *total);   // exclusive u64 scan of cnt - drop
+// kd_near.hip: the same two questions within k <= BCE_HIP_NEAR_MAX_K mismatches (near_step.h).  Counts: d_out[npat * (k + 1)].  The
+// locate's halves as kd_locate's, with the distance of every position beside it.
+int kd_near_count(bce_hip_ctx *c, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, uint32_t k, uint64_t *d_out);
+int kd_near_size(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, uint32_t k, bool linear,
+                 uint64_t *d_hits, uint64_t *rows, uint64_t *total);
+int kd_near_fill(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, uint32_t k, bool linear,
+                 uint64_t rows, uint64_t total, uint32_t *d_pos, uint8_t *d_dist);
 // kd_match.hip: d_len[i] (and d_pos[i], unless null) of the longest string that ends at d_query[i] and occurs in the text, at most
 // max_len bytes; queued, the caller waits.  kd_coverage: the bytes of the query inside matches of min_len or more, from such lengths.
 int kd_match(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_query, uint32_t q, uint32_t max_len, bool linear, uint32_t *d_len,

@@ -123,7 +123,10 @@ uint32_t stride_grid(uint64_t items) {
   return (uint32_t)(g < LOC_MAXGRID ? g : LOC_MAXGRID);
 }
 
-// start[0, npat] = exclusive scan of cnt[i] - drop[i] (drop may be null); *total = its last word
+}  // namespace
+
+// start[0, npat] = exclusive scan of cnt[i] - drop[i] (drop may be null); *total = its last word, read back through loc_res's
+// second word (the caller has made loc_res).  Also kd_near.hip's scan.
 int locate_scan(bce_hip_ctx *c, const uint32_t *cnt, const uint32_t *drop, uint32_t npat, uint64_t *start, uint64_t *total) {
   const uint32_t nb = (uint32_t)(((uint64_t)npat + LOC_BLOCK - 1) / LOC_BLOCK);
   BCE_TRY(ensure(c, c->qbuf[qb::loc_bsum], (size_t)nb * 8));
@@ -137,8 +140,6 @@ int locate_scan(bce_hip_ctx *c, const uint32_t *cnt, const uint32_t *drop, uint3
   BCE_HIP_TRY(c, hipGetLastError());
   return BCE_HIP_OK;
 }
-
-}  // namespace
 
 // First half of a locate: the search, the row counts and the CSR offsets.  d_hits[0, npat] receives the offsets of the hits of
 // d_pat[d_off[p], d_off[p + 1]), p < npat, in the text of the context's planes and suffix array (sa: K1's, or null for a text of one

@@ -6,6 +6,8 @@
 //   bce -g PATTERN file                     (extension) how often the bytes of PATTERN occur in "file", counted on the GPU from its BWT planes
 //   bce -gd PATTERN archive                 (extension) the same in what an archive or container holds
 //   bce -gl PATTERN file, -gld PATTERN archive   (extension) where they occur: the byte offsets, gathered on the GPU from K1's suffix array
+//   bce -gn K PATTERN file, -gnd K PATTERN archive   (extension) how often something occurs that differs from PATTERN in at most K (0..2) bytes, per distance
+//   bce -gnl K PATTERN file, -gnld K PATTERN archive (extension) where: the byte offsets, each with its distance
 //   bce -gm MINLEN file query_file, -gmd MINLEN archive query_file   (extension) how much of a second file lies in strings of MINLEN bytes or more that occur in the first
 //   bce -gr MINLEN file query_file out.bcd, -grd ... archive ...   (extension) writes query_file as a delta against the first: copies out of it plus the new bytes
 //   bce -ga file in.bcd out_file, -gad archive in.bcd out_file     (extension) rebuilds a file from the first and a delta, both sides checked by CRC-32
@@ -138,6 +140,9 @@ extern "C" int bce_hip_estimate_host(bce_hip_ctx *ctx, const uint8_t *in, uint32
 extern "C" int bce_hip_count(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint64_t *counts) __attribute__((weak));
 extern "C" int bce_hip_locate(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t flags, uint64_t *hit_offsets,
                               uint32_t *positions, uint64_t cap, uint64_t *total) __attribute__((weak));
+extern "C" int bce_hip_count_near(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t k, uint64_t *counts) __attribute__((weak));
+extern "C" int bce_hip_locate_near(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t k, uint32_t flags,
+                                   uint64_t *hit_offsets, uint32_t *positions, uint8_t *dists, uint64_t cap, uint64_t *total) __attribute__((weak));
 extern "C" int bce_hip_coverage(bce_hip_ctx *ctx, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t flags, uint64_t *covered) __attribute__((weak));
 extern "C" int bce_hip_kgrams(bce_hip_ctx *ctx, const uint32_t *ks, uint32_t nk, bce_hip_kgram *out) __attribute__((weak));
 extern "C" int bce_hip_longest_repeat(bce_hip_ctx *ctx, uint32_t max_len, uint32_t *len, uint32_t *pos_a, uint32_t *pos_b) __attribute__((weak));
@@ -497,7 +502,7 @@ static void write_delta_header(uint8_t *p, const DeltaHeader &h) {
   memcpy(p, "BCED", 4); memcpy(p + 4, &ver, 4); memcpy(p + 8, &h.n, 8); memcpy(p + 16, &h.base_crc, 4); memcpy(p + 20, &h.q, 8);
   memcpy(p + 28, &h.crc, 4); memcpy(p + 32, &h.min_len, 4); memcpy(p + 36, &h.max_len, 4); memcpy(p + 40, &h.nops, 8); memcpy(p + 48, &h.nlits, 8);
 }
-// ---- the front of all nineteen index commands ----
+// ---- the front of all twenty-three index commands ----
 // The indexed file (or archive) and the command's second file are read beside the runtime's start-up and judged in this order: the
 // file or archive, the second file, the device; an archive's blocks are then decoded into one text.  Owns the context: an error
 // path destroys it, index_done() leaves it to fast_exit.
@@ -625,6 +630,59 @@ static int locate_command(const char *pattern, const char *path, bool in_archive
     if (rc != 0) return index_failed(in, "Locate", rc);
   }
   for (uint32_t at : where) printf("%u\n", at);
+  printf("%llu occurrences\n", (unsigned long long)count);
+  return index_done(in);
+}
+
+// -gn / -gnd: the hits of -g with up to K bytes different, per distance.  bce_hip_count_near counts them in the circular text; the
+// windows that start in the text's last m - 1 bytes and run into its first come off here, each at its own distance.
+static int count_near_command(uint32_t K, const char *pattern, const char *path, bool in_archive) {
+  IndexInput in;
+  if (const int ec = index_open(in, path, in_archive, nullptr, kNoSecond, bce_hip_count_near != nullptr)) return ec;
+  const size_t m = strlen(pattern);
+  const uint8_t *pat = reinterpret_cast<const uint8_t *>(pattern);
+  uint64_t per[BCE_HIP_NEAR_MAX_K + 1] = {0, 0, 0}, count = 0;
+  if (m <= in.n) {                                                  // (as -g)
+    const uint64_t offsets[2] = {0, m};
+    int rc = index_text(in);
+    if (rc == 0) rc = bce_hip_count_near(in.ctx, pat, offsets, 1, K, per);
+    if (rc != 0) return index_failed(in, "Count", rc);
+    for (size_t at = in.n - m + 1; at < in.n; ++at) {
+      uint32_t d = 0;
+      for (size_t j = 0; j < m && d <= K; ++j) d += pat[j] != in.text[at + j < in.n ? at + j : at + j - in.n];
+      if (d <= K) per[d] -= 1;
+    }
+  }
+  for (uint32_t d = 0; d <= K; ++d) {
+    printf("distance %u: %llu\n", d, (unsigned long long)per[d]);
+    count += per[d];
+  }
+  printf("%llu occurrences\n", (unsigned long long)count);
+  return index_done(in);
+}
+
+// -gnl / -gnld: the linear hits of bce_hip_locate_near, "POS d" per line in ascending position, before the count line
+static int locate_near_command(uint32_t K, const char *pattern, const char *path, bool in_archive) {
+  IndexInput in;
+  if (const int ec = index_open(in, path, in_archive, nullptr, kNoSecond, bce_hip_locate_near != nullptr)) return ec;
+  const size_t m = strlen(pattern);
+  const uint8_t *pat = reinterpret_cast<const uint8_t *>(pattern);
+  uint64_t count = 0;
+  std::vector<uint32_t> where;
+  std::vector<uint8_t> dist;
+  if (m <= in.n) {                                                  // (as -g)
+    const uint64_t offsets[2] = {0, m};
+    uint64_t hits[2] = {0, 0};
+    int rc = index_text(in);
+    if (rc == 0) rc = bce_hip_locate_near(in.ctx, pat, offsets, 1, K, BCE_HIP_LOCATE_LINEAR, hits, nullptr, nullptr, 0, &count);   // how many
+    if (rc == 0 && count) {
+      where.resize(count);
+      dist.resize(count);
+      rc = bce_hip_locate_near(in.ctx, pat, offsets, 1, K, BCE_HIP_LOCATE_LINEAR, hits, where.data(), dist.data(), count, &count);
+    }
+    if (rc != 0) return index_failed(in, "Locate", rc);
+  }
+  for (size_t r = 0; r < where.size(); ++r) printf("%u %u\n", where[r], (unsigned)dist[r]);
   printf("%llu occurrences\n", (unsigned long long)count);
   return index_done(in);
 }
@@ -808,6 +866,11 @@ static uint32_t parse_min_len(const char *s) {
   return v;
 }
 
+// K of -gn / -gnl: one decimal digit, 0 .. 2 (BCE_HIP_NEAR_MAX_K); anything else: -1
+static int parse_near_k(const char *s) {
+  return s[0] >= '0' && s[0] <= (char)('0' + BCE_HIP_NEAR_MAX_K) && s[1] == 0 ? s[0] - '0' : -1;
+}
+
 // K of -gk / -gkd: decimal digits only, 0 .. 32; anything else: -1
 static int parse_order(const char *s) {
   uint32_t v = 0;
@@ -880,6 +943,18 @@ static int usage() {
   printf("\n");
   printf("  bce -gl PATTERN file\n");
   printf("   Prints where the bytes of PATTERN occur in \"file\": the byte offsets, one per line, ascending, then the count; they come from the index and the suffix array on the GPU (extension)\n");
+  printf("\n");
+  printf("  bce -gn K PATTERN file\n");
+  printf("   Counts how often something occurs in \"file\" that differs from PATTERN in at most K (0..2) bytes: one line \"distance d: N\" for d = 0..K, then the sum; backward search that branches at every allowed mismatch, on the GPU (extension)\n");
+  printf("\n");
+  printf("  bce -gnd K PATTERN archive.bce\n");
+  printf("   The same counts in what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
+  printf("\n");
+  printf("  bce -gnl K PATTERN file\n");
+  printf("   Prints where they occur: \"POS d\" per hit, the byte offset and its number of different bytes, ascending by offset, then the count (extension)\n");
+  printf("\n");
+  printf("  bce -gnld K PATTERN archive.bce\n");
+  printf("   The same lines for what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
   printf("\n");
   printf("  bce -gld PATTERN archive.bce\n");
   printf("   The same offsets in what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
@@ -1184,6 +1259,10 @@ int main(int argc, char **argv) {
     return count_command(argv[2], argv[3], argv[1][2] == 'd');
   } else if (argc == 4 && argv[2][0] != 0 && (strcmp(argv[1], "-gl") == 0 || strcmp(argv[1], "-gld") == 0)) {
     return locate_command(argv[2], argv[3], argv[1][3] == 'd');
+  } else if (argc == 5 && argv[3][0] != 0 && (strcmp(argv[1], "-gn") == 0 || strcmp(argv[1], "-gnd") == 0) && parse_near_k(argv[2]) >= 0) {
+    return count_near_command((uint32_t)parse_near_k(argv[2]), argv[3], argv[4], argv[1][3] == 'd');
+  } else if (argc == 5 && argv[3][0] != 0 && (strcmp(argv[1], "-gnl") == 0 || strcmp(argv[1], "-gnld") == 0) && parse_near_k(argv[2]) >= 0) {
+    return locate_near_command((uint32_t)parse_near_k(argv[2]), argv[3], argv[4], argv[1][4] == 'd');
   } else if (argc == 5 && (strcmp(argv[1], "-gm") == 0 || strcmp(argv[1], "-gmd") == 0) && parse_min_len(argv[2]) != 0) {
     return coverage_command(parse_min_len(argv[2]), argv[3], argv[1][3] == 'd', argv[4]);
   } else if (argc == 4 && (strcmp(argv[1], "-gz") == 0 || strcmp(argv[1], "-gzd") == 0) && parse_min_len(argv[2]) != 0) {

@@ -333,6 +333,40 @@ int bce_hip_locate(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *of
 int bce_hip_locate_device(bce_hip_ctx *ctx, const void *d_patterns, const void *d_offsets, uint32_t npat, uint32_t flags,
                           void *d_hit_offsets, void *d_positions, uint64_t cap, uint64_t *total);
 
+/* ---- extension: the same two questions with mismatches allowed (kd_near.hip, near_step.h) ---------------------------------------
+ * T: the indexed text, n bytes, read circularly.  P: a pattern of m bytes.  The distance of P at position i in [0, n) is the Hamming
+ * distance d(i) = #{ j < m : P[j] != T[(i + j) mod n] }.
+ *   cyclic hits: the i with d(i) <= k.  Every i has exactly one distance and is counted once, under it.  Defined for every m:
+ *     m == 0 gives all n positions at distance 0, k >= m gives all n positions, m > n wraps as it does for bce_hip_count.
+ *   linear hits (BCE_HIP_LOCATE_LINEAR): those with i + m <= n, what a sliding window over the text finds; none for m > n.
+ * 0 <= k <= BCE_HIP_NEAR_MAX_K and m <= BCE_HIP_NEAR_MAX_LEN: WORK bounds, not limits of any format (as BCE_HIP_MATCH_MAX_LEN);
+ * outside them BCE_HIP_E_ARG.  The search is backward search that branches: two different strings of one length own disjoint row
+ * intervals, so the hits are the disjoint union of the intervals of the strings within k mismatches of P that occur -- counts add
+ * and nothing is found twice.  Its work grows with the number of such strings that occur, up to C(m, k) * 255^k on a text that holds
+ * everything: that, on machines that are shared, is why k stops at 2 (DESIGN.md 4.17 has the figures).
+ * Patterns arrive as for bce_hip_count.
+ * bce_hip_count_near: counts[p * (k + 1) + d] = the cyclic hits of pattern p at distance exactly d, d = 0 .. k.  Cyclic only, as
+ * bce_hip_count (the linear correction is the caller's, from the text's two ends: bce_amd/api.py: RankFile.count_near).  State,
+ * order of the checks and npat == 0 as bce_hip_count, with k judged beside ctx; k == 0 gives bce_hip_count's counts.
+ * bce_hip_locate_near: bce_hip_locate's protocol word for word -- the CSR answer (positions ascending within each pattern), the
+ * sizing call (positions and dists NULL, cap 0), BCE_HIP_E_OVERFLOW with exact hit_offsets and *total when total > cap or the
+ * batch's cyclic rows exceed 2^31 - 1, the validity (planes AND suffix array; BCE_HIP_E_STATE after bce_hip_set_bwt), the order of
+ * the checks (k beside the flags), no change to the compression state -- plus dists[r], the distance of positions[r]; positions and
+ * dists are given together or not at all.  k == 0 gives bce_hip_locate's positions.  npat <= 2^30 for this call (the distance
+ * travels in the two low bits of the pattern's number through the sorts): more is BCE_HIP_E_ARG. */
+#define BCE_HIP_NEAR_MAX_K 2u
+#define BCE_HIP_NEAR_MAX_LEN 4096u
+int bce_hip_count_near(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t k, uint64_t *counts);
+/* The same with all three arrays in device memory of the context's device.  Stream rule and the kernel's checks (decreasing
+ * offsets, and here a pattern longer than BCE_HIP_NEAR_MAX_LEN): as bce_hip_count_device. */
+int bce_hip_count_near_device(bce_hip_ctx *ctx, const void *d_patterns, const void *d_offsets, uint32_t npat, uint32_t k, void *d_counts);
+int bce_hip_locate_near(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t k, uint32_t flags,
+                        uint64_t *hit_offsets, uint32_t *positions, uint8_t *dists, uint64_t cap, uint64_t *total);
+/* The same with patterns, offsets, hit offsets, positions and distances in device memory of the context's device; total stays a
+ * host pointer.  Stream rule and the kernel's checks: as bce_hip_count_near_device. */
+int bce_hip_locate_near_device(bce_hip_ctx *ctx, const void *d_patterns, const void *d_offsets, uint32_t npat, uint32_t k, uint32_t flags,
+                               void *d_hit_offsets, void *d_positions, void *d_dists, uint64_t cap, uint64_t *total);
+
 /* ---- extension: the longest matches of a SECOND buffer in the input (kd_match.hip, fm_step.h) -----------------------------------
  * The matching statistics of a query Q (q bytes, 1 <= q <= 2^31 - 1) against the text T (the n bytes the context indexed).  For
  * every END position i in [0, q):
