@@ -134,6 +134,10 @@ SYMBOLS = [
     ("bce_hip_count_near_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, _vp]),
     ("bce_hip_locate_near", C.c_int, [C.c_void_p, _u8p, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("bce_hip_locate_near_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("bce_hip_count_classes", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    ("bce_hip_count_classes_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
+    ("bce_hip_locate_classes", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("bce_hip_locate_classes_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("bce_hip_match", C.c_int, [C.c_void_p, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp]),
     ("bce_hip_match_device", C.c_int, [C.c_void_p, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp]),
     ("bce_hip_coverage", C.c_int, [C.c_void_p, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
@@ -201,6 +205,11 @@ def _as_u8(data):
 LOCATE_LINEAR = 1                               # BCE_HIP_LOCATE_LINEAR
 NEAR_MAX_K = 2                                  # BCE_HIP_NEAR_MAX_K: mismatches allowed at most; a work bound, not a format limit
 NEAR_MAX_LEN = 4096                             # BCE_HIP_NEAR_MAX_LEN: bytes of a pattern searched with mismatches
+CLASS_MAX_LEN = 4096                            # BCE_HIP_CLASS_MAX_LEN: classes of a pattern searched by byte classes
+CLASS_MAX_WIDE = 64                             # BCE_HIP_CLASS_MAX_WIDE: of them, those with two members or more
+CLASS_DEFAULT_NODES = 1 << 16                   # BCE_HIP_CLASS_DEFAULT_NODES: the budget of search nodes per pattern when none is given
+CLASS_MAX_NODES = 1 << 16                       # BCE_HIP_CLASS_MAX_NODES: the largest budget a call takes
+CLASS_OVER = 1                                  # BCE_HIP_CLASS_OVER: status of a pattern whose search ran out of its budget
 MATCH_LINEAR = 1                                # BCE_HIP_MATCH_LINEAR
 MATCH_MAX_LEN = 4096                            # BCE_HIP_MATCH_MAX_LEN: a work bound per end position, not a format limit
 KGRAMS_MAX = 64                                 # BCE_HIP_KGRAMS_MAX: values of k in one bce_hip_kgrams call
@@ -265,6 +274,139 @@ def near_linear_counts(cyclic, patterns, n, ends):
             d = (np.lib.stride_tricks.sliding_window_view(seam, m)[:m - 1] != np.frombuffer(bytes(p), dtype=np.uint8)).sum(axis=1)
             out[i] -= np.bincount(d[d <= k], minlength=k + 1)[:k + 1].astype(np.uint64)
     return out
+
+
+_CLASS_ESCAPES = b"\\.[]^-{}"
+
+
+def compile_classes(expr, ignore_case=False):
+    """An expression over bytes (bytes-like, or str taken as UTF-8) -> its classes: a numpy uint32 array of shape (m, 8), one
+    256-bit set per position, byte c being bit c & 31 of word c >> 5 -- what the class searches take (bce_amd/csrc/class_expr.h
+    is the same grammar for `bce -ge`).
+      .        any byte
+      [...]    a set: bytes and ranges a-b (a > b is an error); a leading ^ negates.  Inside a set only ] \\ and - are special (and
+               ^ in front); a - that is not between the two ends of a range, and the empty set, are errors
+      \\xHH    the byte HH; \\ before one of \\ . [ ] ^ - { } is that byte; both inside and outside sets; any other escape is an error
+      {N}      after an atom: the atom N times in all, 1 <= N <= 4096
+    Every other byte is itself; outside a set ] { } must be escaped.  More than CLASS_MAX_LEN classes, or anything malformed:
+    ValueError.  ignore_case adds the other ASCII case of every letter of a literal or a set, before the set is negated."""
+    s = expr.encode("utf-8") if isinstance(expr, str) else bytes(expr)
+    out, at, atom = [], 0, False
+
+    def escape(at):
+        if at >= len(s):
+            raise ValueError("a backslash at the end")
+        if s[at] == 0x78:
+            digits = s[at + 1:at + 3]
+            if len(digits) != 2 or any(d not in b"0123456789abcdefABCDEF" for d in digits):
+                raise ValueError("\\x wants two hex digits")
+            return int(digits, 16), at + 3
+        if s[at] in _CLASS_ESCAPES:
+            return s[at], at + 1
+        raise ValueError("an escape that is not one of \\xHH \\\\ \\. \\[ \\] \\^ \\- \\{ \\}")
+
+    def item(at):
+        return escape(at + 1) if s[at] == 0x5C else (s[at], at + 1)
+
+    while at < len(s):
+        ch = s[at]
+        at += 1
+        if ch == 0x7B:                                          # {N}
+            end = at
+            while end < len(s) and end - at < 8 and 0x30 <= s[end] <= 0x39:
+                end += 1
+            if not atom or end == at or end >= len(s) or s[end] != 0x7D:
+                raise ValueError("{N} wants an atom before it, decimal digits and its }")
+            count, at = int(s[at:end]), end + 1
+            if not 1 <= count <= CLASS_MAX_LEN:
+                raise ValueError("a repeat count outside 1 .. %d" % CLASS_MAX_LEN)
+            if len(out) + count - 1 > CLASS_MAX_LEN:
+                raise ValueError("more than %d classes" % CLASS_MAX_LEN)
+            out += [out[-1]] * (count - 1)
+            atom = False
+            continue
+        if ch in (0x5D, 0x7D):
+            raise ValueError("] or } outside a set or a repeat")
+        member, fold, negate = np.zeros(256, dtype=bool), True, False
+        if ch == 0x2E:
+            member[:], fold = True, False
+        elif ch == 0x5B:
+            if at < len(s) and s[at] == 0x5E:
+                negate, at = True, at + 1
+            while True:
+                if at >= len(s):
+                    raise ValueError("a set without its ]")
+                if s[at] == 0x5D:
+                    at += 1
+                    break
+                if s[at] == 0x2D:
+                    raise ValueError("a - that is not inside a range")
+                a, at = item(at)
+                b = a
+                if at < len(s) and s[at] == 0x2D:
+                    at += 1
+                    if at >= len(s):
+                        raise ValueError("a set without its ]")
+                    if s[at] in (0x5D, 0x2D):
+                        raise ValueError("a - that is not inside a range")
+                    b, at = item(at)
+                    if a > b:
+                        raise ValueError("a range whose first byte is above its last")
+                member[a:b + 1] = True
+            if not member.any():
+                raise ValueError("an empty set")
+        else:
+            c, at = escape(at) if ch == 0x5C else (ch, at)
+            member[c] = True
+        if fold and ignore_case:
+            both = member[0x41:0x5B] | member[0x61:0x7B]
+            member[0x41:0x5B] = member[0x61:0x7B] = both
+        if negate:
+            member = ~member
+        if len(out) >= CLASS_MAX_LEN:
+            raise ValueError("more than %d classes" % CLASS_MAX_LEN)
+        out.append(np.packbits(member, bitorder="little").view("<u4").astype(np.uint32))
+        atom = True
+    return np.array(out, dtype=np.uint32).reshape(len(out), 8)
+
+
+def _class_member(masks, data):
+    """masks: (m, 8) classes; data: uint8 array whose last axis has m bytes -> which of them lie in their position's class"""
+    at = np.arange(masks.shape[0])
+    return ((masks[at, data >> 5] >> (data & 31).astype(np.uint32)) & 1).astype(bool)
+
+
+def class_linear_counts(cyclic, patterns, n, ends, over=None):
+    """Cyclic counts of patterns of byte classes (RankFile.count_classes; `patterns`: their (m, 8) mask arrays) -> the counts a
+    sliding window over the n-byte text gives.  ends: as for linear_counts.  A pattern longer than the text is nowhere; otherwise
+    the windows that start in the text's last m - 1 bytes and match come off.  `over`: the patterns whose search ran out of its
+    budget -- they have no count and stay at 0."""
+    out = np.array(cyclic, dtype=np.uint64)
+    longest = max([len(p) for p in patterns if len(p) <= n] + [1])
+    head, tail = ends(longest - 1)
+    for i, p in enumerate(patterns):
+        m = len(p)
+        if m > n or (over is not None and over[i]):
+            out[i] = 0
+        elif m > 1:
+            seam = np.frombuffer(bytes(tail[len(tail) - (m - 1):]) + bytes(head[:m - 1]), dtype=np.uint8)
+            inside = _class_member(np.asarray(p, dtype=np.uint32), np.lib.stride_tricks.sliding_window_view(seam, m)[:m - 1])
+            out[i] -= np.uint64(inside.all(axis=1).sum())
+    return out
+
+
+def _is_one_class_pattern(patterns):
+    return isinstance(patterns, (bytes, bytearray, memoryview, str)) or (isinstance(patterns, np.ndarray) and patterns.dtype != object and patterns.ndim == 2)
+
+
+def _as_classes(pattern, ignore_case):
+    """one pattern of a class search: an expression is compiled, an array of masks is taken as it stands"""
+    if isinstance(pattern, (bytes, bytearray, memoryview, str)):
+        return compile_classes(pattern, ignore_case=ignore_case)
+    masks = np.ascontiguousarray(pattern, dtype=np.uint32)
+    if masks.ndim != 2 or masks.shape[1] != 8:
+        raise ValueError("a pattern of classes is an expression or an array of shape (m, 8), not %r" % (masks.shape,))
+    return masks
 
 
 class KGram(C.Structure):
@@ -564,6 +706,92 @@ class RankFile:
         self._c.check(self._c.lib.bce_hip_locate_near_device(self._c.h, ptr(patterns_ptr), ptr(offsets_ptr), int(npat), int(k),
                                                              0 if cyclic else LOCATE_LINEAR, ptr(hit_offsets_ptr), ptr(positions_ptr), ptr(dists_ptr),
                                                              int(cap), C.byref(total)), "bce_hip_locate_near_device")
+        return total.value
+
+    def _class_args(self, patterns, cyclic, max_nodes, ignore_case, what):
+        """-> (one, pats, flat, offsets, budget) of a search by byte classes, judged as count() and locate() judge theirs"""
+        budget = 0 if max_nodes is None else int(max_nodes)
+        if max_nodes is not None and not 1 <= budget <= CLASS_MAX_NODES:
+            raise ValueError("max_nodes = %r, outside 1 .. %d" % (max_nodes, CLASS_MAX_NODES))
+        one = _is_one_class_pattern(patterns)
+        pats = [_as_classes(p, ignore_case) for p in ([patterns] if one else patterns)]
+        if not cyclic:
+            if not self._has_text:
+                raise ValueError("a RankFile built from an injected BWT holds no text: only cyclic=True %s are defined" % what)
+            if any(len(p) == 0 for p in pats):
+                raise ValueError("an empty pattern has no linear %s (cyclic=True: every position)" % what)
+        if any(len(p) > CLASS_MAX_LEN for p in pats):
+            raise ValueError("a pattern of more than %d classes" % CLASS_MAX_LEN)
+        if any(int((np.unpackbits(p.view(np.uint8), axis=1).sum(axis=1) > 1).sum()) > CLASS_MAX_WIDE for p in pats if len(p)):
+            raise ValueError("a pattern with more than %d classes of two bytes or more" % CLASS_MAX_WIDE)
+        offsets = np.zeros(len(pats) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([len(p) for p in pats], dtype=np.uint64)
+        flat = np.concatenate(pats).reshape(-1) if pats and int(offsets[-1]) else np.zeros(8, dtype=np.uint32)
+        return one, pats, np.ascontiguousarray(flat, dtype=np.uint32), offsets, budget
+
+    def count_classes(self, patterns, cyclic=False, max_nodes=None, ignore_case=False, return_work=False):
+        """How often something occurs in the text that a pattern of byte CLASSES describes: every position of the pattern is a set of
+        bytes (bce_hip_count_classes: backward search that branches at every set of two bytes or more, on the GPU).  `patterns`:
+        one expression (bytes or str: compile_classes) or one (m, 8) uint32 array of masks -> (count, over); a sequence of them ->
+        (counts uint64[npat], over bool[npat]).  over: the pattern's search tree has more than `max_nodes` nodes (None:
+        CLASS_DEFAULT_NODES; at most CLASS_MAX_NODES) and the search gave up -- its count is 0, not a part of the answer.
+        return_work adds a third value, the nodes counted: exactly the tree's size within budget, something above max_nodes over it.
+        cyclic=False: what a sliding window over the text finds; 0 for a pattern longer than the text; an empty pattern raises
+        ValueError.  cyclic=True: the hits in the circular text, defined for every length (the empty pattern: n).  ignore_case is
+        for expressions (masks are taken as they stand).  More than CLASS_MAX_LEN classes, or more than CLASS_MAX_WIDE of them
+        with two bytes or more: ValueError."""
+        one, pats, flat, offsets, budget = self._class_args(patterns, cyclic, max_nodes, ignore_case, "counts")
+        out, work, status = np.zeros(len(pats), dtype=np.uint64), np.zeros(len(pats), dtype=np.uint64), np.zeros(len(pats), dtype=np.uint32)
+        if pats:
+            self._c.check(self._c.lib.bce_hip_count_classes(self._c.h, flat.ctypes.data, offsets.ctypes.data, len(pats), budget, out.ctypes.data,
+                                                            work.ctypes.data, status.ctypes.data), "bce_hip_count_classes")
+        over = status != 0
+        if pats and not cyclic:
+            out = class_linear_counts(out, pats, self._n, self._text_ends, over)
+        res = (int(out[0]), bool(over[0])) if one else (out, over)
+        return res + ((int(work[0]) if one else work),) if return_work else res
+
+    def count_classes_device(self, masks_ptr, offsets_ptr, npat, counts_ptr, status_ptr, work_ptr=None, max_nodes=None):
+        """bce_hip_count_classes_device: the cyclic counts of `npat` patterns of classes that lie concatenated in device memory (int
+        pointers: 8 uint32 words per class, npat + 1 uint64 offsets counted in classes; out: npat uint64 counts, npat uint32
+        verdicts and, unless None, npat uint64 node counts).  Stream rule: as count_device."""
+        ptr = lambda v: None if v is None else int(v)  # noqa: E731
+        self._c.check(self._c.lib.bce_hip_count_classes_device(self._c.h, ptr(masks_ptr), ptr(offsets_ptr), int(npat), int(max_nodes or 0),
+                                                               ptr(counts_ptr), ptr(work_ptr), ptr(status_ptr)), "bce_hip_count_classes_device")
+
+    def locate_classes(self, patterns, cyclic=False, limit=None, max_hits=1 << 26, max_nodes=None, ignore_case=False):
+        """Where something occurs that a pattern of byte classes describes: (positions uint32 ascending, over) for one pattern,
+        (a list of such arrays, over bool[npat]) for a sequence (bce_hip_locate_classes).  Patterns, max_nodes, over and
+        ignore_case: as count_classes -- a pattern over budget has no positions.  cyclic, the empty pattern and an injected BWT: as
+        locate().  `max_hits` and `limit`: locate()'s rules."""
+        one, pats, flat, offsets, budget = self._class_args(patterns, cyclic, max_nodes, ignore_case, "hits")
+        if limit is not None and limit < 0:
+            raise ValueError("limit must not be negative")
+        if not pats:
+            return [], np.zeros(0, dtype=bool)
+        lib, flags = self._c.lib, 0 if cyclic else LOCATE_LINEAR
+        hits, status, total = np.zeros(len(pats) + 1, dtype=np.uint64), np.zeros(len(pats), dtype=np.uint32), C.c_uint64(0)
+        rc = lib.bce_hip_locate_classes(self._c.h, flat.ctypes.data, offsets.ctypes.data, len(pats), budget, flags, hits.ctypes.data, status.ctypes.data,
+                                        None, 0, C.byref(total))
+        if rc in (0, E_OVERFLOW) and total.value > max_hits:
+            raise ValueError("%d hits in all, more than max_hits = %d" % (total.value, max_hits))
+        self._c.check(rc, "bce_hip_locate_classes")
+        pos = _positions_buffer(total.value)
+        self._c.check(lib.bce_hip_locate_classes(self._c.h, flat.ctypes.data, offsets.ctypes.data, len(pats), budget, flags, hits.ctypes.data,
+                                                 status.ctypes.data, pos.ctypes.data, total.value, C.byref(total)), "bce_hip_locate_classes")
+        out = [pos[int(hits[i]):int(hits[i + 1])][:limit].copy() for i in range(len(pats))]
+        over = status != 0
+        return (out[0], bool(over[0])) if one else (out, over)
+
+    def locate_classes_device(self, masks_ptr, offsets_ptr, npat, hit_offsets_ptr, status_ptr, positions_ptr, cap, cyclic=False, max_nodes=None) -> int:
+        """bce_hip_locate_classes_device: locate_device for patterns of classes (in: as count_classes_device; out: npat + 1 uint64 hit
+        offsets, npat uint32 verdicts, up to `cap` uint32 positions) -> the total.  positions_ptr None with cap 0 only sizes.
+        Stream rule: as count_device."""
+        total = C.c_uint64(0)
+        ptr = lambda v: None if v is None else int(v)  # noqa: E731
+        self._c.check(self._c.lib.bce_hip_locate_classes_device(self._c.h, ptr(masks_ptr), ptr(offsets_ptr), int(npat), int(max_nodes or 0),
+                                                                0 if cyclic else LOCATE_LINEAR, ptr(hit_offsets_ptr), ptr(status_ptr),
+                                                                ptr(positions_ptr), int(cap), C.byref(total)), "bce_hip_locate_classes_device")
         return total.value
 
     def _match_flags(self, cyclic, what):
@@ -967,6 +1195,27 @@ def locate_near(data, patterns, k, cyclic=False, limit=None, max_hits=1 << 26, d
     rf = RankFile(data, device=device, ctx=ctx)
     try:
         return rf.locate_near(patterns, k, cyclic=cyclic, limit=limit, max_hits=max_hits)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def count_classes(data, patterns, cyclic=False, max_nodes=None, ignore_case=False, device=0, ctx=None):
+    """The hits of patterns of byte classes in `data` -> (counts, over) as RankFile.count_classes: K1 and K2 index the data on the
+    GPU, the branching backward search asks the index."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.count_classes(patterns, cyclic=cyclic, max_nodes=max_nodes, ignore_case=ignore_case)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def locate_classes(data, patterns, cyclic=False, limit=None, max_hits=1 << 26, max_nodes=None, ignore_case=False, device=0, ctx=None):
+    """Where patterns of byte classes occur in `data` -> (positions, over) as RankFile.locate_classes."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.locate_classes(patterns, cyclic=cyclic, limit=limit, max_hits=max_hits, max_nodes=max_nodes, ignore_case=ignore_case)
     finally:
         if ctx is None:
             rf.close()

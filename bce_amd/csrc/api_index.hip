@@ -1,4 +1,5 @@
-// api_index.hip -- C ABI of the index queries (include/bce_hip.h): counts, positions, both within k mismatches, longest matches and coverage, the LCP array and
+// api_index.hip -- C ABI of the index queries (include/bce_hip.h): counts, positions, both within k mismatches and both for patterns of byte classes
+// (kd_classes.hip), longest matches and coverage, the LCP array and
 // its reductions, the list of the most frequent k-grams, parse and patch, the longest previous factors and the self-parse; and the test hooks that run their block scans alone.  The device work is in kd_count /
 // kd_locate / kd_near / kd_match / kd_lcp / kd_parse / kd_self.hip.  Every query comes twice, for host buffers and for device buffers: the two differ
 // in staging and in the copy out, and in nothing else.
@@ -310,6 +311,112 @@ int bce_hip_locate_near_device(bce_hip_ctx *c, const void *d_patterns, const voi
     return locate_near_run(c, sa, static_cast<const uint8_t *>(d_patterns), static_cast<const uint64_t *>(d_offsets), npat, k,
                            flags & BCE_HIP_LOCATE_LINEAR, static_cast<uint64_t *>(d_hit_offsets), nullptr, static_cast<uint32_t *>(d_positions),
                            static_cast<uint8_t *>(d_dists), nullptr, nullptr, !d_positions, cap, total);
+  });
+}
+
+// ---- counts and positions of patterns of byte classes, under a budget (kd_classes.hip) --------------------------------------------
+// The count's and the locate's rules, checks and protocol; max_nodes is judged beside ctx and the flags.  The patterns' lengths and
+// their wide classes are judged by the prepare pass on the device, for host buffers too.
+static bool class_budget(uint32_t &max_nodes) {
+  if (max_nodes == 0) max_nodes = BCE_HIP_CLASS_DEFAULT_NODES;
+  return max_nodes <= BCE_HIP_CLASS_MAX_NODES;
+}
+static int stage_classes(bce_hip_ctx *c, const uint32_t *masks, const uint64_t *offsets, uint32_t npat) {
+  BCE_TRY(stage(c, c->qbuf[qb::cls_mask], masks, (size_t)offsets[npat] * 32));
+  BCE_TRY(stage(c, c->qbuf[qb::cls_off], offsets, ((size_t)npat + 1) * 8));
+  return ensure(c, c->qbuf[qb::cls_status], (size_t)npat * 4);
+}
+
+int bce_hip_count_classes(bce_hip_ctx *c, const uint32_t *masks, const uint64_t *offsets, uint32_t npat, uint32_t max_nodes, uint64_t *counts,
+                          uint64_t *work, uint32_t *status) {
+  if (!c || !class_budget(max_nodes)) return BCE_HIP_E_ARG;
+  if (npat == 0) return BCE_HIP_OK;
+  BCE_TRY(planes_state(c, "count_classes"));
+  if (!counts || !status) return BCE_HIP_E_ARG;
+  BCE_TRY(pattern_list_args(c, "count_classes", reinterpret_cast<const uint8_t *>(masks), offsets, npat));
+  return query_call(c, 3, [&]() -> int {
+    DevBuf &out = c->qbuf[qb::cls_out], &wrk = c->qbuf[qb::cls_work], &st = c->qbuf[qb::cls_status];
+    BCE_TRY(ensure(c, out, (size_t)npat * 8));
+    BCE_TRY(ensure(c, wrk, (size_t)npat * 8));
+    BCE_TRY(stage_classes(c, masks, offsets, npat));
+    BCE_TRY(kd_class_count(c, c->qbuf[qb::cls_mask].as<uint32_t>(), c->qbuf[qb::cls_off].as<uint64_t>(), npat, max_nodes, out.as<uint64_t>(),
+                           wrk.as<uint64_t>(), st.as<uint32_t>()));
+    BCE_TRY(copy_out(c, counts, out, (size_t)npat * 8));
+    if (work) BCE_TRY(copy_out(c, work, wrk, (size_t)npat * 8));
+    return copy_out(c, status, st, (size_t)npat * 4);
+  });
+}
+
+int bce_hip_count_classes_device(bce_hip_ctx *c, const void *d_masks, const void *d_offsets, uint32_t npat, uint32_t max_nodes, void *d_counts,
+                                 void *d_work, void *d_status) {
+  if (!c || !class_budget(max_nodes)) return BCE_HIP_E_ARG;
+  if (npat == 0) return BCE_HIP_OK;
+  BCE_TRY(planes_state(c, "count_classes"));
+  if (!d_masks || !d_offsets || !d_counts || !d_status) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&] {
+    return kd_class_count(c, static_cast<const uint32_t *>(d_masks), static_cast<const uint64_t *>(d_offsets), npat, max_nodes,
+                          static_cast<uint64_t *>(d_counts), static_cast<uint64_t *>(d_work), static_cast<uint32_t *>(d_status));
+  });
+}
+
+// locate_run with the verdicts beside the hit offsets
+static int locate_classes_run(bce_hip_ctx *c, const uint32_t *sa, const uint32_t *d_masks, const uint64_t *d_off, uint32_t npat, uint32_t max_nodes,
+                              bool linear, uint64_t *d_hits, uint64_t *h_hits, uint32_t *d_status, uint32_t *h_status, uint32_t *d_pos, uint32_t *h_pos,
+                              bool sizing, uint64_t cap, uint64_t *total) {
+  uint64_t rows = 0, hits = 0;
+  const int rc = kd_class_size(c, sa, d_masks, d_off, npat, max_nodes, linear, d_hits, d_status, &rows, &hits);
+  if (rc != BCE_HIP_OK && rc != BCE_HIP_E_OVERFLOW) return rc;
+  if (h_hits) {
+    BCE_HIP_TRY(c, hipMemcpyAsync(h_hits, d_hits, ((size_t)npat + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    BCE_HIP_TRY(c, hipMemcpyAsync(h_status, d_status, (size_t)npat * 4, hipMemcpyDeviceToHost, c->stream));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  *total = hits;
+  if (rc != BCE_HIP_OK || sizing) return rc;
+  if (hits > cap) { snprintf(c->err, sizeof c->err, "locate_classes: %llu hits, room for %llu", (unsigned long long)hits, (unsigned long long)cap); return BCE_HIP_E_OVERFLOW; }
+  if (hits == 0) return BCE_HIP_OK;
+  if (h_pos) {
+    BCE_TRY(ensure(c, c->qbuf[qb::cls_pos], (size_t)hits * 4));
+    d_pos = c->qbuf[qb::cls_pos].as<uint32_t>();
+  }
+  BCE_TRY(kd_class_fill(c, sa, d_masks, d_off, npat, max_nodes, linear, rows, hits, d_status, d_pos));
+  return h_pos ? copy_out(c, h_pos, c->qbuf[qb::cls_pos], (size_t)hits * 4) : BCE_HIP_OK;
+}
+
+int bce_hip_locate_classes(bce_hip_ctx *c, const uint32_t *masks, const uint64_t *offsets, uint32_t npat, uint32_t max_nodes, uint32_t flags,
+                           uint64_t *hit_offsets, uint32_t *status, uint32_t *positions, uint64_t cap, uint64_t *total) {
+  if (!c || !total || (flags & ~BCE_HIP_LOCATE_LINEAR) || !class_budget(max_nodes)) return BCE_HIP_E_ARG;
+  *total = 0;
+  if (npat == 0) { if (hit_offsets) hit_offsets[0] = 0; return BCE_HIP_OK; }
+  const uint32_t *sa = nullptr;
+  BCE_TRY(sa_state(c, &sa, "locate_classes"));
+  if (!hit_offsets || !status || (!positions && cap)) return BCE_HIP_E_ARG;
+  BCE_TRY(pattern_list_args(c, "locate_classes", reinterpret_cast<const uint8_t *>(masks), offsets, npat));
+  return query_call(c, 3, [&]() -> int {
+    DevBuf &hits = c->qbuf[qb::cls_hits];
+    BCE_TRY(ensure(c, hits, ((size_t)npat + 1) * 8));
+    BCE_TRY(stage_classes(c, masks, offsets, npat));
+    return locate_classes_run(c, sa, c->qbuf[qb::cls_mask].as<uint32_t>(), c->qbuf[qb::cls_off].as<uint64_t>(), npat, max_nodes,
+                              flags & BCE_HIP_LOCATE_LINEAR, hits.as<uint64_t>(), hit_offsets, c->qbuf[qb::cls_status].as<uint32_t>(), status, nullptr,
+                              positions, !positions, cap, total);
+  });
+}
+
+int bce_hip_locate_classes_device(bce_hip_ctx *c, const void *d_masks, const void *d_offsets, uint32_t npat, uint32_t max_nodes, uint32_t flags,
+                                  void *d_hit_offsets, void *d_status, void *d_positions, uint64_t cap, uint64_t *total) {
+  if (!c || !total || (flags & ~BCE_HIP_LOCATE_LINEAR) || !class_budget(max_nodes)) return BCE_HIP_E_ARG;
+  *total = 0;
+  if (npat == 0) {
+    if (!d_hit_offsets) return BCE_HIP_OK;
+    return query_call(c, 0, [&]() -> int { BCE_HIP_TRY(c, hipMemsetAsync(d_hit_offsets, 0, 8, c->stream)); return BCE_HIP_OK; });
+  }
+  const uint32_t *sa = nullptr;
+  BCE_TRY(sa_state(c, &sa, "locate_classes"));
+  if (!d_masks || !d_offsets || !d_hit_offsets || !d_status || (!d_positions && cap)) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&] {
+    return locate_classes_run(c, sa, static_cast<const uint32_t *>(d_masks), static_cast<const uint64_t *>(d_offsets), npat, max_nodes,
+                              flags & BCE_HIP_LOCATE_LINEAR, static_cast<uint64_t *>(d_hit_offsets), nullptr, static_cast<uint32_t *>(d_status), nullptr,
+                              static_cast<uint32_t *>(d_positions), nullptr, !d_positions, cap, total);
   });
 }
 

@@ -143,6 +143,10 @@ enum Id {
   near_res,                                      // kd_near.hip: its flag word (a buffer of its own, as loc_res); its scratch is the locate's loc_cnt .. loc_val1
   near_pat, near_off, near_out,                  // bce_hip_count_near / _locate_near: the patterns, their offsets and the counts of a call with host buffers, staged (grow-only)
   near_hits, near_pos, near_dist,                // bce_hip_locate_near with host buffers: the CSR offsets, positions and distances, staged (grow-only)
+  cls_res,                                       // kd_classes.hip: its flag word (a buffer of its own, as near_res); its locate's scratch is loc_cnt .. loc_val1
+  cls_kind, cls_pat,                             // the prepare pass: 16 bits per class of the batch (class_summary), two words per pattern (wide classes, the leftmost)
+  cls_mask, cls_off, cls_out, cls_work, cls_status,   // bce_hip_count_classes / _locate_classes: masks, offsets, counts, nodes and verdicts of a call with host buffers, staged (grow-only)
+  cls_hits, cls_pos,                             // bce_hip_locate_classes with host buffers: the CSR offsets and positions, staged (grow-only)
   mat_res,                                       // kd_match.hip: the coverage's result word (a buffer of its own, as loc_res)
   mat_bsum,                                      // the coverage scan's block maxima and block counts
   mat_qry, mat_len, mat_pos,                     // bce_hip_match / _coverage: the query of a call with a host buffer, the lengths and the positions, staged (all grow-only)
@@ -502,6 +506,14 @@ int kd_near_size(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, const
                  uint64_t *d_hits, uint64_t *rows, uint64_t *total);
 int kd_near_fill(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, uint32_t k, bool linear,
                  uint64_t rows, uint64_t total, uint32_t *d_pos, uint8_t *d_dist);
+// kd_classes.hip: the same two questions for patterns of byte classes (class_step.h), under a budget of max_nodes search nodes per
+// pattern.  d_masks: 8 words per class, d_off counts classes.  d_status[npat]: 0 or BCE_HIP_CLASS_OVER; d_work (may be null): the nodes.
+int kd_class_count(bce_hip_ctx *c, const uint32_t *d_masks, const uint64_t *d_off, uint32_t npat, uint32_t max_nodes, uint64_t *d_counts,
+                   uint64_t *d_work, uint32_t *d_status);
+int kd_class_size(bce_hip_ctx *c, const uint32_t *sa, const uint32_t *d_masks, const uint64_t *d_off, uint32_t npat, uint32_t max_nodes, bool linear,
+                  uint64_t *d_hits, uint32_t *d_status, uint64_t *rows, uint64_t *total);
+int kd_class_fill(bce_hip_ctx *c, const uint32_t *sa, const uint32_t *d_masks, const uint64_t *d_off, uint32_t npat, uint32_t max_nodes, bool linear,
+                  uint64_t rows, uint64_t total, const uint32_t *d_status, uint32_t *d_pos);
 // kd_match.hip: d_len[i] (and d_pos[i], unless null) of the longest string that ends at d_query[i] and occurs in the text, at most
 // max_len bytes; queued, the caller waits.  kd_coverage: the bytes of the query inside matches of min_len or more, from such lengths.
 int kd_match(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_query, uint32_t q, uint32_t max_len, bool linear, uint32_t *d_len,

@@ -22,11 +22,12 @@
 //           pattern's segment: no atomics.  Then the locate's order -- two stable radix_sort_pairs, on the position bits and on
 //           the pattern-id bits above the distance's two -- and one pass that splits the pairs into positions and distances,
 //           keeping in linear mode the first rows of each sorted segment (those across the end are its largest positions).
-// Intervals of up to NEAR_SERIAL rows are read by the lane that found them, wider ones by the whole wave, 64 neighbouring words at a time.
+// Intervals of up to WAVE_SERIAL rows (wave_walk.h) are read by the lane that found them, wider ones by the whole wave, 64 neighbouring words at a time.
 // Everything written is the locate's scratch (qb::loc_* of c->qbuf: the two calls never run together), near_res or the caller's outputs.
 #include "common.h"
 #include "near_step.h"
 #include "scan_util.h"
+#include "wave_walk.h"
 
 namespace bce {
 
@@ -34,35 +35,11 @@ namespace {
 
 constexpr int NEAR_T = 256;                  // lanes per workgroup (4 waves = 4 patterns)
 constexpr uint32_t NEAR_WAVES = NEAR_T / 64;
-constexpr uint32_t NEAR_SERIAL = 8;          // rows of an interval that its own lane reads
 constexpr uint32_t NEAR_MAXGRID = 8192;      // grid-stride kernels: workgroups at most
 constexpr uint64_t NEAR_MAXROWS = 0x7FFFFFFFull;
 constexpr uint32_t NEAR_BAD_ORDER = 1u, NEAR_BAD_LEN = 2u;   // bits of the flag word
 
 static_assert(BCE_NEAR_MAX_K == BCE_HIP_NEAR_MAX_K, "near_step.h and bce_hip.h name one bound");
-
-struct Zeros8 { uint32_t v[8]; };
-
-// rank2 of fm_step on the context's granules: both loads of a level go out before either rank (count_kernel's lambda)
-struct PlaneRank {
-  const Granule *gran;
-  uint32_t ngran;
-  __device__ __forceinline__ void operator()(int j, uint32_t ia, uint32_t ib, uint32_t &ra, uint32_t &rb) const {
-    const Granule *G = gran + (size_t)j * ngran;                    // (64-bit, as count_kernel)
-    const uint32_t ga = div96(ia), gb = div96(ib);
-    const Granule qa = G[ga], qb = G[gb];
-    ra = granule_rank1(qa, ia - ga * 96u);
-    rb = granule_rank1(qb, ib - gb * 96u);
-  }
-};
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint32_t from_lane(uint32_t v, int l) { return (uint32_t)__shfl((int)v, l); }
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // The branch whose mismatch spends the budget, at the wave-uniform node (lo, hi, pos), pos > 0: every lane takes four candidate
 // bytes, finishes the children that have rows, and the wave emits 64 intervals (most of them empty) four times, at distance d.
@@ -114,24 +91,6 @@ __device__ __forceinline__ void near_wave(const PlaneRank &R, const Zeros8 &z, c
     --pos0;
   }
   emit(lo0, lane == 0 && hi0 > lo0 ? hi0 - lo0 : 0u, 0u);
-}
-
-// All 64 lanes together: lane l brings the rows [lo, lo + rows).  f(o, row) once for every row of every lane, o = its index in
-// the order of the lanes.  Returns the rows of all lanes (below 2^31: the intervals of one pattern are disjoint).
-template <class F>
-__device__ __forceinline__ uint32_t wave_rows(uint32_t lo, uint32_t rows, uint32_t lane, F &&f) {
-  const uint32_t incl = wave_incl_sum(rows);
-  const uint32_t total = from_lane(incl, 63);
-  if (total == 0) return 0;
-  const uint32_t off = incl - rows;
-  const bool wide = rows > NEAR_SERIAL;
-  if (!wide) for (uint32_t i = 0; i < rows; ++i) f(off + i, lo + i);
-  for (uint64_t todo = __ballot(wide); todo; todo &= todo - 1) {
-    const int l = __ffsll((unsigned long long)todo) - 1;
-    const uint32_t L = from_lane(lo, l), S = from_lane(rows, l), O = from_lane(off, l);
-    for (uint32_t i = lane; i < S; i += 64u) f(O + i, L + i);
-  }
-  return total;
 }
 
 // the wave's pattern: false when there is none, or its offsets are refused (then the flag word says why)

@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "../../include/bce_hip.h"
+#include "class_expr.h"
 #include "top_step.h"
 
 // "Coded: %u.%02u %%\r" as BCE::code prints it (bce.cpp:1354-1358); cleared at the end like :1372
@@ -143,6 +144,10 @@ extern "C" int bce_hip_locate(bce_hip_ctx *ctx, const uint8_t *patterns, const u
 extern "C" int bce_hip_count_near(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t k, uint64_t *counts) __attribute__((weak));
 extern "C" int bce_hip_locate_near(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t k, uint32_t flags,
                                    uint64_t *hit_offsets, uint32_t *positions, uint8_t *dists, uint64_t cap, uint64_t *total) __attribute__((weak));
+extern "C" int bce_hip_count_classes(bce_hip_ctx *ctx, const uint32_t *masks, const uint64_t *offsets, uint32_t npat, uint32_t max_nodes, uint64_t *counts,
+                                     uint64_t *work, uint32_t *status) __attribute__((weak));
+extern "C" int bce_hip_locate_classes(bce_hip_ctx *ctx, const uint32_t *masks, const uint64_t *offsets, uint32_t npat, uint32_t max_nodes, uint32_t flags,
+                                      uint64_t *hit_offsets, uint32_t *status, uint32_t *positions, uint64_t cap, uint64_t *total) __attribute__((weak));
 extern "C" int bce_hip_coverage(bce_hip_ctx *ctx, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t flags, uint64_t *covered) __attribute__((weak));
 extern "C" int bce_hip_kgrams(bce_hip_ctx *ctx, const uint32_t *ks, uint32_t nk, bce_hip_kgram *out) __attribute__((weak));
 extern "C" int bce_hip_longest_repeat(bce_hip_ctx *ctx, uint32_t max_len, uint32_t *len, uint32_t *pos_a, uint32_t *pos_b) __attribute__((weak));
@@ -687,6 +692,51 @@ static int locate_near_command(uint32_t K, const char *pattern, const char *path
   return index_done(in);
 }
 
+// -ge[i] / -ge[i]d / -ge[i]l / -ge[i]ld: the hits of an expression of byte classes (class_expr.h), one 256-bit set per position, under
+// the default budget of search nodes.  Linear semantics, as -g: bce_hip_count_classes counts in the circular text and the windows
+// that start in the text's last m - 1 bytes and match come off here; bce_hip_locate_classes filters on the GPU.  A search that runs
+// out of its budget says so and nothing else.
+static const int kExitGaveUp = 1;
+static int classes_command(const std::vector<uint32_t> &masks, bool list, const char *path, bool in_archive) {
+  IndexInput in;
+  if (const int ec = index_open(in, path, in_archive, nullptr, kNoSecond, list ? bce_hip_locate_classes != nullptr : bce_hip_count_classes != nullptr)) return ec;
+  const size_t m = masks.size() / 8;
+  uint64_t count = 0;
+  std::vector<uint32_t> where;
+  if (m <= in.n) {                                                  // (as -g)
+    const uint64_t offsets[2] = {0, m};
+    uint64_t hits[2] = {0, 0};
+    uint32_t status = 0;
+    int rc = index_text(in);
+    if (rc == 0 && list) {
+      rc = bce_hip_locate_classes(in.ctx, masks.data(), offsets, 1, 0, BCE_HIP_LOCATE_LINEAR, hits, &status, nullptr, 0, &count);   // how many
+      if (rc == 0 && count) {
+        where.resize(count);
+        rc = bce_hip_locate_classes(in.ctx, masks.data(), offsets, 1, 0, BCE_HIP_LOCATE_LINEAR, hits, &status, where.data(), count, &count);
+      }
+    } else if (rc == 0) {
+      rc = bce_hip_count_classes(in.ctx, masks.data(), offsets, 1, 0, &count, nullptr, &status);
+    }
+    if (rc != 0) return index_failed(in, list ? "Locate" : "Count", rc);
+    if (status == BCE_HIP_CLASS_OVER) {
+      printf("search gave up: more than %u partial matches\n", BCE_HIP_CLASS_DEFAULT_NODES);
+      return kExitGaveUp;
+    }
+    for (size_t at = in.n - m + 1; !list && at < in.n; ++at) {
+      size_t j = 0;
+      while (j < m) {
+        const uint8_t c = in.text[at + j < in.n ? at + j : at + j - in.n];
+        if (!((masks[8 * j + (c >> 5)] >> (c & 31)) & 1u)) break;
+        ++j;
+      }
+      count -= j == m;
+    }
+  }
+  for (uint32_t at : where) printf("%u\n", at);
+  printf("%llu occurrences\n", (unsigned long long)count);
+  return index_done(in);
+}
+
 // -gm / -gmd
 static int coverage_command(uint32_t min_len, const char *path, bool in_archive, const char *query_path) {
   IndexInput in;
@@ -871,6 +921,16 @@ static int parse_near_k(const char *s) {
   return s[0] >= '0' && s[0] <= (char)('0' + BCE_HIP_NEAR_MAX_K) && s[1] == 0 ? s[0] - '0' : -1;
 }
 
+// the letters behind -ge: i, l, d, each at most once and in that order; anything else: false
+static bool parse_class_option(const char *s, bool &ignore_case, bool &list, bool &in_archive) {
+  if (strncmp(s, "-ge", 3) != 0) return false;
+  s += 3;
+  ignore_case = *s == 'i'; s += ignore_case;
+  list = *s == 'l'; s += list;
+  in_archive = *s == 'd'; s += in_archive;
+  return *s == 0;
+}
+
 // K of -gk / -gkd: decimal digits only, 0 .. 32; anything else: -1
 static int parse_order(const char *s) {
   uint32_t v = 0;
@@ -928,6 +988,18 @@ static int usage() {
   printf("\n");
   printf("  bce -gsc file in.sa\n");
   printf("   Checks on the GPU, in linear time, that \"in.sa\" is the suffix array of \"file\" (extension; exit status 0 = in order, %d = not: the line names the row or the position)\n", kExitDiffers);
+  printf("\n");
+  printf("  bce -ge[i] EXPR file\n");
+  printf("   Counts how often something occurs in \"file\" that EXPR describes byte by byte: . is any byte, [a-f0-9] a set with ranges, [^...] its complement, \\xHH a byte in hex, \\ before one of \\ . [ ] ^ - { } that byte, {N} after any of these the same N (1..4096) times, every other byte itself; with i letters match both cases. Backward search that branches at every set, on the GPU; a search of more than %u partial matches gives up: \"search gave up\", exit status %d (extension)\n", BCE_HIP_CLASS_DEFAULT_NODES, kExitGaveUp);
+  printf("\n");
+  printf("  bce -ge[i]d EXPR archive.bce\n");
+  printf("   The same count in what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
+  printf("\n");
+  printf("  bce -ge[i]l EXPR file\n");
+  printf("   Prints where they occur: the byte offsets, one per line, ascending, then the count (extension)\n");
+  printf("\n");
+  printf("  bce -ge[i]ld EXPR archive.bce\n");
+  printf("   The same offsets in what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
   printf("\n");
   printf("  bce -g PATTERN file\n");
   printf("   Counts how often the bytes of PATTERN occur in \"file\", overlapping matches included: the file is indexed on the GPU and the count comes from the index (extension)\n");
@@ -1263,6 +1335,13 @@ int main(int argc, char **argv) {
     return count_near_command((uint32_t)parse_near_k(argv[2]), argv[3], argv[4], argv[1][3] == 'd');
   } else if (argc == 5 && argv[3][0] != 0 && (strcmp(argv[1], "-gnl") == 0 || strcmp(argv[1], "-gnld") == 0) && parse_near_k(argv[2]) >= 0) {
     return locate_near_command((uint32_t)parse_near_k(argv[2]), argv[3], argv[4], argv[1][4] == 'd');
+  } else if (argc == 4 && argv[2][0] != 0 && strncmp(argv[1], "-ge", 3) == 0) {
+    bool ignore_case = false, list = false, in_archive = false;
+    std::vector<uint32_t> masks;
+    if (!parse_class_option(argv[1], ignore_case, list, in_archive) ||
+        !bce::compile_classes(reinterpret_cast<const uint8_t *>(argv[2]), strlen(argv[2]), ignore_case, masks) || masks.empty())
+      return usage();
+    return classes_command(masks, list, argv[3], in_archive);
   } else if (argc == 5 && (strcmp(argv[1], "-gm") == 0 || strcmp(argv[1], "-gmd") == 0) && parse_min_len(argv[2]) != 0) {
     return coverage_command(parse_min_len(argv[2]), argv[3], argv[1][3] == 'd', argv[4]);
   } else if (argc == 4 && (strcmp(argv[1], "-gz") == 0 || strcmp(argv[1], "-gzd") == 0) && parse_min_len(argv[2]) != 0) {

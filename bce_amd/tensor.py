@@ -223,6 +223,79 @@ def locate_near_in_archive(blob, patterns, k, cyclic=False, device="cuda:0"):
     return locate_near_tensor(decompress_container_tensor(blob, device=device), patterns, k, cyclic=cyclic)
 
 
+def count_classes_tensor(t, patterns, cyclic=False, max_nodes=None, ignore_case=False, ctx=None):
+    """The hits of patterns of byte classes in the 1-D uint8 CUDA tensor `t` (or slice, any offset) -> (counts, over), numpy, as
+    api.RankFile.count_classes.  Indexed where it lies; of the text only the few bytes at its two ends that the longest pattern
+    asks for reach the host.  Synchronises t's current stream first; `ctx` (an api._Ctx of t's device) is reused if given."""
+    _check(t, "t")
+    n = t.numel()
+    if n == 0:
+        raise api.BceError(-1, "count_classes_tensor", "empty input")
+    if n > _MAX_BLOCK:
+        raise ValueError("one index covers one text of less than 2^31 bytes, not %d" % n)
+    _ready(t)
+    own = ctx is None
+    c = ctx or api._Ctx(t.device.index)
+    try:
+        return api.RankFile(n=n, device_ptr=t.data_ptr(), ctx=c).count_classes(patterns, cyclic=cyclic, max_nodes=max_nodes, ignore_case=ignore_case)
+    finally:
+        if own:
+            c.close()
+
+
+def count_classes_in_archive(blob, patterns, cyclic=False, max_nodes=None, ignore_case=False, device="cuda:0"):
+    """count_classes_tensor on what an archive holds, decoded as count_in_archive decodes it: hits across block boundaries included."""
+    total = sum(t[0] for t in _blocks_of(blob))
+    if total > _MAX_BLOCK:
+        raise ValueError("the archive holds %d bytes: one index covers one text of less than 2^31" % total)
+    return count_classes_tensor(decompress_container_tensor(blob, device=device), patterns, cyclic=cyclic, max_nodes=max_nodes, ignore_case=ignore_case)
+
+
+def locate_classes_tensor(t, patterns, cyclic=False, max_nodes=None, ignore_case=False, ctx=None):
+    """Where patterns of byte classes occur in the 1-D uint8 CUDA tensor `t` (or slice, any offset) -> (offsets, positions, over),
+    all tensors on t's device: int64[npat + 1], int32[total] and bool[npat].  Pattern p owns positions[offsets[p]:offsets[p + 1]],
+    ascending byte offsets into t; over[p]: its search ran out of `max_nodes` and it has none.  Patterns, cyclic, max_nodes and
+    ignore_case: as api.RankFile.locate_classes.  Searched, gathered and ordered on the device (bce_hip_locate_classes_device, a
+    sizing call first); of the answer only its total reaches the host.
+    Synchronises t's current stream first; `ctx` (an api._Ctx of t's device) is reused if given."""
+    _check(t, "t")
+    n = t.numel()
+    if n == 0:
+        raise api.BceError(-1, "locate_classes_tensor", "empty input")
+    if n > _MAX_BLOCK:
+        raise ValueError("one index covers one text of less than 2^31 bytes, not %d" % n)
+    own = ctx is None
+    c = ctx or api._Ctx(t.device.index)
+    try:
+        _ready(t)
+        rf = api.RankFile(n=n, device_ptr=t.data_ptr(), ctx=c)
+        _, pats, flat, lens, _ = rf._class_args(patterns, cyclic, max_nodes, ignore_case, "hits")
+        offsets = torch.zeros(len(pats) + 1, dtype=torch.int64, device=t.device)
+        status = torch.zeros(len(pats), dtype=torch.int32, device=t.device)
+        if not pats:
+            return offsets, torch.empty(0, dtype=torch.int32, device=t.device), status != 0
+        d_mask, d_off = torch.from_numpy(flat.view(np.int32)).to(t.device), torch.from_numpy(lens.astype(np.int64)).to(t.device)
+        torch.cuda.current_stream(t.device).synchronize()
+        args = (d_mask.data_ptr(), d_off.data_ptr(), len(pats), offsets.data_ptr(), status.data_ptr())
+        total = rf.locate_classes_device(*args, None, 0, cyclic=cyclic, max_nodes=max_nodes)
+        positions = torch.empty(total, dtype=torch.int32, device=t.device)
+        if total:
+            torch.cuda.current_stream(t.device).synchronize()        # (the allocator may hand out memory a queued kernel still uses)
+            rf.locate_classes_device(*args, positions.data_ptr(), total, cyclic=cyclic, max_nodes=max_nodes)
+        return offsets, positions, status != 0
+    finally:
+        if own:
+            c.close()
+
+
+def locate_classes_in_archive(blob, patterns, cyclic=False, max_nodes=None, ignore_case=False, device="cuda:0"):
+    """locate_classes_tensor on what an archive holds, decoded as count_in_archive decodes it -> (offsets, positions, over) on `device`."""
+    total = sum(t[0] for t in _blocks_of(blob))
+    if total > _MAX_BLOCK:
+        raise ValueError("the archive holds %d bytes: one index covers one text of less than 2^31" % total)
+    return locate_classes_tensor(decompress_container_tensor(blob, device=device), patterns, cyclic=cyclic, max_nodes=max_nodes, ignore_case=ignore_case)
+
+
 def _match_args(t, query, what):
     _check(t, "t")
     _check(query, "query")

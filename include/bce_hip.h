@@ -367,6 +367,55 @@ int bce_hip_locate_near(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_
 int bce_hip_locate_near_device(bce_hip_ctx *ctx, const void *d_patterns, const void *d_offsets, uint32_t npat, uint32_t k, uint32_t flags,
                                void *d_hit_offsets, void *d_positions, void *d_dists, uint64_t cap, uint64_t *total);
 
+/* ---- extension: the same two questions for patterns of byte CLASSES (kd_classes.hip, class_step.h) ------------------------------
+ * T: the indexed text, n bytes, read circularly.  A pattern P is m classes S_0 .. S_(m-1); every class is a set of bytes: a wildcard,
+ * a range, both cases of a letter, one byte.
+ *   layout: a class is 256 bits in 8 uint32_t words; byte c is in S iff bit c & 31 of word c >> 5 is set.  masks holds
+ *     8 * offsets[npat] words; offsets has npat + 1 entries counted in CLASSES, as the other batch calls count bytes.
+ *   cyclic hits: the i in [0, n) with T[(i + j) mod n] in S_j for all j < m.  m == 0 matches all n positions; an empty class
+ *     matches nothing; m > n wraps as it does for bce_hip_count.
+ *   linear hits (BCE_HIP_LOCATE_LINEAR): those with i + m <= n, what a sliding window over the text finds; none for m > n.
+ * The search is backward search that branches at every class of two members or more (a WIDE class): two different strings of one
+ * length own disjoint row intervals, so the hits are the disjoint union of the intervals of the strings of P's language that occur.
+ * The WORK of a pattern is fixed by the text and the pattern, not by the order of the walk:
+ *   nodes(P) = #{ (j, s) : 1 <= j <= m, s a string of j bytes with s[t] in S_(m-j+t) for all t, s occurs in the circular text },
+ * the non-root nodes of the right-to-left search tree that have rows.  `.{8}` asks for every distinct 8-gram of the text: so every
+ * call takes a BUDGET, max_nodes per pattern (0: BCE_HIP_CLASS_DEFAULT_NODES; above BCE_HIP_CLASS_MAX_NODES: BCE_HIP_E_ARG).  Both are
+ * 2^16: a batch of 4096 patterns that all exhaust that budget was measured at 0.9 to 1.1 s on an MI355X, four times the budget at
+ * four times that -- the cap keeps one call on a shared machine at about a second, and the default cannot exceed it.
+ * Both values are PROVISIONAL: they follow the walk's measured cost per node and rise when that falls.
+ *   nodes(P) <= max_nodes: status[p] = 0, work[p] = nodes(P) exactly, the answer is complete.
+ *   otherwise: status[p] = BCE_HIP_CLASS_OVER, the count is 0 and the locate's segment empty, work[p] is some value > max_nodes.
+ *     The walk stops within one frame's expansion and one finish chain of crossing the budget -- at most 256 m further steps;
+ *     it never walks the whole tree first.  One pattern over budget fails neither the call nor the other patterns.
+ * WORK bounds, as BCE_HIP_NEAR_MAX_LEN: m <= BCE_HIP_CLASS_MAX_LEN classes, of which at most BCE_HIP_CLASS_MAX_WIDE are wide (the
+ * only ones that need a frame of the walk's stack); more, or offsets that decrease: BCE_HIP_E_ARG, found by the kernel in both forms
+ * of the calls (after it has run; the outputs are then undefined).
+ * bce_hip_count_classes: counts[p] = the cyclic hits of pattern p.  Cyclic only, as bce_hip_count (the linear correction is the
+ * caller's, from the text's two ends: bce_amd/api.py: class_linear_counts).  work may be NULL.  State, order of the checks and
+ * npat == 0 as bce_hip_count, with max_nodes judged beside ctx.  A pattern of one-member classes gives bce_hip_count's count.
+ * bce_hip_locate_classes: bce_hip_locate's protocol word for word -- the CSR answer (positions ascending within each pattern), the
+ * sizing call (positions NULL, cap 0), BCE_HIP_E_OVERFLOW with exact hit_offsets and *total when total > cap or the batch's cyclic
+ * rows exceed 2^31 - 1, the validity (planes AND suffix array; BCE_HIP_E_STATE after bce_hip_set_bwt), the order of the checks
+ * (max_nodes beside the flags), no change to the compression state -- plus status[p], written whenever hit_offsets is.  A pattern
+ * of one-member classes gives bce_hip_locate's positions. */
+#define BCE_HIP_CLASS_MAX_LEN 4096u
+#define BCE_HIP_CLASS_MAX_WIDE 64u
+#define BCE_HIP_CLASS_DEFAULT_NODES (1u << 16)
+#define BCE_HIP_CLASS_MAX_NODES (1u << 16)
+#define BCE_HIP_CLASS_OVER 1u
+int bce_hip_count_classes(bce_hip_ctx *ctx, const uint32_t *masks, const uint64_t *offsets, uint32_t npat, uint32_t max_nodes, uint64_t *counts,
+                          uint64_t *work, uint32_t *status);
+/* The same with every array in device memory of the context's device (d_work may be NULL).  Stream rule: as bce_hip_count_device. */
+int bce_hip_count_classes_device(bce_hip_ctx *ctx, const void *d_masks, const void *d_offsets, uint32_t npat, uint32_t max_nodes, void *d_counts,
+                                 void *d_work, void *d_status);
+int bce_hip_locate_classes(bce_hip_ctx *ctx, const uint32_t *masks, const uint64_t *offsets, uint32_t npat, uint32_t max_nodes, uint32_t flags,
+                           uint64_t *hit_offsets, uint32_t *status, uint32_t *positions, uint64_t cap, uint64_t *total);
+/* The same with masks, offsets, hit offsets, verdicts and positions in device memory of the context's device; total stays a host
+ * pointer.  Stream rule: as bce_hip_count_device. */
+int bce_hip_locate_classes_device(bce_hip_ctx *ctx, const void *d_masks, const void *d_offsets, uint32_t npat, uint32_t max_nodes, uint32_t flags,
+                                  void *d_hit_offsets, void *d_status, void *d_positions, uint64_t cap, uint64_t *total);
+
 /* ---- extension: the longest matches of a SECOND buffer in the input (kd_match.hip, fm_step.h) -----------------------------------
  * The matching statistics of a query Q (q bytes, 1 <= q <= 2^31 - 1) against the text T (the n bytes the context indexed).  For
  * every END position i in [0, q):
