@@ -102,6 +102,7 @@ SYMBOLS = [
     ("bce_hip_model_begin", C.c_int, [C.c_void_p]),
     ("bce_hip_model_flush", C.c_int, [C.c_void_p, _u32p, _u32p, C.c_uint64, _vp, C.POINTER(C.c_uint32)]),
     ("bce_hip_scan", C.c_int, [C.c_void_p, _u8p, C.POINTER(C.c_double)]),
+    ("bce_hip_scan_records", C.c_int, [C.c_void_p, _u32p, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("bce_hip_decompress", C.c_int, [_u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("bce_hip_decompress_device", C.c_int, [C.c_void_p, _u8p, C.c_size_t, _u8p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("bce_hip_decompress_to_device", C.c_int, [C.c_void_p, _u8p, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -1226,16 +1226,15 @@ static int compress_early(bce_hip_ctx *c) {
 // `bce -s`: BCE<ScanCoder<31>, unbwt::noop>::encode + save_config (bce.cpp:1384-1402, 726-834).  The enumeration
 // runs on the GPU in scan mode (raw symbol tuples instead of model records); the eight ScanCoders consume them on
 // the host in stream order, then pick the context bits.
-static int scan_body(bce_hip_ctx *c, uint8_t *config288, double *result_bytes);
-int bce_hip_scan(bce_hip_ctx *c, uint8_t config288[BCE_HIP_CONFIG_BYTES], double result_bytes[9]) {
-  const int r = bce_guarded(c, [&] { return scan_body(c, config288, result_bytes); });
-  if (c) gate_release(c);                        // (-s keeps the gate to its end: its host part is short)
-  return r;
-}
-static int scan_body(bce_hip_ctx *c, uint8_t *config288, double *result_bytes) {
+// One body, two sinks: `take(records, spans)` gets every flush's words -- the ScanSet of bce_hip_scan, or the plain per-plane
+// streams of the test hook bce_hip_scan_records -- and `finish(times)` runs once the enumeration is through.
+struct ScanTimes { double begin = 0, pin = 0, copy = 0, record = 0; };
+extern "C++" template <class Take, class Finish>
+static int scan_body(bce_hip_ctx *c, bool args_ok, Take &&take, Finish &&finish) {
   BCE_TRY(check_stage(c, 3));
-  if (!config288) return BCE_HIP_E_ARG;
-  const double t_begin = now_s();
+  if (!args_ok) return BCE_HIP_E_ARG;
+  ScanTimes t;
+  t.begin = now_s();
   gate_acquire(c);
   BCE_HIP_TRY(c, hipSetDevice(c->device));
   c->coder->drain();
@@ -1245,7 +1244,6 @@ static int scan_body(bce_hip_ctx *c, uint8_t *config288, double *result_bytes) {
   BCE_TRY(k4_prepare(c));
   BCE_TRY(k3_begin(c));
   c->stats.t_coder = 0;
-  ScanSet coders;                                          // planes 0-7 + the header coder, on a pool of host threads
   // the records come over through pinned memory (a copy into a fresh std::vector ran at a fifth of the bus)
   struct PinnedWords {
     uint32_t *p = nullptr; size_t cap = 0;
@@ -1258,23 +1256,22 @@ static int scan_body(bce_hip_ctx *c, uint8_t *config288, double *result_bytes) {
       return 0;
     }
   } host;
-  double t_copy = 0, t_record = 0, t_pin = 0;
   auto consume = [&](uint64_t nsym) -> int {
     if (nsym) {
       const double tp0 = now_s();
       if (host.ensure((size_t)nsym > (size_t)c->sym_cap ? (size_t)nsym : (size_t)c->sym_cap)) return BCE_HIP_E_NOMEM;
       const double tc0 = now_s();
-      t_pin += tc0 - tp0;
+      t.pin += tc0 - tp0;
       BCE_HIP_TRY(c, hipMemcpyAsync(host.p, c->scanrec.p, (size_t)nsym * 4, hipMemcpyDeviceToHost, c->stream));
       BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
-      t_copy += now_s() - tc0;
+      t.copy += now_s() - tc0;
       std::vector<ScanSpan> spans[8];
       for (int p = 0; p < 8; ++p)
         for (const RunEntry &e : c->run_log[p]) spans[p].push_back(ScanSpan{e.start, e.count});
       const double t0 = now_s();
-      coders.consume(host.p, spans);
+      take(host.p, spans);
       c->stats.t_coder += now_s() - t0;
-      t_record += now_s() - t0;
+      t.record += now_s() - t0;
     }
     return k3_reset_symbols(c);
   };
@@ -1284,25 +1281,61 @@ static int scan_body(bce_hip_ctx *c, uint8_t *config288, double *result_bytes) {
   c->stats.rounds = e.ctl.done_round;
   c->stats.nodes = e.ctl.nodes_total;
   c->enum_active = false;
-  uint8_t init[9][32];
-  memset(init, 0, sizeof init);                            // ScanCoder::init_ is a zero-initialised static (:834)
-  double res[9];
-  const double tf0 = now_s();
-  coders.flush(init, res);                                 // coder_[i].flush() :1135-1138, then main(-1).flush() :1141-1149
-  c->stats.t_coder += now_s() - tf0;
-  if (getenv("BCE_HIP_SCAN_DEBUG"))
-    fprintf(stderr, "scan: %llu symbols in %llu batches: pinned buffer %.3f s, device-to-host copies %.3f s, recording %.3f s, optimisation %.3f s on %u host threads; K3 %.1f ms; %.3f s since entry\n",
-            (unsigned long long)c->stats.symbols, (unsigned long long)c->stats.flushes, t_pin, t_copy, t_record, now_s() - tf0, coders.threads(), c->stats.k3_ms, now_s() - t_begin);
-  if (result_bytes) memcpy(result_bytes, res, sizeof res);
-  memcpy(config288, init, BCE_HIP_CONFIG_BYTES);
+  const int rc = finish(t);
   if (getenv("BCE_HIP_SCAN_DEBUG")) {
-    const double t0 = now_s();
-    coders.release();
     const double t1 = now_s();
-    host.ensure(0); if (host.p) { (void)hipHostFree(host.p); host.p = nullptr; host.cap = 0; }
-    fprintf(stderr, "scan: giving back the recorded streams %.3f s, the pinned buffer %.3f s\n", t1 - t0, now_s() - t1);
+    if (host.p) { (void)hipHostFree(host.p); host.p = nullptr; host.cap = 0; }
+    fprintf(stderr, "scan: giving back the pinned buffer %.3f s\n", now_s() - t1);
   }
-  return BCE_HIP_OK;
+  return rc;
+}
+int bce_hip_scan(bce_hip_ctx *c, uint8_t config288[BCE_HIP_CONFIG_BYTES], double result_bytes[9]) {
+  const int r = bce_guarded(c, [&] {
+    ScanSet coders;                                          // planes 0-7 + the header coder, on a pool of host threads
+    return scan_body(c, config288 != nullptr,
+      [&](const uint32_t *records, const std::vector<ScanSpan> spans[8]) { coders.consume(records, spans); },
+      [&](const ScanTimes &t) -> int {
+        uint8_t init[9][32];
+        memset(init, 0, sizeof init);                        // ScanCoder::init_ is a zero-initialised static (:834)
+        double res[9];
+        const double tf0 = now_s();
+        coders.flush(init, res);                             // coder_[i].flush() :1135-1138, then main(-1).flush() :1141-1149
+        c->stats.t_coder += now_s() - tf0;
+        if (getenv("BCE_HIP_SCAN_DEBUG"))
+          fprintf(stderr, "scan: %llu symbols in %llu batches: pinned buffer %.3f s, device-to-host copies %.3f s, recording %.3f s, optimisation %.3f s on %u host threads; K3 %.1f ms; %.3f s since entry\n",
+                  (unsigned long long)c->stats.symbols, (unsigned long long)c->stats.flushes, t.pin, t.copy, t.record, now_s() - tf0, coders.threads(), c->stats.k3_ms, now_s() - t.begin);
+        if (result_bytes) memcpy(result_bytes, res, sizeof res);
+        memcpy(config288, init, BCE_HIP_CONFIG_BYTES);
+        if (getenv("BCE_HIP_SCAN_DEBUG")) {
+          const double t0 = now_s();
+          coders.release();
+          fprintf(stderr, "scan: giving back the recorded streams %.3f s\n", now_s() - t0);
+        }
+        return BCE_HIP_OK;
+      });
+  });
+  if (c) gate_release(c);                        // (-s keeps the gate to its end: its host part is short)
+  return r;
+}
+// Test hook: the words themselves.  The sink keeps plane p's spans of every flush, in order, as plane p's stream.
+int bce_hip_scan_records(bce_hip_ctx *c, uint32_t *out, uint64_t cap_words, uint64_t counts[8]) {
+  const int r = bce_guarded(c, [&] {
+    std::vector<uint32_t> stream[8];
+    return scan_body(c, counts != nullptr && (out != nullptr || cap_words == 0),
+      [&](const uint32_t *records, const std::vector<ScanSpan> spans[8]) {
+        for (int p = 0; p < 8; ++p)
+          for (const ScanSpan &s : spans[p]) stream[p].insert(stream[p].end(), records + s.start, records + s.start + s.count);
+      },
+      [&](const ScanTimes &) -> int {
+        uint64_t total = 0;
+        for (int p = 0; p < 8; ++p) { counts[p] = stream[p].size(); total += counts[p]; }
+        if (total > cap_words) return BCE_HIP_E_OVERFLOW;
+        for (int p = 0; p < 8; ++p) { if (counts[p]) memcpy(out, stream[p].data(), counts[p] * 4); out += counts[p]; }
+        return BCE_HIP_OK;
+      });
+  });
+  if (c) gate_release(c);
+  return r;
 }
 
 int bce_hip_set_plane_mask(bce_hip_ctx *c, uint32_t mask) {

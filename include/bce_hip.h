@@ -222,6 +222,15 @@ int bce_hip_model_flush(bce_hip_ctx *ctx, const uint32_t *key_words, const uint3
  * their cost optimisation on the host.  config288 = the .bcc file content; result_bytes[9] (optional) = the values
  * of the nine "Result size: %.1f B" lines (bce.cpp:799). */
 int bce_hip_scan(bce_hip_ctx *ctx, uint8_t config288[BCE_HIP_CONFIG_BYTES], double result_bytes[9]);
+/* Test hook (tests/test_gpu_scan_routes.py): bce_hip_scan with the ScanCoders left out -- the same body (stage check, gate, scan
+ * mode, enumeration, the per-flush copy and its spans) hands every flush's words to a plain sink instead.  Each word is one
+ * symbol as bce_core.h's scan_pack lays it out: [4:0] sym, [9:5] k (2..31), [17:10] (c1 << 8) / cs, [25:18] (c2 << 8) / cs,
+ * [30:26] k > 31 escapes.  Stream p = plane p's spans of every flush, in order: what ScanCoder p is fed.  counts[p] = the words of
+ * stream p; out receives the streams of planes 0..7 back to back.  Their sum above cap_words: BCE_HIP_E_OVERFLOW with counts
+ * filled and out untouched (out may be NULL with cap_words == 0: a sizing call, which runs the enumeration all the same).
+ * bce_hip_stats afterwards reads as after bce_hip_scan.  Before bce_hip_build_planes: BCE_HIP_E_STATE; then a null counts, or a
+ * null out with cap_words > 0: BCE_HIP_E_ARG. */
+int bce_hip_scan_records(bce_hip_ctx *ctx, uint32_t *out, uint64_t cap_words, uint64_t counts[8]);
 
 /* ---- decoder (SURVEY section 8f "next #1"): bce_hip_decompress = plain host C++ (`bce -ds`),
  *      bce_hip_decompress_device = the GPU-assisted decoder of kd_decode.hip (`bce -d`); same bytes.

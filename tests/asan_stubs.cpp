@@ -17,6 +17,7 @@ int bce_hip_load_host(bce_hip_ctx *, const uint8_t *, uint32_t) { return BCE_HIP
 int bce_hip_bwt(bce_hip_ctx *, uint32_t *) { return BCE_HIP_E_DEVICE; }
 int bce_hip_build_planes(bce_hip_ctx *, uint32_t *) { return BCE_HIP_E_DEVICE; }
 int bce_hip_scan(bce_hip_ctx *, uint8_t *, double *) { return BCE_HIP_E_DEVICE; }
+int bce_hip_scan_records(bce_hip_ctx *, uint32_t *, uint64_t, uint64_t *) { return BCE_HIP_E_DEVICE; }
 int bce_hip_compress(bce_hip_ctx *, const uint8_t *, uint32_t, uint8_t *, size_t, size_t *) { return BCE_HIP_E_DEVICE; }
 int bce_hip_archive_copy(bce_hip_ctx *, uint8_t *, size_t) { return BCE_HIP_E_DEVICE; }
 int bce_hip_decompress_device(bce_hip_ctx *, const uint8_t *, size_t, uint8_t *, size_t, size_t *) { return BCE_HIP_E_DEVICE; }

@@ -219,6 +219,12 @@ extern "C" int emul_scan(const uint32_t *syms6, size_t nsym, unsigned threads, u
   return 0;
 }
 
+// bce_core.h's scan_pack on trace rows (plane, s, k, c1, c2, cs): out[i] = the word the scan-mode kernels write for row i
+// (tests/scanrec_ref.py restates it in numpy).
+extern "C" void emul_scan_pack(const uint32_t *syms6, size_t n, uint32_t *out) {
+  for (size_t i = 0; i < n; ++i) { const uint32_t *r = syms6 + 6 * i; out[i] = scan_pack(r[1], r[2], r[3], r[4], r[5]); }
+}
+
 // scan_add_repeated against the loop it replaces
 extern "C" int emul_add_repeated(double z, double c, uint64_t m, double *fast, double *slow) {
   *fast = bce::scan_add_repeated(z, c, m);

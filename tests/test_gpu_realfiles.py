@@ -66,9 +66,10 @@ def test_real_file_scan_then_compress_matches_oracle():
     data = _python_sources(1 << 20)
     if len(data) < 1000:
         pytest.skip("input files not present in this image")
-    cfg_want, _ = oracle.scan(data)
-    cfg_got, _ = bce_amd.scan(data)
+    cfg_want, res_want = oracle.scan(data)
+    cfg_got, res_got = bce_amd.scan(data)
     assert bytes(cfg_got) == bytes(cfg_want)
+    assert list(res_got) == list(res_want)                   # the nine "Result size" doubles: same additions in the same order
     want = oracle.compress(data, bytes(cfg_want))
     got = bce_amd.compress(data, bytes(cfg_got))
     assert got == want

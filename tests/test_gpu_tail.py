@@ -7,14 +7,9 @@ import pytest
 
 import bce_amd
 import oracle
+from scanrec_ref import STAIRCASE_CASES, _region, _spine_input, many_copies, repeat_input, staircase_input   # (the builders: shared with the scan-mode tests)
 
 pytestmark = pytest.mark.gpu
-
-
-def repeat_input(n, rep, seed=21):
-    base = oracle.synth_text(seed, n)
-    chunk = base[1000:1000 + rep]
-    return base[:n // 2] + chunk + base[n // 2:]
 
 
 @pytest.mark.parametrize("n,rep", [(200000, 3000), (1 << 20, 20000)])
@@ -97,16 +92,6 @@ def test_exactly_periodic_input_with_a_large_period():
     print("exactly periodic input: encode %.2f s" % dt)
 
 
-def many_copies(copies, length, seed):
-    """`copies` copies of one block, each followed by a different separator: chains of `copies` rows."""
-    block = oracle.synth_text(seed, length)
-    out = bytearray(oracle.synth_text(seed + 1, 20000))
-    for i in range(copies):
-        out += block + b"<%06d>" % (i * 7919 % 1000003)
-    out += oracle.synth_text(seed + 2, 20000)
-    return bytes(out)
-
-
 @pytest.mark.parametrize("copies,length", [(40, 3000), (150, 600), (9, 200), (700, 40), (3, 70000)])
 def test_many_row_chains_match_oracle(copies, length):
     """Chains of many rows: the skip compares all rows (one lane per row for the near bytes, then the whole wave
@@ -130,51 +115,11 @@ def test_periodic_blocks_with_many_rows():
         assert arch == want, "knobs %r" % (knobs,)
 
 
-def _region(unit, length):
-    return (unit * (length // len(unit) + 1))[:length]
-
-
-@pytest.mark.parametrize("case", ["zeros", "ff", "period2", "period3", "period7-in-random", "two-regions", "at-start", "at-end",
-                                  "record-table", "period2-twice", "three-regions-phases", "many-zero-runs", "same-length-twice",
-                                  "whole-text-periodic", "two-tables-first-at-start"])
+@pytest.mark.parametrize("case", STAIRCASE_CASES)
 def test_staircase_chains_match_oracle(case):
     """Long runs of one byte and periodic tables (executables): chains whose rows are equally spaced text positions.
     The walkers expand them analytically (stair_run); every other path must give the same archive."""
-    import numpy as np
-    rs = np.random.RandomState(5)
-    text = oracle.synth_text(91, 60000)
-    rnd = rs.randint(0, 256, 60000).astype(np.uint8).tobytes()
-    if case == "zeros":
-        data = text[:30000] + bytes(9000) + text[30000:]
-    elif case == "ff":
-        data = text[:30000] + b"\xff" * 7000 + text[30000:] + b"\xff" * 100 + b"z"
-    elif case == "period2":
-        data = text[:20000] + _region(b"\x00\x02", 12001) + text[20000:]
-    elif case == "period3":
-        data = rnd[:20000] + _region(b"abc", 10000) + text[:20000] + _region(b"cab", 500) + rnd[20000:40000]
-    elif case == "period7-in-random":
-        data = rnd[:30000] + _region(b"\x01\x00\x00\x00\x00\x00\x80", 15000) + rnd[30000:]
-    elif case == "two-regions":     # the same pattern twice: the node is a staircase only below the shorter one
-        data = text[:20000] + bytes(6000) + text[20000:40000] + bytes(4000) + b"\x01" + bytes(300) + text[40000:]
-    elif case == "at-start":        # the region reaches position 0: the walkers must not take the shortcut blindly
-        data = bytes(5000) + text + _region(b"\x00\x07", 3000) + b"q"
-    elif case == "at-end":
-        data = text + _region(b"xy", 8000)
-    elif case == "period2-twice":   # the same table in two places, same bytes before it: two rows leave together
-        data = text[:20000] + b"\x00\x00" + _region(b"\x00\x02", 9001) + b"\x01" + text[20000:40000] + b"\x00\x00" + _region(b"\x00\x02", 7000) + text[40000:]
-    elif case == "three-regions-phases":   # three places, different phases at the start and different bytes before
-        data = (rnd[:10000] + b"Q" + _region(b"abc", 6000) + rnd[10000:20000] + b"R" + _region(b"bca", 5000) + b"a" + text[:20000] +
-                b"Q" + _region(b"cab", 4001) + b"\xff" + rnd[20000:30000])
-    elif case == "many-zero-runs":  # more regions than the closed form takes at once: the walkers take over until few are left
-        data = b"".join(text[i * 3000:(i + 1) * 3000] + bytes(300 * (i + 1) + (i % 3)) for i in range(14)) + text[42000:]
-    elif case == "whole-text-periodic":   # the region IS the text up to its last byte: it starts at position 0, where the
-        data = b"ab" * 30000 + b"c"          # byte "before" is the last one (rotations)
-    elif case == "two-tables-first-at-start":
-        data = _region(b"\x00\x00\x01", 20000) + text[:30000] + b"\x07" + _region(b"\x00\x01\x00", 14000) + text[30000:]
-    elif case == "same-length-twice":
-        data = text[:20000] + b"A" + bytes(5000) + b"B" + text[20000:40000] + b"A" + bytes(5000) + b"C" + text[40000:]
-    else:                           # 16-byte records that differ in one counter byte, then identical ones
-        data = text[:10000] + b"".join(b"REC" + bytes([i & 255]) + bytes(12) for i in range(300)) + (b"REC\x00" + bytes(12)) * 400 + text[10000:]
+    data = staircase_input(case)
     want = oracle.compress(data)
     for knobs in ({}, {3: 1}, {0: 9}, {1: 1}):
         arch, st = _encode_with_knobs(data, knobs)
@@ -273,28 +218,6 @@ def test_model_flushes_beside_the_rounds_with_many_small_flushes():
 
 
 # ---- spine bursts (k3_dfs.hip): chains of many rows that lose a few rows per byte ---------------------------------------
-def _spine_input(kind, seed=5):
-    import numpy as np
-    rng = np.random.RandomState(seed)
-    text = oracle.synth_text(70 + seed, 120000)
-    if kind == "zero-runs":            # runs of zeros of hundreds of different lengths between random bytes: the all-zero context keeps
-        parts = []                     # thousands of rows for thousands of bytes, a few runs end at every length
-        for _ in range(1500):
-            parts.append(rng.bytes(int(rng.randint(1, 24))))
-            parts.append(bytes(int(rng.randint(1, 3000))))
-        return text[:60000] + b"".join(parts) + text[60000:]
-    if kind == "equal-runs":           # hundreds of runs of the SAME length: the first rows of the chain all leave at once
-        return text[:50000] + b"".join(rng.bytes(3) + bytes(2048) for _ in range(300)) + text[50000:] + b"".join(
-            rng.bytes(5) + bytes(int(rng.randint(1500, 2500))) for _ in range(200))
-    if kind == "u16-ramps":            # little-endian 16-bit arrays with small values: the context alternates between two bytes
-        arrs = [np.minimum(rng.geometric(0.2, int(rng.randint(200, 4000))), 200).astype("<u2").tobytes() for _ in range(300)]
-        return text[:30000] + b"".join(a + rng.bytes(2) for a in arrs) + text[30000:]
-    if kind == "records":              # records of 12 bytes whose last 9 are constant, in tables of many lengths
-        recs = [b"".join(rng.bytes(3) + b"\x00\x00\x00\x01\x00\x00\x00\xff\x10" for _ in range(int(rng.randint(50, 1500)))) for _ in range(200)]
-        return text[:40000] + b"".join(r + rng.bytes(int(rng.randint(1, 9))) for r in recs) + text[40000:]
-    raise ValueError(kind)
-
-
 @pytest.mark.parametrize("kind", ["zero-runs", "equal-runs", "u16-ramps", "records"])
 def test_spine_bursts_match_oracle(kind, monkeypatch):
     data = _spine_input(kind)
