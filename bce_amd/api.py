@@ -57,6 +57,15 @@ class ParseInfo(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class MaxRepInfo(C.Structure):
+    """bce_hip_maxrep_info: what a list of maximal repeats comes with (RankFile.maximal_repeats): `total` repeats of min_len bytes or
+    more, `capped` of them at the bound, the runs of the BWT, and the entries written."""
+    _fields_ = [("total", C.c_uint64), ("capped", C.c_uint64), ("bwt_runs", C.c_uint64), ("found", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
 class Op(C.Structure):
     """bce_hip_op: src == OP_LITERAL: the next len bytes of the literal stream; else text[src : src + len]."""
     _fields_ = [("len", C.c_uint32), ("src", C.c_uint32)]
@@ -149,6 +158,9 @@ SYMBOLS = [
     ("bce_hip_longest_repeat", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("bce_hip_top_kgrams", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _vp]),
     ("bce_hip_top_kgrams_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _vp]),
+    ("bce_hip_maximal_repeats", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint64, C.POINTER(MaxRepInfo)]),
+    ("bce_hip_maximal_repeats_device", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint64, C.POINTER(MaxRepInfo)]),
+    ("bce_hip_maxrep_of_arrays_device", C.c_int, [C.c_void_p, _vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.POINTER(MaxRepInfo)]),
     ("bce_hip_parse", C.c_int, [C.c_void_p, _u8p, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _u8p, C.c_uint64, C.POINTER(ParseInfo)]),
     ("bce_hip_parse_device", C.c_int, [C.c_void_p, _vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_uint64, _vp, C.c_uint64, C.POINTER(ParseInfo)]),
     ("bce_hip_patch", C.c_int, [C.c_void_p, _vp, C.c_uint64, _u8p, C.c_uint64, _u8p, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -216,6 +228,9 @@ MATCH_MAX_LEN = 4096                            # BCE_HIP_MATCH_MAX_LEN: a work 
 KGRAMS_MAX = 64                                 # BCE_HIP_KGRAMS_MAX: values of k in one bce_hip_kgrams call
 TOP_MAX = 1 << 20                               # BCE_HIP_TOP_MAX: the longest list of one bce_hip_top_kgrams call
 TOP_DTYPE = np.dtype([("count", "<u4"), ("row", "<u4"), ("pos", "<u4")])   # bce_hip_top_kgram as a numpy record
+MAXREP_DTYPE = np.dtype([("len", "<u4"), ("count", "<u4"), ("row", "<u4"), ("pos", "<u4")])   # bce_hip_maxrep as a numpy record
+MAXREP_ORDERS = {"len": 0, "count": 1, "gain": 2}   # BCE_HIP_MAXREP_BY_LEN / _BY_COUNT / _BY_GAIN
+MAXREP_BYTES_MAX = 4096                         # the most bytes of one repeat a call hands out
 E_OVERFLOW = -5                                 # BCE_HIP_E_OVERFLOW
 OP_LITERAL = 0xFFFFFFFF                         # BCE_HIP_OP_LITERAL: bce_hip_op::src of a literal run
 PARSE_MAX_LEN = 256                             # the default length bound of a parse: the search costs up to q * max_len lane steps
@@ -444,6 +459,18 @@ def _top_limit(k, limit):
     if limit < 0 or limit > 0xFFFFFFFF:
         raise ValueError("limit is 1 .. %d" % TOP_MAX)
     return k, limit
+
+
+def _maxrep_args(min_len, max_len, order, limit, bytes_per):
+    """The arguments of a maximal_repeats call as the library takes them (`order` a name of MAXREP_ORDERS or its number)."""
+    if isinstance(order, str):
+        if order not in MAXREP_ORDERS:
+            raise ValueError("order is one of %s" % ", ".join(sorted(MAXREP_ORDERS)))
+        order = MAXREP_ORDERS[order]
+    vals = [int(min_len), int(max_len), int(order), int(limit), int(bytes_per)]
+    if any(v < 0 or v > 0xFFFFFFFF for v in vals):
+        raise ValueError("min_len, max_len, order, limit and bytes_per are unsigned 32-bit numbers")
+    return vals
 
 
 def entropy_from_sums(n, s_k, s_k1) -> float:
@@ -911,6 +938,35 @@ class RankFile:
                                                             None if bytes_ptr is None else int(bytes_ptr), int(bytes_cap), C.byref(found), C.byref(distinct),
                                                             C.addressof(hist)), "bce_hip_top_kgrams_device")
         return found.value, distinct.value, [int(v) for v in hist]
+
+    def maximal_repeats(self, min_len=1, max_len=MATCH_MAX_LEN, order="len", limit=100, bytes_per=64):
+        """The maximal repeats of the circular text (bce_hip_maximal_repeats: found, weighed, selected, sorted and gathered on the
+        GPU): the strings of min_len bytes or more that occur twice or more and can be extended neither to the right nor to the left
+        without losing an occurrence -> (entries, strings, info).  entries: a numpy record array (len, count, row, pos), heaviest
+        first -- order "len": longest first, the most frequent among equal lengths; "count": most frequent first; "gain":
+        len * (count - 1) -- and equal weights in row order; len == max_len means "max_len bytes or more".  strings: the first
+        min(len, bytes_per) bytes of every entry (None with bytes_per=0).  info: a dict (total, capped, bwt_runs, found)."""
+        min_len, max_len, order, limit, bytes_per = _maxrep_args(min_len, max_len, order, limit, bytes_per)
+        sound = 1 <= limit <= TOP_MAX and bytes_per <= MAXREP_BYTES_MAX  # (otherwise the library refuses: no room is made)
+        out = np.zeros(limit if sound else 1, dtype=MAXREP_DTYPE)
+        raw = np.zeros(max(1, limit * bytes_per) if sound else 1, dtype=np.uint8) if bytes_per else None
+        info = MaxRepInfo()
+        self._c.check(self._c.lib.bce_hip_maximal_repeats(self._c.h, min_len, max_len, order, limit, out.ctypes.data, raw.ctypes.data if bytes_per else None,
+                                                          bytes_per, limit * bytes_per if bytes_per else 0, C.byref(info)), "bce_hip_maximal_repeats")
+        ents = out[:info.found].copy()
+        strs = [raw[i * bytes_per:i * bytes_per + min(int(e["len"]), bytes_per)].tobytes() for i, e in enumerate(ents)] if bytes_per else None
+        return ents, strs, info.as_dict()
+
+    def maximal_repeats_device(self, min_len, max_len, order, limit, out_ptr, bytes_ptr=None, bytes_per=0, bytes_cap=0):
+        """bce_hip_maximal_repeats_device: the same into device memory (int pointers: room for `limit` entries of four uint32 -- len,
+        count, row, pos -- and, unless bytes_ptr is None, for bytes_cap >= limit * bytes_per bytes, a slot of bytes_per per entry,
+        zero behind the repeat) -> the info dict.  Stream rule: as count_device."""
+        min_len, max_len, order, limit, bytes_per = _maxrep_args(min_len, max_len, order, limit, bytes_per)
+        info = MaxRepInfo()
+        self._c.check(self._c.lib.bce_hip_maximal_repeats_device(self._c.h, min_len, max_len, order, limit, None if out_ptr is None else int(out_ptr),
+                                                                 None if bytes_ptr is None else int(bytes_ptr), bytes_per, int(bytes_cap), C.byref(info)),
+                      "bce_hip_maximal_repeats_device")
+        return info.as_dict()
 
     def parse(self, query, min_len, max_len=PARSE_MAX_LEN):
         """`query` (a bytes-like, a second buffer) written as copies out of the text plus the bytes that are new (bce_hip_parse: the
@@ -1413,6 +1469,16 @@ def kgrams(data, ks, device=0, ctx=None):
             rf.close()
 
 
+def maximal_repeats(data, min_len=1, max_len=MATCH_MAX_LEN, order="len", limit=100, bytes_per=64, device=0, ctx=None):
+    """The maximal repeats of `data` (RankFile.maximal_repeats): indexed, found, selected and sorted on the GPU."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.maximal_repeats(min_len=min_len, max_len=max_len, order=order, limit=limit, bytes_per=bytes_per)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
 def top_kgrams(data, k, limit, with_bytes=True, device=0, ctx=None):
     """The `limit` most frequent cyclic k-grams of `data` (RankFile.top_kgrams): indexed, selected and sorted on the GPU."""
     rf = RankFile(data, device=device, ctx=ctx)
@@ -1794,6 +1860,18 @@ def top_classes_of_lcp_device(ptr_lcp, n, ptr_sa, k, limit, ctx):
     ctx.check(ctx.lib.bce_hip_top_classes_of_lcp_device(ctx.h, _ptr(ptr_lcp), int(n), _ptr(ptr_sa), int(k), int(limit), out.ctypes.data, C.byref(found),
                                                         C.byref(distinct), C.addressof(hist)), "bce_hip_top_classes_of_lcp_device")
     return out[:found.value], distinct.value, [int(v) for v in hist]
+
+
+def maxrep_of_arrays_device(ptr_lcp, n, ptr_sa, ptr_bw, min_len, max_len, order, limit, ctx):
+    """Test hook (bce_hip_maxrep_of_arrays_device): the launches of maximal_repeats() behind the LCP pass on `n` uint32 words at device
+    pointer `ptr_lcp` read as the LCP array, the `n` words at `ptr_sa` as the suffix array and the `n` bytes at `ptr_bw` as the
+    preceding bytes -> (a numpy record array (len, count, row, pos) of the entries found, the info dict)."""
+    min_len, max_len, order, limit, _ = _maxrep_args(min_len, max_len, order, limit, 0)
+    out = np.zeros(max(1, min(limit, TOP_MAX)), dtype=MAXREP_DTYPE)
+    info = MaxRepInfo()
+    ctx.check(ctx.lib.bce_hip_maxrep_of_arrays_device(ctx.h, _ptr(ptr_lcp), int(n), _ptr(ptr_sa), _ptr(ptr_bw), min_len, max_len, order, limit, out.ctypes.data,
+                                                      C.byref(info)), "bce_hip_maxrep_of_arrays_device")
+    return out[:info.found].copy(), info.as_dict()
 
 
 def coverage_of_lengths_device(ptr_len, q, min_len, ctx) -> int:

@@ -622,6 +622,86 @@ int bce_hip_top_kgrams_device(bce_hip_ctx *c, uint32_t k, uint32_t limit, void *
   return BCE_HIP_OK;
 }
 
+// ---- the maximal repeats of the text, as a list (kd_maxrep.hip; maxrep_step.h) -------------------------------------------------------
+// bce_hip_top_kgrams' rule and order of refusals.  *info is written once everything queued has completed.
+static int maxrep_list_args(bce_hip_ctx *c, uint32_t min_len, uint32_t max_len, uint32_t order, uint32_t limit, const void *info) {
+  BCE_TRY(length_bound(c, "maximal repeats", max_len));
+  if (min_len < 1 || min_len > max_len) { snprintf(c->err, sizeof c->err, "maximal repeats: a least length of %u, outside 1 .. %u", min_len, max_len); return BCE_HIP_E_ARG; }
+  if (order > BCE_HIP_MAXREP_BY_GAIN) { snprintf(c->err, sizeof c->err, "maximal repeats: order %u is none of len (0), count (1), gain (2)", order); return BCE_HIP_E_ARG; }
+  if (limit < 1 || limit > BCE_HIP_TOP_MAX) { snprintf(c->err, sizeof c->err, "maximal repeats: a limit of %u, outside 1 .. %u", limit, BCE_HIP_TOP_MAX); return BCE_HIP_E_ARG; }
+  if (!info) { snprintf(c->err, sizeof c->err, "maximal repeats: no place for the counts"); return BCE_HIP_E_ARG; }
+  return BCE_HIP_OK;
+}
+static int maxrep_args(bce_hip_ctx *c, uint32_t min_len, uint32_t max_len, uint32_t order, uint32_t limit, const void *bytes, uint32_t bytes_per,
+                       uint64_t bytes_cap, const void *info, const uint32_t **sa) {
+  if (!c) return BCE_HIP_E_ARG;
+  BCE_TRY(maxrep_list_args(c, min_len, max_len, order, limit, info));
+  if (bytes_per > BCE_HIP_MATCH_MAX_LEN) { snprintf(c->err, sizeof c->err, "maximal repeats: %u bytes per entry, more than %u", bytes_per, BCE_HIP_MATCH_MAX_LEN); return BCE_HIP_E_ARG; }
+  if (bytes && bytes_cap < (uint64_t)limit * bytes_per) {
+    snprintf(c->err, sizeof c->err, "maximal repeats: room for %llu bytes, %u entries of %u bytes need %llu", (unsigned long long)bytes_cap, limit, bytes_per,
+             (unsigned long long)((uint64_t)limit * bytes_per));
+    return BCE_HIP_E_ARG;
+  }
+  return text_state(c, sa, "maximal repeats");
+}
+
+int bce_hip_maximal_repeats(bce_hip_ctx *c, uint32_t min_len, uint32_t max_len, uint32_t order, uint32_t limit, bce_hip_maxrep *out, uint8_t *bytes,
+                            uint32_t bytes_per, uint64_t bytes_cap, bce_hip_maxrep_info *info) {
+  const uint32_t *sa = nullptr;
+  BCE_TRY(maxrep_args(c, min_len, max_len, order, limit, bytes, bytes_per, bytes_cap, info, &sa));
+  if (!out) return BCE_HIP_E_ARG;
+  bce_hip_maxrep_info got;
+  BCE_TRY(query_call(c, 3, [&]() -> int {
+    DevBuf &ent = c->qbuf[qb::mxr_out], &str = c->qbuf[qb::mxr_bytes];
+    const bool with_bytes = bytes && bytes_per;
+    const uint32_t room = limit < c->n ? limit : c->n;                 // (there are fewer intervals than rows)
+    BCE_TRY(lcp_own(c, sa, max_len));
+    BCE_TRY(ensure(c, ent, (size_t)room * sizeof(bce_hip_maxrep)));
+    if (with_bytes) BCE_TRY(ensure(c, str, (size_t)room * bytes_per));
+    BCE_TRY(kd_maxrep(c, sa, c->qbuf[qb::rep_lcp].as<uint32_t>(), c->n, c->text.as<uint8_t>(), nullptr, min_len, max_len, order, limit,
+                      ent.as<bce_hip_maxrep>(), with_bytes ? str.as<uint8_t>() : nullptr, bytes_per, &got));
+    BCE_TRY(copy_out(c, out, ent, (size_t)got.found * sizeof(bce_hip_maxrep)));
+    return with_bytes ? copy_out(c, bytes, str, (size_t)got.found * bytes_per) : BCE_HIP_OK;
+  }));
+  *info = got;
+  return BCE_HIP_OK;
+}
+
+int bce_hip_maximal_repeats_device(bce_hip_ctx *c, uint32_t min_len, uint32_t max_len, uint32_t order, uint32_t limit, void *d_out, void *d_bytes,
+                                   uint32_t bytes_per, uint64_t bytes_cap, bce_hip_maxrep_info *info) {
+  const uint32_t *sa = nullptr;
+  BCE_TRY(maxrep_args(c, min_len, max_len, order, limit, d_bytes, bytes_per, bytes_cap, info, &sa));
+  if (!d_out) return BCE_HIP_E_ARG;
+  bce_hip_maxrep_info got;
+  BCE_TRY(query_call(c, 3, [&]() -> int {
+    BCE_TRY(lcp_own(c, sa, max_len));
+    return kd_maxrep(c, sa, c->qbuf[qb::rep_lcp].as<uint32_t>(), c->n, c->text.as<uint8_t>(), nullptr, min_len, max_len, order, limit,
+                     static_cast<bce_hip_maxrep *>(d_out), static_cast<uint8_t *>(d_bytes), bytes_per, &got);
+  }));
+  *info = got;
+  return BCE_HIP_OK;
+}
+
+// test hook: the same launches on arrays of the caller's, phase 0 as the other hooks; the entries are staged in mxr_out
+int bce_hip_maxrep_of_arrays_device(bce_hip_ctx *c, const void *d_lcp, uint32_t n, const void *d_sa, const void *d_bw, uint32_t min_len, uint32_t max_len,
+                                    uint32_t order, uint32_t limit, bce_hip_maxrep *out, bce_hip_maxrep_info *info) {
+  if (!c || !d_lcp || !d_sa || !d_bw || !out || n == 0 || n > 0x7FFFFFFFu) return BCE_HIP_E_ARG;
+  BCE_TRY(maxrep_list_args(c, min_len, max_len, order, limit, info));
+  bce_hip_maxrep_info got;
+  BCE_TRY(query_call(c, 0, [&]() -> int {
+    DevBuf &lcp = c->qbuf[qb::rep_lcp], &ent = c->qbuf[qb::mxr_out];
+    const size_t words = (size_t)n * 4;
+    BCE_TRY(ensure(c, lcp, words));
+    BCE_TRY(ensure(c, ent, (size_t)(limit < n ? limit : n) * sizeof(bce_hip_maxrep)));
+    BCE_HIP_TRY(c, hipMemcpyAsync(lcp.p, d_lcp, words, hipMemcpyDeviceToDevice, c->stream));
+    BCE_TRY(kd_maxrep(c, static_cast<const uint32_t *>(d_sa), lcp.as<uint32_t>(), n, nullptr, static_cast<const uint8_t *>(d_bw), min_len, max_len, order,
+                      limit, ent.as<bce_hip_maxrep>(), nullptr, 0, &got));
+    return copy_out(c, out, ent, (size_t)got.found * sizeof(bce_hip_maxrep));
+  }));
+  *info = got;
+  return BCE_HIP_OK;
+}
+
 // ---- a second buffer as a delta against the text: parse and patch (kd_parse.hip) ----------------------------------------------------
 // The parse: the match's rule with positions (sa_state).  The query of a call with a host buffer and the statistics are staged in
 // the match's mat_qry / mat_len / mat_pos; every other temporary is a par_* buffer of the feature's own.  The patch reads the text

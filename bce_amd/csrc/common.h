@@ -166,6 +166,11 @@ enum Id {
   slf_tree, slf_top,                             // kd_self.hip: the blocks' min-trees (2048 words a block) and the tree over the blocks' minima
   slf_rlen, slf_rsrc, slf_rtext,                 // the self-parse: lpf, src and the text written at n - 1 - i, what kd_parse's chain runs on
   slf_lpf, slf_src, slf_ops, slf_lits,           // bce_hip_lpf / _self_parse with host buffers: the arrays, the ops and the literal bytes, staged (all grow-only)
+  mxr_res,                                       // kd_maxrep.hip: the 64 weight counters, the capped count and the BWT's change count (a buffer of its own, as top_res)
+  mxr_bsum,                                      // per block: its changes / candidates (then their offsets) and its 65 counters
+  mxr_chg, mxr_wt, mxr_first,                    // per row: the changes up to it (4 bytes), the weight it represents or 0 (8), that interval's first row (4)
+  mxr_lo0, mxr_lo1, mxr_hi0, mxr_hi1, mxr_val0, mxr_val1,   // (complement of the weight, representative row) of every candidate: the sort's ping-pong, sized by the histogram's count
+  mxr_out, mxr_bytes,                            // bce_hip_maximal_repeats with host buffers, and the hook: the entries and the repeats' bytes, staged (grow-only)
   sfc_res,                                       // kd_sufsort.hip: the checker's three result words (a buffer of its own, as par_res)
   sfc_inv, sfc_bsum,                             // the checker's inverse (n words) and the three stages' block results
   sfc_text, sfc_sa,                              // bce_hip_sufcheck with host buffers: the text and the array, staged (grow-only)
@@ -536,6 +541,14 @@ int kd_patch(bce_hip_ctx *c, const uint32_t *d_ops, uint32_t nops, const uint8_t
 // the mirrors of lengths, sources and text in slf_rlen / slf_rsrc / slf_rtext; kd_parse's chain over those, turned round.  The
 // first three are queued and the caller waits; the last is complete on return.
 int kd_nsv(bce_hip_ctx *c, const uint32_t *d_vals, uint32_t n, uint32_t *d_psv, uint32_t *d_nsv);
+constexpr uint32_t NSV_TREE_BLOCK = 2048;           // rows per block tree
+// the blocks' trees and the top tree over vals[0, n), n >= 1, into slf_tree / slf_top, *NB_out = the top tree's leaves; queued
+int nsv_trees(bce_hip_ctx *c, const uint32_t *vals, uint32_t n, uint32_t *NB_out);
+// kd_maxrep.hip: the maximal repeats of n >= 2 rows from the capped LCP array in rep_lcp (32-byte aligned, d_lcp), heaviest first
+// (maxrep_step.h).  bw: null (the preceding bytes come from sa and text) or n bytes in their place; d_bytes: null, or room for
+// limit * bytes_per bytes, then `text` is read.  info->found entries are written to d_out; complete on return.
+int kd_maxrep(bce_hip_ctx *c, const uint32_t *sa, const uint32_t *d_lcp, uint32_t n, const uint8_t *text, const uint8_t *bw, uint32_t min_len,
+              uint32_t max_len, uint32_t order, uint32_t limit, bce_hip_maxrep *d_out, uint8_t *d_bytes, uint32_t bytes_per, bce_hip_maxrep_info *info);
 int kd_lpf(bce_hip_ctx *c, const uint32_t *sa, uint32_t max_len, bool mirror, uint32_t *d_lpf, uint32_t *d_src);
 int kd_self_mirror(bce_hip_ctx *c, const uint32_t *d_lpf, const uint32_t *d_src, const uint8_t *d_text, uint32_t n);
 int kd_self_parse(bce_hip_ctx *c, uint32_t n, uint32_t min_len, bool with_src, bool sizing, uint32_t *d_ops, uint64_t ops_cap, uint8_t *d_lits,

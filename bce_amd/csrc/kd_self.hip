@@ -131,6 +131,10 @@ __global__ __launch_bounds__(SLF_T) void self_turn_bytes_kernel(uint8_t *__restr
 
 inline dim3 slf_grid(uint32_t n) { return dim3((uint32_t)(((uint64_t)n + SLF_T - 1) / SLF_T)); }
 
+}  // namespace
+
+static_assert(SLF_BLOCK == NSV_TREE_BLOCK, "kd_maxrep.hip solves on the same blocks");
+
 // the two storeys over vals[0, n), n >= 1, into slf_tree / slf_top; queued
 int nsv_trees(bce_hip_ctx *c, const uint32_t *vals, uint32_t n, uint32_t *NB_out) {
   const uint32_t nb = slf_blocks(n), NB = slf_top_leaves(nb);
@@ -144,8 +148,6 @@ int nsv_trees(bce_hip_ctx *c, const uint32_t *vals, uint32_t n, uint32_t *NB_out
   *NB_out = NB;
   return BCE_HIP_OK;
 }
-
-}  // namespace
 
 // d_psv[r], d_nsv[r], r < n, of the n >= 1 words d_vals (NSV_NONE: no smaller value on that side).  Queued; the caller waits.
 int kd_nsv(bce_hip_ctx *c, const uint32_t *d_vals, uint32_t n, uint32_t *d_psv, uint32_t *d_nsv) {

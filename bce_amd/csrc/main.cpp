@@ -12,6 +12,7 @@
 //   bce -gr MINLEN file query_file out.bcd, -grd ... archive ...   (extension) writes query_file as a delta against the first: copies out of it plus the new bytes
 //   bce -ga file in.bcd out_file, -gad archive in.bcd out_file     (extension) rebuilds a file from the first and a delta, both sides checked by CRC-32
 //   bce -gk K file, -gkd K archive          (extension) the k-grams of the circular text for k = 0..K: how many, how many occur once, the most frequent, H_k; the longest repeat
+//   bce -gp ORDER MINLEN N file, -gpd ..   (extension) the N heaviest maximal repeats of MINLEN bytes or more: length, count, one position and the bytes
 //   bce -gf K N file, -gfd K N archive      (extension) the N most frequent K-grams of the circular text: count, one position and the bytes of each
 //   bce -gz MINLEN file, -gzd MINLEN archive   (extension) the text as copies of its own earlier bytes: the greedy LZ77 factorisation, counted on the GPU
 //   bce -gs file out.sa, -gsd archive out.sa   (extension) the suffix array of the text, sorted on the GPU, as native 32-bit words
@@ -153,6 +154,8 @@ extern "C" int bce_hip_kgrams(bce_hip_ctx *ctx, const uint32_t *ks, uint32_t nk,
 extern "C" int bce_hip_longest_repeat(bce_hip_ctx *ctx, uint32_t max_len, uint32_t *len, uint32_t *pos_a, uint32_t *pos_b) __attribute__((weak));
 extern "C" int bce_hip_top_kgrams(bce_hip_ctx *ctx, uint32_t k, uint32_t limit, bce_hip_top_kgram *out, uint8_t *bytes, uint64_t bytes_cap,
                                   uint32_t *found, uint64_t *distinct, uint64_t size_hist[32]) __attribute__((weak));
+extern "C" int bce_hip_maximal_repeats(bce_hip_ctx *ctx, uint32_t min_len, uint32_t max_len, uint32_t order, uint32_t limit, bce_hip_maxrep *out,
+                                       uint8_t *bytes, uint32_t bytes_per, uint64_t bytes_cap, bce_hip_maxrep_info *info) __attribute__((weak));
 extern "C" int bce_hip_parse(bce_hip_ctx *ctx, const uint8_t *query, uint64_t q, uint32_t min_len, uint32_t max_len, bce_hip_op *ops, uint64_t ops_cap,
                              uint8_t *lits, uint64_t lits_cap, bce_hip_parse_info *info) __attribute__((weak));
 extern "C" int bce_hip_patch(bce_hip_ctx *ctx, const bce_hip_op *ops, uint64_t nops, const uint8_t *lits, uint64_t nlits, uint8_t *out, uint64_t cap,
@@ -850,6 +853,39 @@ static int top_command(uint32_t K, uint32_t N, const char *path, bool in_archive
   return index_done(in);
 }
 
+// -gp / -gpd: the maximal repeats of MINLEN bytes or more at the search bound 4096, the N heaviest in ORDER.  A head line, one line
+// per repeat -- its length ("4096+": that many or more), its occurrences, the position of one, its first 64 bytes in top_escape's
+// escaping ("..." behind a longer one) -- then the counts, the runs of the BWT and the text's size.
+constexpr uint32_t kMaxRepShown = 64;
+static const char *const kMaxRepOrders[3] = {"len", "count", "gain"};
+static int parse_maxrep_order(const char *s) {
+  for (int o = 0; o < 3; ++o) if (strcmp(s, kMaxRepOrders[o]) == 0) return o;
+  return -1;
+}
+static int maxrep_command(uint32_t order, uint32_t min_len, uint32_t N, const char *path, bool in_archive) {
+  IndexInput in;
+  if (const int ec = index_open(in, path, in_archive, nullptr, kNoSecond, bce_hip_maximal_repeats != nullptr)) return ec;
+  std::vector<bce_hip_maxrep> ent(N);
+  std::vector<uint8_t> str((size_t)N * kMaxRepShown);
+  bce_hip_maxrep_info info{};
+  int rc = index_text(in);
+  if (rc == 0) rc = bce_hip_maximal_repeats(in.ctx, min_len, BCE_HIP_MATCH_MAX_LEN, order, N, ent.data(), str.data(), kMaxRepShown, str.size(), &info);
+  if (rc != 0) return index_failed(in, "Maximal repeats", rc);
+  printf("maximal repeats of the circular text by %s: length count position bytes\n", kMaxRepOrders[order]);
+  std::string line;
+  for (uint32_t e = 0; e < info.found; ++e) {
+    line.clear();
+    char esc[5];
+    const uint32_t shown = ent[e].len < kMaxRepShown ? ent[e].len : kMaxRepShown;
+    for (uint32_t j = 0; j < shown; ++j) { bce::top_escape(str[(size_t)e * kMaxRepShown + j], esc); line += esc; }
+    if (ent[e].len > kMaxRepShown) line += "...";
+    printf("%u%s %u %u %s\n", ent[e].len, ent[e].len >= BCE_HIP_MATCH_MAX_LEN ? "+" : "", ent[e].count, ent[e].pos, line.c_str());
+  }
+  printf("%llu maximal repeats of %u bytes or more (%llu of %u or more), %llu BWT runs, %zu bytes\n", (unsigned long long)info.total, min_len,
+         (unsigned long long)info.capped, BCE_HIP_MATCH_MAX_LEN, (unsigned long long)info.bwt_runs, in.n);
+  return index_done(in);
+}
+
 // -gr / -grd
 static int delta_command(uint32_t min_len, const char *path, bool in_archive, const char *query_path, const char *out_path) {
   IndexInput in;
@@ -979,6 +1015,12 @@ static int usage() {
   printf("\n");
   printf("  bce -e file [config.bcc]\n");
   printf("   Estimates the size -c would give for \"file\" [using config \"config.bcc\"]: the model's code lengths are summed on the GPU, nothing is coded or written (extension)\n");
+  printf("\n");
+  printf("  bce -gp ORDER MINLEN N file\n");
+  printf("   Prints the N (1..65536) heaviest maximal repeats of MINLEN (1..4096) bytes or more of the circular text of \"file\": strings that occur twice or more and lose an occurrence when extended by a byte on either side.  ORDER is len (longest first), count (most frequent first) or gain (length times the occurrences after the first).  Per repeat: length (4096+: that or more), occurrences, the position of one and the first 64 bytes (\\xHH for all but printable ASCII); then their number, the runs of the BWT and the size; found, selected and sorted on the GPU (extension)\n");
+  printf("\n");
+  printf("  bce -gpd ORDER MINLEN N archive.bce\n");
+  printf("   The same list for what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
   printf("\n");
   printf("  bce -gs file out.sa\n");
   printf("   Writes the suffix array of \"file\" to \"out.sa\": one native 32-bit word per suffix in sorted order (the layout of libdivsufsort's mksary), sorted on the GPU (extension)\n");
@@ -1355,6 +1397,9 @@ int main(int argc, char **argv) {
   } else if (argc == 5 && (strcmp(argv[1], "-gf") == 0 || strcmp(argv[1], "-gfd") == 0) && parse_count(argv[2], kMaxTopLen) != 0 &&
              parse_count(argv[3], kMaxTopCount) != 0) {
     return top_command(parse_count(argv[2], kMaxTopLen), parse_count(argv[3], kMaxTopCount), argv[4], argv[1][3] == 'd');
+  } else if (argc == 6 && (strcmp(argv[1], "-gp") == 0 || strcmp(argv[1], "-gpd") == 0) && parse_maxrep_order(argv[2]) >= 0 && parse_min_len(argv[3]) != 0 &&
+             parse_count(argv[4], kMaxTopCount) != 0) {
+    return maxrep_command((uint32_t)parse_maxrep_order(argv[2]), parse_min_len(argv[3]), parse_count(argv[4], kMaxTopCount), argv[5], argv[1][3] == 'd');
   } else if (argc == 4 && (strcmp(argv[1], "-gs") == 0 || strcmp(argv[1], "-gsd") == 0)) {
     return sa_command(argv[2], argv[1][3] == 'd', argv[3]);
   } else if (argc == 4 && strcmp(argv[1], "-gsc") == 0) {

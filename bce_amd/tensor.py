@@ -577,6 +577,41 @@ def top_kgrams_in_archive(blob, k, limit, with_bytes=True, device="cuda:0"):
     return top_kgrams_tensor(decompress_container_tensor(blob, device=device), k, limit, with_bytes=with_bytes)
 
 
+def maximal_repeats_tensor(t, min_len=1, max_len=api.MATCH_MAX_LEN, order="len", limit=100, bytes_per=64, ctx=None):
+    """The maximal repeats of the circular text in the 1-D uint8 CUDA tensor `t` (api.RankFile.maximal_repeats with everything left
+    on the device: bce_hip_maximal_repeats_device) -> (entries, strings, info): entries an int32 tensor (found, 4) of (len, count,
+    row, pos) on t's device, heaviest first; strings a uint8 tensor (found, bytes_per), every row the first min(len, bytes_per)
+    bytes of its repeat and zeros behind them (None with bytes_per=0); info the dict (total, capped, bwt_runs, found), all that
+    reaches the host.  Synchronises t's current stream first; `ctx` (an api._Ctx of t's device) is reused if given."""
+    min_len, max_len, order, limit, bytes_per = api._maxrep_args(min_len, max_len, order, limit, bytes_per)
+    sound = 1 <= limit <= api.TOP_MAX and bytes_per <= api.MAXREP_BYTES_MAX   # (otherwise the library refuses: no room is made)
+
+    def use(rf):
+        ent = torch.zeros((limit if sound else 1, 4), dtype=torch.int32, device=t.device)
+        raw = torch.zeros((limit if sound else 1, bytes_per if sound else 1), dtype=torch.uint8, device=t.device) if bytes_per else None
+        torch.cuda.current_stream(t.device).synchronize()            # (the zero fills are done before the library's stream writes)
+        info = rf.maximal_repeats_device(min_len, max_len, order, limit, ent.data_ptr(), raw.data_ptr() if bytes_per else None, bytes_per,
+                                         limit * bytes_per if bytes_per else 0)
+        return ent[:info["found"]], raw[:info["found"]] if bytes_per else None, info
+    return _indexed(t, "maximal_repeats_tensor", ctx, use)
+
+
+def maximal_repeats_in_archive(blob, min_len=1, max_len=api.MATCH_MAX_LEN, order="len", limit=100, bytes_per=64, device="cuda:0", per_block=False):
+    """maximal_repeats_tensor on what an archive holds, decoded as count_in_archive decodes it: into ONE tensor on the device, so
+    the repeats across block boundaries count.  A container of 2^31 bytes or more: ValueError, before anything is decoded.
+    per_block: every block of a container is a text of its own -- a list with one (entries, strings, info) per block (one for a
+    plain archive), each block decoded into a tensor of its own and indexed there."""
+    table = _blocks_of(blob)
+    if per_block:
+        view = memoryview(blob)
+        return [maximal_repeats_tensor(decompress_container_tensor(bytes(view[pos:pos + alen]), device=device), min_len, max_len, order, limit, bytes_per)
+                for _raw, pos, alen, _crc in table]
+    total = sum(t[0] for t in table)
+    if total > _MAX_BLOCK:
+        raise ValueError("the archive holds %d bytes: one index covers one text of less than 2^31" % total)
+    return maximal_repeats_tensor(decompress_container_tensor(blob, device=device), min_len, max_len, order, limit, bytes_per)
+
+
 def decompress_tensor(archive, device="cuda:0", out=None, ctx=None):
     """The GPU-assisted decoder with the text left on the device (bce_hip_decompress_to_device) -> a 1-D uint8 tensor there.
 

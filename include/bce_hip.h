@@ -534,6 +534,46 @@ int bce_hip_top_kgrams(bce_hip_ctx *ctx, uint32_t k, uint32_t limit, bce_hip_top
 int bce_hip_top_kgrams_device(bce_hip_ctx *ctx, uint32_t k, uint32_t limit, void *d_out, void *d_bytes, uint64_t bytes_cap,
                               uint32_t *found, uint64_t *distinct, uint64_t size_hist[32]);
 
+/* ---- extension: the MAXIMAL REPEATS of the input, as a list (kd_maxrep.hip, maxrep_step.h) ---------------------------------------
+ * Which strings the circular text repeats, how long they are and how often they occur.  lcp: the array of bce_hip_lcp at bound
+ * max_len; bw[r] = T[(sa[r] + n - 1) mod n].  A row r >= 1 with l = lcp[r] >= 1 lies in the LCP interval [p, q): p the nearest row
+ * above with lcp[p] < l, q the nearest row below with lcp[q] < l, or n.  The interval is the class of one l-gram w with q - p >= 2
+ * cyclic occurrences that are followed by at least two different bytes (for l < max_len); w is a MAXIMAL repeat when bw[p .. q) holds
+ * at least two different bytes as well.  Each interval is reported once, by the lowest of its rows that carry l.
+ *   out[e].len    l; len == max_len means "max_len bytes or more" (as bce_hip_longest_repeat's *len == max_len);
+ *   out[e].count  q - p;    out[e].row  p;    out[e].pos  sa[p], the start of ONE occurrence (which of tied rotations is not specified).
+ * len, count and row are functions of the text and max_len alone.  Ordered by a weight, descending, and among equal weights by the
+ * reporting row ascending (for BY_LEN and BY_COUNT that is the lexicographic order of the strings):
+ *   BCE_HIP_MAXREP_BY_LEN  (len << 31) | count;   BCE_HIP_MAXREP_BY_COUNT  (count << 13) | len;   BCE_HIP_MAXREP_BY_GAIN  len * (count - 1).
+ * The first min(limit, total) repeats with len >= min_len are returned; info->found is their number, info->total and info->capped
+ * count all of them (capped: those with len == max_len), info->bwt_runs = 1 + #{1 <= r < n : bw[r] != bw[r - 1]} is the number of
+ * runs of the BWT.  A text of one byte, or one without repeats: found = total = 0, nothing is written to out.
+ *   bytes (may be NULL)  bytes[e * bytes_per + j] = T[(pos + j) mod n] for j < min(len, bytes_per), the rest of the slot zero;
+ *                        bytes_per <= 4096 and bytes_cap >= limit * bytes_per.  bytes_per == 0: as NULL.
+ * Own LCP pass; nothing is cached; only buffers of the feature's own (and the LCP and tree buffers of bce_hip_lcp / _lpf) are
+ * written and no compression state changes.
+ * A null ctx, 1 <= min_len <= max_len <= BCE_HIP_MATCH_MAX_LEN violated, an unknown order, a limit outside 1 .. BCE_HIP_TOP_MAX, a
+ * null info, bytes_per > 4096, bytes with bytes_cap < limit * bytes_per: BCE_HIP_E_ARG (bce_hip_last_error has the words) before any
+ * device call; then the state, as bce_hip_top_kgrams; then a null out: BCE_HIP_E_ARG.  A refused call leaves its outputs untouched. */
+#define BCE_HIP_MAXREP_BY_LEN 0u
+#define BCE_HIP_MAXREP_BY_COUNT 1u
+#define BCE_HIP_MAXREP_BY_GAIN 2u
+typedef struct bce_hip_maxrep {
+  uint32_t len, count, row, pos;
+} bce_hip_maxrep;
+typedef struct bce_hip_maxrep_info {
+  uint64_t total;  /* maximal repeats with len >= min_len at this bound */
+  uint64_t capped; /* those of them with len == max_len */
+  uint64_t bwt_runs;
+  uint32_t found, reserved;
+} bce_hip_maxrep_info;
+int bce_hip_maximal_repeats(bce_hip_ctx *ctx, uint32_t min_len, uint32_t max_len, uint32_t order, uint32_t limit, bce_hip_maxrep *out,
+                            uint8_t *bytes, uint32_t bytes_per, uint64_t bytes_cap, bce_hip_maxrep_info *info);
+/* The same into device memory of the context's device (d_out 4-byte aligned); info stays a host pointer.  Stream rule: as
+ * bce_hip_count_device. */
+int bce_hip_maximal_repeats_device(bce_hip_ctx *ctx, uint32_t min_len, uint32_t max_len, uint32_t order, uint32_t limit, void *d_out,
+                                   void *d_bytes, uint32_t bytes_per, uint64_t bytes_cap, bce_hip_maxrep_info *info);
+
 /* ---- extension: a second buffer as a DELTA against the input: parse and patch (kd_parse.hip, parse_step.h) ----------------------
  * T: the n bytes the context indexed.  Q: a query of q bytes, 0 <= q < 2^31.  1 <= min_len <= max_len <= BCE_HIP_MATCH_MAX_LEN.
  * len[i], pos[i]: the LINEAR matching statistics of Q at bound max_len, exactly what bce_hip_match_device gives with
@@ -747,6 +787,14 @@ int bce_hip_lcp_reduce_device(bce_hip_ctx *ctx, const void *d_lcp, uint32_t n, c
  * BCE_HIP_MATCH_MAX_LEN, a limit outside 1 .. BCE_HIP_TOP_MAX: BCE_HIP_E_ARG before any device call. */
 int bce_hip_top_classes_of_lcp_device(bce_hip_ctx *ctx, const void *d_lcp, uint32_t n, const void *d_sa, uint32_t k, uint32_t limit,
                                       bce_hip_top_kgram *out, uint32_t *found, uint64_t *distinct, uint64_t size_hist[32]);
+/* Test hook: the launches of bce_hip_maximal_repeats behind its LCP pass, with the same geometry, on arrays of the caller's: the n
+ * words at d_lcp read as the LCP array (d_lcp[0] must be 0; words of 0xFFFFFFFF name no interval; copied and aligned as above), the n
+ * words at d_sa as the suffix array (pos = d_sa[row]) and the n bytes at d_bw in place of the text's preceding bytes.  No bytes are
+ * gathered.  out: a HOST array with room for limit entries.  Valid in any state of the context; writes only rep_lcp, slf_tree,
+ * slf_top and the feature's mxr_* buffers.  A null ctx, d_lcp, d_sa, d_bw, out or info, n == 0, n >= 2^31, 1 <= min_len <= max_len <=
+ * BCE_HIP_MATCH_MAX_LEN violated, an unknown order, a limit outside 1 .. BCE_HIP_TOP_MAX: BCE_HIP_E_ARG before any device call. */
+int bce_hip_maxrep_of_arrays_device(bce_hip_ctx *ctx, const void *d_lcp, uint32_t n, const void *d_sa, const void *d_bw, uint32_t min_len,
+                                    uint32_t max_len, uint32_t order, uint32_t limit, bce_hip_maxrep *out, bce_hip_maxrep_info *info);
 /* Test hook: kd_coverage, the reduction of bce_hip_coverage, on q lengths of the caller's (u32, 4-byte aligned) with
  * d_len[i] <= i + 1 (a match does not start in front of the query): *covered = the j < q for which some i >= j has
  * d_len[i] >= min_len and i - d_len[i] + 1 <= j.  Writes only mat_res and mat_bsum.  q == 0: *covered = 0, d_len ignored.  A null
