@@ -144,6 +144,10 @@ SYMBOLS = [
     ("bce_hip_count_near_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, _vp]),
     ("bce_hip_locate_near", C.c_int, [C.c_void_p, _u8p, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("bce_hip_locate_near_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("bce_hip_count_edit", C.c_int, [C.c_void_p, _u8p, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
+    ("bce_hip_count_edit_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp]),
+    ("bce_hip_locate_edit", C.c_int, [C.c_void_p, _u8p, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("bce_hip_locate_edit_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("bce_hip_count_classes", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     ("bce_hip_count_classes_device", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     ("bce_hip_locate_classes", C.c_int, [C.c_void_p, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
@@ -218,6 +222,9 @@ def _as_u8(data):
 LOCATE_LINEAR = 1                               # BCE_HIP_LOCATE_LINEAR
 NEAR_MAX_K = 2                                  # BCE_HIP_NEAR_MAX_K: mismatches allowed at most; a work bound, not a format limit
 NEAR_MAX_LEN = 4096                             # BCE_HIP_NEAR_MAX_LEN: bytes of a pattern searched with mismatches
+EDIT_MAX_K = 2                                  # BCE_HIP_EDIT_MAX_K: edits allowed at most; a work bound, as NEAR_MAX_K
+EDIT_MAX_LEN = 4096                             # BCE_HIP_EDIT_MAX_LEN: bytes of a pattern searched with edits
+EDIT_MAX_PATTERNS = 1 << 28                     # BCE_HIP_EDIT_MAX_PATTERNS: patterns of one call
 CLASS_MAX_LEN = 4096                            # BCE_HIP_CLASS_MAX_LEN: classes of a pattern searched by byte classes
 CLASS_MAX_WIDE = 64                             # BCE_HIP_CLASS_MAX_WIDE: of them, those with two members or more
 CLASS_DEFAULT_NODES = 1 << 16                   # BCE_HIP_CLASS_DEFAULT_NODES: the budget of search nodes per pattern when none is given
@@ -736,6 +743,80 @@ class RankFile:
                                                              int(cap), C.byref(total)), "bce_hip_locate_near_device")
         return total.value
 
+    def _edit_args(self, patterns, k, cyclic, what):
+        """-> (one, pats, flat, offsets) of a search with edits, judged as _near_args judges its own"""
+        if not 0 <= int(k) <= EDIT_MAX_K:
+            raise ValueError("k = %r, outside 0 .. %d" % (k, EDIT_MAX_K))
+        one = _is_one_pattern(patterns)
+        pats = [_as_u8(patterns)] if one else [_as_u8(p) for p in patterns]
+        if not cyclic:
+            if not self._has_text:
+                raise ValueError("a RankFile built from an injected BWT holds no text: only cyclic=True %s are defined" % what)
+            if any(len(p) == 0 for p in pats):
+                raise ValueError("an empty pattern has no linear %s (cyclic=True: every position, at distance 0)" % what)
+        if any(len(p) > EDIT_MAX_LEN for p in pats):
+            raise ValueError("a pattern of more than %d bytes" % EDIT_MAX_LEN)
+        offsets = np.zeros(len(pats) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([len(p) for p in pats], dtype=np.uint64)
+        flat = np.concatenate(pats) if pats and int(offsets[-1]) else np.zeros(1, dtype=np.uint8)
+        return one, pats, flat, offsets
+
+    def count_edit(self, patterns, k, cyclic=False):
+        """How often something occurs in the text within k edits of a pattern -- substitutions, insertions and deletions, the
+        anchored edit distance of include/bce_hip.h, k = 0 .. EDIT_MAX_K -- searched and reduced on the GPU (bce_hip_count_edit).
+        `patterns`: one bytes-like -> a numpy uint64 array of k + 1 counts, the positions whose least distance is exactly
+        0 .. k; a sequence -> shape (npat, k + 1).  cyclic=False: over the alignments that end inside the text; an empty pattern
+        raises ValueError.  cyclic=True: in the circular text, defined for every length.  Needs the suffix array, so a RankFile
+        built from an injected BWT is refused (BceError) in either mode.  Patterns of more than EDIT_MAX_LEN bytes: ValueError."""
+        one, pats, flat, offsets = self._edit_args(patterns, k, cyclic, "counts")
+        out = np.zeros((len(pats), int(k) + 1), dtype=np.uint64)
+        if pats:
+            self._c.check(self._c.lib.bce_hip_count_edit(self._c.h, flat.ctypes.data, offsets.ctypes.data, len(pats), int(k),
+                                                         0 if cyclic else LOCATE_LINEAR, out.ctypes.data), "bce_hip_count_edit")
+        return out[0] if one else out
+
+    def count_edit_device(self, patterns_ptr, offsets_ptr, npat, k, counts_ptr, cyclic=False):
+        """bce_hip_count_edit_device: the counts per distance of `npat` patterns that lie concatenated in device memory (int
+        pointers: the bytes, npat + 1 uint64 offsets, npat * (k + 1) uint64 counts out).  Stream rule: as count_device."""
+        ptr = lambda v: None if v is None else int(v)  # noqa: E731
+        self._c.check(self._c.lib.bce_hip_count_edit_device(self._c.h, ptr(patterns_ptr), ptr(offsets_ptr), int(npat), int(k),
+                                                            0 if cyclic else LOCATE_LINEAR, ptr(counts_ptr)), "bce_hip_count_edit_device")
+
+    def locate_edit(self, patterns, k, cyclic=False, limit=None, max_hits=1 << 26):
+        """Where something occurs within k edits of a pattern: (positions uint32 ascending, lens uint16, dists uint8: the length
+        and the distance of the best alignment that starts at each) for one bytes-like, a list of such triples for a sequence
+        (bce_hip_locate_edit).  cyclic and the empty pattern: as count_edit().  `max_hits` and `limit`: locate()'s rules -- a
+        sizing call first (here a whole search), ValueError above max_hits before any room is made; limit keeps each pattern's
+        first hits in text order and bounds the result, not the work."""
+        one, pats, flat, offsets = self._edit_args(patterns, k, cyclic, "hits")
+        if limit is not None and limit < 0:
+            raise ValueError("limit must not be negative")
+        if not pats:
+            return []
+        lib, flags = self._c.lib, 0 if cyclic else LOCATE_LINEAR
+        hits, total = np.zeros(len(pats) + 1, dtype=np.uint64), C.c_uint64(0)
+        rc = lib.bce_hip_locate_edit(self._c.h, flat.ctypes.data, offsets.ctypes.data, len(pats), int(k), flags, hits.ctypes.data, None, None, None, 0,
+                                     C.byref(total))
+        if rc in (0, E_OVERFLOW) and total.value > max_hits:
+            raise ValueError("%d hits in all, more than max_hits = %d" % (total.value, max_hits))
+        self._c.check(rc, "bce_hip_locate_edit")
+        room = max(total.value, 1)
+        pos, lens, dist = _positions_buffer(total.value), np.empty(room, dtype=np.uint16), np.empty(room, dtype=np.uint8)
+        self._c.check(lib.bce_hip_locate_edit(self._c.h, flat.ctypes.data, offsets.ctypes.data, len(pats), int(k), flags, hits.ctypes.data,
+                                              pos.ctypes.data, lens.ctypes.data, dist.ctypes.data, total.value, C.byref(total)), "bce_hip_locate_edit")
+        out = [tuple(a[int(hits[i]):int(hits[i + 1])][:limit].copy() for a in (pos, lens, dist)) for i in range(len(pats))]
+        return out[0] if one else out
+
+    def locate_edit_device(self, patterns_ptr, offsets_ptr, npat, k, hit_offsets_ptr, positions_ptr, lens_ptr, dists_ptr, cap, cyclic=False) -> int:
+        """bce_hip_locate_edit_device: locate_near_device with edits (out, beside the positions: up to `cap` uint16 lengths and uint8
+        distances) -> the total.  positions_ptr, lens_ptr and dists_ptr None with cap 0 only sizes.  Stream rule: as count_device."""
+        total = C.c_uint64(0)
+        ptr = lambda v: None if v is None else int(v)  # noqa: E731
+        self._c.check(self._c.lib.bce_hip_locate_edit_device(self._c.h, ptr(patterns_ptr), ptr(offsets_ptr), int(npat), int(k),
+                                                             0 if cyclic else LOCATE_LINEAR, ptr(hit_offsets_ptr), ptr(positions_ptr), ptr(lens_ptr),
+                                                             ptr(dists_ptr), int(cap), C.byref(total)), "bce_hip_locate_edit_device")
+        return total.value
+
     def _class_args(self, patterns, cyclic, max_nodes, ignore_case, what):
         """-> (one, pats, flat, offsets, budget) of a search by byte classes, judged as count() and locate() judge theirs"""
         budget = 0 if max_nodes is None else int(max_nodes)
@@ -1252,6 +1333,27 @@ def locate_near(data, patterns, k, cyclic=False, limit=None, max_hits=1 << 26, d
     rf = RankFile(data, device=device, ctx=ctx)
     try:
         return rf.locate_near(patterns, k, cyclic=cyclic, limit=limit, max_hits=max_hits)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def count_edit(data, patterns, k, cyclic=False, device=0, ctx=None):
+    """The hits of `patterns` in `data` within k edits, per distance (RankFile.count_edit): K1 and K2 index the data on the GPU,
+    the search and its reduce ask the index and K1's suffix array."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.count_edit(patterns, k, cyclic=cyclic)
+    finally:
+        if ctx is None:
+            rf.close()
+
+
+def locate_edit(data, patterns, k, cyclic=False, limit=None, max_hits=1 << 26, device=0, ctx=None):
+    """Where `patterns` occur in `data` within k edits -> (positions, lens, dists) as RankFile.locate_edit."""
+    rf = RankFile(data, device=device, ctx=ctx)
+    try:
+        return rf.locate_edit(patterns, k, cyclic=cyclic, limit=limit, max_hits=max_hits)
     finally:
         if ctx is None:
             rf.close()

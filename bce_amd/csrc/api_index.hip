@@ -1,8 +1,9 @@
-// api_index.hip -- C ABI of the index queries (include/bce_hip.h): counts, positions, both within k mismatches and both for patterns of byte classes
-// (kd_classes.hip), longest matches and coverage, the LCP array and
-// its reductions, the list of the most frequent k-grams, parse and patch, the longest previous factors and the self-parse; and the test hooks that run their block scans alone.  The device work is in kd_count /
-// kd_locate / kd_near / kd_match / kd_lcp / kd_parse / kd_self.hip.  Every query comes twice, for host buffers and for device buffers: the two differ
-// in staging and in the copy out, and in nothing else.
+// api_index.hip -- C ABI of the index queries (include/bce_hip.h): counts and positions; the same two within k mismatches
+// (kd_near.hip), within k edits (kd_edit.hip) and for patterns of byte classes (kd_classes.hip); longest matches and coverage,
+// the LCP array and its reductions, the list of the most frequent k-grams, parse and patch, the longest previous factors and the
+// self-parse; and the test hooks that run their block scans alone.  The device work is in kd_count / kd_locate / kd_near /
+// kd_edit / kd_classes / kd_match / kd_lcp / kd_parse / kd_self.hip.  Every query comes twice, for host buffers and for device
+// buffers: the two differ in staging and in the copy out, and in nothing else.
 //
 // All of them judge the arguments before the context's state and the state before the arrays, then run their body through
 // query_call in phase 3, as bce_hip_rank1: the planes are read, so what an allocation may give back is what an enumeration beside
@@ -311,6 +312,118 @@ int bce_hip_locate_near_device(bce_hip_ctx *c, const void *d_patterns, const voi
     return locate_near_run(c, sa, static_cast<const uint8_t *>(d_patterns), static_cast<const uint64_t *>(d_offsets), npat, k,
                            flags & BCE_HIP_LOCATE_LINEAR, static_cast<uint64_t *>(d_hit_offsets), nullptr, static_cast<uint32_t *>(d_positions),
                            static_cast<uint8_t *>(d_dists), nullptr, nullptr, !d_positions, cap, total);
+  });
+}
+
+// ---- counts and positions within k edits (kd_edit.hip) ------------------------------------------------------------------------------
+// The near calls' rules, checks and protocol; k, the flags and npat's cap are judged beside ctx, the patterns' lengths with the list.
+// Both need the suffix array: the hits are reduced from candidates by position.
+static bool edit_args(uint32_t npat, uint32_t k, uint32_t flags) {
+  return !(flags & ~BCE_HIP_LOCATE_LINEAR) && k <= BCE_HIP_EDIT_MAX_K && npat <= BCE_HIP_EDIT_MAX_PATTERNS;
+}
+static int edit_lengths(bce_hip_ctx *c, const char *what, const uint64_t *offsets, uint32_t npat) {
+  for (uint32_t p = 0; p < npat; ++p)
+    if (offsets[p + 1] - offsets[p] > BCE_HIP_EDIT_MAX_LEN) {
+      snprintf(c->err, sizeof c->err, "%s: pattern %u has %llu bytes, more than %u", what, p, (unsigned long long)(offsets[p + 1] - offsets[p]), BCE_HIP_EDIT_MAX_LEN);
+      return BCE_HIP_E_ARG;
+    }
+  return BCE_HIP_OK;
+}
+
+int bce_hip_count_edit(bce_hip_ctx *c, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t k, uint32_t flags, uint64_t *counts) {
+  if (!c || !edit_args(npat, k, flags)) return BCE_HIP_E_ARG;
+  if (npat == 0) return BCE_HIP_OK;
+  const uint32_t *sa = nullptr;
+  BCE_TRY(sa_state(c, &sa, "count_edit"));
+  if (!counts) return BCE_HIP_E_ARG;
+  BCE_TRY(pattern_list_args(c, "count_edit", patterns, offsets, npat));
+  BCE_TRY(edit_lengths(c, "count_edit", offsets, npat));
+  return query_call(c, 3, [&]() -> int {
+    DevBuf &pat = c->qbuf[qb::edit_pat], &off = c->qbuf[qb::edit_off], &out = c->qbuf[qb::edit_out];
+    const size_t bytes = (size_t)npat * (k + 1) * 8;
+    BCE_TRY(ensure(c, out, bytes));
+    BCE_TRY(stage_patterns(c, pat, off, patterns, offsets, npat));
+    BCE_TRY(kd_edit_count(c, sa, pat.as<uint8_t>(), off.as<uint64_t>(), npat, k, flags & BCE_HIP_LOCATE_LINEAR, out.as<uint64_t>()));
+    return copy_out(c, counts, out, bytes);
+  });
+}
+
+int bce_hip_count_edit_device(bce_hip_ctx *c, const void *d_patterns, const void *d_offsets, uint32_t npat, uint32_t k, uint32_t flags, void *d_counts) {
+  if (!c || !edit_args(npat, k, flags)) return BCE_HIP_E_ARG;
+  if (npat == 0) return BCE_HIP_OK;
+  const uint32_t *sa = nullptr;
+  BCE_TRY(sa_state(c, &sa, "count_edit"));
+  if (!d_patterns || !d_offsets || !d_counts) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&] {
+    return kd_edit_count(c, sa, static_cast<const uint8_t *>(d_patterns), static_cast<const uint64_t *>(d_offsets), npat, k,
+                         flags & BCE_HIP_LOCATE_LINEAR, static_cast<uint64_t *>(d_counts));
+  });
+}
+
+// locate_near_run with the lengths beside the positions and distances; the sizing is the whole search and reduce
+static int locate_edit_run(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, uint32_t k, bool linear,
+                           uint64_t *d_hits, uint64_t *h_hits, uint32_t *d_pos, uint16_t *d_len, uint8_t *d_dist, uint32_t *h_pos, uint16_t *h_len,
+                           uint8_t *h_dist, bool sizing, uint64_t cap, uint64_t *total) {
+  uint64_t hits = 0;
+  const uint32_t *pos = nullptr, *tag = nullptr;
+  BCE_TRY(kd_edit_size(c, sa, d_pat, d_off, npat, k, linear, d_hits, &hits, &pos, &tag));
+  if (h_hits) {
+    BCE_HIP_TRY(c, hipMemcpyAsync(h_hits, d_hits, ((size_t)npat + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    BCE_HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  *total = hits;
+  if (sizing) return BCE_HIP_OK;
+  if (hits > cap) { snprintf(c->err, sizeof c->err, "locate_edit: %llu hits, room for %llu", (unsigned long long)hits, (unsigned long long)cap); return BCE_HIP_E_OVERFLOW; }
+  if (hits == 0) return BCE_HIP_OK;
+  if (h_pos) {
+    BCE_TRY(ensure(c, c->qbuf[qb::edit_pos], (size_t)hits * 4));
+    BCE_TRY(ensure(c, c->qbuf[qb::edit_len], (size_t)hits * 2));
+    BCE_TRY(ensure(c, c->qbuf[qb::edit_dist], (size_t)hits));
+    d_pos = c->qbuf[qb::edit_pos].as<uint32_t>();
+    d_len = c->qbuf[qb::edit_len].as<uint16_t>();
+    d_dist = c->qbuf[qb::edit_dist].as<uint8_t>();
+  }
+  BCE_TRY(kd_edit_fill(c, d_off, npat, k, d_hits, hits, pos, tag, d_pos, d_len, d_dist));
+  if (!h_pos) return BCE_HIP_OK;
+  BCE_TRY(copy_out(c, h_pos, c->qbuf[qb::edit_pos], (size_t)hits * 4));
+  BCE_TRY(copy_out(c, h_len, c->qbuf[qb::edit_len], (size_t)hits * 2));
+  return copy_out(c, h_dist, c->qbuf[qb::edit_dist], (size_t)hits);
+}
+
+int bce_hip_locate_edit(bce_hip_ctx *c, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t k, uint32_t flags,
+                        uint64_t *hit_offsets, uint32_t *positions, uint16_t *lens, uint8_t *dists, uint64_t cap, uint64_t *total) {
+  if (!c || !total || !edit_args(npat, k, flags)) return BCE_HIP_E_ARG;
+  *total = 0;
+  if (npat == 0) { if (hit_offsets) hit_offsets[0] = 0; return BCE_HIP_OK; }
+  const uint32_t *sa = nullptr;
+  BCE_TRY(sa_state(c, &sa, "locate_edit"));
+  if (!hit_offsets || (!positions && cap) || !positions != !dists || !positions != !lens) return BCE_HIP_E_ARG;
+  BCE_TRY(pattern_list_args(c, "locate_edit", patterns, offsets, npat));
+  BCE_TRY(edit_lengths(c, "locate_edit", offsets, npat));
+  return query_call(c, 3, [&]() -> int {
+    DevBuf &pat = c->qbuf[qb::edit_pat], &off = c->qbuf[qb::edit_off], &hits = c->qbuf[qb::edit_hits];
+    BCE_TRY(ensure(c, hits, ((size_t)npat + 1) * 8));
+    BCE_TRY(stage_patterns(c, pat, off, patterns, offsets, npat));
+    return locate_edit_run(c, sa, pat.as<uint8_t>(), off.as<uint64_t>(), npat, k, flags & BCE_HIP_LOCATE_LINEAR, hits.as<uint64_t>(), hit_offsets,
+                           nullptr, nullptr, nullptr, positions, lens, dists, !positions, cap, total);
+  });
+}
+
+int bce_hip_locate_edit_device(bce_hip_ctx *c, const void *d_patterns, const void *d_offsets, uint32_t npat, uint32_t k, uint32_t flags,
+                               void *d_hit_offsets, void *d_positions, void *d_lens, void *d_dists, uint64_t cap, uint64_t *total) {
+  if (!c || !total || !edit_args(npat, k, flags)) return BCE_HIP_E_ARG;
+  *total = 0;
+  if (npat == 0) {
+    if (!d_hit_offsets) return BCE_HIP_OK;
+    return query_call(c, 0, [&]() -> int { BCE_HIP_TRY(c, hipMemsetAsync(d_hit_offsets, 0, 8, c->stream)); return BCE_HIP_OK; });
+  }
+  const uint32_t *sa = nullptr;
+  BCE_TRY(sa_state(c, &sa, "locate_edit"));
+  if (!d_patterns || !d_offsets || !d_hit_offsets || (!d_positions && cap) || !d_positions != !d_dists || !d_positions != !d_lens) return BCE_HIP_E_ARG;
+  return query_call(c, 3, [&] {
+    return locate_edit_run(c, sa, static_cast<const uint8_t *>(d_patterns), static_cast<const uint64_t *>(d_offsets), npat, k,
+                           flags & BCE_HIP_LOCATE_LINEAR, static_cast<uint64_t *>(d_hit_offsets), nullptr, static_cast<uint32_t *>(d_positions),
+                           static_cast<uint16_t *>(d_lens), static_cast<uint8_t *>(d_dists), nullptr, nullptr, nullptr, !d_positions, cap, total);
   });
 }
 

@@ -175,6 +175,10 @@ enum Id {
   sfc_inv, sfc_bsum,                             // the checker's inverse (n words) and the three stages' block results
   sfc_text, sfc_sa,                              // bce_hip_sufcheck with host buffers: the text and the array, staged (grow-only)
   sfa_sa, sfa_isa,                               // bce_hip_suffix_array with host buffers: the array and its inverse, staged (grow-only)
+  edit_res,                                      // kd_edit.hip: its flag word (a buffer of its own, as near_res); its scratch is the locate's loc_res .. loc_val1
+  edit_cnt,                                      // the reduce: every pattern's hits, what the scan turns into hit_offsets
+  edit_pat, edit_off, edit_out,                  // bce_hip_count_edit / _locate_edit: the patterns, their offsets and the counts of a call with host buffers, staged (grow-only)
+  edit_hits, edit_pos, edit_len, edit_dist,      // bce_hip_locate_edit with host buffers: the CSR offsets, positions, lengths and distances, staged (grow-only)
   count
 };
 }  // namespace qb
@@ -511,6 +515,15 @@ int kd_near_size(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, const
                  uint64_t *d_hits, uint64_t *rows, uint64_t *total);
 int kd_near_fill(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, uint32_t k, bool linear,
                  uint64_t rows, uint64_t total, uint32_t *d_pos, uint8_t *d_dist);
+// kd_edit.hip: the same two questions within k <= BCE_HIP_EDIT_MAX_K edits (edit_step.h), both reduced from candidates through the
+// suffix array.  Counts: d_out[npat * (k + 1)], queued.  _size: the whole search, d_hits[npat + 1] and their total, and the sorted
+// candidates (pos, tag) that _fill, straight after it, writes the heads of: d_pos, d_len, d_dist[total].
+int kd_edit_count(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, uint32_t k, bool linear,
+                  uint64_t *d_out);
+int kd_edit_size(bce_hip_ctx *c, const uint32_t *sa, const uint8_t *d_pat, const uint64_t *d_off, uint32_t npat, uint32_t k, bool linear,
+                 uint64_t *d_hits, uint64_t *total, const uint32_t **pos, const uint32_t **tag);
+int kd_edit_fill(bce_hip_ctx *c, const uint64_t *d_off, uint32_t npat, uint32_t k, const uint64_t *d_hits, uint64_t total, const uint32_t *pos,
+                 const uint32_t *tag, uint32_t *d_pos, uint16_t *d_len, uint8_t *d_dist);
 // kd_classes.hip: the same two questions for patterns of byte classes (class_step.h), under a budget of max_nodes search nodes per
 // pattern.  d_masks: 8 words per class, d_off counts classes.  d_status[npat]: 0 or BCE_HIP_CLASS_OVER; d_work (may be null): the nodes.
 int kd_class_count(bce_hip_ctx *c, const uint32_t *d_masks, const uint64_t *d_off, uint32_t npat, uint32_t max_nodes, uint64_t *d_counts,

@@ -8,6 +8,8 @@
 //   bce -gl PATTERN file, -gld PATTERN archive   (extension) where they occur: the byte offsets, gathered on the GPU from K1's suffix array
 //   bce -gn K PATTERN file, -gnd K PATTERN archive   (extension) how often something occurs that differs from PATTERN in at most K (0..2) bytes, per distance
 //   bce -gnl K PATTERN file, -gnld K PATTERN archive (extension) where: the byte offsets, each with its distance
+//   bce -gw K PATTERN file, -gwd K PATTERN archive   (extension) how often something occurs within K (0..2) edits of PATTERN -- substitutions, insertions, deletions -- per distance
+//   bce -gwl K PATTERN file, -gwld K PATTERN archive (extension) where: the byte offsets, each with the length and the distance of its best alignment
 //   bce -gm MINLEN file query_file, -gmd MINLEN archive query_file   (extension) how much of a second file lies in strings of MINLEN bytes or more that occur in the first
 //   bce -gr MINLEN file query_file out.bcd, -grd ... archive ...   (extension) writes query_file as a delta against the first: copies out of it plus the new bytes
 //   bce -ga file in.bcd out_file, -gad archive in.bcd out_file     (extension) rebuilds a file from the first and a delta, both sides checked by CRC-32
@@ -145,6 +147,10 @@ extern "C" int bce_hip_locate(bce_hip_ctx *ctx, const uint8_t *patterns, const u
 extern "C" int bce_hip_count_near(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t k, uint64_t *counts) __attribute__((weak));
 extern "C" int bce_hip_locate_near(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t k, uint32_t flags,
                                    uint64_t *hit_offsets, uint32_t *positions, uint8_t *dists, uint64_t cap, uint64_t *total) __attribute__((weak));
+extern "C" int bce_hip_count_edit(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t k, uint32_t flags,
+                                  uint64_t *counts) __attribute__((weak));
+extern "C" int bce_hip_locate_edit(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t k, uint32_t flags,
+                                   uint64_t *hit_offsets, uint32_t *positions, uint16_t *lens, uint8_t *dists, uint64_t cap, uint64_t *total) __attribute__((weak));
 extern "C" int bce_hip_count_classes(bce_hip_ctx *ctx, const uint32_t *masks, const uint64_t *offsets, uint32_t npat, uint32_t max_nodes, uint64_t *counts,
                                      uint64_t *work, uint32_t *status) __attribute__((weak));
 extern "C" int bce_hip_locate_classes(bce_hip_ctx *ctx, const uint32_t *masks, const uint64_t *offsets, uint32_t npat, uint32_t max_nodes, uint32_t flags,
@@ -695,6 +701,50 @@ static int locate_near_command(uint32_t K, const char *pattern, const char *path
   return index_done(in);
 }
 
+// -gw / -gwd: the positions within K edits of PATTERN (the anchored edit distance of include/bce_hip.h), per distance.  Linear
+// semantics, as -g: bce_hip_count_edit restricts the alignments to those that end inside the text on the GPU, nothing is corrected
+// here.  The pattern's length is not judged against the text's: a shorter alignment may still fit.
+static int count_edit_command(uint32_t K, const char *pattern, const char *path, bool in_archive) {
+  IndexInput in;
+  if (const int ec = index_open(in, path, in_archive, nullptr, kNoSecond, bce_hip_count_edit != nullptr)) return ec;
+  const size_t m = strlen(pattern);
+  const uint64_t offsets[2] = {0, m};
+  uint64_t per[BCE_HIP_EDIT_MAX_K + 1] = {0, 0, 0}, count = 0;
+  int rc = index_text(in);
+  if (rc == 0) rc = bce_hip_count_edit(in.ctx, reinterpret_cast<const uint8_t *>(pattern), offsets, 1, K, BCE_HIP_LOCATE_LINEAR, per);
+  if (rc != 0) return index_failed(in, "Count", rc);
+  for (uint32_t d = 0; d <= K; ++d) {
+    printf("distance %u: %llu\n", d, (unsigned long long)per[d]);
+    count += per[d];
+  }
+  printf("%llu occurrences\n", (unsigned long long)count);
+  return index_done(in);
+}
+
+// -gwl / -gwld: the linear hits of bce_hip_locate_edit, "POS LEN d" per line in ascending position, before the count line
+static int locate_edit_command(uint32_t K, const char *pattern, const char *path, bool in_archive) {
+  IndexInput in;
+  if (const int ec = index_open(in, path, in_archive, nullptr, kNoSecond, bce_hip_locate_edit != nullptr)) return ec;
+  const uint64_t offsets[2] = {0, strlen(pattern)};
+  const uint8_t *pat = reinterpret_cast<const uint8_t *>(pattern);
+  uint64_t count = 0, hits[2] = {0, 0};
+  std::vector<uint32_t> where;
+  std::vector<uint16_t> lens;
+  std::vector<uint8_t> dist;
+  int rc = index_text(in);
+  if (rc == 0) rc = bce_hip_locate_edit(in.ctx, pat, offsets, 1, K, BCE_HIP_LOCATE_LINEAR, hits, nullptr, nullptr, nullptr, 0, &count);   // how many
+  if (rc == 0 && count) {
+    where.resize(count);
+    lens.resize(count);
+    dist.resize(count);
+    rc = bce_hip_locate_edit(in.ctx, pat, offsets, 1, K, BCE_HIP_LOCATE_LINEAR, hits, where.data(), lens.data(), dist.data(), count, &count);
+  }
+  if (rc != 0) return index_failed(in, "Locate", rc);
+  for (size_t r = 0; r < where.size(); ++r) printf("%u %u %u\n", where[r], (unsigned)lens[r], (unsigned)dist[r]);
+  printf("%llu occurrences\n", (unsigned long long)count);
+  return index_done(in);
+}
+
 // -ge[i] / -ge[i]d / -ge[i]l / -ge[i]ld: the hits of an expression of byte classes (class_expr.h), one 256-bit set per position, under
 // the default budget of search nodes.  Linear semantics, as -g: bce_hip_count_classes counts in the circular text and the windows
 // that start in the text's last m - 1 bytes and match come off here; bce_hip_locate_classes filters on the GPU.  A search that runs
@@ -1015,6 +1065,18 @@ static int usage() {
   printf("\n");
   printf("  bce -e file [config.bcc]\n");
   printf("   Estimates the size -c would give for \"file\" [using config \"config.bcc\"]: the model's code lengths are summed on the GPU, nothing is coded or written (extension)\n");
+  printf("\n");
+  printf("  bce -gw K PATTERN file\n");
+  printf("   Counts the positions of \"file\" where something starts that is within K (0..2) edits of PATTERN -- bytes substituted, inserted or deleted between PATTERN's first and last byte, which stay aligned: one line \"distance d: N\" for d = 0..K, each position under its least distance, then the sum; backward search that branches three ways, reduced per position through the suffix array, on the GPU (extension)\n");
+  printf("\n");
+  printf("  bce -gwd K PATTERN archive.bce\n");
+  printf("   The same counts in what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
+  printf("\n");
+  printf("  bce -gwl K PATTERN file\n");
+  printf("   Prints where they start: \"POS LEN d\" per hit, the byte offset, the length of the best alignment there and its number of edits, ascending by offset, then the count (extension)\n");
+  printf("\n");
+  printf("  bce -gwld K PATTERN archive.bce\n");
+  printf("   The same lines for what \"archive.bce\" (or a -cN / -CN container) holds, decoded on the GPU; writes nothing (extension)\n");
   printf("\n");
   printf("  bce -gp ORDER MINLEN N file\n");
   printf("   Prints the N (1..65536) heaviest maximal repeats of MINLEN (1..4096) bytes or more of the circular text of \"file\": strings that occur twice or more and lose an occurrence when extended by a byte on either side.  ORDER is len (longest first), count (most frequent first) or gain (length times the occurrences after the first).  Per repeat: length (4096+: that or more), occurrences, the position of one and the first 64 bytes (\\xHH for all but printable ASCII); then their number, the runs of the BWT and the size; found, selected and sorted on the GPU (extension)\n");
@@ -1375,6 +1437,10 @@ int main(int argc, char **argv) {
     return locate_command(argv[2], argv[3], argv[1][3] == 'd');
   } else if (argc == 5 && argv[3][0] != 0 && (strcmp(argv[1], "-gn") == 0 || strcmp(argv[1], "-gnd") == 0) && parse_near_k(argv[2]) >= 0) {
     return count_near_command((uint32_t)parse_near_k(argv[2]), argv[3], argv[4], argv[1][3] == 'd');
+  } else if (argc == 5 && argv[3][0] != 0 && (strcmp(argv[1], "-gw") == 0 || strcmp(argv[1], "-gwd") == 0) && parse_near_k(argv[2]) >= 0) {
+    return count_edit_command((uint32_t)parse_near_k(argv[2]), argv[3], argv[4], argv[1][3] == 'd');
+  } else if (argc == 5 && argv[3][0] != 0 && (strcmp(argv[1], "-gwl") == 0 || strcmp(argv[1], "-gwld") == 0) && parse_near_k(argv[2]) >= 0) {
+    return locate_edit_command((uint32_t)parse_near_k(argv[2]), argv[3], argv[4], argv[1][4] == 'd');
   } else if (argc == 5 && argv[3][0] != 0 && (strcmp(argv[1], "-gnl") == 0 || strcmp(argv[1], "-gnld") == 0) && parse_near_k(argv[2]) >= 0) {
     return locate_near_command((uint32_t)parse_near_k(argv[2]), argv[3], argv[4], argv[1][4] == 'd');
   } else if (argc == 4 && argv[2][0] != 0 && strncmp(argv[1], "-ge", 3) == 0) {

@@ -223,6 +223,89 @@ def locate_near_in_archive(blob, patterns, k, cyclic=False, device="cuda:0"):
     return locate_near_tensor(decompress_container_tensor(blob, device=device), patterns, k, cyclic=cyclic)
 
 
+def count_edit_tensor(t, patterns, k, cyclic=False, ctx=None):
+    """The hits of `patterns` within k edits in the 1-D uint8 CUDA tensor `t` (or slice, any offset), per distance: one bytes-like
+    -> a numpy uint64 array of k + 1, a sequence -> shape (npat, k + 1) (api.RankFile.count_edit).  Indexed, searched and
+    reduced where it lies.  Synchronises t's current stream first; `ctx` (an api._Ctx of t's device) is reused if given."""
+    _check(t, "t")
+    n = t.numel()
+    if n == 0:
+        raise api.BceError(-1, "count_edit_tensor", "empty input")
+    if n > _MAX_BLOCK:
+        raise ValueError("one index covers one text of less than 2^31 bytes, not %d" % n)
+    _ready(t)
+    own = ctx is None
+    c = ctx or api._Ctx(t.device.index)
+    try:
+        return api.RankFile(n=n, device_ptr=t.data_ptr(), ctx=c).count_edit(patterns, k, cyclic=cyclic)
+    finally:
+        if own:
+            c.close()
+
+
+def count_edit_in_archive(blob, patterns, k, cyclic=False, device="cuda:0"):
+    """count_edit_tensor on what an archive holds, decoded as count_in_archive decodes it: hits across block boundaries included."""
+    total = sum(t[0] for t in _blocks_of(blob))
+    if total > _MAX_BLOCK:
+        raise ValueError("the archive holds %d bytes: one index covers one text of less than 2^31" % total)
+    return count_edit_tensor(decompress_container_tensor(blob, device=device), patterns, k, cyclic=cyclic)
+
+
+def locate_edit_tensor(t, patterns, k, cyclic=False, ctx=None):
+    """Where `patterns` occur within k edits in the 1-D uint8 CUDA tensor `t` (or slice, any offset) -> (offsets, positions, lens,
+    dists), all tensors on t's device: int64[npat + 1], int32[total], int16[total] and uint8[total].  Pattern p owns
+    positions[offsets[p]:offsets[p + 1]], ascending byte offsets into t; lens and dists hold the length and the distance of the
+    best alignment that starts at each.  cyclic and k: as api.RankFile.locate_edit.  Searched, reduced and ordered on the device
+    (bce_hip_locate_edit_device, a sizing call first); of the answer only its total reaches the host.
+    Synchronises t's current stream first; `ctx` (an api._Ctx of t's device) is reused if given."""
+    _check(t, "t")
+    n = t.numel()
+    if n == 0:
+        raise api.BceError(-1, "locate_edit_tensor", "empty input")
+    if n > _MAX_BLOCK:
+        raise ValueError("one index covers one text of less than 2^31 bytes, not %d" % n)
+    if not 0 <= int(k) <= api.EDIT_MAX_K:
+        raise ValueError("k = %r, outside 0 .. %d" % (k, api.EDIT_MAX_K))
+    pats = [api._as_u8(patterns)] if api._is_one_pattern(patterns) else [api._as_u8(p) for p in patterns]
+    if not cyclic and any(len(p) == 0 for p in pats):
+        raise ValueError("an empty pattern has no linear hits (cyclic=True: every position, at distance 0)")
+    if any(len(p) > api.EDIT_MAX_LEN for p in pats):
+        raise ValueError("a pattern of more than %d bytes" % api.EDIT_MAX_LEN)
+    offsets = torch.zeros(len(pats) + 1, dtype=torch.int64, device=t.device)
+    if not pats:
+        return (offsets, torch.empty(0, dtype=torch.int32, device=t.device), torch.empty(0, dtype=torch.int16, device=t.device),
+                torch.empty(0, dtype=torch.uint8, device=t.device))
+    ends = np.zeros(len(pats) + 1, dtype=np.int64)
+    ends[1:] = np.cumsum([len(p) for p in pats], dtype=np.int64)
+    flat = np.concatenate(pats) if int(ends[-1]) else np.zeros(1, dtype=np.uint8)
+    d_pat, d_off = torch.from_numpy(flat).to(t.device), torch.from_numpy(ends).to(t.device)
+    _ready(t)
+    own = ctx is None
+    c = ctx or api._Ctx(t.device.index)
+    try:
+        rf = api.RankFile(n=n, device_ptr=t.data_ptr(), ctx=c)
+        total = rf.locate_edit_device(d_pat.data_ptr(), d_off.data_ptr(), len(pats), k, offsets.data_ptr(), None, None, None, 0, cyclic=cyclic)
+        positions = torch.empty(total, dtype=torch.int32, device=t.device)
+        lens = torch.empty(total, dtype=torch.int16, device=t.device)
+        dists = torch.empty(total, dtype=torch.uint8, device=t.device)
+        if total:
+            torch.cuda.current_stream(t.device).synchronize()        # (the allocator may hand out memory a queued kernel still uses)
+            rf.locate_edit_device(d_pat.data_ptr(), d_off.data_ptr(), len(pats), k, offsets.data_ptr(), positions.data_ptr(), lens.data_ptr(),
+                                  dists.data_ptr(), total, cyclic=cyclic)
+        return offsets, positions, lens, dists
+    finally:
+        if own:
+            c.close()
+
+
+def locate_edit_in_archive(blob, patterns, k, cyclic=False, device="cuda:0"):
+    """locate_edit_tensor on what an archive holds, decoded as count_in_archive decodes it -> (offsets, positions, lens, dists) on `device`."""
+    total = sum(t[0] for t in _blocks_of(blob))
+    if total > _MAX_BLOCK:
+        raise ValueError("the archive holds %d bytes: one index covers one text of less than 2^31" % total)
+    return locate_edit_tensor(decompress_container_tensor(blob, device=device), patterns, k, cyclic=cyclic)
+
+
 def count_classes_tensor(t, patterns, cyclic=False, max_nodes=None, ignore_case=False, ctx=None):
     """The hits of patterns of byte classes in the 1-D uint8 CUDA tensor `t` (or slice, any offset) -> (counts, over), numpy, as
     api.RankFile.count_classes.  Indexed where it lies; of the text only the few bytes at its two ends that the longest pattern

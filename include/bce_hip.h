@@ -376,6 +376,59 @@ int bce_hip_locate_near(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_
 int bce_hip_locate_near_device(bce_hip_ctx *ctx, const void *d_patterns, const void *d_offsets, uint32_t npat, uint32_t k, uint32_t flags,
                                void *d_hit_offsets, void *d_positions, void *d_dists, uint64_t cap, uint64_t *total);
 
+/* ---- extension: the same two questions within k EDITS: substitutions, insertions and deletions (kd_edit.hip, edit_step.h) --------
+ * T: the indexed text, n bytes, read circularly.  P: a pattern of m bytes.  0 <= k <= BCE_HIP_EDIT_MAX_K.
+ * For a string S of l bytes the ANCHORED edit distance e(P, S) is the least number of substitutions, insertions and deletions that
+ * turn P into S among the alignments in which P's first byte is aligned with S's first byte and P's last byte with S's last byte,
+ * each of those two a match or a substitution, never an indel (what aligners do at the ends of a seed: an exact hit at i does not
+ * also report i - 1 and i + 1 at distance 1):
+ *   m == 0: e = 0 for l == 0, otherwise infinite.    m == 1: e = [P[0] != S[0]] for l == 1, otherwise infinite.
+ *   m >= 2: e is infinite for l < 2, otherwise [P[0] != S[0]] + Lev(P[1 .. m-1), S[1 .. l-1)) + [P[m-1] != S[l-1]], Lev the plain
+ *           Levenshtein distance.
+ * For a position i in [0, n) let S(i, l) = T[(i + j) mod n], j < l, with l in [max(0, m - k), m + k].
+ *   cyclic: E(i) = min over l of e(P, S(i, l)).  i is a hit when E(i) <= k; its distance is E(i), its length L(i) the smallest l
+ *     that attains E(i).  m == 0 gives all n positions at distance 0 and length 0, k >= m gives every position, m > n wraps as it
+ *     does for bce_hip_count.
+ *   linear (BCE_HIP_LOCATE_LINEAR): the same with l restricted to i + l <= n BEFORE the minimum is taken: a position whose best cyclic
+ *     alignment runs across the end of the text can still be a hit through a shorter or dearer one, at that one's distance and
+ *     length.  P = "abcd", a text that ends in "abc" and starts with "d", k = 2: cyclic (n - 3, distance 0, length 4), linear
+ *     (n - 3, distance 2, length 3).
+ * Every position is reported at most once per pattern.  k == 0 gives bce_hip_count / bce_hip_locate, every length m.  For m <= 1 no
+ * indel is possible and the answer is bce_hip_count_near's; for m == 2 the only indel is an insertion between the two bytes.
+ * k <= BCE_HIP_EDIT_MAX_K and m <= BCE_HIP_EDIT_MAX_LEN are WORK bounds in the sense of BCE_HIP_NEAR_MAX_LEN; outside them
+ * BCE_HIP_E_ARG.  npat <= BCE_HIP_EDIT_MAX_PATTERNS for all four calls (a candidate's edits and length travel in the four low bits
+ * of the pattern's number through the sorts): more is BCE_HIP_E_ARG.
+ * The search enumerates edit scripts by backward search and finds CANDIDATES: different scripts reach one string and strings of
+ * different lengths nest, so a position is found many times, and the answer is the least (distance, length) per position, reduced
+ * on the device through the suffix array.  Hence:
+ *   - both calls need the planes AND the suffix array, counting included: BCE_HIP_E_STATE after bce_hip_set_bwt, as bce_hip_locate;
+ *   - both take the flags: the linear restriction is part of the reduce, not a correction of the caller's;
+ *   - what one call bounds is the batch's CANDIDATE rows, not its hits: more than 2^31 - 1 of them is BCE_HIP_E_OVERFLOW with
+ *     nothing written (no offsets, *total = 0), whatever cap is;
+ *   - a sizing call costs a whole search: the hits are only known after the reduce.
+ * Patterns arrive as for bce_hip_count.
+ * bce_hip_count_edit: counts[p * (k + 1) + d] = the hits of pattern p at distance exactly d, d = 0 .. k.  Order of the checks: ctx,
+ * k, flags and npat's cap first, then npat == 0, then the state, then the arrays.
+ * bce_hip_locate_edit: bce_hip_locate_near's protocol word for word -- the CSR answer (positions ascending within each pattern), the
+ * sizing call (positions, lens and dists NULL, cap 0), BCE_HIP_E_OVERFLOW with exact hit_offsets and *total when total > cap and
+ * then no byte of positions, lens or dists written, the order of the checks, no change to the compression state -- plus lens[r] =
+ * L(positions[r]); positions, lens and dists are given together or not at all. */
+#define BCE_HIP_EDIT_MAX_K 2u
+#define BCE_HIP_EDIT_MAX_LEN 4096u
+#define BCE_HIP_EDIT_MAX_PATTERNS (1u << 28)
+int bce_hip_count_edit(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t k, uint32_t flags,
+                       uint64_t *counts);
+/* The same with all three arrays in device memory of the context's device.  Stream rule and the kernel's checks (decreasing
+ * offsets, a pattern longer than BCE_HIP_EDIT_MAX_LEN): as bce_hip_count_near_device. */
+int bce_hip_count_edit_device(bce_hip_ctx *ctx, const void *d_patterns, const void *d_offsets, uint32_t npat, uint32_t k, uint32_t flags,
+                              void *d_counts);
+int bce_hip_locate_edit(bce_hip_ctx *ctx, const uint8_t *patterns, const uint64_t *offsets, uint32_t npat, uint32_t k, uint32_t flags,
+                        uint64_t *hit_offsets, uint32_t *positions, uint16_t *lens, uint8_t *dists, uint64_t cap, uint64_t *total);
+/* The same with patterns, offsets, hit offsets, positions, lengths (2-byte words) and distances in device memory of the context's
+ * device; total stays a host pointer.  Stream rule and the kernel's checks: as bce_hip_count_edit_device. */
+int bce_hip_locate_edit_device(bce_hip_ctx *ctx, const void *d_patterns, const void *d_offsets, uint32_t npat, uint32_t k, uint32_t flags,
+                               void *d_hit_offsets, void *d_positions, void *d_lens, void *d_dists, uint64_t cap, uint64_t *total);
+
 /* ---- extension: the same two questions for patterns of byte CLASSES (kd_classes.hip, class_step.h) ------------------------------
  * T: the indexed text, n bytes, read circularly.  A pattern P is m classes S_0 .. S_(m-1); every class is a set of bytes: a wildcard,
  * a range, both cases of a letter, one byte.
